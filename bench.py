@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Headline benchmark: scenes/sec of the GeoFormer eval forward on ScanNet-like scenes.
 
-    python bench.py --gpus N --steps K --warmup W
-    (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    (--dump-outputs: the outputs of the last timed step as DIR/<name>.npy, see dump_outputs; N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A "step" is one full ``GeoFormer.forward(batch, epoch, training=False)`` over one ~150k-point synthetic
 scene (BASELINE.json configs[1]; test yaml: nq=256, nc=2048, batch 1) with the batch dict already
@@ -1026,6 +1026,66 @@ def compare_outputs(outg, outc, ulps=PARITY_ULPS):
     return par
 
 
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: every file of the dump together
+DUMP_SAMPLE_SEED = 1234  # positions of the fixed sample taken of an output the budget cannot hold whole
+
+
+def _output_arrays(out, name=""):
+    """(name, numpy array) of every array in a forward's outputs: dict keys and list positions joined by '.'
+    (``mask_predictions.0.mask_logits.0``, ``proposal_scores.2``); None entries are skipped."""
+    if out is None:
+        return []
+    if isinstance(out, dict):
+        items = out.items()
+    elif isinstance(out, (list, tuple)):
+        items = enumerate(out)
+    elif torch.is_tensor(out):
+        return [(name, out.detach().cpu().numpy())]
+    elif isinstance(out, (bool, int, float, np.number, np.ndarray)):
+        return [(name, np.asarray(out))]
+    else:
+        raise TypeError(f"--dump-outputs: output {name!r} is a {type(out).__name__}, not an array")
+    res = []
+    for k, v in items:
+        res += _output_arrays(v, f"{name}.{k}" if name else str(k))
+    return res
+
+
+def _dump_dtype(a):
+    """float64 stays, other floats become float32, integers and booleans float32 where every value is exact in it."""
+    if a.dtype == np.float64:
+        return a
+    if a.dtype.kind == "f" or a.size == 0 or int(np.abs(a.astype(np.int64)).max()) <= 1 << 24:
+        return a.astype(np.float32)
+    return a.astype(np.float64)
+
+
+def dump_outputs(out, path, meta):
+    """Write the outputs of one forward as ``path/<name>.npy`` (float32 / float64), DUMP_BUDGET_BYTES in all.  The smallest
+    arrays are written whole; an array larger than its share of what is left becomes a fixed sample: the 1-D values at
+    the sorted flat positions ``np.random.default_rng(DUMP_SAMPLE_SEED).choice(size, k, replace=False)``.
+    ``path/manifest.json`` holds every array's full shape, its sampling and ``meta``."""
+    arrays = sorted(((n, _dump_dtype(a)) for n, a in _output_arrays(out)), key=lambda na: (na[1].nbytes, na[0]))
+    os.makedirs(path, exist_ok=True)
+    budget = DUMP_BUDGET_BYTES - 4096 * (len(arrays) + 1)  # (.npy headers, the manifest)
+    manifest = dict(meta, arrays={})
+    for i, (name, a) in enumerate(arrays):
+        entry = {"shape": list(a.shape), "dtype": str(a.dtype)}
+        share = budget // (len(arrays) - i)
+        if a.nbytes > share:
+            k = share // a.itemsize
+            entry["sample"] = {"elements": int(k), "of": int(a.size),
+                               "positions": f"np.sort(np.random.default_rng({DUMP_SAMPLE_SEED}).choice(of, elements, "
+                                            "replace=False)) over the flattened array"}
+            a = a.reshape(-1)[np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, k, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+        budget -= a.nbytes
+        manifest["arrays"][name] = entry
+    with open(os.path.join(path, "manifest.json"), "w") as f:
+        json.dump(manifest, f, indent=1)
+    return manifest
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1041,8 +1101,14 @@ def main():
                     help="two staggered scenes in flight (geoformer_amd/serving.py) instead of one scene at a time")
     ap.add_argument("--no-pipeline", dest="pipeline", action="store_false", help="(default) one scene at a time")
     ap.set_defaults(pipeline=False)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed step as DIR/<name>.npy (float32 / "
+                         "float64, at most 64 MB in all: a fixed seeded sample of an output too large for that) and "
+                         "DIR/manifest.json (rank 0)")
     ap.add_argument("--plumbing-test", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args, sys.argv[1:]))
     if args.plumbing_test:
@@ -1175,6 +1241,13 @@ def main():
         hb[rank] = host_busy
         dist.all_reduce(hb)
         busy_all = [float(x) for x in hb.tolist()]
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller (proposals collected), before any later forward can reuse its buffers
+        last = args.warmup + args.steps - 1
+        dump_outputs(loop.last, args.dump_outputs, {
+            "step": last, "numpy_seed": 1000 + last, "scene_seed": 1234 + rank * ns + last % ns, "points": args.points,
+            "scenes": ns, "steps": args.steps, "warmup": args.warmup, "loop": "staggered" if args.pipeline else "one at a time",
+            "ahead": not args.no_ahead, "bias_shift": model._bench_bias_shift})
 
     dp = None
     if world > 1 and not args.no_secondary:

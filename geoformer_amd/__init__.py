@@ -17,8 +17,10 @@ __version__ = "0.1.0"
 # environment: a harness calls ``configure_runtime()`` before its first HIP call (bench.py, tools/train_dp.py,
 # tests/conftest.py and __graft_entry__.py do), or exports the variable itself; ``_lib.load()`` warns when the library
 # is loaded into a process whose runtime is already up with fewer queues.
-HW_QUEUES_WANTED = 16
-HW_QUEUES_MIN = 8
+# The package asks for 2, the most one process should claim on a shared MI355X node; a larger value can only come from
+# the user's own environment.
+HW_QUEUES_WANTED = 2
+HW_QUEUES_MIN = 2
 
 
 def hw_queues_setting():
