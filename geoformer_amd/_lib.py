@@ -117,6 +117,8 @@ def _declare(lib):
         "gf_decoder_token_stage": (I, [P, P, P, I, I, I, I, I, P, P, P, P, P, P]),
         "gf_mask_intersections_scratch_bytes": (c_size_t, [I, I]),
         "gf_mask_intersections": (I, [P, I, I, P, P, P]),
+        "gf_instance_overlaps_scratch_bytes": (c_size_t, [I, I]),
+        "gf_instance_overlaps": (I, [P, I, I, P, I, P, P, I, I, P, P, P, P, P, P]),
         "gf_voxelize_idx_scratch_bytes": (c_size_t, [I]),
         "gf_voxelize_idx_count": (I, [P, I, I, I, P, P, P, P]),
         "gf_voxelize_idx_fill": (I, [P, I, I, I, P, P, I, I, P, P, P]),
@@ -221,7 +223,7 @@ def load():
     _check_hw_queues(torch)
     lib = ctypes.CDLL(LIB_PATH)
     EXPORTS = _declare(lib)
-    if lib.gf_abi_version() != 5:
+    if lib.gf_abi_version() != 6:
         raise GeoFormerHipError("libgeoformer_hip.so ABI version mismatch")
     _lib = lib
     return lib

@@ -1,0 +1,424 @@
+"""ScanNet v2 instance-segmentation evaluation (AP, AP50, AP25): the last stage of the reference's test loop
+(test.py:98-148, test_fs.py:219-259, util/eval.py), written from the published ScanNet benchmark algorithm
+(BenchmarkScripts/3d_evaluation/evaluate_semantic_instance.py).
+
+The per-scene part -- every picked mask against every ground-truth instance and the void points over all N points -- is
+one native call (gf_instance_overlaps, csrc/inst_eval.hip) on device tensors, followed by one small device-to-host copy
+of its tables.  Host arrays take a numpy path with the same semantics (the CPU reference).  What is kept per scene is a
+few KB: the instances' ids and sizes and, per kept prediction, its label, confidence, size and overlap row.  The
+dataset-level matching and AP integration run on the host once per evaluation.
+
+    ev = InstanceEvaluator(classes=0)                 # cvfold 0 / 1, or "all" (the 18 benchmark classes)
+    ev.add_scene(name, gt_ids, label_ids, scores, masks, pick)
+    ap, avgs = ev.evaluate(); print(ev.format_results(avgs))
+"""
+from __future__ import annotations
+
+import warnings
+
+import numpy as np
+
+# ---- label tables of the ScanNet v2 benchmark --------------------------------------------------------------------------
+# the 18 evaluated nyu40 ids and their names
+VALID_CLASS_IDS = (3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 14, 16, 24, 28, 33, 34, 36, 39)
+CLASS_NAMES = ("cabinet", "bed", "chair", "sofa", "table", "door", "window", "bookshelf", "picture", "counter", "desk",
+               "curtain", "refrigerator", "shower curtain", "toilet", "sink", "bathtub", "otherfurniture")
+# nyu40 id of each of the dataset's 20 semantic labels (0..19: wall, floor, then the 18 above)
+BENCHMARK_SEMANTIC_LABELS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 14, 16, 24, 28, 33, 34, 36, 39)
+# the few-shot folds: dataset semantic labels of the nine classes of each cvfold
+FOLD_SEMANTIC_LABELS = {0: (2, 3, 4, 7, 9, 11, 12, 13, 18), 1: (5, 6, 8, 10, 14, 15, 16, 17, 19)}
+FOLD_CLASS_IDS = {k: tuple(BENCHMARK_SEMANTIC_LABELS[s] for s in v) for k, v in FOLD_SEMANTIC_LABELS.items()}
+
+DEFAULT_OVERLAPS = tuple(np.append(np.arange(0.5, 0.95, 0.05), 0.25))
+MIN_REGION_SIZE = 100
+DEFAULT_MAX_GT = 256  # capacity of the native call's instance tables before it is grown
+
+
+def class_set(classes=0):
+    """(nyu40 ids, names) of an evaluated class set: cvfold 0 or 1, "all", or an explicit sequence of nyu40 ids."""
+    if isinstance(classes, str):
+        if classes != "all":
+            raise ValueError(f"classes: 0, 1, 'all' or a sequence of nyu40 ids, not {classes!r}")
+        ids = VALID_CLASS_IDS
+    elif isinstance(classes, (int, np.integer)):
+        if int(classes) not in FOLD_CLASS_IDS:
+            raise ValueError(f"cvfold {classes}: 0 or 1")
+        ids = FOLD_CLASS_IDS[int(classes)]
+    else:
+        ids = tuple(int(c) for c in classes)
+    ids = np.asarray(ids, dtype=np.int64)
+    if len(ids) == 0 or len(set(ids.tolist())) != len(ids) or (ids <= 0).any():
+        raise ValueError("classes: distinct positive nyu40 ids")
+    name = dict(zip(VALID_CLASS_IDS, CLASS_NAMES))
+    return ids, [name.get(int(i), str(int(i))) for i in ids]
+
+
+def benchmark_label_ids(cls_final, cvfold):
+    """nyu40 ids of the model's classes (4..12 in fold space) as test.py:65-68 maps them; on the tensor's device."""
+    ids = FOLD_CLASS_IDS[int(cvfold)]
+    if _is_tensor(cls_final):
+        import torch
+
+        return torch.tensor(ids, dtype=torch.int64, device=cls_final.device)[cls_final.long() - 4]
+    return np.asarray(ids, dtype=np.int64)[np.asarray(cls_final, dtype=np.int64) - 4]
+
+
+def gt_ids_from_labels(semantic_label, instance_label):
+    """val_gt ids of a scene from its per-point dataset labels (semantic 0..19 or -100, instance 0..I-1 or -100), as
+    data/scannetv2/prepare_data_inst_gttxt.py writes them: nyu40_id * 1000 + instance + 1, 0 where unannotated; an
+    instance takes the semantic label of its first point (-100 counts as label 0).  numpy in, numpy out; a tensor stays
+    on its device."""
+    if _is_tensor(instance_label):
+        import torch
+
+        inst = instance_label.long()
+        sem = semantic_label.to(inst.device).long()
+        N = inst.shape[0]
+        out = torch.zeros(N, dtype=torch.int64, device=inst.device)
+        on = inst >= 0
+        if N == 0 or not bool(on.any()):
+            return out
+        n_inst = int(inst.max()) + 1
+        pos = torch.arange(N, device=inst.device)
+        first = torch.full((n_inst,), N, dtype=torch.int64, device=inst.device)
+        first.scatter_reduce_(0, inst[on], pos[on], "amin")
+        s = sem[first.clamp(max=N - 1)]
+        s = torch.where(s == -100, torch.zeros_like(s), s)
+        bench = torch.tensor(BENCHMARK_SEMANTIC_LABELS, dtype=torch.int64, device=inst.device)
+        code = bench[s] * 1000 + torch.arange(1, n_inst + 1, device=inst.device)
+        out[on] = code[inst[on]]
+        return out
+    inst = np.asarray(instance_label).astype(np.int64)
+    sem = np.asarray(semantic_label).astype(np.int64)
+    out = np.zeros(inst.shape[0], dtype=np.int64)
+    on = inst >= 0
+    if not on.any():
+        return out
+    ids, first = np.unique(inst[on], return_index=True)
+    s = sem[np.nonzero(on)[0][first]]
+    s[s == -100] = 0
+    code = np.zeros(int(ids.max()) + 1, dtype=np.int64)
+    code[ids] = np.asarray(BENCHMARK_SEMANTIC_LABELS, dtype=np.int64)[s] * 1000 + ids + 1
+    out[on] = code[inst[on]]
+    return out
+
+
+def _is_tensor(x):
+    return type(x).__module__.startswith("torch") and hasattr(x, "device")
+
+
+# ---- per-scene tables ----------------------------------------------------------------------------------------------------
+def scene_overlaps_host(masks, gt_ids, class_ids, rows=None):
+    """numpy statement of gf_instance_overlaps: (gt_id [G], gt_count [G], inter [n, G+1]) with the instances of the
+    class set in ascending id order and the void points in the last column."""
+    gt = np.asarray(gt_ids, dtype=np.int64)
+    masks = np.asarray(masks)
+    if masks.ndim != 2 or masks.shape[1] != gt.shape[0]:
+        raise ValueError(f"masks {masks.shape} against {gt.shape[0]} points")
+    valid = np.isin(gt // 1000, np.asarray(class_ids, dtype=np.int64))
+    gt_id, slot, gt_count = np.unique(gt[valid], return_inverse=True, return_counts=True)
+    G = len(gt_id)
+    key = np.full(gt.shape[0], G, dtype=np.int64)
+    key[valid] = slot
+    m = masks if rows is None else masks[np.asarray(rows, dtype=np.int64)]
+    r, p = np.nonzero(m)
+    n = m.shape[0]
+    inter = np.bincount(r * (G + 1) + key[p], minlength=n * (G + 1)).reshape(n, G + 1)
+    return gt_id, gt_count.astype(np.int64), inter
+
+
+class _Scene:
+    """What a scene leaves behind: its instances (ids ascending, sizes) and the kept predictions in order (nyu40
+    label, confidence, size, void points, overlap with every instance)."""
+
+    __slots__ = ("name", "gt_id", "gt_count", "label", "conf", "count", "void", "inter")
+
+    def __init__(self, name, gt_id, gt_count, inter, labels, conf, class_ids, min_region_size):
+        count = inter.sum(1)
+        keep = np.isin(labels, class_ids) & (count >= min_region_size)
+        self.name = name
+        self.gt_id = np.asarray(gt_id, dtype=np.int64)
+        self.gt_count = np.asarray(gt_count, dtype=np.int64)
+        self.label = labels[keep]
+        self.conf = conf[keep]
+        self.count = count[keep]
+        self.void = inter[keep, -1]
+        self.inter = np.ascontiguousarray(inter[keep, :-1])
+
+    def by_class(self, cid):
+        """(instances, predictions) of one class in the form the matching reads:
+        instances: [(id, size, [(pred key, pred size, confidence, intersection), ...])]  (predictions in order)
+        predictions: [(key, confidence, size, void points, [(instance id, instance size, intersection), ...])]"""
+        gcols = np.nonzero(self.gt_id // 1000 == cid)[0]
+        prows = np.nonzero(self.label == cid)[0]
+        sub = self.inter[np.ix_(prows, gcols)]
+        keys = [(self.name, int(k)) for k in prows]
+        gts = []
+        for j, g in enumerate(gcols):
+            hit = np.nonzero(sub[:, j])[0]
+            gts.append((int(self.gt_id[g]), int(self.gt_count[g]),
+                        [(keys[i], int(self.count[prows[i]]), float(self.conf[prows[i]]), int(sub[i, j])) for i in hit]))
+        preds = []
+        for i, pr in enumerate(prows):
+            hit = np.nonzero(sub[i])[0]
+            preds.append((keys[i], float(self.conf[pr]), int(self.count[pr]), int(self.void[pr]),
+                          [(int(self.gt_id[gcols[j]]), int(self.gt_count[gcols[j]]), int(sub[i, j])) for j in hit]))
+        return gts, preds
+
+
+# ---- dataset-level matching and AP -------------------------------------------------------------------------------------
+def _average_precision(y_true, y_score, hard_fn):
+    """Area under the precision-recall curve with one point per distinct score (plus the artificial (r=0, p=1) end),
+    integrated with the [-0.5, 0, 0.5] step widths of the benchmark."""
+    order = np.argsort(y_score)
+    ys = y_score[order]
+    csum = np.cumsum(y_true[order])
+    _, first = np.unique(ys, return_index=True)
+    n_true = csum[-1] if len(csum) else 0
+    below = np.append(csum, 0)[first - 1]  # true examples scored strictly below each threshold
+    tp = n_true - below
+    fp = len(ys) - first - tp
+    fn = below + hard_fn
+    precision = np.append(tp / (tp + fp), 1.0)
+    recall = np.append(tp / (tp + fn), 0.0)
+    widths = np.convolve(np.concatenate(([recall[0]], recall, [0.0])), [-0.5, 0, 0.5], "valid")
+    return np.dot(precision, widths)
+
+
+def _ap_table(scenes, n_classes, overlaps, min_region_size):
+    """scenes: per scene a list over classes of (instances, predictions) as _Scene.by_class gives them.  Greedy matching
+    per overlap threshold in prediction order, a prediction matched once per threshold across the whole set."""
+    ap = np.zeros((n_classes, len(overlaps)))
+    for oi, th in enumerate(overlaps):
+        visited = set()
+        for li in range(n_classes):
+            y_true, y_score = [], []
+            hard_fn = 0
+            has_gt = has_pred = False
+            for sc in scenes:
+                gts, preds = sc[li]
+                gts = [g for g in gts if g[0] >= 1000 and g[1] >= min_region_size]
+                has_gt |= len(gts) > 0
+                has_pred |= len(preds) > 0
+                for gid, gsize, cands in gts:
+                    score = None
+                    for key, psize, conf, inter in cands:
+                        if key in visited or not inter / (gsize + psize - inter) > th:
+                            continue
+                        if score is None:
+                            score = conf
+                            visited.add(key)
+                        else:  # a second match of this instance: the lower-scored one is a false positive
+                            y_true.append(0.0)
+                            y_score.append(min(score, conf))
+                            score = max(score, conf)
+                    if score is None:
+                        hard_fn += 1
+                    else:
+                        y_true.append(1.0)
+                        y_score.append(score)
+                for key, conf, psize, void, cands in preds:
+                    if any(inter / (gsize + psize - inter) > th for _, gsize, inter in cands):
+                        continue
+                    ignore = void
+                    for gid, gsize, inter in cands:
+                        if gid < 1000:  # a group
+                            ignore += inter
+                        if gsize < min_region_size:  # a small instance
+                            ignore += inter
+                    if ignore / psize <= th:
+                        y_true.append(0.0)
+                        y_score.append(conf)
+            if has_gt and has_pred:
+                ap[li, oi] = _average_precision(np.asarray(y_true, dtype=np.float64),
+                                                np.asarray(y_score, dtype=np.float64), hard_fn)
+            elif has_gt:
+                ap[li, oi] = 0.0
+            else:
+                ap[li, oi] = float("nan")
+    return ap
+
+
+def _averages(ap, names, overlaps):
+    """The benchmark's summary of an AP table [C, n_overlaps]: mean over classes (ignoring nan) of AP over the
+    thresholds other than 0.25, of AP50 and of AP25, and the same per class."""
+    aps = np.asarray(ap)[None]
+    ov = np.asarray(overlaps)
+    o50 = np.where(np.isclose(ov, 0.5))
+    o25 = np.where(np.isclose(ov, 0.25))
+    rest = np.where(np.logical_not(np.isclose(ov, 0.25)))
+    with warnings.catch_warnings():  # (nanmean of an all-nan slice: a class set with no instance at all)
+        warnings.simplefilter("ignore", RuntimeWarning)
+        avgs = {"all_ap": np.nanmean(aps[0, :, rest]), "all_ap_50%": np.nanmean(aps[0, :, o50]),
+                "all_ap_25%": np.nanmean(aps[0, :, o25]), "classes": {}}
+        for li, name in enumerate(names):
+            avgs["classes"][name] = {"ap": np.average(aps[0, li, rest]), "ap50%": np.average(aps[0, li, o50]),
+                                     "ap25%": np.average(aps[0, li, o25])}
+    return avgs
+
+
+def average_over_runs(runs):
+    """Mean (and the std of the three overall numbers) of several evaluate() summaries: test_fs.py's run_num loop."""
+    if not runs:
+        raise ValueError("average_over_runs: no runs")
+    out = {}
+    for k in ("all_ap", "all_ap_50%", "all_ap_25%"):
+        v = np.array([r[k] for r in runs])
+        out[k] = np.mean(v)
+        out[k + "_std"] = np.std(v)
+    out["classes"] = {name: {k: np.mean(np.array([r["classes"][name][k] for r in runs])) for k in ("ap", "ap50%", "ap25%")}
+                      for name in runs[0]["classes"]}
+    return out
+
+
+def format_results(avgs):
+    """The summary as a printable table (per class AP / AP50 / AP25, the average and, for a run average, the std)."""
+    lines = ["#" * 64, f"{'what':<15}:{'AP':>15}{'AP_50%':>15}{'AP_25%':>15}", "#" * 64]
+    for name, c in avgs["classes"].items():
+        lines.append(f"{name:<15}:{c['ap']:>15.3f}{c['ap50%']:>15.3f}{c['ap25%']:>15.3f}")
+    lines.append("-" * 64)
+    lines.append(f"{'average':<15}:{avgs['all_ap']:>15.3f}{avgs['all_ap_50%']:>15.3f}{avgs['all_ap_25%']:>15.3f}")
+    if "all_ap_std" in avgs:
+        lines.append(f"{'std':<15}:{avgs['all_ap_std']:>15.3f}{avgs['all_ap_50%_std']:>15.3f}"
+                     f"{avgs['all_ap_25%_std']:>15.3f}")
+    return "\n".join(lines)
+
+
+class InstanceEvaluator:
+    """AP / AP50 / AP25 of instance predictions over a set of scenes (ScanNet v2 benchmark rules).
+
+    classes: cvfold 0 or 1 (nine classes each), "all" (the 18 benchmark classes) or a sequence of nyu40 ids.
+    min_region_size: predictions and instances smaller than this many points are ignored.
+    overlaps: IoU thresholds; AP averages all but 0.25, AP50 / AP25 are the 0.5 / 0.25 columns."""
+
+    def __init__(self, classes=0, min_region_size=MIN_REGION_SIZE, overlaps=DEFAULT_OVERLAPS):
+        self.class_ids, self.class_names = class_set(classes)
+        self.min_region_size = int(min_region_size)
+        self.overlaps = tuple(float(o) for o in overlaps)
+        self.scenes = []
+        self._dev_classes = {}
+        self.max_gt = DEFAULT_MAX_GT
+
+    def add_scene(self, name, gt_ids, label_ids, scores, masks, pick=None):
+        """One scene's predictions: masks [n_rows, N] (nonzero = member), label_ids [n_rows] nyu40 ids (e.g.
+        benchmark_label_ids(cls_final, cvfold)), scores [n_rows], pick: the rows to evaluate, in order (the NMS result;
+        default all rows), gt_ids [N] val_gt ids (gt_ids_from_labels).  Device tensors: the native overlap call and one
+        device-to-host copy; host arrays: the numpy path."""
+        if any(s.name == name for s in self.scenes):
+            raise ValueError(f"scene {name!r} was added already")
+        if _is_tensor(masks) and masks.is_cuda:
+            gt_id, gt_count, inter, labels, conf = self._tables_device(gt_ids, label_ids, scores, masks, pick)
+        else:
+            gt_id, gt_count, inter = scene_overlaps_host(masks, gt_ids, self.class_ids, pick)
+            sel = slice(None) if pick is None else np.asarray(pick, dtype=np.int64)
+            labels = np.asarray(label_ids).astype(np.int64)[sel]
+            conf = np.asarray(scores)[sel]
+        self.scenes.append(_Scene(name, gt_id, gt_count, inter, np.asarray(labels, dtype=np.int64),
+                                  np.asarray(conf), self.class_ids, self.min_region_size))
+
+    def _tables_device(self, gt_ids, label_ids, scores, masks, pick):
+        import torch
+
+        from . import pointops
+
+        dev = masks.device
+        if masks.dtype != torch.int32:
+            masks = (masks != 0).int()
+        masks = masks.contiguous()
+        gt = torch.as_tensor(gt_ids, device=dev).to(torch.int64).contiguous()
+        cls = self._dev_classes.get(dev)
+        if cls is None:
+            cls = self._dev_classes[dev] = torch.tensor(self.class_ids, dtype=torch.int32, device=dev)
+        labels = torch.as_tensor(label_ids, device=dev)
+        scores = torch.as_tensor(scores, device=dev)
+        rows = None
+        if pick is not None:
+            rows = torch.as_tensor(pick, device=dev).to(torch.int32).contiguous()
+            labels, scores = labels[rows.long()], scores[rows.long()]
+        n = masks.shape[0] if rows is None else rows.shape[0]
+        sdt = scores.dtype if scores.dtype in (torch.float32, torch.float64) else torch.float32
+        sw = n * (2 if sdt == torch.float64 else 1)
+        while True:
+            buf, lay = pointops.instance_overlaps_packed(masks, gt, cls, rows, self.max_gt, extra_words=2 * n + sw)
+            e = lay["extra"]
+            if n:  # the predictions' labels and scores ride along in the same copy
+                buf[e:e + 2 * n].view(torch.int64).copy_(labels.to(torch.int64))
+                buf[e + 2 * n:e + 2 * n + sw].view(sdt).copy_(scores.to(sdt))
+            h = buf.cpu().numpy()
+            G = int(h[0])
+            if G <= self.max_gt:
+                break
+            self.max_gt = G  # the instance tables were too small: nothing was written past them, run again
+        gt_id = h[lay["id"]:lay["id"] + 2 * G].view(np.int64)
+        gt_count = h[lay["count"]:lay["count"] + G].astype(np.int64)
+        inter = h[lay["inter"]:lay["inter"] + n * (G + 1)].reshape(n, G + 1).astype(np.int64)
+        labels = h[e:e + 2 * n].view(np.int64)
+        conf = h[e + 2 * n:e + 2 * n + sw].view(np.float64 if sdt == torch.float64 else np.float32)
+        return gt_id, gt_count, inter, labels, conf
+
+    def evaluate(self):
+        """(ap [C, n_overlaps], summary dict with all_ap, all_ap_50%, all_ap_25% and classes[name][ap | ap50% | ap25%])."""
+        scenes = [[s.by_class(int(c)) for c in self.class_ids] for s in self.scenes]
+        ap = _ap_table(scenes, len(self.class_ids), self.overlaps, self.min_region_size)
+        return ap, _averages(ap, self.class_names, self.overlaps)
+
+    def format_results(self, avgs=None):
+        return format_results(self.evaluate()[1] if avgs is None else avgs)
+
+    average_over_runs = staticmethod(average_over_runs)
+
+
+# ---- the reference's interface (util/eval.py), with the class set as a keyword instead of the global cfg -------------
+def assign_instances_for_scan(scene_name, pred_info, gt_ids, *, classes=0, min_region_size=MIN_REGION_SIZE):
+    """(gt2pred, pred2gt) of one scene in the reference's dict shapes; pred_info: {"conf", "label_id", "mask"}."""
+    ids, names = class_set(classes)
+    gt_id, gt_count, inter = scene_overlaps_host(pred_info["mask"], gt_ids, ids)
+    name_of = dict(zip(ids.tolist(), names))
+    gt2pred = {nm: [] for nm in names}
+    col = {}
+    for g, (i, c) in enumerate(zip(gt_id.tolist(), gt_count.tolist())):
+        col[g] = {"instance_id": i, "label_id": i // 1000, "vert_count": c, "med_dist": -1, "dist_conf": 0.0,
+                  "matched_pred": []}
+        gt2pred[name_of[i // 1000]].append(col[g])
+    pred2gt = {nm: [] for nm in names}
+    n_kept = 0
+    for i in range(inter.shape[0]):
+        label = int(pred_info["label_id"][i])
+        count = int(inter[i].sum())
+        if label not in name_of or count < min_region_size:
+            continue
+        pred = {"filename": f"{scene_name}_{n_kept:03d}", "pred_id": n_kept, "label_id": label, "vert_count": count,
+                "confidence": pred_info["conf"][i], "void_intersection": int(inter[i, -1])}
+        matched = []
+        for g in range(len(gt_id)):
+            if gt_id[g] // 1000 == label and inter[i, g] > 0:
+                matched.append(dict(col[g], intersection=int(inter[i, g])))
+                col[g]["matched_pred"].append(dict(pred, intersection=int(inter[i, g])))
+        pred["matched_gt"] = matched
+        pred2gt[name_of[label]].append(pred)
+        n_kept += 1
+    return gt2pred, pred2gt
+
+
+def evaluate_matches(matches, *, classes=0, min_region_size=MIN_REGION_SIZE, overlaps=DEFAULT_OVERLAPS):
+    """AP [1, C, n_overlaps] of {scene: {"gt": gt2pred, "pred": pred2gt}} as assign_instances_for_scan builds them."""
+    _, names = class_set(classes)
+    scenes = []
+    for m in matches.values():
+        per = []
+        for nm in names:
+            gts = [(g["instance_id"], g["vert_count"],
+                    [(p["filename"], p["vert_count"], float(p["confidence"]), p["intersection"]) for p in g["matched_pred"]])
+                   for g in m["gt"][nm]]
+            preds = [(p["filename"], float(p["confidence"]), p["vert_count"], p["void_intersection"],
+                      [(g["instance_id"], g["vert_count"], g["intersection"]) for g in p["matched_gt"]])
+                     for p in m["pred"][nm]]
+            per.append((gts, preds))
+        scenes.append(per)
+    return _ap_table(scenes, len(names), tuple(overlaps), min_region_size)[None]
+
+
+def compute_averages(aps, *, classes=0, overlaps=DEFAULT_OVERLAPS):
+    """The summary dict of an AP array [1, C, n_overlaps] (evaluate_matches' shape)."""
+    _, names = class_set(classes)
+    return _averages(np.asarray(aps)[0], names, overlaps)

@@ -898,6 +898,64 @@ def mask_intersections(masks):
     return inter
 
 
+def overlap_layout(n, max_gt, extra_words=0):
+    """Word offsets (int32 words) of instance_overlaps_packed's buffer: G at 0, gt_id (int64) at `id`, gt_count at `count`,
+    inter [n, G+1] at `inter`, `extra_words` caller words at `extra` (an even offset: 8-byte values fit), `total` words."""
+    o_id = 2
+    o_cnt = o_id + 2 * max_gt
+    o_inter = o_cnt + max_gt
+    o_extra = (o_inter + n * (max_gt + 1) + 1) // 2 * 2
+    return {"id": o_id, "count": o_cnt, "inter": o_inter, "extra": o_extra, "total": o_extra + extra_words}
+
+
+def instance_overlaps_packed(masks, gt_ids, class_ids, rows=None, max_gt=256, extra_words=0):
+    """One gf_instance_overlaps call into a single int32 device buffer laid out by overlap_layout(n, max_gt, extra_words),
+    so that one device-to-host copy brings every table back.  No synchronisation: buf[0] (G) may exceed max_gt, in which
+    case only buf[0] is meaningful.  Returns (buf, layout)."""
+    _i32c(masks, "masks")
+    if masks.dim() != 2:
+        raise RuntimeError("masks: expected [n_rows, N]")
+    if not (gt_ids.is_cuda and gt_ids.dtype == torch.int64 and gt_ids.is_contiguous() and gt_ids.dim() == 1):
+        raise RuntimeError("gt_ids: expected a contiguous int64 vector on the GPU")
+    _i32c(class_ids, "class_ids")
+    n_rows, N = masks.shape
+    if gt_ids.shape[0] != N:
+        raise RuntimeError(f"gt_ids has {gt_ids.shape[0]} points, the masks {N}")
+    if rows is not None:
+        _i32c(rows, "rows")
+    n = n_rows if rows is None else rows.shape[0]
+    C = class_ids.shape[0]
+    lay = overlap_layout(n, max_gt, extra_words)
+    buf = torch.empty(lay["total"], dtype=torch.int32, device=masks.device)
+    lib = _lib.load()
+    scratch = torch.empty(lib.gf_instance_overlaps_scratch_bytes(N, C) // 4 + 1, dtype=torch.int32, device=masks.device)
+    base = buf.data_ptr()
+    check(lib.gf_instance_overlaps(ptr(masks), n_rows, N, ptr(rows), n, ptr(gt_ids), ptr(class_ids), C, max_gt,
+                                   ptr(scratch), base, base + 4 * lay["id"], base + 4 * lay["count"],
+                                   base + 4 * lay["inter"], stream_ptr()), "gf_instance_overlaps")
+    return buf, lay
+
+
+def instance_overlaps(masks, gt_ids, class_ids, rows=None, max_gt=256):
+    """Overlap tables of the instance evaluation for one scene (gf_instance_overlaps): device tensors
+    (gt_id int64 [G], gt_count int32 [G], inter int32 [n, G+1]) -- instances in ascending id order, inter[i, g] the
+    points of picked mask i in instance g, inter[i, G] its void points.  masks int32 [n_rows, N] (any nonzero is a
+    member), gt_ids int64 [N] (val_gt encoding), class_ids int32 [C] (the evaluated nyu40 ids), rows int32 [n] (the
+    picked rows, default all).  Reads G back (one synchronisation) and repeats the call with room for G instances when
+    max_gt was too small."""
+    while True:
+        buf, lay = instance_overlaps_packed(masks, gt_ids, class_ids, rows, max_gt)
+        G = int(buf[0])
+        if G <= max_gt:
+            break
+        max_gt = G
+    n = masks.shape[0] if rows is None else rows.shape[0]
+    gt_id = buf[lay["id"]:lay["id"] + 2 * G].view(torch.int64)
+    gt_count = buf[lay["count"]:lay["count"] + G]
+    inter = buf[lay["inter"]:lay["inter"] + n * (G + 1)].view(n, G + 1)
+    return gt_id, gt_count, inter
+
+
 def backbone_transformer_params(before, transformer, after):
     """Device-pointer table of gf_backbone_transformer in the order include/geoformer_hip.h documents."""
     import ctypes

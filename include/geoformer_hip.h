@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GF_ABI_VERSION 5
+#define GF_ABI_VERSION 6
 
 typedef enum {
     GF_OK = 0,
@@ -722,6 +722,25 @@ int gf_proposal_select(const int32_t* final_, const int32_t* cls_pred, const flo
  * output), inter int32 [n,n], scratch: gf_mask_intersections_scratch_bytes(n, N). */
 size_t gf_mask_intersections_scratch_bytes(int n, int N);
 int gf_mask_intersections(const int32_t* masks, int n, int N, void* scratch, int32_t* inter, void* stream);
+
+/* ===================================================================================
+ * Overlap tables of the ScanNet instance evaluation for one scene (assign_instances_for_scan, util/eval.py:290-355,
+ * with get_instances, util/utils_3d.py:18-73): everything the evaluation derives from the N points.
+ *   masks int32 [n_rows,N] (gf_proposal_scatter layout; any nonzero is a member), rows int32 [n] (may be NULL: row i
+ *   is mask i, n <= n_rows; otherwise the picked rows in order, an index outside [0,n_rows) selects nothing),
+ *   gt_ids int64 [N] in the val_gt encoding nyu40_id * 1000 + inst + 1 (0 = unannotated), class_ids int32 [C] the
+ *   evaluated nyu40 ids (distinct, positive; 1 <= C <= 64).  A point is void iff floor(gt_ids / 1000) is not among
+ *   class_ids; every other distinct id is an instance, numbered 0..G-1 in ascending id order (np.unique's).
+ *   Outputs: *d_G = G; for G <= max_gt: gt_id int64 [max_gt] (first G valid), gt_count int32 [max_gt] (points of each
+ *   instance), inter int32 [n, G+1] packed in a buffer of n * (max_gt + 1) words: inter[i, g] = |mask_i AND id_g|,
+ *   inter[i, G] = |mask_i AND void| (the row sum is the mask's point count).  G > max_gt: only *d_G is meaningful and
+ *   nothing is written past the capacities; the caller grows them and repeats the call.
+ *   Exact integer counts (integer atomics), four commands on `stream`, no host synchronisation.
+ *   scratch: gf_instance_overlaps_scratch_bytes(N, C).  (ABI 6.) */
+size_t gf_instance_overlaps_scratch_bytes(int N, int C);
+int gf_instance_overlaps(const int32_t* masks, int n_rows, int N, const int32_t* rows, int n, const long long* gt_ids,
+                         const int32_t* class_ids, int C, int max_gt, void* scratch, int32_t* d_G, long long* gt_id,
+                         int32_t* gt_count, int32_t* inter, void* stream);
 
 /* ===================================================================================
  * Backbone voxel transformer of the two deepest U-Net levels, fused (inference)
