@@ -177,6 +177,12 @@ def _declare(lib):
         "gf_three_nn": (I, [P, P, I, I, I, P, P, P]),
         "gf_three_interpolate": (I, [P, P, P, I, I, I, I, P, P]),
         "gf_three_interpolate_grad": (I, [P, P, P, I, I, I, I, P, P]),
+        "gf_aug_scan_blocks": (I, [I]),
+        "gf_aug_draw": (I, [P, ctypes.c_ulonglong, c_longlong, I, P]),
+        "gf_aug_transform": (I, [P, I, I, ctypes.c_double, I, P]),
+        "gf_aug_elastic": (I, [P, I, I, I, I, ctypes.c_double, I, ctypes.c_ulonglong, c_longlong, I, c_longlong, P]),
+        "gf_aug_crop": (I, [P, I, I, I, I, c_longlong, I, P]),
+        "gf_aug_collate": (I, [P, P, I, I, I, I, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -247,6 +253,17 @@ class FeederJob(ctypes.Structure):
                 ("coords_dev", c_void_p), ("N", c_int), ("ncol", c_int), ("mode", c_int), ("pad_", c_int),
                 ("scratch", c_void_p), ("input_map", c_void_p), ("head_dev", c_void_p), ("head_host", c_void_p),
                 ("stream", c_void_p)]
+
+
+class AugBatch(ctypes.Structure):
+    """GfAugBatch of include/geoformer_hip.h (device pointers of one training batch's augmentation)."""
+
+    _fields_ = [("B", c_int), ("n_raw", c_int), ("max_inst", c_int), ("pad_", c_int),
+                ("raw", c_void_p), ("raw_off", c_void_p), ("rec", c_void_p), ("xyz_middle", c_void_p), ("xyz", c_void_p),
+                ("noise", c_void_p * 2), ("work", c_void_p * 2), ("cells", c_longlong * 2)] + [
+        (n, c_void_p) for n in ("flags", "lab", "inst", "start", "cursor", "block_sums", "block_off", "sidx", "bitmap",
+                                "inst_map", "inst_stats", "locs", "locs_float", "feats", "labels", "instance_labels",
+                                "instance_infos", "instance_pointnum", "offsets", "pc_mins", "pc_maxs", "head")]
 
 
 # seconds the host has spent blocked in the package's own Python-level waits (per process; bench.py's host_busy figure)

@@ -172,3 +172,29 @@ def make_batch(scenes, scale: int = 50, full_scale_min: int = 128, mode: int = 4
     batch["p2v_map"] = torch.from_numpy(p2v)
     batch["v2p_map"] = torch.from_numpy(v2p)
     return batch
+
+
+def make_raw_scene(n_points: int = 150_000, seed: int = 1234, n_boxes=None, instances: bool = True, room=None):
+    """A raw training scene as ``data/scannetv2/prepare_data_inst.py`` stores it: float64 [N, 8] = xyz (mean-centred),
+    rgb, 20-class semantic label, instance id.  Floor (0) and walls (1) carry no instance; every box takes a class of
+    either fold (2..19) and an instance id from a sparse set (ids with holes); ~3 % of the points are unannotated
+    (label and instance -100).  instances=False: every point's instance is -100 (a scene without instances); room:
+    (W, D, H) in metres as for make_scene.  xyz and rgb are float32 values (exact in the float64 array)."""
+    sc = make_scene(n_points, seed, room=room, n_boxes=n_boxes)
+    rng = np.random.default_rng(seed + 7919)
+    lab, inst = sc["label"].copy(), sc["instance"].copy()
+    boxes = np.unique(inst[inst >= 0])
+    cls = rng.choice(np.arange(2, 20), size=boxes.size)
+    ids = np.sort(rng.choice(3 * boxes.size + 2, size=boxes.size, replace=False))
+    for b, c, i in zip(boxes, cls, ids):
+        sel = sc["instance"] == b
+        lab[sel], inst[sel] = c, i
+    unann = rng.random(lab.size) < 0.03
+    lab[unann], inst[unann] = -100, -100
+    if not instances:
+        inst[:] = -100
+    out = np.empty((lab.size, 8), np.float64)
+    out[:, :3] = sc["xyz"]
+    out[:, 3:6] = sc["rgb"]
+    out[:, 6], out[:, 7] = lab, inst
+    return out

@@ -862,6 +862,84 @@ int gf_three_interpolate(const float* points, const int32_t* idx, const float* w
 int gf_three_interpolate_grad(const float* grad_out, const int32_t* idx, const float* weight, int b, int c, int n, int m,
                               float* grad_points, void* stream);
 
+/* ===================================================================================
+ * Training-batch augmentation and collate (datasets/scannetv2_inst.py:267-387 InstDataset.trainMerge; csrc/augment.hip,
+ * geoformer_amd/augment.py).  All device pointers; every call queues its launches on `stream` and syncs nothing.
+ *   A batch of B raw scenes: raw fp64 [n_raw, 8] (xyz, rgb, label, instance), raw_off int64 [B+1] (device).
+ *   rec int64 [B, GF_AUG_REC]: per-scene record (GF_AUG_R_* words, doubles stored as their bit patterns); the caller
+ *   initialises it (caps / bases of the noise grids, key sentinels) and, with rng="reference", writes the draws.
+ *   noise[p] fp32: raw noise of elastic pass p, scene s's three grids at rec[s][BASE_p] + axis * rec[s][CAP_p];
+ *   work[p]: 2 * cells[p] floats (the blurred grids end in work[p] + cells[p]).
+ *   Outputs at capacity n_raw rows (the first head[GF_AUG_H_N] are the batch; rows behind them hold padding coordinates
+ *   (batch 0xffff) that voxelise into one voxel each behind all real voxels), instance_pointnum capacity B * max_inst.
+ *   head int32 [GF_AUG_HEAD]: kept points, instances, error bits (GF_AUG_ERR_*), max locs (3), spatial shape (3).
+ * =================================================================================== */
+#define GF_AUG_REC 320
+#define GF_AUG_MAX_INST 4096 /* instance ids per scene: 0 .. max_inst-1 (or -100) */
+#define GF_AUG_MAX_CROP 64   /* crop candidates */
+#define GF_AUG_LUT 128       /* raw semantic labels the remap table covers */
+#define GF_AUG_STAT 10       /* per instance: count, fixed-point sums (3), min keys (3), max keys (3) */
+#define GF_AUG_HEAD 16
+enum {
+    GF_AUG_R_M = 0, GF_AUG_R_SHIFT = 9, GF_AUG_R_FLIP = 12, GF_AUG_R_THETA = 13, GF_AUG_R_AMAX0 = 14,
+    GF_AUG_R_AMAX1 = 17, GF_AUG_R_MIN = 20, GF_AUG_R_MAX = 23, GF_AUG_R_CHOSEN = 26, GF_AUG_R_ERR = 27,
+    GF_AUG_R_CAP0 = 28, GF_AUG_R_BASE0 = 29, GF_AUG_R_CAP1 = 30, GF_AUG_R_BASE1 = 31, GF_AUG_R_PCMIN = 32,
+    GF_AUG_R_PCMAX = 35, GF_AUG_R_NINST = 38, GF_AUG_R_IBASE = 39, GF_AUG_R_COUNTS = 64, GF_AUG_R_CROPU = 128
+};
+enum { GF_AUG_H_N = 0, GF_AUG_H_NINST = 1, GF_AUG_H_ERR = 2, GF_AUG_H_LMAX = 3, GF_AUG_H_SHAPE = 6 };
+enum { GF_AUG_ERR_CELLS = 1, GF_AUG_ERR_INST = 2 };
+typedef struct {
+    int B, n_raw, max_inst, pad_;
+    const double* raw;
+    const long long* raw_off;
+    long long* rec;
+    double* xyz_middle; /* [n_raw, 3] */
+    double* xyz;        /* [n_raw, 3]: scaled, distorted, then cropped */
+    float* noise[2];
+    float* work[2];
+    long long cells[2];
+    int32_t* flags;      /* [n_raw] */
+    int32_t* lab;        /* [n_raw] */
+    int32_t* inst;       /* [n_raw] */
+    int32_t* start;      /* [n_raw + 1] */
+    int32_t* cursor;     /* [n_raw] */
+    int32_t* block_sums; /* [gf_aug_scan_blocks(n_raw)] */
+    int32_t* block_off;  /* [gf_aug_scan_blocks(n_raw)] */
+    int32_t* sidx;       /* [n_raw] */
+    uint32_t* bitmap;    /* [B * max_inst / 32] */
+    int32_t* inst_map;   /* [B * max_inst] */
+    long long* inst_stats; /* [B * max_inst * GF_AUG_STAT] */
+    long long* locs;     /* [n_raw, 4] */
+    float* locs_float;   /* [n_raw, 3] */
+    double* feats;       /* [n_raw, 3] */
+    long long* labels;   /* [n_raw] */
+    long long* instance_labels; /* [n_raw] */
+    float* instance_infos;      /* [n_raw, 9] */
+    int32_t* instance_pointnum; /* [B * max_inst] */
+    int32_t* offsets;    /* [B + 1] */
+    float* pc_mins;      /* [B, 3] */
+    float* pc_maxs;      /* [B, 3] */
+    int32_t* head;       /* [GF_AUG_HEAD] */
+} GfAugBatch;
+int gf_aug_scan_blocks(int n_raw);
+/* rng="device": Philox4x32-10 draws of every scene (jitter, flip, angle -> m; colour shift; K crop offsets) into rec */
+int gf_aug_draw(const GfAugBatch* b, unsigned long long seed, long long batch_index, int K, void* stream);
+/* scenes [s0, s0+ns): xyz_middle = x @ m, xyz = xyz_middle * scale, per-scene |xyz| max (grid of elastic pass 0) */
+int gf_aug_transform(const GfAugBatch* b, int s0, int ns, double scale, int max_scene_points, void* stream);
+/* elastic pass 0 / 1 (gran, mag): fill = 1 draws the raw noise (Philox; else the caller uploaded it), six box blurs,
+ * xyz += g(xyz) * mag; pass 0 leaves the |xyz| max of pass 1's grid, pass 1 the per-scene min / max */
+int gf_aug_elastic(const GfAugBatch* b, int s0, int ns, int pass, int gran, double mag, int fill,
+                   unsigned long long seed, long long batch_index, int max_scene_points, long long max_cells,
+                   void* stream);
+/* the K crop candidates of every scene with more than max_npoint points counted in one launch; rec[CHOSEN] = the first
+ * that fits (-1: no crop) */
+int gf_aug_crop(const GfAugBatch* b, int s0, int ns, int full_scale, int K, long long max_npoint, int max_scene_points,
+                void* stream);
+/* all scenes: kept points in order, label remap (fold_classes: HOST int32[n_fold]), getCroppedInstLabel, per-instance
+ * statistics, the collate's outputs, head */
+int gf_aug_collate(const GfAugBatch* b, const int32_t* fold_classes, int n_fold, int full_scale_min, int full_scale,
+                   int max_scene_points, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
