@@ -56,6 +56,7 @@ def _declare(lib):
         "gf_dev_conv_knobs": (I, [I, I, I, I, I]),
         "gf_dev_conv_knob_flat": (I, [I, I]),
         "gf_dev_conv_knob_lw": (I, [I, I]),
+        "gf_dev_conv_plan": (I, [P, P, P, P, P, P, I, I, I, I, I, I, P, P, P, P, P, P, P, P]),
         "gf_resblock_fwd": (I, [P, P, P, P, P, P, P, I, I, I, I, I, P, P, P, P, P, P, P, P]),
         "gf_conv_wgrad": (I, [P, P, P, I, I, I, I, I, P, P]),
         "gf_conv_wgrad_masked": (I, [P, P, P, P, I, I, I, I, I, P, P]),

@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <type_traits>
+
 #include "geoformer_hip.h"
 
 #define GF_WAVE 64
@@ -67,6 +69,17 @@ int gf_rules_down2_chain_all(const int32_t* coords, int M0, int B, int X, int Y,
 bool gf_rules_level_parallel();
 
 static inline int gf_div_up(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// f(std::integral_constant<T, V>{}) for the V among Vs that equals v: a run-time launch parameter -> a template instance
+template <class T, T... Vs, class F>
+static inline void gf_with(T v, F&& f) {
+    (void)((v == Vs && (f(std::integral_constant<T, Vs>{}), true)) || ...);
+}
+
+// Allow `kernel` up to `bytes` of dynamic LDS (hipFuncAttributeMaxDynamicSharedMemorySize) on the current device, before
+// a launch with more than the default allows.  Sets the attribute once per (device, kernel); safe under concurrent
+// callers: a hipGetDevice and a short critical section per call (spconv_rules.hip).
+void gf_allow_lds(const void* kernel, int bytes);
 
 // lane i <- lane i ^ D of a 64-lane wave WITHOUT the LDS crossbar (__shfl_xor is ds_bpermute_b32: ~120 cycles of latency per
 // step, and a wave reduction is six dependent steps): v_permlane32_swap / v_permlane16_swap (gfx950) for the two steps across
@@ -145,6 +158,7 @@ __device__ __forceinline__ float gf_wave_sum(float s) {
 #define GF_FLAT_GOFF 128
 #define GF_FLAT_BINS 1024  // default number of bins: four SIMDs of 256 compute units
 #define GF_FLAT_PAD 32     // records of -1 behind the last step (the conv kernel's loads run ahead)
+#define GF_LW_WPB 12       // waves per workgroup of the LDS-weight kernel (three per SIMD)
 __host__ __device__ static inline size_t gf_flat_ppos_at(int ngroups) { return GF_FLAT_GOFF + (size_t)ngroups + 1; }
 __host__ __device__ static inline size_t gf_flat_desc_at(int ngroups) { return (GF_FLAT_GOFF + 2 * (size_t)ngroups + 1 + 63) / 64 * 64; }
 __host__ __device__ static inline size_t gf_flat_steps_at(int ngroups, int nbins) {

@@ -559,11 +559,7 @@ extern "C" int gf_decoder_cross_attn_cfg(const float* geo_ctx, const float* max_
     //  eight-wave, two-tiles-per-trip instance of the bf16 kernel measured 85-86 against 84 us: HISTORY.md 7; removed.)
     if (wg_waves == 16 && g_da_bf3 != 0) {
         const size_t lds = (size_t)DA_WPACK_BF3_U4 * sizeof(uint4);
-        static bool attr = false;
-        if (!attr) {
-            (void)hipFuncSetAttribute((const void*)k_decoder_cross_attn_bf3<DA_BF3_WAVES, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            attr = true;
-        }
+        gf_allow_lds((const void*)k_decoder_cross_attn_bf3<DA_BF3_WAVES, 1>, (int)lds);
         GF_LAUNCH_OP(GF_OP_CROSS_ATTN, (k_decoder_cross_attn_bf3<DA_BF3_WAVES, 1>), dim3(nq, B), dim3(DA_BF3_WAVES * 64), lds,
                      (hipStream_t)stream, geo_ctx, max_geo, qloc, cloc, lo, hi, gaussB, Q1, K1, Kv,
                      reinterpret_cast<const uint4*>(Wpack + DA_WPACK_F32), nq, nc, out, stat_m, stat_l);

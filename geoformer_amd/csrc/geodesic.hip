@@ -857,12 +857,7 @@ template <int THREADS>
 static void launch_bfs_lds(int nq, size_t lds, hipStream_t st, const float* D, const int32_t* I, int n, int K,
                            const int32_t* src, float radius, int max_step, float* geo, void* keys_ws, void* queue_ws,
                            int qcap) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)k_geodesic_bfs_lds<THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  BFS_LDS_BYTES);
-        attr_set = true;
-    }
+    gf_allow_lds((const void*)k_geodesic_bfs_lds<THREADS>, BFS_LDS_BYTES);
     GF_LAUNCH_OP(GF_OP_BFS, k_geodesic_bfs_lds<THREADS>, dim3(nq), dim3(THREADS), lds, st, D, I, n, K, src, radius, max_step,
                  geo, (unsigned long long*)keys_ws, (int2*)queue_ws, qcap);
 }

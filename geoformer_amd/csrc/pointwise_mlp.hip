@@ -173,11 +173,7 @@ extern "C" int gf_pointwise_mlp_rows(const float* x, const int32_t* rows, int N,
     const int ntiles = (N + 15) / 16;
     int blocks = (ntiles + 3) / 4;
     if (blocks > 256 * 8) blocks = 256 * 8;
-    static bool lds_ok = false;
-    if (!lds_ok) {
-        (void)hipFuncSetAttribute((const void*)k_pointwise_mlp, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        lds_ok = true;
-    }
+    gf_allow_lds((const void*)k_pointwise_mlp, 96 * 1024);
     hipLaunchKernelGGL(k_pointwise_mlp, dim3(blocks), dim3(256), gm_lds_bytes(A), (hipStream_t)stream, x, rows, N, A, out);
     GF_CHECK_LAUNCH("gf_pointwise_mlp");
     return GF_OK;
@@ -313,12 +309,7 @@ __global__ __launch_bounds__(256) void k_group_mlp_max(const float* __restrict__
 
 template <bool GATHER>
 static void gm_allow_lds() {
-    static bool done = false;
-    if (!done) {
-        (void)hipFuncSetAttribute((const void*)k_group_mlp_max<GATHER>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  96 * 1024);
-        done = true;
-    }
+    gf_allow_lds((const void*)k_group_mlp_max<GATHER>, 96 * 1024);
 }
 
 static int pm_fill_args(const char* who, int n_layers, const float* const* W, const float* const* scale,

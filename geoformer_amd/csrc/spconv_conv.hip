@@ -1282,29 +1282,8 @@ __global__ __launch_bounds__(64 * WPB, CONV_G16P_WAVES) void k_conv_g16p(const f
 #endif
 }
 
-template <int NCH, bool LDSW>
-static void launch_g16(dim3 grid, size_t lds, hipStream_t st, const float* in, const float4* Wp, const int4* steps,
-                       const uint32_t* gmask, int K, int M_out, unsigned in_bytes, int gpw, const float* sc,
-                       const float* sh, const float* res, const float* osc, const float* osh, float* out) {
-    if (LDSW) {
-        static bool attr = false;
-        if (!attr) {
-            (void)hipFuncSetAttribute((const void*)k_conv_g16<NCH, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-            (void)hipFuncSetAttribute((const void*)k_conv_g16<NCH, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-            (void)hipFuncSetAttribute((const void*)k_conv_g16<NCH, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-            (void)hipFuncSetAttribute((const void*)k_conv_g16<NCH, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-            attr = true;
-        }
-    }
-#define G16_LAUNCH(AFF_, RES_)                                                                                        \
-    hipLaunchKernelGGL((k_conv_g16<NCH, AFF_, RES_, LDSW>), grid, dim3(256), lds, st, in, Wp, steps, gmask, K, M_out, \
-                       in_bytes, gpw, sc, sh, res, osc, osh, out)
-    if (sc && res) G16_LAUNCH(true, true);
-    else if (sc) G16_LAUNCH(true, false);
-    else if (res) G16_LAUNCH(false, true);
-    else G16_LAUNCH(false, false);
-#undef G16_LAUNCH
-}
+// ---- which kernel a call takes: conv_plan (a pure function of the call's sizes, tables, operands, pointer alignment
+// and the dev knobs), then one launch switch in conv_fwd_impl ----
 
 // dev hook (bench.py's roofline probe): two events that the NEXT launch of the pipelined kernel on this host thread
 // binds to the kernel itself (hipExtLaunchKernelGGL: start and stop are the dispatch's own begin / end timestamps, what
@@ -1320,284 +1299,249 @@ extern "C" int gf_dev_conv_kernel_events(void* start, void* stop) {
 }
 extern "C" int gf_dev_conv_kernel_events_taken(void) { return t_kev_taken ? 1 : 0; }
 
+// Dev knobs (include/geoformer_hip_dev.h: gf_dev_conv_*): force a launch shape regardless of the level's size; -1 / 0:
+// not set.  Read by conv_plan only (and `chunks` by the rulebooks, gf_conv_chunks).
+struct ConvKnobs {
+    int split = -1, wide = -1, pair = -1;      // shapes of k_conv_os, k_conv_pair
+    int block = 0;                             // threads per workgroup of k_conv_os' one-wave-per-group shape (0: 256)
+    int g16 = -1, g16_ldsw = -1, g16_gpw = 0;  // counted-loop kernel: use / weights in LDS / groups per wave
+    int g16_pipe = -1, g16p_wpb = 0;           // its pipelined form: use / waves per workgroup (0: conv_plan's choice)
+    int flat = -1, flat_items = 0;             // flat-chain kernel: use / item bound of the size-based choice
+    int lw = -1, lw_groups = 0;                // LDS-weight kernel: use / group bound of the size-based choice
+    int chunks = GF_CONV_CHUNKS;               // equal-cost chunks the next step tables are built with
+};
+static ConvKnobs g_knobs;
+static int knob_tri(int v) { return v < 0 ? -1 : (v != 0); }
+
+extern "C" int gf_dev_conv_knobs(int split, int wide, int pair, int ldsw, int block) {
+    g_knobs.split = knob_tri(split);
+    g_knobs.wide = knob_tri(wide);
+    g_knobs.pair = knob_tri(pair);
+    (void)ldsw;  // (the LDS-weight form of k_conv_os is gone: round 6)
+    g_knobs.block = block <= 0 ? 0 : (block > 256 ? 256 : block);
+    return GF_OK;
+}
+extern "C" int gf_dev_conv_knobs_g16(int use, int ldsw, int gpw, int pipe) {
+    g_knobs.g16 = knob_tri(use);
+    g_knobs.g16_ldsw = knob_tri(ldsw);
+    g_knobs.g16_gpw = gpw > 0 ? gpw : 0;
+    g_knobs.g16_pipe = knob_tri(pipe);
+    return GF_OK;
+}
+extern "C" int gf_dev_conv_knob_flat(int use, int max_items) {
+    g_knobs.flat = knob_tri(use);
+    g_knobs.flat_items = max_items > 0 ? max_items : 0;
+    return GF_OK;
+}
+extern "C" int gf_dev_conv_knob_lw(int use, int min_groups) {
+    g_knobs.lw = knob_tri(use);
+    g_knobs.lw_groups = min_groups > 0 ? min_groups : 0;
+    return GF_OK;
+}
 // waves per workgroup of the pipelined kernel.  12 = ONE workgroup per compute unit with the default 3072 chunks (256
 // workgroups, the kernel's 133-148 VGPRs allow three waves per SIMD): the 27 KiB of packed weights are staged once per
 // compute unit instead of three times.  Measured on the S150k level-1 launch (tools/conv_wpb_exp.py, back-to-back
 // launches): residual epilogue 18.95 -> 17.32 us, activation epilogue 18.62 -> 18.23; 8 or 16 waves leave compute units
 // with a second round (23-25 us).  0 = 12 when the table's chunk count is a multiple of 12, else 4.
-static int g_g16p_wpb = 0;
 extern "C" int gf_dev_conv_g16p_wpb(int wpb) {
     GF_CHECK_ARG(wpb == 0 || wpb == 4 || wpb == 8 || wpb == 12 || wpb == 16, "gf_dev_conv_g16p_wpb: %d (4, 8, 12 or 16)", wpb);
-    g_g16p_wpb = wpb;
+    g_knobs.g16p_wpb = wpb;
     return GF_OK;
 }
-
-template <int NCH, bool LDSW, int WPB>
-static void launch_g16p_w(size_t lds, hipStream_t st, const float* in, const float4* Wp, const int32_t* steps,
-                          const uint32_t* gmask, int K, int M_out, int ld, unsigned in_bytes, const float* sc,
-                          const float* sh, const float* res, const float* osc, const float* osh, float* out,
-                          float* out2) {
-    if (LDSW) {
-        static bool attr = false;
-        if (!attr) {
-            (void)hipFuncSetAttribute((const void*)k_conv_g16p<NCH, false, false, true, WPB>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-            (void)hipFuncSetAttribute((const void*)k_conv_g16p<NCH, false, true, true, WPB>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-            (void)hipFuncSetAttribute((const void*)k_conv_g16p<NCH, true, false, true, WPB>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-            (void)hipFuncSetAttribute((const void*)k_conv_g16p<NCH, true, true, true, WPB>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-            attr = true;
-        }
-    }
-    const size_t step_words = (size_t)(ld / 16) * GF_STEP_BLKS * 64;
-    const int32_t* chunks = steps + step_words + 1;  // [-1] = number of chunks the table was built with
-    const unsigned steps_bytes = (unsigned)(step_words * 4);
-    dim3 grid((GF_CONV_CHUNKS_MAX + WPB - 1) / WPB);  // waves of chunks past the table's count leave at once
-#define G16P_LAUNCH(AFF_, RES_)                                                                                       \
-    do {                                                                                                              \
-        if (t_kev_start) {                                                                                            \
-            hipExtLaunchKernelGGL((k_conv_g16p<NCH, AFF_, RES_, LDSW, WPB>), grid, dim3(64 * WPB), (std::uint32_t)lds, st, \
-                                  t_kev_start, t_kev_stop, 0u, in, Wp, steps, gmask, chunks, K, M_out, in_bytes,      \
-                                  steps_bytes, sc, sh, res, osc, osh, out, out2);                                     \
-            t_kev_start = t_kev_stop = nullptr;                                                                       \
-            t_kev_taken = true;                                                                                       \
-        } else {                                                                                                      \
-            hipLaunchKernelGGL((k_conv_g16p<NCH, AFF_, RES_, LDSW, WPB>), grid, dim3(64 * WPB), lds, st, in, Wp, steps, gmask,  \
-                               chunks, K, M_out, in_bytes, steps_bytes, sc, sh, res, osc, osh, out, out2);            \
-        }                                                                                                             \
-    } while (0)
-    if (sc && res) G16P_LAUNCH(true, true);
-    else if (sc) G16P_LAUNCH(true, false);
-    else if (res) G16P_LAUNCH(false, true);
-    else G16P_LAUNCH(false, false);
-#undef G16P_LAUNCH
-}
-
-template <int NCH, bool LDSW>
-static void launch_g16p(size_t lds, hipStream_t st, const float* in, const float4* Wp, const int32_t* steps,
-                        const uint32_t* gmask, int K, int M_out, int ld, unsigned in_bytes, const float* sc,
-                        const float* sh, const float* res, const float* osc, const float* osh, float* out,
-                        float* out2) {
-#define G16P_W(W_) launch_g16p_w<NCH, LDSW, W_>(lds, st, in, Wp, steps, gmask, K, M_out, ld, in_bytes, sc, sh, res, osc, osh, out, out2)
-    // (S150k level 1, back-to-back launches: residual epilogue 18.4 -> 17.0 us, activation epilogue 17.9 -> 17.4 us)
-    // (the 32 -> 16 launch, NCH = 2, keeps four waves: 55.7 us against 59.9 us with twelve)
-    const int wpb = g_g16p_wpb ? g_g16p_wpb : (NCH == 1 && gf_conv_chunks() % 12 == 0 ? 12 : 4);
-    switch (wpb) {
-        case 8: G16P_W(8); break;
-        case 12: G16P_W(12); break;
-        case 16: G16P_W(16); break;
-        default: G16P_W(4); break;
-    }
-#undef G16P_W
-}
-
-struct ConvArgs {
-    const float* in;
-    const float4* Wp;
-    const int32_t* nbr;
-    const uint32_t* gmask;
-    int K, M_out, ld, Cin, Cout, NCH, NCB, nsplit;
-    unsigned in_bytes;
-    const float *sc, *sh, *res, *osc, *osh;
-    float* out;
-};
-
-static int g_conv_block = 256;
-static int g_conv_chunks = GF_CONV_CHUNKS;
-int gf_conv_chunks() { return g_conv_chunks; }
 extern "C" int gf_dev_conv_chunks(int n) {
     if (n <= 0) n = GF_CONV_CHUNKS;
     GF_CHECK_ARG(n % 4 == 0 && n <= GF_CONV_CHUNKS_MAX, "gf_dev_conv_chunks: %d (multiple of 4, at most %d)", n, GF_CONV_CHUNKS_MAX);
-    g_conv_chunks = n;
+    g_knobs.chunks = n;
     return GF_OK;
 }
-template <int NCBW, int SW>
-static void launch_conv(bool vec, dim3 grid, hipStream_t st, const ConvArgs& a) {
-    const int bs = SW ? SW * 64 : g_conv_block;
-    if (vec)
-        hipLaunchKernelGGL((k_conv_os<NCBW, SW, true>), grid, dim3(bs), 0, st, a.in, a.Wp, a.nbr, a.gmask, a.K,
-                           a.M_out, a.ld, a.Cin, a.Cout, a.NCH, a.NCB, a.nsplit, a.in_bytes, a.sc, a.sh, a.res, a.osc, a.osh, a.out);
-    else
-        hipLaunchKernelGGL((k_conv_os<NCBW, SW, false>), grid, dim3(bs), 0, st, a.in, a.Wp, a.nbr, a.gmask, a.K,
-                           a.M_out, a.ld, a.Cin, a.Cout, a.NCH, a.NCB, a.nsplit, a.in_bytes, a.sc, a.sh, a.res, a.osc, a.osh, a.out);
-}
+int gf_conv_chunks() { return g_knobs.chunks; }
 
-template <int SW>
-static void dispatch_conv(int ncbw, bool vec, dim3 grid, hipStream_t st, const ConvArgs& a) {
-    switch (ncbw) {
-        case 1: launch_conv<1, SW>(vec, grid, st, a); break;
-        case 2: launch_conv<2, SW>(vec, grid, st, a); break;
-        case 3: launch_conv<3, SW>(vec, grid, st, a); break;
-        case 4: launch_conv<4, SW>(vec, grid, st, a); break;
-        case 5: launch_conv<5, SW>(vec, grid, st, a); break;
-        case 6: launch_conv<6, SW>(vec, grid, st, a); break;
-        case 7: launch_conv<7, SW>(vec, grid, st, a); break;
-        default: launch_conv<8, SW>(vec, grid, st, a); break;
-    }
-}
-
-// Dev knobs (include/geoformer_hip_dev.h: gf_dev_conv_knobs*): force a launch shape regardless of the level's size.
-struct ConvKnobs {
-    int split = -1, wide = -1, block = 0, pair = -1;  // -1 / 0: not set
-    int g16 = -1, g16_ldsw = -1, g16_gpw = 0;         // counted-loop kernel: use / weights in LDS / groups per wave
-    int g16_pipe = -1;                                // its pipelined form (one chunk of groups per wave)
-    int flat = -1, flat_items = 0;                    // flat-chain kernel: use / item bound of the size-based choice
+// What the planner sees of a (validated) call: sizes, the tables and operands given, 16-byte alignment of the pointers
+// (in_scale and in_shift together; an absent operand counts as aligned).  out_scale / out_shift are aligned whenever
+// given (conv_fwd_impl's argument check).
+struct ConvQuery {
+    int K, M_in, M_out, ld, Cin, Cout;
+    bool nbr = false, gmask = false, steps = false, flat = false;  // [K,ld] table, group masks, step table, flat step table
+    bool prologue = false, residual = false, out2 = false;          // in_scale / in_shift, residual, second output
+    bool in16 = true, sc16 = true, out16 = true, res16 = true, out2_16 = true;
 };
-static ConvKnobs& conv_knobs_mut() {
-    static ConvKnobs k;
-    return k;
-}
-static const ConvKnobs& conv_knobs() { return conv_knobs_mut(); }
 
-// Dev hook (include/geoformer_hip_dev.h): force a launch shape regardless of the level's size; -1 = size-based.
-extern "C" int gf_dev_conv_knobs_g16(int use, int ldsw, int gpw, int pipe) {
-    ConvKnobs& k = conv_knobs_mut();
-    k.g16_pipe = pipe < 0 ? -1 : (pipe != 0);
-    k.g16 = use < 0 ? -1 : (use != 0);
-    k.g16_ldsw = ldsw < 0 ? -1 : (ldsw != 0);
-    k.g16_gpw = gpw > 0 ? gpw : 0;
-    return GF_OK;
+enum { CONV_NONE, CONV_LW, CONV_FLAT, CONV_G16P, CONV_G16, CONV_PAIR, CONV_OS };
+// A launch: the kernel family, its template parameters, grid, block and dynamic LDS bytes (gf_dev_conv_plan's desc), or
+// the call's argument error.  NONE: nothing to launch (no output rows).  p[] by family:
+//   LW    passes, input chunks of the first / last pass, NCB, WPB, AFF  k_conv_lw<27, n, NCB, D, AFF, WPB> per pass
+//   FLAT  MAXB                                                          k_conv_flat<MAXB>
+//   G16P  NCH, LDSW, WPB, AFF, RES                                      k_conv_g16p<NCH, AFF, RES, LDSW, WPB>
+//   G16   NCH, LDSW, groups per wave, AFF, RES                          k_conv_g16<NCH, AFF, RES, LDSW>
+//   PAIR  AFF                                                           k_conv_pair<AFF>
+//   OS    NCBW, SW, VEC                                                 k_conv_os<NCBW, SW, VEC>
+struct ConvPlan {
+    int family = CONV_NONE;
+    int p[6] = {};
+    unsigned grid = 0, block = 0, lds = 0;
+    const char* err = nullptr;
+};
+static ConvPlan conv_error(const char* err) {
+    ConvPlan P;
+    P.err = err;
+    return P;
 }
-extern "C" int gf_dev_conv_knob_flat(int use, int max_items) {
-    ConvKnobs& k = conv_knobs_mut();
-    k.flat = use < 0 ? -1 : (use != 0);
-    k.flat_items = max_items > 0 ? max_items : 0;
-    return GF_OK;
-}
-extern "C" int gf_dev_conv_knobs(int split, int wide, int pair, int ldsw, int block) {
-    ConvKnobs& k = conv_knobs_mut();
-    k.split = split < 0 ? -1 : (split != 0);
-    k.wide = wide < 0 ? -1 : (wide != 0);
-    k.pair = pair < 0 ? -1 : (pair != 0);
-    (void)ldsw;  // (the LDS-weight form of k_conv_os is gone: round 6)
-    k.block = block <= 0 ? 0 : (block > 256 ? 256 : block);
-    g_conv_block = k.block > 0 ? k.block : 256;
-    return GF_OK;
+
+static ConvPlan conv_plan(const ConvQuery& q) {
+    const ConvKnobs& kn = g_knobs;
+    if (q.M_out <= 0) return ConvPlan{};
+    const int K = q.K, ngroups = (q.M_out + 15) / 16;
+    const int ncb = (q.Cout + 15) / 16, nch = (q.Cin + 15) / 16;
+    const unsigned long long in_bytes = (unsigned long long)q.M_in * q.Cin * 4ull;
+    const bool vec = (q.Cin % 16) == 0 && q.in16 && in_bytes < 0xfffffff0ull && (!q.prologue || q.sc16);
+    // Big levels: one wave per 16-row group owning every column block.  Small levels (not enough groups to fill 1024
+    // SIMDs with several waves each): a workgroup per (group, <=2 column blocks), steps split over its four waves.
+    const bool split = kn.split >= 0 ? kn.split != 0 : ngroups < 6000;
+    // tiny levels (<= 256 workgroups of 16 waves, all resident at once): 16 waves share an item, each wave's chain
+    // of gather batches is 4x shorter again (S150k levels 5-7: 13.5/15.8/16.0 -> 10.6/11.4/11.5 us)
+    const bool wide = split && (kn.wide >= 0 ? kn.wide != 0 : (long long)ngroups * ncb <= 256);
+    // the flat-chain kernel wherever the wide shape would go (every address known at launch: k_conv_flat)
+    const bool flat = vec && nch <= 16 && K * nch <= 16 * FLAT_PF * FLAT_MAXB &&
+                      (kn.flat >= 0 ? kn.flat != 0 : split && (long long)ngroups * ncb <= (kn.flat_items > 0 ? kn.flat_items : 256));
+    // counted-loop kernel over the step table: 16 output channels, one or two input chunks
+    const bool g16 = q.steps && q.gmask && vec && q.Cout == 16 && nch <= 2 && q.out16 && q.res16 && in_bytes <= 0xffffff00ull &&
+                     (kn.g16 >= 0 ? kn.g16 != 0 : !split);
+    // LDS-weight kernel over the flat step table (spconv_lw.hip), where the caller built one: 27 offsets, 16-channel
+    // multiples, passes of one or two input chunks over one or two column blocks
+    if (q.flat && q.gmask && kn.lw != 0 && vec && q.out16 && q.res16 && q.out2_16 && K == 27 && (q.Cout % 16) == 0) {
+        const int npass = (nch + 1) / 2, n0 = (nch + npass - 1) / npass;  // (every pass: one or two chunks, n0 the most)
+        // measured on S150k (tools/conv_lw_exp.py, profiles/r6_conv_lw_notes.md): 32 -> 32 21.8 against 27.1 us, 32 -> 16
+        // 30.2 against 46.6; 16 -> 16 equal to k_conv_g16p (17.7 / 17.9), two passes (64 -> 32) slower than k_conv_os (49 / 44)
+        const bool pays = npass == 1 && nch == 2 && ngroups >= (kn.lw_groups > 0 ? kn.lw_groups : 1500);
+        // 24-bit row multiply; an absent row's offset 0xFFFFFF * row_bytes (mod 2^32) >= 2^30 - row_bytes must lie beyond
+        // the buffer.  A wave keeps its groups' descriptors one per lane.
+        if (ncb <= 2 && q.M_in < (1 << 24) && in_bytes <= (1ull << 30) - 4096ull && ngroups <= 64 * 3 * GF_FLAT_BINS &&
+            (kn.lw == 1 || pays))
+            return ConvPlan{CONV_LW, {npass, n0, nch - n0 * (npass - 1), ncb, GF_LW_WPB, q.prologue}, GF_FLAT_BINS / 4,
+                            64 * GF_LW_WPB, (unsigned)(K * n0 * ncb * 1024)};
+    }
+    if (flat && (q.nbr || K == 1) && !q.out2)
+        return ConvPlan{CONV_FLAT, {K * nch <= 16 * FLAT_PF * FLAT_MAXB_SMALL ? FLAT_MAXB_SMALL : FLAT_MAXB},
+                        (unsigned)((long long)ngroups * ncb), 1024, 0};
+    const size_t wbytes = (size_t)K * nch * ncb * 1024;
+    if (g16) {
+        const bool gl = wbytes <= 64 * 1024 && kn.g16_ldsw != 0;
+        const unsigned lds = gl ? (unsigned)wbytes : 0;
+        if ((size_t)(q.ld / 16) * GF_STEP_BLKS * 256 < 0xfffff000ull && q.ld >= q.M_out && kn.g16_pipe != 0) {
+            // (S150k level 1, back-to-back launches: residual epilogue 18.4 -> 17.0 us, activation epilogue 17.9 -> 17.4 us)
+            // (the 32 -> 16 launch, NCH = 2, keeps four waves: 55.7 us against 59.9 us with twelve)
+            const int wpb = kn.g16p_wpb ? kn.g16p_wpb : (nch == 1 && kn.chunks % 12 == 0 ? 12 : 4);
+            // (waves of chunks past the table's count leave at once)
+            return ConvPlan{CONV_G16P, {nch, gl, wpb, q.prologue, q.residual}, (unsigned)((GF_CONV_CHUNKS_MAX + wpb - 1) / wpb),
+                            (unsigned)(64 * wpb), lds};
+        }
+        if (q.out2) return conv_error("gf_conv_fwd_dual: this launch shape has no second output");
+        const int gpw = kn.g16_gpw > 0 ? kn.g16_gpw : (gl ? 2 : 1);
+        return ConvPlan{CONV_G16, {nch, gl, gpw, q.prologue, q.residual}, (unsigned)(((long long)ngroups + 4 * gpw - 1) / (4 * gpw)),
+                        256, lds};
+    }
+    if (q.out2) return conv_error("gf_conv_fwd_dual: this launch shape has no second output");
+    if (!q.nbr && K != 1) return conv_error("gf_conv_fwd: this launch shape needs the [K,ld] neighbour table");
+    if (!split && vec && ncb == 1 && q.nbr && nch <= 8 && in_bytes <= 0xfffff000ull - 4096ull && kn.pair != 0)
+        return ConvPlan{CONV_PAIR, {q.prologue}, (unsigned)std::min(((long long)(ngroups + 1) / 2 + 3) / 4, 256ll * 64), 256, 0};
+    const int ncbw = split ? (!wide && ncb >= 2 && ngroups >= 2048 ? 2 : 1) : std::min(ncb, 8);
+    const int sw = wide ? 16 : split ? 4 : 0;  // waves sharing an item (0: one wave per item, `block` threads per workgroup)
+    const int block = sw ? 64 * sw : (kn.block > 0 ? kn.block : 256);
+    const long long nitems = (long long)ngroups * ((ncb + ncbw - 1) / ncbw);
+    const long long blocks = split ? nitems : (nitems + block / 64 - 1) / (block / 64);
+    return ConvPlan{CONV_OS, {ncbw, sw, vec}, (unsigned)std::min(blocks, 256ll * 64), (unsigned)block, 0};
 }
 
 static int conv_fwd_impl(const float* in, const float* Wp, const int32_t* nbr, const uint32_t* gmask,
                          const int32_t* steps, const int32_t* fsteps, int K, int M_in, int M_out, int ld, int Cin, int Cout,
-                         const float* in_scale, const float* in_shift, const float* residual,
-                         const float* out_scale, const float* out_shift, float* out, float* out2, void* stream) {
+                         const float* sc, const float* sh, const float* res, const float* osc, const float* osh, float* out,
+                         float* out2, void* stream, int* desc = nullptr) {
     GF_CHECK_ARG(K >= 1 && K <= 32, "gf_conv_fwd: K=%d out of range [1,32]", K);
     GF_CHECK_ARG(Cin >= 1 && Cout >= 1, "gf_conv_fwd: Cin=%d Cout=%d", Cin, Cout);
-    GF_CHECK_ARG(in_scale == nullptr || Cin <= CONV_MAX_CIN - 16, "gf_conv_fwd: fused prologue supports Cin <= %d",
-                 CONV_MAX_CIN - 16);
+    GF_CHECK_ARG(sc == nullptr || Cin <= CONV_MAX_CIN - 16, "gf_conv_fwd: fused prologue supports Cin <= %d", CONV_MAX_CIN - 16);
     GF_CHECK_ARG(nbr != nullptr || steps != nullptr || K == 1, "gf_conv_fwd: no table requires K==1");
-    GF_CHECK_ARG((in_scale == nullptr) == (in_shift == nullptr), "gf_conv_fwd: in_scale/in_shift must come together");
-    GF_CHECK_ARG((out_scale == nullptr) == (out_shift == nullptr), "gf_conv_fwd: out_scale/out_shift must come together");
-    GF_CHECK_ARG(out_scale == nullptr || ((((uintptr_t)out_scale) | ((uintptr_t)out_shift)) % 16) == 0,
+    GF_CHECK_ARG((sc == nullptr) == (sh == nullptr), "gf_conv_fwd: in_scale/in_shift must come together");
+    GF_CHECK_ARG((osc == nullptr) == (osh == nullptr), "gf_conv_fwd: out_scale/out_shift must come together");
+    GF_CHECK_ARG(osc == nullptr || ((((uintptr_t)osc) | ((uintptr_t)osh)) % 16) == 0,
                  "gf_conv_fwd: out_scale/out_shift must be 16-byte aligned");
-    if (M_out <= 0) return GF_OK;
-    const int ngroups = (M_out + 15) / 16;
-    const int ncb = (Cout + 15) / 16, nch = (Cin + 15) / 16;
+    GF_CHECK_ARG(out2 == nullptr || (osc != nullptr && ((uintptr_t)out2 % 16) == 0),
+                 "gf_conv_fwd: the second output needs its scale / shift and 16-byte alignment");
+    const auto a16 = [](const void* p) { return ((uintptr_t)p % 16) == 0; };
+    ConvQuery q{K, M_in, M_out, ld, Cin, Cout};
+    q.nbr = nbr, q.gmask = gmask, q.steps = steps, q.flat = fsteps;
+    q.prologue = sc, q.residual = res, q.out2 = out2;
+    q.in16 = a16(in), q.sc16 = a16((const void*)((uintptr_t)sc | (uintptr_t)sh)), q.out16 = a16(out), q.res16 = a16(res);
+    q.out2_16 = a16(out2);
+    const ConvPlan P = conv_plan(q);
+    GF_CHECK_ARG(P.err == nullptr, "%s", P.err);
+    if (desc) {
+        const int d[10] = {P.family, P.p[0], P.p[1], P.p[2], P.p[3], P.p[4], P.p[5], (int)P.grid, (int)P.block, (int)P.lds};
+        for (int i = 0; i < 10; i++) desc[i] = d[i];
+        return GF_OK;
+    }
+    const hipStream_t st = (hipStream_t)stream;
+    const float4* W4 = reinterpret_cast<const float4*>(Wp);
+    const int nch = (Cin + 15) / 16, ncb = (Cout + 15) / 16;
     const unsigned long long in_bytes64 = (unsigned long long)M_in * Cin * 4ull;
-    const bool vec = (Cin % 16) == 0 && (((uintptr_t)in) % 16) == 0 && in_bytes64 < 0xfffffff0ull &&
-                     (in_scale == nullptr || ((((uintptr_t)in_scale) | ((uintptr_t)in_shift)) % 16) == 0);
-    // Big levels: one wave per 16-row group owning every column block.  Small levels (not enough groups
-    // to fill 1024 SIMDs with several waves each): a workgroup per (group, <=2 column blocks), steps split
-    // over its four waves.
-    bool split = ngroups < 6000;
-    const ConvKnobs& knobs = conv_knobs();
-    if (knobs.split >= 0) split = knobs.split != 0;
-    // tiny levels (all items resident at once with room to spare): 16 waves per item, 4x shorter chains again
-    // tiny levels (<= 256 workgroups of 16 waves, all resident at once): 16 waves share an item, each wave's chain
-    // of gather batches is 4x shorter again (S150k levels 5-7: 13.5/15.8/16.0 -> 10.6/11.4/11.5 us)
-    bool wide = split && (long long)ngroups * ncb <= 256;
-    if (knobs.wide >= 0) wide = split && knobs.wide != 0;
-    // the flat-chain kernel wherever the wide shape would go (every address known at launch: k_conv_flat)
-    const bool flat_ok = vec && nch <= 16 && K * nch <= 16 * FLAT_PF * FLAT_MAXB && in_bytes64 < 0xfffffff0ull;
-    bool flat = flat_ok && (knobs.flat < 0 ? (split && (long long)ngroups * ncb <= (knobs.flat_items > 0 ? knobs.flat_items : 256))
-                                           : knobs.flat != 0);
-    const int ncbw = split ? (!wide && ncb >= 2 && ngroups >= 2048 ? 2 : 1) : (ncb > 8 ? 8 : ncb);
-    const int nsplit = (ncb + ncbw - 1) / ncbw;
-    const long long nitems = (long long)ngroups * nsplit;
-    if (knobs.block > 0) g_conv_block = knobs.block;
-    const int wpb = g_conv_block / 64;
-    long long blocks = split ? nitems : (nitems + wpb - 1) / wpb;
-    if (blocks > 256 * 64) blocks = 256 * 64;
-    ConvArgs a{in, reinterpret_cast<const float4*>(Wp), nbr, gmask, K, M_out, ld, Cin, Cout, nch, ncb, nsplit,
-               (unsigned)(in_bytes64 < 0xfffffff0ull ? in_bytes64 : 0), in_scale, in_shift, residual, out_scale, out_shift, out};
-    dim3 grid((unsigned)blocks);
-    hipStream_t st = (hipStream_t)stream;
-    const size_t wbytes = (size_t)K * nch * ncb * 1024;
-    // counted-loop kernel over the step table: 16 output channels, one or two input chunks
-    bool g16 = steps != nullptr && gmask != nullptr && vec && Cout == 16 && nch <= 2 && (((uintptr_t)out) % 16) == 0 &&
-               (residual == nullptr || (((uintptr_t)residual) % 16) == 0) && in_bytes64 <= 0xffffff00ull;
-    if (knobs.g16 >= 0) g16 = g16 && knobs.g16 != 0;
-    else g16 = g16 && !split;
-    // LDS-weight kernel over the flat step table (spconv_lw.hip), where the caller built one
-    if (fsteps != nullptr && gmask != nullptr) {
-        int forced = 0;
-        const bool aligned = vec && (((uintptr_t)out) % 16) == 0 && (residual == nullptr || (((uintptr_t)residual) % 16) == 0) &&
-                             (out2 == nullptr || (((uintptr_t)out2) % 16) == 0) &&
-                             (out_scale == nullptr || ((((uintptr_t)out_scale) | ((uintptr_t)out_shift)) % 16) == 0);
-        if (gf_conv_lw_supported(K, M_in, M_out, Cin, Cout, aligned, &forced) && (forced || !(g16 && nch == 1)))
-            return gf_conv_lw(in, Wp, gmask, fsteps, K, M_in, M_out, Cin, Cout, in_scale, in_shift, residual, out_scale, out_shift,
-                              out, out2, st);
-    }
-    if (flat && (nbr != nullptr || K == 1) && out2 == nullptr) {
-        if (K * nch <= 16 * FLAT_PF * FLAT_MAXB_SMALL)
-            hipLaunchKernelGGL(k_conv_flat<FLAT_MAXB_SMALL>, dim3((unsigned)((long long)ngroups * ncb)), dim3(1024), 0, st, a.in,
-                               a.Wp, a.nbr, a.K, a.M_out, a.ld, a.Cin, a.Cout, a.NCH, a.NCB, a.in_bytes, a.sc, a.sh, a.res, a.osc,
-                               a.osh, a.out);
-        else
-            hipLaunchKernelGGL(k_conv_flat<FLAT_MAXB>, dim3((unsigned)((long long)ngroups * ncb)), dim3(1024), 0, st, a.in, a.Wp,
-                               a.nbr, a.K, a.M_out, a.ld, a.Cin, a.Cout, a.NCH, a.NCB, a.in_bytes, a.sc, a.sh, a.res, a.osc, a.osh,
-                               a.out);
-        GF_CHECK_LAUNCH("gf_conv_fwd");
-        return GF_OK;
-    }
-    if (g16) {
-        bool gl = wbytes <= 64 * 1024;
-        if (knobs.g16_ldsw >= 0) gl = gl && knobs.g16_ldsw != 0;
-        const size_t step_bytes64 = (size_t)(ld / 16) * GF_STEP_BLKS * 256;
-        bool pipe = step_bytes64 < 0xfffff000ull && M_out > 0 && ld >= M_out;
-        if (knobs.g16_pipe >= 0) pipe = pipe && knobs.g16_pipe != 0;
-        if (pipe) {
-            if (nch == 1) {
-                if (gl) launch_g16p<1, true>(wbytes, st, a.in, a.Wp, steps, gmask, K, M_out, ld, a.in_bytes, a.sc, a.sh, a.res, a.osc, a.osh, out, out2);
-                else launch_g16p<1, false>(0, st, a.in, a.Wp, steps, gmask, K, M_out, ld, a.in_bytes, a.sc, a.sh, a.res, a.osc, a.osh, out, out2);
-            } else {
-                if (gl) launch_g16p<2, true>(wbytes, st, a.in, a.Wp, steps, gmask, K, M_out, ld, a.in_bytes, a.sc, a.sh, a.res, a.osc, a.osh, out, out2);
-                else launch_g16p<2, false>(0, st, a.in, a.Wp, steps, gmask, K, M_out, ld, a.in_bytes, a.sc, a.sh, a.res, a.osc, a.osh, out, out2);
-            }
-            GF_CHECK_LAUNCH("gf_conv_fwd");
-            return GF_OK;
+    const unsigned in_bytes = (unsigned)(in_bytes64 < 0xfffffff0ull ? in_bytes64 : 0);
+    const dim3 grid(P.grid), block(P.block);
+    const int* p = P.p;
+    switch (P.family) {
+        case CONV_NONE: return GF_OK;
+        case CONV_LW: return gf_conv_lw(in, Wp, gmask, fsteps, K, M_in, M_out, Cin, Cout, sc, sh, res, osc, osh, out, out2, st);
+        case CONV_FLAT:
+            gf_with<int, FLAT_MAXB_SMALL, FLAT_MAXB>(p[0], [&](auto maxb) {
+                hipLaunchKernelGGL(k_conv_flat<maxb>, grid, block, 0, st, in, W4, nbr, K, M_out, ld, Cin, Cout, nch, ncb, in_bytes,
+                                   sc, sh, res, osc, osh, out);
+            });
+            break;
+        case CONV_G16P: {
+            const size_t step_words = (size_t)(ld / 16) * GF_STEP_BLKS * 64;
+            const int32_t* chunks = steps + step_words + 1;  // [-1] = number of chunks the table was built with
+            const unsigned steps_bytes = (unsigned)(step_words * 4);
+            gf_with<int, 1, 2>(p[0], [&](auto NCH) { gf_with<bool, false, true>(p[1], [&](auto LDSW) {
+            gf_with<int, 4, 8, 12, 16>(p[2], [&](auto WPB) { gf_with<bool, false, true>(p[3], [&](auto AFF) {
+            gf_with<bool, false, true>(p[4], [&](auto RES) {
+                if (LDSW) gf_allow_lds((const void*)k_conv_g16p<NCH, AFF, RES, LDSW, WPB>, 64 * 1024);
+                if (t_kev_start) {
+                    hipExtLaunchKernelGGL((k_conv_g16p<NCH, AFF, RES, LDSW, WPB>), grid, block, P.lds, st, t_kev_start, t_kev_stop, 0u,
+                                          in, W4, steps, gmask, chunks, K, M_out, in_bytes, steps_bytes, sc, sh, res, osc, osh, out, out2);
+                    t_kev_start = t_kev_stop = nullptr;
+                    t_kev_taken = true;
+                } else {
+                    hipLaunchKernelGGL((k_conv_g16p<NCH, AFF, RES, LDSW, WPB>), grid, block, P.lds, st, in, W4, steps, gmask, chunks,
+                                       K, M_out, in_bytes, steps_bytes, sc, sh, res, osc, osh, out, out2);
+                }
+            }); }); }); }); });
+            break;
         }
-        GF_CHECK_ARG(out2 == nullptr, "gf_conv_fwd_dual: this launch shape has no second output");
-        int gpw = knobs.g16_gpw > 0 ? knobs.g16_gpw : (gl ? 2 : 1);
-        const long long wgs = ((long long)ngroups + 4 * gpw - 1) / (4 * gpw);
-        dim3 gg((unsigned)wgs);
-        const int4* st4 = reinterpret_cast<const int4*>(steps);
-        if (nch == 1) {
-            if (gl) launch_g16<1, true>(gg, wbytes, st, a.in, a.Wp, st4, gmask, K, M_out, a.in_bytes, gpw, a.sc, a.sh, a.res, a.osc, a.osh, out);
-            else launch_g16<1, false>(gg, 0, st, a.in, a.Wp, st4, gmask, K, M_out, a.in_bytes, gpw, a.sc, a.sh, a.res, a.osc, a.osh, out);
-        } else {
-            if (gl) launch_g16<2, true>(gg, wbytes, st, a.in, a.Wp, st4, gmask, K, M_out, a.in_bytes, gpw, a.sc, a.sh, a.res, a.osc, a.osh, out);
-            else launch_g16<2, false>(gg, 0, st, a.in, a.Wp, st4, gmask, K, M_out, a.in_bytes, gpw, a.sc, a.sh, a.res, a.osc, a.osh, out);
+        case CONV_G16:
+            gf_with<int, 1, 2>(p[0], [&](auto NCH) { gf_with<bool, false, true>(p[1], [&](auto LDSW) {
+            gf_with<bool, false, true>(p[3], [&](auto AFF) { gf_with<bool, false, true>(p[4], [&](auto RES) {
+                if (LDSW) gf_allow_lds((const void*)k_conv_g16<NCH, AFF, RES, LDSW>, 64 * 1024);
+                hipLaunchKernelGGL((k_conv_g16<NCH, AFF, RES, LDSW>), grid, block, P.lds, st, in, W4,
+                                   reinterpret_cast<const int4*>(steps), gmask, K, M_out, in_bytes, p[2], sc, sh, res, osc, osh, out);
+            }); }); }); });
+            break;
+        case CONV_PAIR:
+            gf_with<bool, false, true>(p[0], [&](auto AFF) {
+                hipLaunchKernelGGL(k_conv_pair<AFF>, grid, block, 0, st, in, W4, nbr, gmask, K, M_out, ld, Cin, Cout, nch, in_bytes,
+                                   sc, sh, res, osc, osh, out);
+            });
+            break;
+        case CONV_OS: {
+            const int nsplit = (ncb + p[0] - 1) / p[0];
+            const auto os = [&](auto NCBW, auto SW) {
+                gf_with<bool, false, true>(p[2], [&](auto VEC) {
+                    hipLaunchKernelGGL((k_conv_os<NCBW, SW, VEC>), grid, block, 0, st, in, W4, nbr, gmask, K, M_out, ld, Cin, Cout,
+                                       nch, ncb, nsplit, in_bytes, sc, sh, res, osc, osh, out);
+                });
+            };
+            if (p[1] == 16) os(std::integral_constant<int, 1>{}, std::integral_constant<int, 16>{});
+            else gf_with<int, 0, 4>(p[1], [&](auto SW) { gf_with<int, 1, 2, 3, 4, 5, 6, 7, 8>(p[0], [&](auto NCBW) { os(NCBW, SW); }); });
+            break;
         }
-        GF_CHECK_LAUNCH("gf_conv_fwd");
-        return GF_OK;
     }
-    GF_CHECK_ARG(out2 == nullptr, "gf_conv_fwd_dual: this launch shape has no second output");
-    GF_CHECK_ARG(nbr != nullptr || K == 1, "gf_conv_fwd: this launch shape needs the [K,ld] neighbour table");
-    bool pair = !split && vec && ncb == 1 && nbr != nullptr && K <= 32 && nch <= 8 && in_bytes64 <= 0xfffff000ull - 4096ull;
-    if (knobs.pair >= 0) pair = pair && knobs.pair != 0;
-    if (pair) {
-        const long long npairs = (ngroups + 1) / 2;
-        long long pb = (npairs + 3) / 4;
-        if (pb > 256 * 64) pb = 256 * 64;
-        if (a.sc)
-            hipLaunchKernelGGL(k_conv_pair<true>, dim3((unsigned)pb), dim3(256), 0, st, a.in, a.Wp, a.nbr, a.gmask, a.K,
-                               a.M_out, a.ld, a.Cin, a.Cout, a.NCH, a.in_bytes, a.sc, a.sh, a.res, a.osc, a.osh, a.out);
-        else
-            hipLaunchKernelGGL(k_conv_pair<false>, dim3((unsigned)pb), dim3(256), 0, st, a.in, a.Wp, a.nbr, a.gmask, a.K,
-                               a.M_out, a.ld, a.Cin, a.Cout, a.NCH, a.in_bytes, a.sc, a.sh, a.res, a.osc, a.osh, a.out);
-    } else if (split && wide)
-        launch_conv<1, 16>(vec, grid, st, a);
-    else if (split)
-        dispatch_conv<4>(ncbw, vec, grid, st, a);
-    else
-        dispatch_conv<0>(ncbw, vec, grid, st, a);
     GF_CHECK_LAUNCH("gf_conv_fwd");
     return GF_OK;
 }
@@ -1617,24 +1561,39 @@ extern "C" int gf_conv_fwd_flat(const float* in, const float* Wp, const int32_t*
                                 const int32_t* steps, const int32_t* flat, int K, int M_in, int M_out, int ld, int Cin, int Cout,
                                 const float* in_scale, const float* in_shift, const float* residual,
                                 const float* out_scale, const float* out_shift, float* out, float* out_act, void* stream) {
-    GF_CHECK_ARG(out_act == nullptr || (out_scale != nullptr && out_shift != nullptr && ((uintptr_t)out_act % 16) == 0),
-                 "gf_conv_fwd_flat: the second output needs its scale / shift and 16-byte alignment");
     return conv_fwd_impl(in, Wp, nbr, gmask, steps, flat, K, M_in, M_out, ld, Cin, Cout, in_scale, in_shift, residual, out_scale,
                          out_shift, out, out_act, stream);
+}
+
+// Dev hook (include/geoformer_hip_dev.h): the launch gf_conv_fwd_flat would make, without making it
+extern "C" int gf_dev_conv_plan(const float* in, const float* Wp, const int32_t* nbr, const uint32_t* gmask,
+                                const int32_t* steps, const int32_t* flat, int K, int M_in, int M_out, int ld, int Cin, int Cout,
+                                const float* in_scale, const float* in_shift, const float* residual,
+                                const float* out_scale, const float* out_shift, float* out, float* out_act, int* desc) {
+    GF_CHECK_ARG(desc != nullptr, "gf_dev_conv_plan: desc is null");
+    return conv_fwd_impl(in, Wp, nbr, gmask, steps, flat, K, M_in, M_out, ld, Cin, Cout, in_scale, in_shift, residual, out_scale,
+                         out_shift, out, out_act, nullptr, desc);
+}
+
+// 1 if the LDS-weight kernel takes this convolution, given a flat table (gf_unet_fwd: whether to wait for the table)
+int gf_conv_lw_supported(int K, int M_in, int M_out, int Cin, int Cout, bool aligned, int* forced) {
+    if (forced) *forced = g_knobs.lw == 1;
+    ConvQuery q{K, M_in, M_out, 0, Cin, Cout};
+    q.nbr = q.gmask = q.flat = true;
+    q.in16 = q.out16 = aligned;
+    return conv_plan(q).family == CONV_LW;
 }
 
 // gf_conv_fwd with TWO outputs: out = the raw sums (+ residual), out_act = max(out*out_scale + out_shift, 0).  The next
 // residual block reads `out` as its residual operand and gathers from `out_act`, which takes the BatchNorm + ReLU out
 // of its first convolution's prologue.  Level-1 shape only (the pipelined counted-loop kernel); gf_conv_dual_supported
-// tells beforehand.
+// tells beforehand: the planner's answer for such a call (27 offsets, M_in = M_out, aligned operands, no flat table).
 extern "C" int gf_conv_dual_supported(int M_out, int ld, int Cin, int Cout, int has_steps) {
-    const ConvKnobs& knobs = conv_knobs();
-    const int ngroups = (M_out + 15) / 16;
-    bool split = ngroups < 6000;
-    if (knobs.split >= 0) split = knobs.split != 0;
-    bool g16 = has_steps && Cout == 16 && (Cin == 16 || Cin == 32) && (knobs.g16 >= 0 ? knobs.g16 != 0 : !split);
-    bool pipe = M_out > 0 && ld >= M_out && (knobs.g16_pipe < 0 || knobs.g16_pipe != 0);
-    return g16 && pipe ? 1 : 0;
+    ConvQuery q{27, M_out, M_out, ld, Cin, Cout};
+    q.nbr = q.gmask = true;
+    q.steps = has_steps != 0;
+    q.out2 = true;
+    return conv_plan(q).family != CONV_NONE;
 }
 extern "C" int gf_conv_fwd_dual(const float* in, const float* Wp, const int32_t* nbr, const uint32_t* gmask,
                                 const int32_t* steps, int K, int M_in, int M_out, int ld, int Cin, int Cout,

@@ -345,57 +345,16 @@ __global__ __launch_bounds__(64 * WPB) void k_conv_lw(const LwArgs A) {
 #endif
 }
 
-namespace {
-
-int g_lw_use = -1;         // -1 size-based, 0 never, 1 whenever the shape allows
-int g_lw_min_groups = 0;   // size-based choice: at least this many 16-row groups (0 = default)
-
-template <int K, int NCH, int NCB, int D>
-int lw_launch(bool aff, hipStream_t st, const LwArgs& a) {
-    constexpr int WPB = 12;
-    constexpr size_t lds = (size_t)K * NCH * NCB * 1024;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)k_conv_lw<K, NCH, NCB, D, true, WPB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)k_conv_lw<K, NCH, NCB, D, false, WPB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-    }
-    const dim3 grid((unsigned)(a.nbins / 4));
-    if (aff) hipLaunchKernelGGL((k_conv_lw<K, NCH, NCB, D, true, WPB>), grid, dim3(64 * WPB), lds, st, a);
-    else hipLaunchKernelGGL((k_conv_lw<K, NCH, NCB, D, false, WPB>), grid, dim3(64 * WPB), lds, st, a);
-    return 0;
+// one pass: NCH input chunks of the window, NCB column blocks, D steps of gathers in flight
+template <int NCH, int NCB, bool AFF>
+static void lw_launch(hipStream_t st, const LwArgs& a) {
+    constexpr int D = NCH == 2 && NCB == 2 ? 6 : 8;
+    constexpr size_t lds = (size_t)27 * NCH * NCB * 1024;
+    gf_allow_lds((const void*)k_conv_lw<27, NCH, NCB, D, AFF, GF_LW_WPB>, (int)lds);
+    hipLaunchKernelGGL((k_conv_lw<27, NCH, NCB, D, AFF, GF_LW_WPB>), dim3((unsigned)(a.nbins / 4)), dim3(64 * GF_LW_WPB), lds, st, a);
 }
 
-}  // namespace
-
-extern "C" int gf_dev_conv_knob_lw(int use, int min_groups) {
-    g_lw_use = use < 0 ? -1 : (use != 0);
-    g_lw_min_groups = min_groups > 0 ? min_groups : 0;
-    return GF_OK;
-}
-
-// chunks per input pass and column blocks the kernel is instantiated for: (window chunks, column blocks)
-static bool lw_shape(int nchw, int ncb) { return (nchw == 1 || nchw == 2) && (ncb == 1 || ncb == 2); }
-
-// 1 if the LDS-weight kernel takes this convolution (gf_conv_fwd's dispatch, given a flat table); `forced`: the dev knob said so
-int gf_conv_lw_supported(int K, int M_in, int M_out, int Cin, int Cout, bool aligned, int* forced) {
-    if (forced) *forced = g_lw_use == 1;
-    if (g_lw_use == 0) return 0;
-    if (!aligned || K != 27) return 0;
-    if ((Cin & 15) || (Cout & 15)) return 0;
-    const int nch = Cin / 16, ncb = Cout / 16;
-    const int npass = (nch + 1) / 2;
-    if (!lw_shape((nch + npass - 1) / npass, ncb) || !lw_shape(nch / npass, ncb)) return 0;
-    // measured on S150k (tools/conv_lw_exp.py, profiles/r6_conv_lw_notes.md): 32 -> 32 21.8 against 27.1 us, 32 -> 16 30.2
-    // against 46.6; 16 -> 16 equal to k_conv_g16p (17.7 / 17.9), two passes (64 -> 32) slower than k_conv_os (49 / 44)
-    const bool pays = npass == 1 && nch == 2;
-    // 24-bit row multiply; an absent row's offset 0xFFFFFF * row_bytes (mod 2^32) >= 2^30 - row_bytes must lie beyond the buffer
-    if (M_in >= (1 << 24) || (unsigned long long)M_in * Cin * 4ull > (1ull << 30) - 4096ull) return 0;
-    if ((M_out + 15) / 16 > 64 * 3 * GF_FLAT_BINS) return 0;  // (a wave keeps its groups' descriptors one per lane)
-    if (g_lw_use == 1) return 1;
-    return pays && (M_out + 15) / 16 >= (g_lw_min_groups > 0 ? g_lw_min_groups : 1500);
-}
-
+// the launches of spconv_conv.hip's plan CONV_LW (27 offsets, 16-channel multiples, at most two column blocks)
 int gf_conv_lw(const float* in, const float* Wp, const uint32_t* gmask, const int32_t* flat, int K, int M_in, int M_out, int Cin,
                int Cout, const float* in_scale, const float* in_shift, const float* residual, const float* out_scale,
                const float* out_shift, float* out, float* out2, hipStream_t st) {
@@ -429,11 +388,9 @@ int gf_conv_lw(const float* in, const float* Wp, const uint32_t* gmask, const in
         a.nbins = GF_FLAT_BINS;  // (tables are built with the default bins: gf_rules_flat_steps(..., 0, ...))
         a.ngroups = ngroups;
         a.rounds = (ngroups + a.nbins - 1) / a.nbins;
-        const bool aff = in_scale != nullptr;
-        if (n == 1 && ncb == 1) lw_launch<27, 1, 1, 8>(aff, st, a);
-        else if (n == 2 && ncb == 1) lw_launch<27, 2, 1, 8>(aff, st, a);
-        else if (n == 1 && ncb == 2) lw_launch<27, 1, 2, 8>(aff, st, a);
-        else lw_launch<27, 2, 2, 6>(aff, st, a);
+        gf_with<int, 1, 2>(n, [&](auto NCH) { gf_with<int, 1, 2>(ncb, [&](auto NCB) {
+            gf_with<bool, false, true>(in_scale != nullptr, [&](auto AFF) { lw_launch<NCH, NCB, AFF>(st, a); });
+        }); });
         ch0 += n;
     }
     GF_CHECK_LAUNCH("gf_conv_fwd (LDS-weight kernel)");

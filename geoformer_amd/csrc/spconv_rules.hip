@@ -13,6 +13,8 @@
 #include <stdarg.h>
 
 #include <cstdlib>
+#include <map>
+#include <mutex>
 #include "common.h"
 
 // ------------------------------------------------------------------------------------
@@ -26,6 +28,18 @@ void gf_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 extern "C" const char* gf_last_error(void) { return g_err; }
+
+// (device, kernel) -> the dynamic LDS bytes the kernel is allowed there: the attribute is a property of the kernel on ONE
+// device, so a process that launches on a second device sets it again there
+void gf_allow_lds(const void* kernel, int bytes) {
+    static std::mutex mu;
+    static std::map<std::pair<int, const void*>, int> allowed;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::lock_guard<std::mutex> lock(mu);
+    int& have = allowed[{dev, kernel}];
+    if (have < bytes && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess) have = bytes;
+}
 
 // dev hook (common.h: GF_LAUNCH_OP): events bound to the next launch of an operator's main kernel.  Process-wide, not
 // per host thread: a backward kernel is launched from the framework's autograd thread, not from the thread that armed

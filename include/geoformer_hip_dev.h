@@ -42,6 +42,15 @@ int gf_dev_conv_knob_flat(int use, int max_items);
  * table): use 0 / 1 (whenever the shape allows) or -1 (size-based: at least `min_groups` 16-row groups, 0 = default). */
 int gf_dev_conv_knob_lw(int use, int min_groups);
 
+/* The launch gf_conv_fwd_flat would make for these arguments, without making it (the pointers are only compared, never
+ * dereferenced): desc[10] = family (0 none, 1 k_conv_lw, 2 k_conv_flat, 3 k_conv_g16p, 4 k_conv_g16, 5 k_conv_pair,
+ * 6 k_conv_os), six template parameters (spconv_conv.hip ConvPlan), grid, block, dynamic LDS bytes.  Returns the status
+ * gf_conv_fwd_flat would return. */
+int gf_dev_conv_plan(const float* in, const float* Wp, const int32_t* nbr, const uint32_t* gmask, const int32_t* steps,
+                     const int32_t* flat, int K, int M_in, int M_out, int ld, int Cin, int Cout, const float* in_scale,
+                     const float* in_shift, const float* residual, const float* out_scale, const float* out_shift, float* out,
+                     float* out_act, int* desc);
+
 /* Number of equal-cost chunks (= waves of the pipelined kernel) the NEXT rulebooks are built with: a multiple of 4,
  * at most 4096; 0 = default (3072 = 12 waves per compute unit). */
 int gf_dev_conv_chunks(int n);
