@@ -184,6 +184,8 @@ def _declare(lib):
         "gf_aug_elastic": (I, [P, I, I, I, I, ctypes.c_double, I, ctypes.c_ulonglong, c_longlong, I, c_longlong, P]),
         "gf_aug_crop": (I, [P, I, I, I, I, c_longlong, I, P]),
         "gf_aug_collate": (I, [P, P, I, I, I, I, P]),
+        "gf_aug_collate_fs": (I, [P, I, I, I, P]),
+        "gf_aug_support": (I, [P, P, ctypes.c_double, I, I, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -230,7 +232,7 @@ def load():
     _check_hw_queues(torch)
     lib = ctypes.CDLL(LIB_PATH)
     EXPORTS = _declare(lib)
-    if lib.gf_abi_version() != 6:
+    if lib.gf_abi_version() != 7:
         raise GeoFormerHipError("libgeoformer_hip.so ABI version mismatch")
     _lib = lib
     return lib

@@ -16,6 +16,13 @@ Two sources of randomness share every kernel but the draw:
 
 One deliberate deviation: a scene left without instances counts 0 instances; the reference's
 ``int(max) + 1`` counts -99 there and shifts the ids of every later scene of the batch.
+
+Few-shot episodes (``FSInstDataset.trainMergeFS``, ``datasets/scannetv2_fs_inst.py:397-566``) reuse the
+query kernels and add the few-shot collate and the support path:
+
+    index = FSIndex.build(scenes_by_name)
+    support, query, scene_infos = train_merge_fs(scenes_by_name, index, 8, rng="device", seed=7, batch_index=i)
+    for support, query, scene_infos in FSTrainFeeder(scenes_by_name, index, 8, seed=7, device="cuda"): ...
 """
 from __future__ import annotations
 
@@ -33,6 +40,7 @@ REC = 320
 R_M, R_SHIFT, R_FLIP, R_THETA, R_AMAX0, R_AMAX1 = 0, 9, 12, 13, 14, 17
 R_MIN, R_MAX, R_CHOSEN, R_ERR, R_CAP0, R_BASE0, R_CAP1, R_BASE1 = 20, 23, 26, 27, 28, 29, 30, 31
 R_PCMIN, R_PCMAX, R_NINST, R_IBASE, R_COUNTS, R_CROPU = 32, 35, 38, 39, 64, 128
+R_PBASE, R_CLASS, R_SUPID = 40, 41, 42
 H_N, H_NINST, H_ERR, H_SHAPE = 0, 1, 2, 6
 HEAD = 16
 MAX_INST = 4096
@@ -139,8 +147,10 @@ class _Batch:
         self.s.noise[p], self.s.work[p], self.s.cells[p] = ptr(self.noise[p]), ptr(self.work[p]), cells * 3
 
 
-def _rec_init(B, caps=None):
+def _rec_init(B, caps=None, classes=None):
     rec = np.zeros((B, REC), np.int64)
+    if classes is not None:
+        rec[:, R_CLASS] = classes
     rec[:, R_MIN:R_MIN + 3] = -1  # order keys: min starts at the largest key, max at 0 (the smallest)
     rec[:, R_PCMIN:R_PCMIN + 3] = -1
     rec[:, R_CHOSEN] = -1
@@ -169,7 +179,7 @@ class _Pending:
     """A batch whose kernels are queued; its sizes arrive in pinned words."""
 
     __slots__ = ("bt", "head_host", "vhead", "vhead_host", "input_map", "vscratch", "done", "mode", "fs_min", "ids",
-                 "draws")
+                 "draws", "kind")
 
 
 def _voxelise_count(bt, mode, st):
@@ -184,12 +194,21 @@ def _voxelise_count(bt, mode, st):
     return p
 
 
-def _launch_tail(bt, cvfold, full_scale, mode, st, pinned=None):
-    """Collate + first half of the voxelisation + the sizes on their way to pinned words; returns the _Pending."""
+def _launch_tail(bt, cvfold, full_scale, mode, st, pinned=None, kind="merge"):
+    """Collate (kind "merge": trainMerge's; "fs_query": the few-shot query's) + first half of the voxelisation + the
+    sizes on their way to pinned words; returns the _Pending."""
     lib = _lib.load()
-    fold = (ctypes.c_int32 * 9)(*FOLD[cvfold])
-    check(lib.gf_aug_collate(bt.ref, fold, 9, int(full_scale[0]), int(full_scale[1]), bt.max_scene, st),
-          "gf_aug_collate")
+    if kind == "fs_query":
+        check(lib.gf_aug_collate_fs(bt.ref, int(full_scale[0]), int(full_scale[1]), bt.max_scene, st),
+              "gf_aug_collate_fs")
+    else:
+        fold = (ctypes.c_int32 * 9)(*FOLD[cvfold])
+        check(lib.gf_aug_collate(bt.ref, fold, 9, int(full_scale[0]), int(full_scale[1]), bt.max_scene, st),
+              "gf_aug_collate")
+    return _queue_handover(bt, mode, st, pinned, kind)
+
+
+def _queue_handover(bt, mode, st, pinned, kind):
     p = _voxelise_count(bt, mode, st)
     if pinned is None:
         pinned = (torch.empty(HEAD, dtype=torch.int32).pin_memory(), torch.empty(3, dtype=torch.int32).pin_memory())
@@ -198,7 +217,7 @@ def _launch_tail(bt, cvfold, full_scale, mode, st, pinned=None):
     p.vhead_host.copy_(p.vhead, non_blocking=True)
     p.done = torch.cuda.Event()
     p.done.record(torch.cuda.current_stream(bt.device))
-    p.bt, p.mode = bt, mode
+    p.bt, p.mode, p.kind = bt, mode, kind
     return p
 
 
@@ -210,12 +229,13 @@ def _finish(p, stream=None):
     p.done.synchronize()
     head = p.head_host.tolist()
     M_pad, max_active, verr = p.vhead_host.tolist()
+    what = "train_merge" if p.kind == "merge" else "train_merge_fs"
     if head[H_ERR]:
         raise _lib.GeoFormerHipError(
-            "train_merge: " + ("a noise grid exceeds its buffer; " if head[H_ERR] & ERR_CELLS else "")
+            what + ": " + ("a noise grid exceeds its buffer; " if head[H_ERR] & ERR_CELLS else "")
             + (f"an instance id outside [0, {MAX_INST}) (or negative but not -100)" if head[H_ERR] & ERR_INST else ""))
     if verr:
-        raise _lib.GeoFormerHipError("train_merge: a voxel coordinate lies outside [0, 65535]")
+        raise _lib.GeoFormerHipError(what + ": a voxel coordinate lies outside [0, 65535]")
     N, ninst = head[H_N], head[H_NINST]
     M = M_pad - (bt.n - N)
     max_active = max(max_active, 1)
@@ -233,14 +253,24 @@ def _finish(p, stream=None):
     if work is not cur:
         cur.wait_event(ready)
     o = bt.out
-    batch = {
-        "locs": o["locs"][:N], "voxel_locs": out_coords[:M], "p2v_map": p.input_map[:N], "v2p_map": out_map[:M],
-        "locs_float": o["locs_float"][:N], "feats": o["feats"][:N], "labels": o["labels"][:N],
-        "instance_labels": o["instance_labels"][:N], "instance_pointnum": o["instance_pointnum"][:ninst],
-        "instance_infos": o["instance_infos"][:N], "id": p.ids, "offsets": o["offsets"],
-        "spatial_shape": np.asarray(head[H_SHAPE:H_SHAPE + 3], np.int64), "pc_mins": o["pc_mins"],
-        "pc_maxs": o["pc_maxs"],
-    }
+    shape = np.asarray(head[H_SHAPE:H_SHAPE + 3], np.int64)
+    if p.kind == "merge":
+        batch = {
+            "locs": o["locs"][:N], "voxel_locs": out_coords[:M], "p2v_map": p.input_map[:N], "v2p_map": out_map[:M],
+            "locs_float": o["locs_float"][:N], "feats": o["feats"][:N], "labels": o["labels"][:N],
+            "instance_labels": o["instance_labels"][:N], "instance_pointnum": o["instance_pointnum"][:ninst],
+            "instance_infos": o["instance_infos"][:N], "id": p.ids, "offsets": o["offsets"],
+            "spatial_shape": shape, "pc_mins": o["pc_mins"], "pc_maxs": o["pc_maxs"],
+        }
+    else:  # the key order of trainMergeFS's support_dict / query_dict (datasets/scannetv2_fs_inst.py:515-565)
+        batch = {"voxel_locs": out_coords[:M], "p2v_map": p.input_map[:N], "v2p_map": out_map[:M],
+                 "locs": o["locs"][:N], "locs_float": o["locs_float"][:N], "feats": o["feats"][:N]}
+        if p.kind == "fs_query":
+            batch.update(labels=o["labels"][:N], instance_labels=o["instance_labels"][:N],
+                         instance_pointnum=o["instance_pointnum"][:ninst])
+        else:
+            batch["support_masks"] = o["support_masks"][:N]
+        batch.update(spatial_shape=shape, batch_offsets=o["offsets"], pc_mins=o["pc_mins"], pc_maxs=o["pc_maxs"])
     if work is not cur:
         for v in batch.values():
             if torch.is_tensor(v):
@@ -264,14 +294,15 @@ def _rec_read(bt, s):
     return bt.rec[s].cpu().numpy()
 
 
-def _queue_device(scenes, raw, sizes, dev, st, scale, full_scale, max_npoint, seed, batch_index):
-    """rng="device": every launch of a batch up to the collate, on stream `st`, nothing read back."""
+def _queue_device(scenes, raw, sizes, dev, st, scale, full_scale, max_npoint, seed, batch_index, classes=None):
+    """rng="device": every launch of a batch up to the collate, on stream `st`, nothing read back (classes: the
+    few-shot query's sampled class per scene)."""
     lib = _lib.load()
     B = len(sizes)
     K = crop_candidates(full_scale[1])
     caps = np.array([device_cell_bounds(_radius(sc), scale) for sc in scenes], np.int64).T
     bt = _Batch(raw, sizes, dev, (3 * int(caps[0].sum()), 3 * int(caps[1].sum())))
-    bt.rec.copy_(torch.from_numpy(_rec_init(B, caps)).pin_memory(), non_blocking=True)
+    bt.rec.copy_(torch.from_numpy(_rec_init(B, caps, classes)).pin_memory(), non_blocking=True)
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     check(lib.gf_aug_draw(bt.ref, seed, int(batch_index), K, st), "gf_aug_draw")
     check(lib.gf_aug_transform(bt.ref, 0, B, float(scale), bt.max_scene, st), "gf_aug_transform")
@@ -280,6 +311,96 @@ def _queue_device(scenes, raw, sizes, dev, st, scale, full_scale, max_npoint, se
                                  int(caps[p].max()), st), "gf_aug_elastic")
     check(lib.gf_aug_crop(bt.ref, 0, B, int(full_scale[1]), K, int(max_npoint), bt.max_scene, st), "gf_aug_crop")
     return bt
+
+
+def _device_draws(bt, scale, colour_shift, dev):
+    """(rng="device", return_draws) every draw of the queued batch, read back after a sync."""
+    (g0, _), (g1, _) = elastic_params(scale)
+    draws = {"m": [], "flip": [], "theta": [], "noise": [], "crop_u": [], "chosen": [], "shift": [], "bb": [],
+             "blurred": []}
+    torch.cuda.current_stream(dev).synchronize()
+    rec = bt.rec.cpu().numpy()
+    nz = [bt.noise[0].cpu().numpy(), bt.noise[1].cpu().numpy()]
+    wk = [bt.work[0].cpu().numpy(), bt.work[1].cpu().numpy()]
+    for s in range(bt.B):
+        r = rec[s]
+        m = r[R_M:R_M + 9].view(np.float64).reshape(3, 3).copy()
+        draws["m"].append(m)
+        draws["flip"].append(int(r[R_FLIP:R_FLIP + 1].view(np.float64)[0]))
+        draws["theta"].append(float(r[R_THETA:R_THETA + 1].view(np.float64)[0]))
+        bbs, grids, blurred = [], [], []
+        for p, (g, amax_at, capw, basew) in enumerate(((g0, R_AMAX0, R_CAP0, R_BASE0),
+                                                       (g1, R_AMAX1, R_CAP1, R_BASE1))):
+            bb = grid_bb(r[amax_at:amax_at + 3].view(np.float64), g)
+            n = int(np.prod(bb))
+            cap, base = int(r[capw]), int(r[basew])
+            bbs.append(bb)
+            grids.append([nz[p][base + a * cap: base + a * cap + n].reshape(bb) for a in range(3)])
+            c = bt.cells[p]
+            blurred.append([wk[p][c + base + a * cap: c + base + a * cap + n].reshape(bb) for a in range(3)])
+        draws["bb"].append(bbs)
+        draws["noise"].append(grids)
+        draws["blurred"].append(blurred)
+        ch = int(r[R_CHOSEN])
+        draws["chosen"].append(ch)
+        draws["crop_u"].append(r[R_CROPU:R_CROPU + 3 * (ch + 1)].view(np.float64).reshape(-1, 3).copy())
+        if colour_shift:
+            draws["shift"].append(r[R_SHIFT:R_SHIFT + 3].view(np.float64).copy())
+    return draws
+
+
+def _queue_reference(bt, scale, full_scale, max_npoint, st, colour_shift, return_draws):
+    """rng="reference": scene by scene, numpy's legacy stream (and, with colour_shift, torch's CPU generator) in the
+    reference's order and amounts, the grid extents and the crop choice read back between the launches.  Returns the
+    draws used."""
+    lib = _lib.load()
+    dev, sizes, B = bt.device, bt.sizes, bt.B
+    K = crop_candidates(full_scale[1])
+    (g0, m0), (g1, m1) = elastic_params(scale)
+    draws = {"m": [], "flip": [], "theta": [], "noise": [], "crop_u": [], "chosen": [], "shift": [], "bb": [],
+             "blurred": []}
+    fdev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    for s in range(B):
+        m, g, flip, theta = _host_draw_m()
+        bt.rec[s, R_M:R_M + 9] = fdev(m.reshape(-1)).view(torch.int64)
+        check(lib.gf_aug_transform(bt.ref, s, 1, float(scale), sizes[s], st), "gf_aug_transform")
+        bbs, grids, blurred = [], [], []
+        for p, (gr, mg, amax_at, capw) in enumerate(((g0, m0, R_AMAX0, R_CAP0), (g1, m1, R_AMAX1, R_CAP1))):
+            r = _rec_read(bt, s)
+            bb = grid_bb(r[amax_at:amax_at + 3].view(np.float64), gr)
+            n = int(np.prod(bb))
+            noise = [np.random.randn(bb[0], bb[1], bb[2]).astype("float32") for _ in range(3)]
+            bt.set_noise(p, n)
+            bt.noise[p].copy_(fdev(np.concatenate([x.reshape(-1) for x in noise])))
+            bt.rec[s, capw] = n
+            bt.rec[s, capw + 1] = 0
+            check(lib.gf_aug_elastic(bt.ref, s, 1, p, int(gr), float(mg), 0, 0, 0, sizes[s], n, st),
+                  "gf_aug_elastic")
+            bbs.append(bb)
+            grids.append(noise)
+            if return_draws:
+                w = bt.work[p][3 * n:].cpu().numpy()
+                blurred.append([w[a * n:(a + 1) * n].reshape(bb) for a in range(3)])
+        chosen = -1
+        u = np.zeros((0, 3))
+        if sizes[s] > max_npoint:
+            state = np.random.get_state()
+            cand = np.random.rand(K, 3)
+            bt.rec[s, R_CROPU:R_CROPU + 3 * K] = fdev(cand.reshape(-1)).view(torch.int64)
+            check(lib.gf_aug_crop(bt.ref, s, 1, int(full_scale[1]), K, int(max_npoint), sizes[s], st),
+                  "gf_aug_crop")
+            chosen = int(_rec_read(bt, s)[R_CHOSEN])
+            np.random.set_state(state)
+            u = np.random.rand(chosen + 1, 3)  # what the reference's loop consumed
+            assert (u == cand[:chosen + 1]).all()
+        if colour_shift:
+            shift = (torch.randn(3) * 0.1).double().numpy()
+            bt.rec[s, R_SHIFT:R_SHIFT + 3] = fdev(shift).view(torch.int64)
+            draws["shift"].append(shift)
+        for k, v in (("m", m), ("flip", int(flip)), ("theta", theta), ("noise", grids), ("crop_u", u),
+                     ("chosen", chosen), ("bb", bbs), ("blurred", blurred)):
+            draws[k].append(v)
+    return draws
 
 
 def train_merge(scenes, *, scale=50, full_scale=(128, 512), max_npoint=250000, mode=4, cvfold=0, rng="reference",
@@ -296,90 +417,20 @@ def train_merge(scenes, *, scale=50, full_scale=(128, 512), max_npoint=250000, m
     dev = torch.device(device)
     if dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())
-    lib = _lib.load()
     st_obj = stream if stream is not None else torch.cuda.current_stream(dev)
     with torch.cuda.stream(st_obj):
         st = st_obj.cuda_stream
         raw, sizes = _raw_upload(scenes, dev)
         B = len(sizes)
-        K = crop_candidates(full_scale[1])
-        if K > MAX_CROP:
+        if crop_candidates(full_scale[1]) > MAX_CROP:
             raise ValueError(f"full_scale[1] allows at most {32 * (MAX_CROP - 1)}")
-        (g0, m0), (g1, m1) = elastic_params(scale)
-        draws = {"m": [], "flip": [], "theta": [], "noise": [], "crop_u": [], "chosen": [], "shift": [], "bb": [],
-                 "blurred": []}
         if rng == "device":
             bt = _queue_device(scenes, raw, sizes, dev, st, scale, full_scale, max_npoint, seed, batch_index)
-            if return_draws:
-                torch.cuda.current_stream(dev).synchronize()
-                rec = bt.rec.cpu().numpy()
-                nz = [bt.noise[0].cpu().numpy(), bt.noise[1].cpu().numpy()]
-                wk = [bt.work[0].cpu().numpy(), bt.work[1].cpu().numpy()]
-                for s in range(B):
-                    r = rec[s]
-                    m = r[R_M:R_M + 9].view(np.float64).reshape(3, 3).copy()
-                    draws["m"].append(m)
-                    draws["flip"].append(int(r[R_FLIP:R_FLIP + 1].view(np.float64)[0]))
-                    draws["theta"].append(float(r[R_THETA:R_THETA + 1].view(np.float64)[0]))
-                    bbs, grids, blurred = [], [], []
-                    for p, (g, amax_at, capw, basew) in enumerate(((g0, R_AMAX0, R_CAP0, R_BASE0),
-                                                                   (g1, R_AMAX1, R_CAP1, R_BASE1))):
-                        bb = grid_bb(r[amax_at:amax_at + 3].view(np.float64), g)
-                        n = int(np.prod(bb))
-                        cap, base = int(r[capw]), int(r[basew])
-                        bbs.append(bb)
-                        grids.append([nz[p][base + a * cap: base + a * cap + n].reshape(bb) for a in range(3)])
-                        c = bt.cells[p]
-                        blurred.append([wk[p][c + base + a * cap: c + base + a * cap + n].reshape(bb) for a in range(3)])
-                    draws["bb"].append(bbs)
-                    draws["noise"].append(grids)
-                    draws["blurred"].append(blurred)
-                    ch = int(r[R_CHOSEN])
-                    draws["chosen"].append(ch)
-                    draws["crop_u"].append(r[R_CROPU:R_CROPU + 3 * (ch + 1)].view(np.float64).reshape(-1, 3).copy())
-                    draws["shift"].append(r[R_SHIFT:R_SHIFT + 3].view(np.float64).copy())
+            draws = _device_draws(bt, scale, True, dev) if return_draws else None
         else:
             bt = _Batch(raw, sizes, dev, (1, 1))
             bt.rec.copy_(torch.from_numpy(_rec_init(B)))
-            fdev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
-            for s in range(B):
-                m, g, flip, theta = _host_draw_m()
-                bt.rec[s, R_M:R_M + 9] = fdev(m.reshape(-1)).view(torch.int64)
-                check(lib.gf_aug_transform(bt.ref, s, 1, float(scale), sizes[s], st), "gf_aug_transform")
-                bbs, grids, blurred = [], [], []
-                for p, (gr, mg, amax_at, capw) in enumerate(((g0, m0, R_AMAX0, R_CAP0), (g1, m1, R_AMAX1, R_CAP1))):
-                    r = _rec_read(bt, s)
-                    bb = grid_bb(r[amax_at:amax_at + 3].view(np.float64), gr)
-                    n = int(np.prod(bb))
-                    noise = [np.random.randn(bb[0], bb[1], bb[2]).astype("float32") for _ in range(3)]
-                    bt.set_noise(p, n)
-                    bt.noise[p].copy_(fdev(np.concatenate([x.reshape(-1) for x in noise])))
-                    bt.rec[s, capw] = n
-                    bt.rec[s, capw + 1] = 0
-                    check(lib.gf_aug_elastic(bt.ref, s, 1, p, int(gr), float(mg), 0, 0, 0, sizes[s], n, st),
-                          "gf_aug_elastic")
-                    bbs.append(bb)
-                    grids.append(noise)
-                    if return_draws:
-                        w = bt.work[p][3 * n:].cpu().numpy()
-                        blurred.append([w[a * n:(a + 1) * n].reshape(bb) for a in range(3)])
-                chosen = -1
-                u = np.zeros((0, 3))
-                if sizes[s] > max_npoint:
-                    state = np.random.get_state()
-                    cand = np.random.rand(K, 3)
-                    bt.rec[s, R_CROPU:R_CROPU + 3 * K] = fdev(cand.reshape(-1)).view(torch.int64)
-                    check(lib.gf_aug_crop(bt.ref, s, 1, int(full_scale[1]), K, int(max_npoint), sizes[s], st),
-                          "gf_aug_crop")
-                    chosen = int(_rec_read(bt, s)[R_CHOSEN])
-                    np.random.set_state(state)
-                    u = np.random.rand(chosen + 1, 3)  # what the reference's loop consumed
-                    assert (u == cand[:chosen + 1]).all()
-                shift = (torch.randn(3) * 0.1).double().numpy()
-                bt.rec[s, R_SHIFT:R_SHIFT + 3] = fdev(shift).view(torch.int64)
-                for k, v in (("m", m), ("flip", int(flip)), ("theta", theta), ("noise", grids), ("crop_u", u),
-                             ("chosen", chosen), ("shift", shift), ("bb", bbs), ("blurred", blurred)):
-                    draws[k].append(v)
+            draws = _queue_reference(bt, scale, full_scale, max_npoint, st, True, return_draws)
         p = _launch_tail(bt, cvfold, full_scale, mode, st)
         p.ids = list(ids) if ids is not None else list(range(B))
     batch = _finish(p)
@@ -469,3 +520,240 @@ class TrainFeeder:
         out = _finish(self.next, self.stream)
         self.next = self._start()
         return out
+
+
+# ============================== few-shot episodes (FSInstDataset.trainMergeFS) ==============================
+# datasets/scannetv2_fs_inst.py:397-566 per episode item: a class of the fold, a query scene listing it (augmented and
+# cropped as in trainMerge, label = (label == class), no colour shift, scene-local instance ids), a support instance of
+# the class whose scene has more than SUPPORT_MIN_LABELLED nonzero labels (no augmentation, no crop).
+
+SUPPORT_MIN_LABELLED = 100  # np.count_nonzero(support_label) > 100 (the whole scene's labels, not the instance's)
+SUPPORT_MAX_INST = 256  # (the support path uses no instance buffers; the smallest legal size)
+DRAW_CHOICE = 5  # Philox draw id of rng="device"'s episode choices (csrc/augment.hip's device draws use 0..4)
+CHOICE_CLASS, CHOICE_QUERY, CHOICE_SUPPORT = 0, 1, 2
+N_CLASSES = 20
+
+
+def _host_array(sc):
+    return sc.detach().cpu().numpy() if torch.is_tensor(sc) else np.asarray(sc)
+
+
+class FSIndex:
+    """The few-shot sampling tables: class2scans {class: [scene, ...]}, class2instances {class: [[scene, id], ...]} and,
+    per scene, the nonzero-label count the support loop tests.  The order of each list decides random.choice."""
+
+    SCAN_RATIO, INST_RATIO, MIN_PTS = 0.05, 0.002, 100  # datasets/scannetv2.py:88-89, 124-125
+
+    def __init__(self, class2scans, class2instances, counts):
+        self.class2scans = {int(k): list(v) for k, v in class2scans.items()}
+        self.class2instances = {int(k): [list(t) for t in v] for k, v in class2instances.items()}
+        self.counts = {str(k): int(v) for k, v in counts.items()}
+        missing = {s for v in self.class2instances.values() for s, _ in v} - set(self.counts)
+        if missing:
+            raise ValueError(f"FSIndex: no nonzero-label count for {sorted(missing)[:5]}")
+
+    @classmethod
+    def from_tables(cls, class2scans, class2instances, counts):
+        """The reference's pickled tables as they are (class2scans.pkl, class2instances.pkl) plus the per-scene counts."""
+        return cls(class2scans, class2instances, counts)
+
+    @classmethod
+    def build(cls, scenes_by_name):
+        """The tables of datasets/scannetv2.py:75-159 over {name: raw [N,8] scene}: a scene lists a class when more
+        than max(int(5 % N), 100) of its points carry it (scenes in the mapping's order, which stands for the glob's);
+        an instance is listed under the label of its first point when it has more than max(int(0.2 % N), 100) points
+        and that label is not -100 (scenes in sorted order, ids ascending)."""
+        c2s = {k: [] for k in range(N_CLASSES)}
+        c2i = {k: [] for k in range(N_CLASSES)}
+        counts, host = {}, {}
+        for name, sc in scenes_by_name.items():
+            data = _host_array(sc)
+            host[name] = data
+            labels = data[:, 6].astype(np.int64)
+            counts[name] = int(np.count_nonzero(labels))
+            threshold = max(int(data.shape[0] * cls.SCAN_RATIO), cls.MIN_PTS)
+            for c, n in zip(*np.unique(labels, return_counts=True)):
+                if c != -100 and n > threshold:
+                    c2s.setdefault(int(c), []).append(name)
+        for name in sorted(host):
+            data = host[name]
+            labels, inst = data[:, 6].astype(np.int64), data[:, 7].astype(np.int64)
+            threshold = max(int(data.shape[0] * cls.INST_RATIO), cls.MIN_PTS)
+            ids, first, n = np.unique(inst, return_index=True, return_counts=True)
+            for i, f, k in zip(ids, first, n):
+                if i != -100 and k > threshold and labels[f] != -100:
+                    c2i.setdefault(int(labels[f]), []).append([name, i])
+        return cls(c2s, c2i, counts)
+
+
+def _philox_host(c, seed):
+    """Philox4x32-10 of csrc/augment.hip on the host (counter of four 32-bit words, key = seed)."""
+    M = 0xFFFFFFFF
+    c0, c1, c2, c3 = (int(v) & M for v in c)
+    k0, k1 = seed & M, (seed >> 32) & M
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
+        c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & M, (p0 >> 32) ^ c3 ^ k1, p0 & M
+        k0, k1 = (k0 + 0x9E3779B9) & M, (k1 + 0xBB67AE85) & M
+    return c0, c1, c2, c3
+
+
+def choice_index(n, seed, batch_index, item, what, attempt=0):
+    """rng="device"'s choice among n: counter (attempt, DRAW_CHOICE << 2 | what, item, batch index), key = seed, a
+    53-bit uniform scaled to [0, n)."""
+    x, y, _, _ = _philox_host((attempt, DRAW_CHOICE << 2 | what, item, batch_index), int(seed) & 0xFFFFFFFFFFFFFFFF)
+    u = ((x >> 5) * 67108864 + (y >> 6)) / 9007199254740992.0
+    return min(int(u * n), n - 1)
+
+
+def sample_episode(index, batch_size, cvfold=0, rng="reference", seed=None, batch_index=0):
+    """The choices of one episode, as trainMergeFS's scene_infos: per item {sampled_class, query_scene, support_scene,
+    support_instance_id}.  rng="reference" calls random.choice in the reference's order (class, query scene, support
+    draws until one fits, item by item); rng="device" takes choice_index keyed by (seed, batch index, item)."""
+    import random
+
+    classes = FOLD[cvfold]
+    if rng == "reference":
+        pick = lambda seq, item, what, attempt: random.choice(seq)  # noqa: E731
+    else:
+        pick = lambda seq, item, what, attempt: seq[choice_index(len(seq), seed, batch_index, item, what,  # noqa: E731
+                                                                 attempt)]
+    infos = []
+    for i in range(batch_size):
+        c = pick(classes, i, CHOICE_CLASS, 0)
+        scans = index.class2scans.get(c, [])
+        if not scans:
+            raise ValueError(f"train_merge_fs: class {c} lists no scene (class2scans)")
+        q = pick(scans, i, CHOICE_QUERY, 0)
+        insts = index.class2instances.get(c, [])
+        if not any(index.counts[s] > SUPPORT_MIN_LABELLED for s, _ in insts):
+            raise ValueError(f"train_merge_fs: class {c} lists no support instance in a scene with more than "
+                             f"{SUPPORT_MIN_LABELLED} labelled points (the reference's loop would not end)")
+        k = 0
+        while True:
+            s, sid = pick(insts, i, CHOICE_SUPPORT, k)
+            k += 1
+            if index.counts[s] > SUPPORT_MIN_LABELLED:
+                break
+        infos.append({"sampled_class": c, "query_scene": q, "support_scene": s, "support_instance_id": sid})
+    return infos
+
+
+def _queue_support(scenes, ids, dev, st, scale, full_scale, mode, pinned=None):
+    """The support batch (load_single(aug=False, support=True) per scene, the collate): three launches and the first
+    half of the voxelisation on stream `st`; returns the _Pending."""
+    lib = _lib.load()
+    raw, sizes = _raw_upload(scenes, dev)
+    bt = _Batch(raw, sizes, dev, (1, 1), max_inst=SUPPORT_MAX_INST)
+    bt.out["support_masks"] = torch.empty(bt.n, dtype=torch.int64, device=dev)
+    rec = _rec_init(bt.B)
+    rec[:, R_SUPID] = np.asarray(ids, np.int64)
+    bt.rec.copy_(torch.from_numpy(rec).pin_memory(), non_blocking=True)
+    check(lib.gf_aug_support(bt.ref, ptr(bt.out["support_masks"]), float(scale), int(full_scale[0]), bt.max_scene, st),
+          "gf_aug_support")
+    return _queue_handover(bt, mode, st, pinned, "fs_support")
+
+
+
+def _queue_fs(scene_of, infos, dev, st, rng, seed, batch_index, scale, full_scale, max_npoint, mode, return_draws,
+              pinned=(None, None)):
+    """Every launch of one episode on stream `st`: the query batch (rng as in train_merge, no colour shift, the
+    few-shot collate), then the support batch.  Returns (query _Pending, support _Pending, draws)."""
+    if crop_candidates(full_scale[1]) > MAX_CROP:
+        raise ValueError(f"full_scale[1] allows at most {32 * (MAX_CROP - 1)}")
+    q_scenes = [scene_of[i["query_scene"]] for i in infos]
+    classes = np.array([i["sampled_class"] for i in infos], np.int64)
+    raw, sizes = _raw_upload(q_scenes, dev)
+    draws = None
+    if rng == "device":
+        bt = _queue_device(q_scenes, raw, sizes, dev, st, scale, full_scale, max_npoint, seed, batch_index, classes)
+        if return_draws:
+            draws = _device_draws(bt, scale, False, dev)
+    else:
+        bt = _Batch(raw, sizes, dev, (1, 1))
+        bt.rec.copy_(torch.from_numpy(_rec_init(len(sizes), classes=classes)))
+        draws = _queue_reference(bt, scale, full_scale, max_npoint, st, False, return_draws)
+    pq = _launch_tail(bt, 0, full_scale, mode, st, pinned[0], kind="fs_query")
+    ps = _queue_support([scene_of[i["support_scene"]] for i in infos], [i["support_instance_id"] for i in infos], dev,
+                        st, scale, full_scale, mode, pinned[1])
+    return pq, ps, draws
+
+
+def train_merge_fs(scene_of, index, batch_size, *, rng="reference", seed=None, batch_index=0, cvfold=0, scale=50,
+                   full_scale=(128, 512), max_npoint=250000, mode=4, device="cuda", stream=None, return_draws=False):
+    """The reference's trainMergeFS on the GPU: returns (support_dict, query_dict, scene_infos) with the reference's
+    keys and dtypes, tensors on the device (spatial_shape a numpy array).  scene_of maps a scene name to its raw [N,8]
+    scene (numpy or device tensor); index is an FSIndex.  rng="reference" consumes Python's random and numpy's legacy
+    stream as the reference does, and no torch draw; rng="device" draws the choices on the host with choice_index and
+    the augmentation with the device Philox, keyed by (seed, batch index).  return_draws adds a fourth value: the query
+    augmentation's draws as train_merge returns them (no colour shift)."""
+    if rng not in ("reference", "device"):
+        raise ValueError("rng: 'reference' or 'device'")
+    if rng == "device" and seed is None:
+        raise ValueError('rng="device" needs a seed')
+    if cvfold not in FOLD:
+        raise ValueError("cvfold: 0 or 1")
+    dev = torch.device(device)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    infos = sample_episode(index, batch_size, cvfold, rng, seed, batch_index)
+    st_obj = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.stream(st_obj):
+        pq, ps, draws = _queue_fs(scene_of, infos, dev, st_obj.cuda_stream, rng, seed, batch_index, scale, full_scale,
+                                  max_npoint, mode, return_draws)
+    query, support = _finish(pq), _finish(ps)
+    return (support, query, infos, draws) if return_draws else (support, query, infos)
+
+
+class FSTrainFeeder:
+    """for support, query, scene_infos in FSTrainFeeder(scenes, index, batch_size=8, seed=7, device="cuda"): ...
+
+    Few-shot episodes (rng="device", batch index = 0, 1, 2, ...) built one episode ahead on the feeder's own stream
+    with TrainFeeder's hand-over: start(i+1) queues every launch of episode i+1 (query and support) and the first half
+    of both voxelisations; finish(i+1), at the next hand-over, reads their sizes from pinned words written by work
+    queued a step earlier, queues the second halves and hands the episode over behind an event.  scene_of maps names to
+    raw [N,8] scenes (resident device tensors: nothing crosses the bus); episodes: how many (None: no end)."""
+
+    def __init__(self, scene_of, index, batch_size, seed, device, episodes=None, **train_merge_fs_kw):
+        for k in ("rng", "return_draws", "batch_index", "seed", "stream"):
+            if k in train_merge_fs_kw:
+                raise TypeError(f"FSTrainFeeder: {k} is set by the feeder")
+        self.kw = dict(scale=50, full_scale=(128, 512), max_npoint=250000, mode=4, cvfold=0)
+        self.kw.update(train_merge_fs_kw)
+        if self.kw["cvfold"] not in FOLD:
+            raise ValueError("cvfold: 0 or 1")
+        self.scene_of, self.index = scene_of, index
+        self.batch_size, self.seed = int(batch_size), int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.episodes = episodes
+        dev = torch.device(device)
+        self.device = dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+        self.stream = torch.cuda.Stream(device=self.device)
+        self.batch_index = 0
+        self.slot = 0
+        pin = lambda n: torch.zeros(n, dtype=torch.int32).pin_memory()  # noqa: E731
+        self.pinned = [((pin(HEAD), pin(3)), (pin(HEAD), pin(3))) for _ in range(3)]
+        self.next = self._start()
+
+    def _start(self):
+        if self.episodes is not None and self.batch_index >= self.episodes:
+            return None
+        kw, bi = self.kw, self.batch_index
+        infos = sample_episode(self.index, self.batch_size, kw["cvfold"], "device", self.seed, bi)
+        with torch.cuda.stream(self.stream):
+            pq, ps, _ = _queue_fs(self.scene_of, infos, self.device, self.stream.cuda_stream, "device", self.seed, bi,
+                                  kw["scale"], kw["full_scale"], kw["max_npoint"], kw["mode"], False,
+                                  self.pinned[self.slot])
+        self.batch_index += 1
+        self.slot = (self.slot + 1) % 3
+        return pq, ps, infos
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        if self.next is None:
+            raise StopIteration
+        pq, ps, infos = self.next
+        query, support = _finish(pq, self.stream), _finish(ps, self.stream)
+        self.next = self._start()
+        return support, query, infos

@@ -10,6 +10,11 @@
 // The coordinate path is fp64 like numpy's; the build compiles with -ffp-contract=off, so no multiply-add is fused
 // that numpy does not fuse.  Per-scene extrema are reduced with integer atomics on order-preserving keys, per-instance
 // sums as int64 fixed point (2^-32): both exact, so the result does not depend on the order the blocks run in.
+//
+// Few-shot episodes (FSInstDataset.trainMergeFS, datasets/scannetv2_fs_inst.py:330-365 and 397-566) reuse every stage
+// of the query up to the crop; the collate kernels take a mode (fs = 1: binary label against the scene's sampled class,
+// scene-local instance ids, raw colours, no instance_infos).  The support scenes take their own three launches
+// (k_sup_*): no augmentation and no crop, xyz = xyz_origin * scale - min, the mask of one instance id.
 #include "common.h"
 
 #define AUG_T 256
@@ -342,10 +347,13 @@ struct LabelLut {
     signed char v[GF_AUG_LUT];  // new label of raw labels 0 .. GF_AUG_LUT-1
 };
 
-__global__ __launch_bounds__(AUG_T) void k_keep(GfAugBatch bt, int fs, LabelLut lut) {
+// fs_mode 0: label through the fold LUT, instances of labels <= 3 dropped; 1: label = (raw label == the scene's
+// sampled class), instances of label 0 dropped (datasets/scannetv2_fs_inst.py:433-434)
+__global__ __launch_bounds__(AUG_T) void k_keep(GfAugBatch bt, int fs, LabelLut lut, int fs_mode) {
     const int y = blockIdx.y;
     long long* r = rec_of(bt.rec, y);
     const long long chosen = r[GF_AUG_R_CHOSEN];
+    const long long cls = r[GF_AUG_R_CLASS];
     double mn[3], o[3] = {0.0, 0.0, 0.0}, fk[3] = {0.0, 0.0, 0.0};
     for (int a = 0; a < 3; a++) mn[a] = dkey_inv((unsigned long long)r[GF_AUG_R_MIN + a]);
     if (chosen >= 0) crop_offset(r, fs, (int)chosen, o, fk);
@@ -364,8 +372,14 @@ __global__ __launch_bounds__(AUG_T) void k_keep(GfAugBatch bt, int fs, LabelLut 
         }
         const long long lab = (long long)bt.raw[p * 8 + 6];
         long long ins = (long long)bt.raw[p * 8 + 7];
-        const int nl = lab == -100 ? 2 : (lab >= 0 && lab < GF_AUG_LUT ? lut.v[lab] : 3);
-        if (nl <= 3) ins = -100;
+        int nl;
+        if (fs_mode) {
+            nl = lab == cls ? 1 : 0;
+            if (nl == 0) ins = -100;
+        } else {
+            nl = lab == -100 ? 2 : (lab >= 0 && lab < GF_AUG_LUT ? lut.v[lab] : 3);
+            if (nl <= 3) ins = -100;
+        }
         if (ins != -100 && (ins < 0 || ins >= bt.max_inst)) {
             err |= GF_AUG_ERR_INST;
             ins = -100;
@@ -380,8 +394,10 @@ __global__ __launch_bounds__(AUG_T) void k_keep(GfAugBatch bt, int fs, LabelLut 
 
 // getCroppedInstLabel (datasets/scannetv2_inst.py:224-232) on the set of present ids, one block: with n ids present
 // the result is {0..n-1}; ids below n keep their value, the largest id fills the lowest hole, the next largest the next
-// hole, ...  Then per scene: instance count, running instance base, batch offsets, kept total.
-__global__ __launch_bounds__(SCAN_THREADS) void k_relabel(GfAugBatch bt) {
+// hole, ...  Then per scene: instance count, running instance base (the scene's first slot of instance_pointnum; also
+// the offset of its instance ids, except with fs_mode, whose ids stay scene-local: datasets/scannetv2_fs_inst.py:442
+// adds total_inst_num, which is never updated), batch offsets, kept total.
+__global__ __launch_bounds__(SCAN_THREADS) void k_relabel(GfAugBatch bt, int fs_mode) {
     __shared__ int holes[GF_AUG_MAX_INST];
     const int per = bt.max_inst / SCAN_THREADS;  // ids per thread (max_inst is a multiple of 32 * SCAN_THREADS / 32)
     long long ibase = 0;
@@ -413,7 +429,8 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_relabel(GfAugBatch bt) {
         __syncthreads();
         if (threadIdx.x == 0) {
             r[GF_AUG_R_NINST] = n;
-            r[GF_AUG_R_IBASE] = ibase;
+            r[GF_AUG_R_IBASE] = fs_mode ? 0 : ibase;
+            r[GF_AUG_R_PBASE] = ibase;
             bt.offsets[s] = bt.start[bt.raw_off[s]];
             err |= (int)r[GF_AUG_R_ERR];
         }
@@ -427,12 +444,13 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_relabel(GfAugBatch bt) {
     }
 }
 
-__global__ __launch_bounds__(AUG_T) void k_collate(GfAugBatch bt) {
+// fs_mode: raw colours (no shift drawn) and only the instance counts (no instance_infos)
+__global__ __launch_bounds__(AUG_T) void k_collate(GfAugBatch bt, int fs_mode) {
     const int y = blockIdx.y;
     const long long* r = rec_of(bt.rec, y);
     const long long ibase = r[GF_AUG_R_IBASE];
     double shift[3];
-    for (int a = 0; a < 3; a++) shift[a] = rec_d(r, GF_AUG_R_SHIFT + a);
+    for (int a = 0; a < 3; a++) shift[a] = fs_mode ? 0.0 : rec_d(r, GF_AUG_R_SHIFT + a);
     const int32_t* map = bt.inst_map + (size_t)y * bt.max_inst;
     long long* st = bt.inst_stats + (size_t)y * bt.max_inst * GF_AUG_STAT;
     double pmn[3] = {INFINITY, INFINITY, INFINITY}, pmx[3] = {-INFINITY, -INFINITY, -INFINITY};
@@ -449,7 +467,7 @@ __global__ __launch_bounds__(AUG_T) void k_collate(GfAugBatch bt) {
             lmax[a] = l > lmax[a] ? l : lmax[a];
             xm[a] = bt.xyz_middle[p * 3 + a];
             bt.locs_float[q * 3 + a] = (float)xm[a];
-            bt.feats[q * 3 + a] = bt.raw[p * 8 + 3 + a] + shift[a];
+            bt.feats[q * 3 + a] = fs_mode ? bt.raw[p * 8 + 3 + a] : bt.raw[p * 8 + 3 + a] + shift[a];
             pmn[a] = fmin(pmn[a], xm[a]);
             pmx[a] = fmax(pmx[a], xm[a]);
         }
@@ -461,7 +479,7 @@ __global__ __launch_bounds__(AUG_T) void k_collate(GfAugBatch bt) {
             bt.sidx[q] = y * bt.max_inst + l;
             long long* sl = st + (size_t)l * GF_AUG_STAT;
             atomicAdd((unsigned long long*)&sl[0], 1ull);
-            for (int a = 0; a < 3; a++) {
+            for (int a = 0; a < 3 && !fs_mode; a++) {
                 atomicAdd((unsigned long long*)&sl[1 + a], (unsigned long long)llrint(xm[a] * 4294967296.0));
                 atomicMin((unsigned long long*)&sl[4 + a], dkey(xm[a]));
                 atomicMax((unsigned long long*)&sl[7 + a], dkey(xm[a]));
@@ -483,26 +501,30 @@ __global__ __launch_bounds__(AUG_T) void k_collate(GfAugBatch bt) {
     }
 }
 
+__device__ __forceinline__ void instance_info_row(const GfAugBatch& bt, long long q) {
+    const int si = bt.sidx[q];
+    float* o = bt.instance_infos + q * 9;
+    if (si < 0) {
+        for (int i = 0; i < 9; i++) o[i] = -100.0f;
+    } else {
+        const long long* sl = bt.inst_stats + (size_t)si * GF_AUG_STAT;
+        const double n = (double)sl[0];
+        for (int a = 0; a < 3; a++) {
+            o[a] = (float)((double)sl[1 + a] * 2.3283064365386963e-10 / n);
+            o[3 + a] = (float)dkey_inv((unsigned long long)sl[4 + a]);
+            o[6 + a] = (float)dkey_inv((unsigned long long)sl[7 + a]);
+        }
+    }
+}
+
 // per kept row: the [9] instance record; rows past the kept count: distinct padding coordinates (batch 0xffff) that
 // voxelise into one voxel each, behind every real voxel; per instance: its point count; per scene: pc_mins / pc_maxs;
 // the spatial shape
-__global__ __launch_bounds__(AUG_T) void k_finish(GfAugBatch bt, int fs_min) {
+__global__ __launch_bounds__(AUG_T) void k_finish(GfAugBatch bt, int fs_min, int fs_mode) {
     const long long N = bt.head[GF_AUG_H_N];
     const long long q = (long long)blockIdx.x * AUG_T + threadIdx.x;
     if (q < N) {
-        const int si = bt.sidx[q];
-        float* o = bt.instance_infos + q * 9;
-        if (si < 0) {
-            for (int i = 0; i < 9; i++) o[i] = -100.0f;
-        } else {
-            const long long* sl = bt.inst_stats + (size_t)si * GF_AUG_STAT;
-            const double n = (double)sl[0];
-            for (int a = 0; a < 3; a++) {
-                o[a] = (float)((double)sl[1 + a] * 2.3283064365386963e-10 / n);
-                o[3 + a] = (float)dkey_inv((unsigned long long)sl[4 + a]);
-                o[6 + a] = (float)dkey_inv((unsigned long long)sl[7 + a]);
-            }
-        }
+        if (!fs_mode) instance_info_row(bt, q);  // (few-shot queries have no instance_infos)
     } else if (q < bt.n_raw) {
         const long long j = q - N;
         bt.locs[q * 4 + 0] = 0xffff;
@@ -514,7 +536,7 @@ __global__ __launch_bounds__(AUG_T) void k_finish(GfAugBatch bt, int fs_min) {
         const int s = (int)(q / bt.max_inst), l = (int)(q % bt.max_inst);
         const long long* r = rec_of(bt.rec, s);
         if (l < r[GF_AUG_R_NINST])
-            bt.instance_pointnum[r[GF_AUG_R_IBASE] + l] = (int32_t)bt.inst_stats[(size_t)q * GF_AUG_STAT];
+            bt.instance_pointnum[r[GF_AUG_R_PBASE] + l] = (int32_t)bt.inst_stats[(size_t)q * GF_AUG_STAT];
     }
     if (q < (long long)bt.B * 3) {
         const int s = (int)(q / 3), a = (int)(q % 3);
@@ -533,6 +555,77 @@ __global__ void k_stats_init(long long* st, long long n) {
     if (i >= n) return;
     const int f = (int)(i % GF_AUG_STAT);
     st[i] = (f >= 4 && f < 7) ? (long long)~0ull : 0;  // count, sums: 0; min keys: largest; max keys: 0 (smallest)
+}
+
+// ======================= few-shot support scenes (load_single(aug=False, support=True)) =======================
+// per scene: the min of xyz_origin * scale (the offset of locs) and the min / max of xyz_origin (pc_mins / pc_maxs)
+__global__ __launch_bounds__(AUG_T) void k_sup_extent(GfAugBatch bt, double scale) {
+    const int y = blockIdx.y;
+    long long* r = rec_of(bt.rec, y);
+    double smn[3] = {INFINITY, INFINITY, INFINITY}, mn[3] = {INFINITY, INFINITY, INFINITY},
+           mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (long long p = bt.raw_off[y] + blockIdx.x * AUG_T + threadIdx.x; p < bt.raw_off[y + 1];
+         p += (long long)gridDim.x * AUG_T) {
+        for (int a = 0; a < 3; a++) {
+            const double x = bt.raw[p * 8 + a];
+            smn[a] = fmin(smn[a], x * scale);
+            mn[a] = fmin(mn[a], x);
+            mx[a] = fmax(mx[a], x);
+        }
+    }
+    for (int a = 0; a < 3; a++) {
+        const double s = wave_min_d(smn[a]), lo = wave_min_d(mn[a]), hi = wave_max_d(mx[a]);
+        if ((threadIdx.x & 63) == 0 && lo <= hi) {
+            atomicMin((unsigned long long*)&r[GF_AUG_R_MIN + a], dkey(s));
+            atomicMin((unsigned long long*)&r[GF_AUG_R_PCMIN + a], dkey(lo));
+            atomicMax((unsigned long long*)&r[GF_AUG_R_PCMAX + a], dkey(hi));
+        }
+    }
+}
+
+// every point is kept, row = raw row: locs (scene, xyz_origin * scale - min truncated), locs_float, raw colours, the
+// mask of the scene's support instance id; the max locs for the spatial shape
+__global__ __launch_bounds__(AUG_T) void k_sup_collate(GfAugBatch bt, long long* __restrict__ masks, double scale) {
+    const int y = blockIdx.y;
+    const long long* r = rec_of(bt.rec, y);
+    const long long id = r[GF_AUG_R_SUPID];
+    double mn[3];
+    for (int a = 0; a < 3; a++) mn[a] = dkey_inv((unsigned long long)r[GF_AUG_R_MIN + a]);
+    long long lmax[3] = {0, 0, 0};
+    for (long long p = bt.raw_off[y] + blockIdx.x * AUG_T + threadIdx.x; p < bt.raw_off[y + 1];
+         p += (long long)gridDim.x * AUG_T) {
+        bt.locs[p * 4] = y;
+        for (int a = 0; a < 3; a++) {
+            const double x = bt.raw[p * 8 + a];
+            const long long l = (long long)(x * scale - mn[a]);
+            bt.locs[p * 4 + 1 + a] = l;
+            lmax[a] = l > lmax[a] ? l : lmax[a];
+            bt.locs_float[p * 3 + a] = (float)x;
+            bt.feats[p * 3 + a] = bt.raw[p * 8 + 3 + a];
+        }
+        masks[p] = (long long)bt.raw[p * 8 + 7] == id ? 1 : 0;
+    }
+    for (int a = 0; a < 3; a++) {
+        const long long lm = wave_max_ll(lmax[a]);
+        if ((threadIdx.x & 63) == 0) atomicMax(&bt.head[GF_AUG_H_LMAX + a], (int)lm);
+    }
+}
+
+// batch offsets (the raw ones), pc_mins / pc_maxs, spatial shape, head: N = n_raw, no instances, no padding rows
+__global__ __launch_bounds__(AUG_T) void k_sup_finish(GfAugBatch bt, int fs_min) {
+    const long long q = (long long)blockIdx.x * AUG_T + threadIdx.x;
+    if (q <= bt.B) bt.offsets[q] = (int32_t)bt.raw_off[q];
+    if (q < (long long)bt.B * 3) {
+        const int s = (int)(q / 3), a = (int)(q % 3);
+        const long long* r = rec_of(bt.rec, s);
+        bt.pc_mins[q] = (float)dkey_inv((unsigned long long)r[GF_AUG_R_PCMIN + a]);
+        bt.pc_maxs[q] = (float)dkey_inv((unsigned long long)r[GF_AUG_R_PCMAX + a]);
+    }
+    if (q < 3) {
+        const int e = bt.head[GF_AUG_H_LMAX + q] + 1;
+        bt.head[GF_AUG_H_SHAPE + q] = e > fs_min ? e : fs_min;
+    }
+    if (q == 0) bt.head[GF_AUG_H_N] = bt.n_raw;
 }
 
 int grid_x(int max_scene_points) {
@@ -610,10 +703,40 @@ extern "C" int gf_aug_crop(const GfAugBatch* b, int s0, int ns, int full_scale, 
     return GF_OK;
 }
 
+namespace {
+
+int collate_impl(const GfAugBatch* b, const LabelLut& lut, int fs_mode, int full_scale_min, int full_scale,
+                 int max_scene_points, hipStream_t st) {
+    const long long nstat = (long long)b->B * b->max_inst * GF_AUG_STAT;
+    GF_TRY(hipMemsetAsync(b->bitmap, 0, (size_t)b->B * (b->max_inst / 32) * 4, st));
+    GF_TRY(hipMemsetAsync(b->head, 0, GF_AUG_HEAD * 4, st));
+    hipLaunchKernelGGL(k_stats_init, dim3(gf_div_up(nstat, 256)), dim3(256), 0, st, b->inst_stats, nstat);
+    const dim3 gp(grid_x(max_scene_points), b->B);
+    hipLaunchKernelGGL(k_keep, gp, dim3(AUG_T), 0, st, *b, full_scale, lut, fs_mode);
+    if (b->n_raw > 0) {
+        gf_iscan(b->flags, b->n_raw, b->start, b->cursor, b->block_sums, b->block_off, st);
+    } else {
+        GF_TRY(hipMemsetAsync(b->start, 0, 4, st));
+    }
+    hipLaunchKernelGGL(k_relabel, dim3(1), dim3(SCAN_THREADS), 0, st, *b, fs_mode);
+    hipLaunchKernelGGL(k_collate, gp, dim3(AUG_T), 0, st, *b, fs_mode);
+    long long nq = b->n_raw;
+    if (nq < (long long)b->B * b->max_inst) nq = (long long)b->B * b->max_inst;
+    hipLaunchKernelGGL(k_finish, dim3(gf_div_up(nq > 3 ? nq : 3, AUG_T)), dim3(AUG_T), 0, st, *b, full_scale_min,
+                       fs_mode);
+    return GF_OK;
+}
+
+bool collate_args_ok(const GfAugBatch* b) {
+    return b && b->B > 0 && b->n_raw >= 0 && b->max_inst > 0 && b->max_inst <= GF_AUG_MAX_INST &&
+           b->max_inst % SCAN_THREADS == 0;
+}
+
+}  // namespace
+
 extern "C" int gf_aug_collate(const GfAugBatch* b, const int32_t* fold_classes, int n_fold, int full_scale_min,
                               int full_scale, int max_scene_points, void* stream) {
-    GF_CHECK_ARG(b && b->B > 0 && b->n_raw >= 0 && b->max_inst > 0 && b->max_inst <= GF_AUG_MAX_INST &&
-                     b->max_inst % SCAN_THREADS == 0 && fold_classes && n_fold >= 0,
+    GF_CHECK_ARG(collate_args_ok(b) && fold_classes && n_fold >= 0,
                  "gf_aug_collate: bad arguments (B %d, n_raw %d, max_inst %d)", b ? b->B : 0, b ? b->n_raw : 0,
                  b ? b->max_inst : 0);
     LabelLut lut;  // datasets/scannetv2_inst.py:314-324: 0 -> 0, 1 -> 1, fold class i -> i + 4, -100 -> 2, else 3
@@ -624,23 +747,35 @@ extern "C" int gf_aug_collate(const GfAugBatch* b, const int32_t* fold_classes, 
         GF_CHECK_ARG(fold_classes[i] >= 0 && fold_classes[i] < GF_AUG_LUT && i + 4 < 127, "gf_aug_collate: fold class");
         lut.v[fold_classes[i]] = (signed char)(i + 4);
     }
-    hipStream_t st = (hipStream_t)stream;
-    const long long nstat = (long long)b->B * b->max_inst * GF_AUG_STAT;
-    GF_TRY(hipMemsetAsync(b->bitmap, 0, (size_t)b->B * (b->max_inst / 32) * 4, st));
-    GF_TRY(hipMemsetAsync(b->head, 0, GF_AUG_HEAD * 4, st));
-    hipLaunchKernelGGL(k_stats_init, dim3(gf_div_up(nstat, 256)), dim3(256), 0, st, b->inst_stats, nstat);
-    const dim3 gp(grid_x(max_scene_points), b->B);
-    hipLaunchKernelGGL(k_keep, gp, dim3(AUG_T), 0, st, *b, full_scale, lut);
-    if (b->n_raw > 0) {
-        gf_iscan(b->flags, b->n_raw, b->start, b->cursor, b->block_sums, b->block_off, st);
-    } else {
-        GF_TRY(hipMemsetAsync(b->start, 0, 4, st));
-    }
-    hipLaunchKernelGGL(k_relabel, dim3(1), dim3(SCAN_THREADS), 0, st, *b);
-    hipLaunchKernelGGL(k_collate, gp, dim3(AUG_T), 0, st, *b);
-    long long nq = b->n_raw;
-    if (nq < (long long)b->B * b->max_inst) nq = (long long)b->B * b->max_inst;
-    hipLaunchKernelGGL(k_finish, dim3(gf_div_up(nq > 3 ? nq : 3, AUG_T)), dim3(AUG_T), 0, st, *b, full_scale_min);
+    const int rc = collate_impl(b, lut, 0, full_scale_min, full_scale, max_scene_points, (hipStream_t)stream);
+    if (rc != GF_OK) return rc;
     GF_CHECK_LAUNCH("gf_aug_collate");
+    return GF_OK;
+}
+
+extern "C" int gf_aug_collate_fs(const GfAugBatch* b, int full_scale_min, int full_scale, int max_scene_points,
+                                 void* stream) {
+    GF_CHECK_ARG(collate_args_ok(b), "gf_aug_collate_fs: bad arguments (B %d, n_raw %d, max_inst %d)", b ? b->B : 0,
+                 b ? b->n_raw : 0, b ? b->max_inst : 0);
+    LabelLut unused;
+    for (int i = 0; i < GF_AUG_LUT; i++) unused.v[i] = 0;
+    const int rc = collate_impl(b, unused, 1, full_scale_min, full_scale, max_scene_points, (hipStream_t)stream);
+    if (rc != GF_OK) return rc;
+    GF_CHECK_LAUNCH("gf_aug_collate_fs");
+    return GF_OK;
+}
+
+extern "C" int gf_aug_support(const GfAugBatch* b, long long* support_masks, double scale, int full_scale_min,
+                              int max_scene_points, void* stream) {
+    GF_CHECK_ARG(b && b->B > 0 && b->n_raw >= 0 && support_masks, "gf_aug_support: bad arguments (B %d, n_raw %d)",
+                 b ? b->B : 0, b ? b->n_raw : 0);
+    hipStream_t st = (hipStream_t)stream;
+    GF_TRY(hipMemsetAsync(b->head, 0, GF_AUG_HEAD * 4, st));
+    const dim3 gp(grid_x(max_scene_points), b->B);
+    hipLaunchKernelGGL(k_sup_extent, gp, dim3(AUG_T), 0, st, *b, scale);
+    hipLaunchKernelGGL(k_sup_collate, gp, dim3(AUG_T), 0, st, *b, support_masks, scale);
+    const int nq = 3 * b->B + 1;
+    hipLaunchKernelGGL(k_sup_finish, dim3(gf_div_up(nq, AUG_T)), dim3(AUG_T), 0, st, *b, full_scale_min);
+    GF_CHECK_LAUNCH("gf_aug_support");
     return GF_OK;
 }

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GF_ABI_VERSION 6
+#define GF_ABI_VERSION 7
 
 typedef enum {
     GF_OK = 0,
@@ -884,7 +884,10 @@ enum {
     GF_AUG_R_M = 0, GF_AUG_R_SHIFT = 9, GF_AUG_R_FLIP = 12, GF_AUG_R_THETA = 13, GF_AUG_R_AMAX0 = 14,
     GF_AUG_R_AMAX1 = 17, GF_AUG_R_MIN = 20, GF_AUG_R_MAX = 23, GF_AUG_R_CHOSEN = 26, GF_AUG_R_ERR = 27,
     GF_AUG_R_CAP0 = 28, GF_AUG_R_BASE0 = 29, GF_AUG_R_CAP1 = 30, GF_AUG_R_BASE1 = 31, GF_AUG_R_PCMIN = 32,
-    GF_AUG_R_PCMAX = 35, GF_AUG_R_NINST = 38, GF_AUG_R_IBASE = 39, GF_AUG_R_COUNTS = 64, GF_AUG_R_CROPU = 128
+    GF_AUG_R_PCMAX = 35, GF_AUG_R_NINST = 38, GF_AUG_R_IBASE = 39, GF_AUG_R_COUNTS = 64, GF_AUG_R_CROPU = 128,
+    /* ABI 7: first instance_pointnum slot of the scene (== IBASE except in few-shot queries, whose ids stay local);
+     * few-shot query: the scene's sampled class; few-shot support: the support instance id (both set by the caller) */
+    GF_AUG_R_PBASE = 40, GF_AUG_R_CLASS = 41, GF_AUG_R_SUPID = 42
 };
 enum { GF_AUG_H_N = 0, GF_AUG_H_NINST = 1, GF_AUG_H_ERR = 2, GF_AUG_H_LMAX = 3, GF_AUG_H_SHAPE = 6 };
 enum { GF_AUG_ERR_CELLS = 1, GF_AUG_ERR_INST = 2 };
@@ -938,6 +941,20 @@ int gf_aug_crop(const GfAugBatch* b, int s0, int ns, int full_scale, int K, long
 /* all scenes: kept points in order, label remap (fold_classes: HOST int32[n_fold]), getCroppedInstLabel, per-instance
  * statistics, the collate's outputs, head */
 int gf_aug_collate(const GfAugBatch* b, const int32_t* fold_classes, int n_fold, int full_scale_min, int full_scale,
+                   int max_scene_points, void* stream);
+
+/* Few-shot episodes (datasets/scannetv2_fs_inst.py:330-365, 397-566 FSInstDataset.trainMergeFS; ABI 7).
+ * Query: gf_aug_draw / _transform / _elastic / _crop as above, then gf_aug_collate_fs instead of gf_aug_collate:
+ *   labels = (raw label == rec[s][GF_AUG_R_CLASS]) as 0/1, instances of label 0 -> -100, getCroppedInstLabel per scene
+ *   with scene-local ids (the reference's offset total_inst_num stays 0), instance_pointnum concatenated over the scenes,
+ *   feats = raw colours (no shift), instance_infos not written (may be NULL).
+ * Support: gf_aug_support on a batch of raw support scenes (no draws, no crop; rec: GF_AUG_R_MIN / _PCMIN initialised to
+ *   -1, _PCMAX to 0, GF_AUG_R_SUPID set): locs = (scene, trunc(xyz * scale - min(xyz * scale))), locs_float, feats,
+ *   support_masks int64 [n_raw] = (instance == rec[s][GF_AUG_R_SUPID]), offsets = raw_off, pc_mins / pc_maxs of xyz,
+ *   head N = n_raw (no padding rows), max locs and spatial shape.  Uses raw, raw_off, rec, locs, locs_float, feats,
+ *   offsets, pc_mins, pc_maxs, head of b. */
+int gf_aug_collate_fs(const GfAugBatch* b, int full_scale_min, int full_scale, int max_scene_points, void* stream);
+int gf_aug_support(const GfAugBatch* b, long long* support_masks, double scale, int full_scale_min,
                    int max_scene_points, void* stream);
 
 #ifdef __cplusplus
