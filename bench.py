@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: scenes/sec of the GeoFormer eval forward on ScanNet-like scenes.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (--dump-outputs: the outputs of the last timed step as DIR/<name>.npy, see dump_outputs; N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run does what the headline figure needs and nothing more: it sets up, warms up, times the K steps, writes the
+dump if asked and prints the JSON line.  ``--full`` adds every measurement that takes work of its own after the timed
+steps (the untimed roofline passes, the secondary workloads, the CPU baseline and the parity legs listed below); the
+headline figure and the dump are the same either way.
 
 A "step" is one full ``GeoFormer.forward(batch, epoch, training=False)`` over one ~150k-point synthetic
 scene (BASELINE.json configs[1]; test yaml: nq=256, nc=2048, batch 1) with the batch dict already
@@ -12,7 +17,7 @@ kNN graph + geodesic BFS, 4 decoder layers, dynamic-conv mask head, proposals.  
 copy of the accepted-proposal count is queued -- ``defer_proposals`` -- and its proposals are collected after scene i+1
 has been issued).  ``--staggered``: the serving loop of geoformer_amd/serving.py instead (two scenes in flight on two
 streams: scene i's decoder + mask head under scene i+1's sampling / BFS stretch); it is timed as
-``secondary.staggered_two_in_flight`` in the default run -- it wins on some boxes and loses on others, so it
+``secondary.staggered_two_in_flight`` under ``--full`` -- it wins on some boxes and loses on others, so it
 is not the headline.  Either way all K scenes, proposals included, are complete inside the timed region.  The steps rotate over
 ``--scenes`` (8) different resident scenes (seeds 1234, 1235, ...), so no step finds the previous step's
 tables or features in L2/MALL.  Weights are random-init of the real architecture (no checkpoints
@@ -23,7 +28,11 @@ scaling "weak").
 The JSON line also carries
   roofline       -- the level-1 (C=16) gather-MFMA sparse-conv launches, HBM-bound: algorithmic bytes
                     4*(R*Cin + M*Cout + K*Cin*Cout) + 8*R per launch / mean launch time from HIP events
-                    recorded natively around those launches inside the timed region;
+                    recorded natively around those launches inside the timed region (under --full: the whole conv
+                    family of roofline_convs, with this level-1 figure inside as level1_16to16);
+  host_busy_ms_per_step -- the host's own cost per step in the timed loop.
+
+With --full (--no-secondary / --no-cpu-baseline drop those legs of it) it further carries
   roofline_convs -- all 71 sparse convolutions of a forward: sum of their algorithmic bytes / sum of their
                     spans (events around every conv call, separate untimed pass);
   parity_s150k   -- max-abs differences between that host forward and the GPU forward of the same scene under
@@ -1093,8 +1102,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--points", type=int, default=150_000)
     ap.add_argument("--scenes", type=int, default=8, help="resident scenes the steps rotate over")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the untimed roofline passes, the secondary workloads, the CPU baseline "
+                         "and the parity legs (off: only what the headline figure needs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and parity legs")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the secondary workloads")
     ap.add_argument("--no-ahead", action="store_true",
                     help="rulebooks behind the caller's stream like every other launch (default: ahead of it, see --help of DESIGN.md 7)")
     ap.add_argument("--staggered", dest="pipeline", action="store_true",
@@ -1250,7 +1262,7 @@ def main():
             "ahead": not args.no_ahead, "bias_shift": model._bench_bias_shift})
 
     dp = None
-    if world > 1 and not args.no_secondary:
+    if args.full and world > 1 and not args.no_secondary:
         # BASELINE config 5: every rank a batch of 4 scenes, bucketed gradient all-reduce over RCCL (all ranks take part)
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import train_dp
@@ -1297,11 +1309,13 @@ def main():
                                               "Python + launch cost of a scene; N ranks share one host's cores"},
         }
         l1 = probe.result()
-        fam = res["roofline_convs"] = all_convs_roofline(model, batches)
         if l1 is not None and l1.get("traffic"):
             # what the level-1 launch really moves at the memory side (PMC: FETCH_SIZE x 2 + WRITE_SIZE), against the same clock
             l1["actual_hbm_frac"] = round(l1["traffic"] / (l1["us_per_launch"] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)
-        if fam is not None:
+        # a plain run quotes the level-1 launches it probed inside its own timed steps; the family takes passes of its own
+        res["roofline"] = l1
+        if args.full:
+            fam = res["roofline_convs"] = all_convs_roofline(model, batches)
             # the headline object is the FAMILY -- the 71 sparse convolutions of a forward, the north star's ">= 50 % of the
             # binding roofline" -- with the level-1 16 -> 16 launch (the family's best kernel, 2-3 % of device time) beside it
             res["roofline"] = {
@@ -1320,12 +1334,10 @@ def main():
                 "compulsory_note": "4 (M_in Cin + M_out Cout) per launch: every element read / written once (SURVEY 8d)",
                 "level1_16to16": l1,
             }
-        else:
-            res["roofline"] = l1
-        res.update(op_rooflines(model, batches))
+            res.update(op_rooflines(model, batches))
         if dp is not None:
             res.setdefault("secondary", {})["train_dp_step"] = dp
-        if not args.no_secondary and world == 1:
+        if args.full and not args.no_secondary and world == 1:
             m128 = build_model(dev, bias_shift=model._bench_bias_shift, cfg_name="geoformer_scannet.yaml")
             k = min(args.steps, 16)
             for i in range(max(min(args.warmup, 4), ns)):  # every scene once: one-time costs per (model, scene) stay out
@@ -1373,7 +1385,7 @@ def main():
             res["secondary"]["train_step_b4"] = secondary_train_step_b4(dev)
             res["secondary"].update(secondary_few_shot(dev))
             torch.cuda.empty_cache()
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"], res["parity_s150k"], cal = cpu_baseline_and_parity(model, batches[0], dev)
             if cal is not None:
                 res["parity_s150k_calibrated"] = cal
