@@ -186,6 +186,8 @@ def _declare(lib):
         "gf_aug_collate": (I, [P, P, I, I, I, I, P]),
         "gf_aug_collate_fs": (I, [P, I, I, I, P]),
         "gf_aug_support": (I, [P, P, ctypes.c_double, I, I, P]),
+        "gf_aug_test_query": (I, [P, ctypes.c_double, I, I, P]),
+        "gf_aug_support_block": (I, [P, P, P, ctypes.c_double, I, I, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

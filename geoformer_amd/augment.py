@@ -41,11 +41,12 @@ R_M, R_SHIFT, R_FLIP, R_THETA, R_AMAX0, R_AMAX1 = 0, 9, 12, 13, 14, 17
 R_MIN, R_MAX, R_CHOSEN, R_ERR, R_CAP0, R_BASE0, R_CAP1, R_BASE1 = 20, 23, 26, 27, 28, 29, 30, 31
 R_PCMIN, R_PCMAX, R_NINST, R_IBASE, R_COUNTS, R_CROPU = 32, 35, 38, 39, 64, 128
 R_PBASE, R_CLASS, R_SUPID = 40, 41, 42
+R_BMIN, R_BMAX, R_BCNT, R_BLMAX = 43, 46, 49, 50
 H_N, H_NINST, H_ERR, H_SHAPE = 0, 1, 2, 6
 HEAD = 16
 MAX_INST = 4096
 MAX_CROP = 64
-ERR_CELLS, ERR_INST = 1, 2
+ERR_CELLS, ERR_INST, ERR_NOINST = 1, 2, 4
 NORMAL_MAX = 6.67  # |Box-Muller normal| from 32-bit uniforms: sqrt(2 ln 2^32) = 6.66
 
 # datasets/scannetv2.py: the training classes of the two folds
@@ -268,7 +269,7 @@ def _finish(p, stream=None):
         if p.kind == "fs_query":
             batch.update(labels=o["labels"][:N], instance_labels=o["instance_labels"][:N],
                          instance_pointnum=o["instance_pointnum"][:ninst])
-        else:
+        elif p.kind == "fs_support":
             batch["support_masks"] = o["support_masks"][:N]
         batch.update(spatial_shape=shape, batch_offsets=o["offsets"], pc_mins=o["pc_mins"], pc_maxs=o["pc_maxs"])
     if work is not cur:
@@ -757,3 +758,176 @@ class FSTrainFeeder:
         query, support = _finish(pq, self.stream), _finish(ps, self.stream)
         self.next = self._start()
         return support, query, infos
+
+
+# ============================== few-shot test time (FSInstDataset.testMergeFS) ==============================
+# datasets/scannetv2_fs_inst.py:568-700 per val scene: the query (load_single(aug=False, val=True): no crop), and, without
+# fix_support, per active label the block support of its (scene, instance id) (load_single_block with get_region_inst,
+# scale_factor 1).  test_fs.py's full-scene supports (fix_support) are full_scene_supports below.
+
+def _keys_to_f64(keys):
+    """Order-preserving keys of csrc/augment.hip (int64 device tensor) back to the doubles, on the device."""
+    k = torch.where(keys < 0, keys & 0x7FFFFFFFFFFFFFFF, ~keys)  # top bit set: the key of a non-negative double
+    return k.contiguous().view(torch.float64)
+
+
+def _device_of(device):
+    dev = torch.device(device)
+    return dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def _voxelise_tail(p, locs, n, mode, M_pad, max_active, stream):
+    """Second half of a voxelisation queued by _voxelise_count on `locs` [n, 4] (its sizes already read)."""
+    lib = _lib.load()
+    max_active = max(max_active, 1)
+    dev = locs.device
+    out_coords = torch.empty((max(M_pad, 0), 4), dtype=torch.int64, device=dev)
+    out_map = torch.empty((max(M_pad, 0), max_active + 1), dtype=torch.int32, device=dev)
+    check(lib.gf_voxelize_idx_fill(ptr(locs), n, 4, int(mode), ptr(p.vscratch), ptr(p.input_map), M_pad, max_active,
+                                   ptr(out_coords), ptr(out_map), stream), "gf_voxelize_idx_fill")
+    return out_coords, out_map
+
+
+def _queue_test_query(scene, dev, st, scale, full_scale, mode):
+    """The few-shot test query of one raw scene: gf_aug_test_query and the first half of the voxelisation."""
+    lib = _lib.load()
+    raw, sizes = _raw_upload([scene], dev)
+    bt = _Batch(raw, sizes, dev, (1, 1), max_inst=SUPPORT_MAX_INST)
+    bt.rec.copy_(torch.from_numpy(_rec_init(1)).pin_memory(), non_blocking=True)
+    check(lib.gf_aug_test_query(bt.ref, float(scale), int(full_scale[0]), bt.max_scene, st), "gf_aug_test_query")
+    return _queue_handover(bt, mode, st, None, "fs_test_query")
+
+
+def _finish_test_query(p):
+    """The query dict of testMergeFS (its key order and dtypes: float32 feats, float64 [1,3] pc_mins / pc_maxs)."""
+    bt = p.bt
+    b = _finish(p)
+    rec = bt.rec[0]
+    return {"voxel_locs": b["voxel_locs"], "p2v_map": b["p2v_map"], "v2p_map": b["v2p_map"], "locs": b["locs"],
+            "locs_float": b["locs_float"], "feats": b["feats"].float(), "spatial_shape": b["spatial_shape"],
+            "batch_offsets": b["batch_offsets"],
+            "pc_mins": _keys_to_f64(rec[R_PCMIN:R_PCMIN + 3]).unsqueeze(0),
+            "pc_maxs": _keys_to_f64(rec[R_PCMAX:R_PCMAX + 3]).unsqueeze(0),
+            "labels": bt.out["labels"][:b["locs"].shape[0]]}
+
+
+class _Range:
+    """One scene's raw range of a batch, with the attributes _voxelise_count reads."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def support_blocks(scene_of, pairs, *, scale=50, full_scale_support=(64, 128), mode=4, device="cuda", stream=None):
+    """load_single_block(scene, id, aug=False, permutate=False) + testMergeFS's support dict for every (scene name,
+    instance id) pair, as one batch (gf_aug_support_block) with one synchronisation for all the sizes.  Returns the list
+    of support dicts in the reference's key order and dtypes.  An id without points in its scene raises
+    GeoFormerHipError (the reference fails inside np.min)."""
+    lib = _lib.load()
+    dev = _device_of(device)
+    if not pairs:
+        return []
+    st_obj = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.stream(st_obj):
+        st = st_obj.cuda_stream
+        raw, sizes = _raw_upload([scene_of[s] for s, _ in pairs], dev)
+        bt = _Batch(raw, sizes, dev, (1, 1), max_inst=SUPPORT_MAX_INST)
+        masks = torch.empty(bt.n, dtype=torch.int64, device=dev)
+        scene_sizes = torch.empty((bt.B, 5), dtype=torch.int32, device=dev)
+        rec = _rec_init(bt.B)
+        rec[:, R_SUPID] = np.asarray([i for _, i in pairs], np.int64)
+        rec[:, R_BMIN:R_BMIN + 3] = -1
+        bt.rec.copy_(torch.from_numpy(rec).pin_memory(), non_blocking=True)
+        check(lib.gf_aug_support_block(bt.ref, ptr(masks), ptr(scene_sizes), float(scale), int(full_scale_support[0]),
+                                       bt.max_scene, st), "gf_aug_support_block")
+        off = bt.off_host
+        pend = []
+        for s in range(bt.B):  # each scene's raw range voxelises on its own (padding rows behind its kept points)
+            locs = bt.out["locs"][off[s]:off[s + 1]]
+            sub = _Range(out={"locs": locs}, n=int(sizes[s]), device=dev)
+            pend.append((_voxelise_count(sub, mode, st), locs))
+        host = torch.empty(HEAD + bt.B * 5 + 3 * bt.B, dtype=torch.int32).pin_memory()
+        host[:HEAD].copy_(bt.head, non_blocking=True)
+        host[HEAD:HEAD + bt.B * 5].copy_(scene_sizes.view(-1), non_blocking=True)
+        vh = host[HEAD + bt.B * 5:]
+        for s, (p, _) in enumerate(pend):
+            vh[3 * s:3 * s + 3].copy_(p.vhead, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record(st_obj)
+    done.synchronize()  # the batch's one synchronisation
+    h = host.tolist()
+    if h[H_ERR]:
+        raise _lib.GeoFormerHipError(
+            "support_blocks: " + ("a support instance id has no point in its scene" if h[H_ERR] & ERR_NOINST else
+                                  f"error bits {h[H_ERR]}"))
+    out = []
+    with torch.cuda.stream(st_obj):
+        st = st_obj.cuda_stream
+        pcmin = _keys_to_f64(bt.rec[:, R_PCMIN:R_PCMIN + 3])
+        pcmax = _keys_to_f64(bt.rec[:, R_PCMAX:R_PCMAX + 3])
+        for s, (p, locs) in enumerate(pend):
+            kept, ninst = h[HEAD + 5 * s], h[HEAD + 5 * s + 1]
+            shape = np.asarray(h[HEAD + 5 * s + 2:HEAD + 5 * s + 5], np.int64)
+            M_pad, max_active, verr = h[HEAD + 5 * bt.B + 3 * s:HEAD + 5 * bt.B + 3 * s + 3]
+            if verr:
+                raise _lib.GeoFormerHipError("support_blocks: a voxel coordinate lies outside [0, 65535]")
+            n = int(sizes[s])
+            coords, vmap = _voxelise_tail(p, locs, n, mode, M_pad, max_active, st)
+            M = M_pad - (n - kept)
+            r0 = int(off[s])
+            out.append({
+                "voxel_locs": coords[:M], "p2v_map": p.input_map[:kept], "v2p_map": vmap[:M], "locs": locs[:kept],
+                "locs_float": bt.out["locs_float"][r0:r0 + kept], "feats": bt.out["feats"][r0:r0 + kept].float(),
+                "support_masks": masks[r0:r0 + kept], "spatial_shape": shape,
+                "batch_offsets": torch.tensor([0, kept], dtype=torch.int32, device=dev),
+                "mask_offsets": torch.tensor([0, ninst], dtype=torch.int32, device=dev),
+                "pc_mins": pcmin[s:s + 1], "pc_maxs": pcmax[s:s + 1]})
+    return out
+
+
+def full_scene_supports(scene_of, pairs, *, scale=50, full_scale=(128, 512), mode=4, device="cuda", stream=None):
+    """The support dict load_set_support builds (test_fs.py:61-108: load_single(aug=False, val=True, support=True), the
+    spatial shape clipped at full_scale[0]) for a BATCH of (scene name, instance id) pairs: one dict with batch index =
+    position, ready for process_support with B = len(pairs).  Keys: the reference's (mask_offsets = running counts of
+    the masks, int32 [B+1]) plus pc_mins / pc_maxs."""
+    dev = _device_of(device)
+    st_obj = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.stream(st_obj):
+        p = _queue_support([scene_of[s] for s, _ in pairs], [i for _, i in pairs], dev, st_obj.cuda_stream, scale,
+                           full_scale, mode)
+    d = _finish(p)
+    counts = torch.zeros(len(pairs) + 1, dtype=torch.int64, device=dev)
+    bidx = d["locs"][:, 0]
+    counts[1:] = torch.bincount(bidx[d["support_masks"] == 1], minlength=len(pairs))
+    return {"voxel_locs": d["voxel_locs"], "p2v_map": d["p2v_map"], "v2p_map": d["v2p_map"], "locs": d["locs"],
+            "locs_float": d["locs_float"], "feats": d["feats"].float(), "support_masks": d["support_masks"],
+            "spatial_shape": d["spatial_shape"], "batch_offsets": d["batch_offsets"],
+            "mask_offsets": counts.cumsum(0).to(torch.int32), "pc_mins": d["pc_mins"], "pc_maxs": d["pc_maxs"]}
+
+
+def test_merge_fs(scene_of, test_set, name, *, fix_support=True, cvfold=0, scale=50, full_scale=(128, 512),
+                  full_scale_support=(64, 128), mode=4, device="cuda", stream=None):
+    """The reference's testMergeFS for val scene `name` on the GPU: (is_valid, list_support_dicts, query_dict,
+    scene_infos) with its keys, values and dtypes (tensors on the device, spatial_shape a numpy array).  test_set: a
+    fs_eval.FSTestSet (its combinations give the active labels and, without fix_support, each label's (scene, id)).
+    A scene without active label gives (False, {}, {}, {}) as the reference does."""
+    if cvfold not in FOLD:
+        raise ValueError("cvfold: 0 or 1")
+    comb = test_set.combination(name)
+    active = list(comb["active_label"])
+    if not active:
+        return False, {}, {}, {}
+    dev = _device_of(device)
+    infos = {"query_scene": name, "active_label": active}
+    st_obj = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.stream(st_obj):
+        pq = _queue_test_query(scene_of[name], dev, st_obj.cuda_stream, scale, full_scale, mode)
+    query = _finish_test_query(pq)
+    if fix_support:
+        return True, [None] * len(active), query, infos
+    pairs = [tuple(comb[l]) for l in active]
+    for l, t in zip(active, pairs):
+        infos[l] = t
+    sups = support_blocks(scene_of, pairs, scale=scale, full_scale_support=full_scale_support, mode=mode, device=dev,
+                          stream=stream)
+    return True, sups, query, infos

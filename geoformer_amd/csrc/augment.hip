@@ -559,13 +559,15 @@ __global__ void k_stats_init(long long* st, long long n) {
 
 // ======================= few-shot support scenes (load_single(aug=False, support=True)) =======================
 // per scene: the min of xyz_origin * scale (the offset of locs) and the min / max of xyz_origin (pc_mins / pc_maxs)
-__global__ __launch_bounds__(AUG_T) void k_sup_extent(GfAugBatch bt, double scale) {
+// (keep: the test-time block supports' in-box flags, NULL: every point)
+__global__ __launch_bounds__(AUG_T) void k_sup_extent(GfAugBatch bt, double scale, const int32_t* __restrict__ keep) {
     const int y = blockIdx.y;
     long long* r = rec_of(bt.rec, y);
     double smn[3] = {INFINITY, INFINITY, INFINITY}, mn[3] = {INFINITY, INFINITY, INFINITY},
            mx[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (long long p = bt.raw_off[y] + blockIdx.x * AUG_T + threadIdx.x; p < bt.raw_off[y + 1];
          p += (long long)gridDim.x * AUG_T) {
+        if (keep && !keep[p]) continue;
         for (int a = 0; a < 3; a++) {
             const double x = bt.raw[p * 8 + a];
             smn[a] = fmin(smn[a], x * scale);
@@ -584,8 +586,10 @@ __global__ __launch_bounds__(AUG_T) void k_sup_extent(GfAugBatch bt, double scal
 }
 
 // every point is kept, row = raw row: locs (scene, xyz_origin * scale - min truncated), locs_float, raw colours, the
-// mask of the scene's support instance id; the max locs for the spatial shape
-__global__ __launch_bounds__(AUG_T) void k_sup_collate(GfAugBatch bt, long long* __restrict__ masks, double scale) {
+// mask of the scene's support instance id (masks != NULL) or the raw semantic label (the few-shot test query,
+// labels != NULL); the max locs for the spatial shape
+__global__ __launch_bounds__(AUG_T) void k_sup_collate(GfAugBatch bt, long long* __restrict__ masks,
+                                                       long long* __restrict__ labels, double scale) {
     const int y = blockIdx.y;
     const long long* r = rec_of(bt.rec, y);
     const long long id = r[GF_AUG_R_SUPID];
@@ -603,7 +607,8 @@ __global__ __launch_bounds__(AUG_T) void k_sup_collate(GfAugBatch bt, long long*
             bt.locs_float[p * 3 + a] = (float)x;
             bt.feats[p * 3 + a] = bt.raw[p * 8 + 3 + a];
         }
-        masks[p] = (long long)bt.raw[p * 8 + 7] == id ? 1 : 0;
+        if (masks) masks[p] = (long long)bt.raw[p * 8 + 7] == id ? 1 : 0;
+        if (labels) labels[p] = (long long)bt.raw[p * 8 + 6];
     }
     for (int a = 0; a < 3; a++) {
         const long long lm = wave_max_ll(lmax[a]);
@@ -626,6 +631,131 @@ __global__ __launch_bounds__(AUG_T) void k_sup_finish(GfAugBatch bt, int fs_min)
         bt.head[GF_AUG_H_SHAPE + q] = e > fs_min ? e : fs_min;
     }
     if (q == 0) bt.head[GF_AUG_H_N] = bt.n_raw;
+}
+
+// ======================= few-shot test-time block supports (load_single_block, get_region_inst) =======================
+// datasets/scannetv2_fs_inst.py:277-309 and 365-395 with scale_factor 1, no augmentation, no permutation.  One batch holds
+// B (scene, instance id) pairs; the kept points of scene y are compacted in order to the front of its own raw range
+// (rows raw_off[y] ..), the rest of the range holds padding coordinates, so every scene voxelises on its own.
+
+// per scene: the fp64 min / max of the support instance's points and their count
+__global__ __launch_bounds__(AUG_T) void k_blk_inst(GfAugBatch bt) {
+    const int y = blockIdx.y;
+    long long* r = rec_of(bt.rec, y);
+    const long long id = r[GF_AUG_R_SUPID];
+    double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    long long cnt = 0;
+    for (long long p = bt.raw_off[y] + blockIdx.x * AUG_T + threadIdx.x; p < bt.raw_off[y + 1];
+         p += (long long)gridDim.x * AUG_T) {
+        if ((long long)bt.raw[p * 8 + 7] != id) continue;
+        cnt++;
+        for (int a = 0; a < 3; a++) {
+            const double x = bt.raw[p * 8 + a];
+            mn[a] = fmin(mn[a], x);
+            mx[a] = fmax(mx[a], x);
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d, 64);
+    for (int a = 0; a < 3; a++) {
+        const double lo = wave_min_d(mn[a]), hi = wave_max_d(mx[a]);
+        if ((threadIdx.x & 63) == 0 && lo <= hi) {
+            atomicMin((unsigned long long*)&r[GF_AUG_R_BMIN + a], dkey(lo));
+            atomicMax((unsigned long long*)&r[GF_AUG_R_BMAX + a], dkey(hi));
+        }
+    }
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd((unsigned long long*)&r[GF_AUG_R_BCNT], (unsigned long long)cnt);
+}
+
+// the box test of get_region_inst: middle = (min + max) / 2, size = max - min + 0.1, kept when
+// middle - size * 0.5 <= x <= middle + size * 0.5 on every axis (numpy's operation order, fp64); a scene whose instance
+// id has no point keeps nothing and sets GF_AUG_ERR_NOINST
+__global__ __launch_bounds__(AUG_T) void k_blk_flags(GfAugBatch bt) {
+    const int y = blockIdx.y;
+    long long* r = rec_of(bt.rec, y);
+    const bool any = r[GF_AUG_R_BCNT] > 0;
+    double lower[3], upper[3];
+    for (int a = 0; a < 3; a++) {
+        const double lo = dkey_inv((unsigned long long)r[GF_AUG_R_BMIN + a]);
+        const double hi = dkey_inv((unsigned long long)r[GF_AUG_R_BMAX + a]);
+        const double middle = (lo + hi) / 2.0;
+        const double size = hi - lo + 0.1;
+        lower[a] = middle - size * 0.5;
+        upper[a] = middle + size * 0.5;
+    }
+    if (!any && blockIdx.x == 0 && threadIdx.x == 0)
+        atomicOr((unsigned long long*)&r[GF_AUG_R_ERR], (unsigned long long)GF_AUG_ERR_NOINST);
+    for (long long p = bt.raw_off[y] + blockIdx.x * AUG_T + threadIdx.x; p < bt.raw_off[y + 1];
+         p += (long long)gridDim.x * AUG_T) {
+        bool keep = any;
+        for (int a = 0; a < 3; a++) {
+            const double x = bt.raw[p * 8 + a];
+            keep = keep && x <= upper[a] && x >= lower[a];
+        }
+        bt.flags[p] = keep ? 1 : 0;
+    }
+}
+
+// kept point p of scene y -> row raw_off[y] + (its rank among the scene's kept points): locs (0, trunc(x * scale -
+// min)), locs_float, raw colours, the mask of the instance id; the scene's max locs
+__global__ __launch_bounds__(AUG_T) void k_blk_collate(GfAugBatch bt, long long* __restrict__ masks, double scale) {
+    const int y = blockIdx.y;
+    long long* r = rec_of(bt.rec, y);
+    const long long id = r[GF_AUG_R_SUPID];
+    const long long base = bt.raw_off[y], first = bt.start[base];
+    double mn[3];
+    for (int a = 0; a < 3; a++) mn[a] = dkey_inv((unsigned long long)r[GF_AUG_R_MIN + a]);
+    long long lmax[3] = {0, 0, 0};
+    for (long long p = base + blockIdx.x * AUG_T + threadIdx.x; p < bt.raw_off[y + 1];
+         p += (long long)gridDim.x * AUG_T) {
+        if (!bt.flags[p]) continue;
+        const long long q = base + (bt.start[p] - first);
+        bt.locs[q * 4] = 0;
+        for (int a = 0; a < 3; a++) {
+            const double x = bt.raw[p * 8 + a];
+            const long long l = (long long)(x * scale - mn[a]);
+            bt.locs[q * 4 + 1 + a] = l;
+            lmax[a] = l > lmax[a] ? l : lmax[a];
+            bt.locs_float[q * 3 + a] = (float)x;
+            bt.feats[q * 3 + a] = bt.raw[p * 8 + 3 + a];
+        }
+        masks[q] = (long long)bt.raw[p * 8 + 7] == id ? 1 : 0;
+    }
+    for (int a = 0; a < 3; a++) {
+        const long long lm = wave_max_ll(lmax[a]);
+        if ((threadIdx.x & 63) == 0 && lm > 0) atomicMax((unsigned long long*)&r[GF_AUG_R_BLMAX + a], (unsigned long long)lm);
+    }
+}
+
+// padding rows behind each scene's kept points (batch 0xffff, distinct, one voxel each behind the real ones); per scene
+// sizes[y] = (kept, instance points, spatial shape); offsets = the kept points' running offsets; head N, error bits
+__global__ __launch_bounds__(AUG_T) void k_blk_finish(GfAugBatch bt, int32_t* __restrict__ sizes, int fs_min) {
+    const int y = blockIdx.y;
+    const long long* r = rec_of(bt.rec, y);
+    const long long base = bt.raw_off[y], end = bt.raw_off[y + 1];
+    const long long kept = bt.start[end] - bt.start[base];
+    for (long long q = base + kept + blockIdx.x * AUG_T + threadIdx.x; q < end; q += (long long)gridDim.x * AUG_T) {
+        const long long j = q - (base + kept);
+        bt.locs[q * 4 + 0] = 0xffff;
+        bt.locs[q * 4 + 1] = j & 0xffff;
+        bt.locs[q * 4 + 2] = (j >> 16) & 0xffff;
+        bt.locs[q * 4 + 3] = 0;
+    }
+    if (blockIdx.x != 0) return;
+    if (threadIdx.x == 0) {
+        sizes[y * 5 + 0] = (int32_t)kept;
+        sizes[y * 5 + 1] = (int32_t)r[GF_AUG_R_BCNT];
+        bt.offsets[y] = bt.start[base];
+        if (y == bt.B - 1) {
+            bt.offsets[bt.B] = bt.start[bt.n_raw];
+            bt.head[GF_AUG_H_N] = bt.start[bt.n_raw];
+        }
+        if (r[GF_AUG_R_ERR]) atomicOr(&bt.head[GF_AUG_H_ERR], (int)r[GF_AUG_R_ERR]);
+    }
+    if (threadIdx.x < 3) {
+        const int e = (int)r[GF_AUG_R_BLMAX + threadIdx.x] + 1;
+        sizes[y * 5 + 2 + threadIdx.x] = e > fs_min ? e : fs_min;
+    }
 }
 
 int grid_x(int max_scene_points) {
@@ -772,10 +902,42 @@ extern "C" int gf_aug_support(const GfAugBatch* b, long long* support_masks, dou
     hipStream_t st = (hipStream_t)stream;
     GF_TRY(hipMemsetAsync(b->head, 0, GF_AUG_HEAD * 4, st));
     const dim3 gp(grid_x(max_scene_points), b->B);
-    hipLaunchKernelGGL(k_sup_extent, gp, dim3(AUG_T), 0, st, *b, scale);
-    hipLaunchKernelGGL(k_sup_collate, gp, dim3(AUG_T), 0, st, *b, support_masks, scale);
+    hipLaunchKernelGGL(k_sup_extent, gp, dim3(AUG_T), 0, st, *b, scale, (const int32_t*)nullptr);
+    hipLaunchKernelGGL(k_sup_collate, gp, dim3(AUG_T), 0, st, *b, support_masks, (long long*)nullptr, scale);
     const int nq = 3 * b->B + 1;
     hipLaunchKernelGGL(k_sup_finish, dim3(gf_div_up(nq, AUG_T)), dim3(AUG_T), 0, st, *b, full_scale_min);
     GF_CHECK_LAUNCH("gf_aug_support");
+    return GF_OK;
+}
+
+extern "C" int gf_aug_test_query(const GfAugBatch* b, double scale, int full_scale_min, int max_scene_points,
+                                 void* stream) {
+    GF_CHECK_ARG(b && b->B > 0 && b->n_raw >= 0 && b->labels, "gf_aug_test_query: bad arguments (B %d, n_raw %d)",
+                 b ? b->B : 0, b ? b->n_raw : 0);
+    hipStream_t st = (hipStream_t)stream;
+    GF_TRY(hipMemsetAsync(b->head, 0, GF_AUG_HEAD * 4, st));
+    const dim3 gp(grid_x(max_scene_points), b->B);
+    hipLaunchKernelGGL(k_sup_extent, gp, dim3(AUG_T), 0, st, *b, scale, (const int32_t*)nullptr);
+    hipLaunchKernelGGL(k_sup_collate, gp, dim3(AUG_T), 0, st, *b, (long long*)nullptr, b->labels, scale);
+    const int nq = 3 * b->B + 1;
+    hipLaunchKernelGGL(k_sup_finish, dim3(gf_div_up(nq, AUG_T)), dim3(AUG_T), 0, st, *b, full_scale_min);
+    GF_CHECK_LAUNCH("gf_aug_test_query");
+    return GF_OK;
+}
+
+extern "C" int gf_aug_support_block(const GfAugBatch* b, long long* support_masks, int32_t* scene_sizes, double scale,
+                                    int full_scale_min, int max_scene_points, void* stream) {
+    GF_CHECK_ARG(b && b->B > 0 && b->n_raw > 0 && support_masks && scene_sizes,
+                 "gf_aug_support_block: bad arguments (B %d, n_raw %d)", b ? b->B : 0, b ? b->n_raw : 0);
+    hipStream_t st = (hipStream_t)stream;
+    GF_TRY(hipMemsetAsync(b->head, 0, GF_AUG_HEAD * 4, st));
+    const dim3 gp(grid_x(max_scene_points), b->B);
+    hipLaunchKernelGGL(k_blk_inst, gp, dim3(AUG_T), 0, st, *b);
+    hipLaunchKernelGGL(k_blk_flags, gp, dim3(AUG_T), 0, st, *b);
+    gf_iscan(b->flags, b->n_raw, b->start, b->cursor, b->block_sums, b->block_off, st);
+    hipLaunchKernelGGL(k_sup_extent, gp, dim3(AUG_T), 0, st, *b, scale, (const int32_t*)b->flags);
+    hipLaunchKernelGGL(k_blk_collate, gp, dim3(AUG_T), 0, st, *b, support_masks, scale);
+    hipLaunchKernelGGL(k_blk_finish, gp, dim3(AUG_T), 0, st, *b, scene_sizes, full_scale_min);
+    GF_CHECK_LAUNCH("gf_aug_support_block");
     return GF_OK;
 }

@@ -887,10 +887,12 @@ enum {
     GF_AUG_R_PCMAX = 35, GF_AUG_R_NINST = 38, GF_AUG_R_IBASE = 39, GF_AUG_R_COUNTS = 64, GF_AUG_R_CROPU = 128,
     /* ABI 7: first instance_pointnum slot of the scene (== IBASE except in few-shot queries, whose ids stay local);
      * few-shot query: the scene's sampled class; few-shot support: the support instance id (both set by the caller) */
-    GF_AUG_R_PBASE = 40, GF_AUG_R_CLASS = 41, GF_AUG_R_SUPID = 42
+    GF_AUG_R_PBASE = 40, GF_AUG_R_CLASS = 41, GF_AUG_R_SUPID = 42,
+    /* few-shot test-time block supports: the instance's min / max keys and point count, the scene's max locs */
+    GF_AUG_R_BMIN = 43, GF_AUG_R_BMAX = 46, GF_AUG_R_BCNT = 49, GF_AUG_R_BLMAX = 50
 };
 enum { GF_AUG_H_N = 0, GF_AUG_H_NINST = 1, GF_AUG_H_ERR = 2, GF_AUG_H_LMAX = 3, GF_AUG_H_SHAPE = 6 };
-enum { GF_AUG_ERR_CELLS = 1, GF_AUG_ERR_INST = 2 };
+enum { GF_AUG_ERR_CELLS = 1, GF_AUG_ERR_INST = 2, GF_AUG_ERR_NOINST = 4 };
 typedef struct {
     int B, n_raw, max_inst, pad_;
     const double* raw;
@@ -956,6 +958,22 @@ int gf_aug_collate(const GfAugBatch* b, const int32_t* fold_classes, int n_fold,
 int gf_aug_collate_fs(const GfAugBatch* b, int full_scale_min, int full_scale, int max_scene_points, void* stream);
 int gf_aug_support(const GfAugBatch* b, long long* support_masks, double scale, int full_scale_min,
                    int max_scene_points, void* stream);
+
+/* Few-shot test time (datasets/scannetv2_fs_inst.py:568-700 FSInstDataset.testMergeFS).
+ * Query: gf_aug_test_query on a batch of raw scenes (no draws, no crop, rec as for gf_aug_support): the support path
+ *   with the raw semantic labels (int64, into labels) instead of a mask; pc_mins / pc_maxs also stay in rec
+ *   (GF_AUG_R_PCMIN / _PCMAX keys, the reference keeps them in fp64).
+ * Block supports: gf_aug_support_block on B (scene, rec[s][GF_AUG_R_SUPID]) pairs (rec: GF_AUG_R_BMIN, _MIN, _PCMIN
+ *   initialised to -1, the rest 0): the instance's bounding box (fp64, get_region_inst with scale_factor 1), the in-box
+ *   points in order compacted to the front of the scene's own raw range (flags / start / cursor / block_* scratch),
+ *   locs = (0, trunc(xyz * scale - min of the kept xyz * scale)), locs_float, feats (fp64), support_masks int64
+ *   [n_raw]; rows behind a scene's kept points hold padding coordinates (batch 0xffff) so each range voxelises on its
+ *   own.  scene_sizes int32 [B, 5]: kept points, instance points, spatial shape (max locs + 1, at least
+ *   full_scale_min); offsets = running kept counts; pc_mins / pc_maxs of the kept xyz as GF_AUG_R_PCMIN / _PCMAX keys;
+ *   head N = kept total, head ERR |= GF_AUG_ERR_NOINST when an instance id has no point in its scene. */
+int gf_aug_test_query(const GfAugBatch* b, double scale, int full_scale_min, int max_scene_points, void* stream);
+int gf_aug_support_block(const GfAugBatch* b, long long* support_masks, int32_t* scene_sizes, double scale,
+                         int full_scale_min, int max_scene_points, void* stream);
 
 #ifdef __cplusplus
 }
