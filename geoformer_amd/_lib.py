@@ -118,6 +118,11 @@ def _declare(lib):
         "gf_decoder_token_stage": (I, [P, P, P, I, I, I, I, I, P, P, P, P, P, P]),
         "gf_mask_intersections_scratch_bytes": (c_size_t, [I, I]),
         "gf_mask_intersections": (I, [P, I, I, P, P, P]),
+        "gf_proposal_stats_batched": (I, [P, I, I, P, P, c_longlong, I, F, F, I, I, P, P, P, P, P]),
+        "gf_proposal_select_batched": (I, [P, P, P, I, I, P, P, P, P, P]),
+        "gf_proposal_scatter_batched": (I, [P, I, I, P, P, I, I, P, F, P, P]),
+        "gf_mask_intersections_batched": (I, [P, I, c_longlong, c_longlong, P, P, P]),
+        "gf_matrix_nms_batched": (I, [P, I, P, I, F, F, P, P, P]),
         "gf_instance_overlaps_scratch_bytes": (c_size_t, [I, I]),
         "gf_instance_overlaps": (I, [P, I, I, P, I, P, P, I, I, P, P, P, P, P, P]),
         "gf_voxelize_idx_scratch_bytes": (c_size_t, [I]),

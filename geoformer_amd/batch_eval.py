@@ -1,0 +1,92 @@
+"""Evaluation of the val set several scenes per forward (test.py:40-150 with batches of B scenes instead of one).
+
+    for name, cls, scores, masks, pick in predict_batches(model, [(name, raw), ...], batch_size=4):
+        ...                                   # masks int32 [n, N] over the scene's points, pick: the NMS result
+    ap, avgs = evaluate(model, [(name, raw), ...], batch_size=4)
+    print(evaluation.format_results(avgs))
+
+A batch of raw scenes ([N, 8] = xyz, rgb, semantic label, instance label, as prepare_data_inst.py stores them) is
+collated on the host (scene.collate_raw), uploaded and voxelised on the GPU one batch ahead (feeder.DeviceFeeder), and
+run through ONE eval forward with ``all_scenes=True``: every scene of the batch gets its proposals (the reference's
+forward keeps scene 0's only).  Matrix NMS of all scenes of the batch is one postprocess.matrix_nms_batched call, on the
+benchmark label ids of test.py:65-68 with final_score_thresh 0.5 (test.py:88-93).  A scene without proposals is left out
+of the evaluation, as test.py's ``continue`` does.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import evaluation, postprocess, scene
+from .feeder import DeviceFeeder
+
+NMS_FINAL_SCORE = 0.5  # test.py:92
+
+
+def scene_dict(raw):
+    """scene.collate_raw's per-scene dict of a raw [N, 8] scene."""
+    r = raw.detach().cpu().numpy() if torch.is_tensor(raw) else np.asarray(raw)
+    return {"xyz": r[:, :3].astype(np.float32), "rgb": r[:, 3:6].astype(np.float32),
+            "label": r[:, 6].astype(np.int64), "instance": r[:, 7].astype(np.int64)}
+
+
+def collate_batches(raw_scenes, batch_size, spatial_shape=None, scale=50, full_scale_min=128):
+    """(chunks of (name, raw), host batch dicts): the scenes in order, batch_size per batch (the last may be short).
+    spatial_shape: a lower bound on every batch's voxel grid (a scene's results depend on the grid it runs on: a
+    stride-2 convolution drops the voxels at an odd extent's edge)."""
+    items = list(raw_scenes)
+    if batch_size < 1:
+        raise ValueError("batch_size >= 1")
+    chunks = [items[i:i + batch_size] for i in range(0, len(items), batch_size)]
+    batches = []
+    for chunk in chunks:
+        b = scene.collate_raw([scene_dict(r) for _, r in chunk], scale, full_scale_min)
+        if spatial_shape is not None:
+            b["spatial_shape"] = np.maximum(b["spatial_shape"], np.asarray(spatial_shape, dtype=b["spatial_shape"].dtype))
+        batches.append(b)
+    return chunks, batches
+
+
+@torch.no_grad()
+def predict_batches(model, raw_scenes, batch_size, *, epoch=300, spatial_shape=None, nms_kernel="gaussian",
+                    sigma=2.0, final_score_thresh=NMS_FINAL_SCORE, cvfold=None, reserve=True, device=None):
+    """Yields (name, cls_final, scores_final, masks_final, pick) per scene, in input order.  raw_scenes: iterable of
+    (name, raw [N, 8]).  The NMS categories are the benchmark label ids of the classes (evaluation.benchmark_label_ids
+    with cvfold, default model.cfg.cvfold).  A scene without proposals yields ([], [], [], empty pick).  reserve: size
+    the allocator for the largest batch first (GeoFormer.reserve_for with the batch's total points)."""
+    cvfold = model.cfg.cvfold if cvfold is None else cvfold
+    dev = torch.device(device) if device is not None else next(model.parameters()).device
+    model.eval()
+    chunks, batches = collate_batches(raw_scenes, batch_size, spatial_shape)
+    if not batches:
+        return
+    most = max(int(b["offsets"][-1]) for b in batches)
+    if reserve:
+        model.reserve_for(most)
+    for chunk, batch in zip(chunks, DeviceFeeder(batches, dev, reserve_points=most)):
+        out = model(batch, epoch, training=False, all_scenes=True)
+        per = out.get("proposal_scores_per_scene") or [([], [], []) for _ in chunk]
+        labels = [evaluation.benchmark_label_ids(c, cvfold) if torch.is_tensor(c) else [] for c, _, _ in per]
+        picks = postprocess.matrix_nms_batched([m for _, _, m in per], [s for _, s, _ in per], labels,
+                                               kernel=nms_kernel, sigma=sigma, final_score_thresh=final_score_thresh)
+        for (name, _), (cls, sc, masks), pick in zip(chunk, per, picks):
+            yield name, cls, sc, masks, pick
+
+
+@torch.no_grad()
+def evaluate(model, scenes_with_gt, batch_size, classes=0, *, cvfold=None, **kw):
+    """ScanNet AP / AP50 / AP25 of the model over (name, raw [N, 8]) scenes whose labels are the ground truth
+    (evaluation.gt_ids_from_labels): (ap [C, n_overlaps], averages), as evaluation.InstanceEvaluator.evaluate.
+    Keywords go to predict_batches."""
+    cvfold = model.cfg.cvfold if cvfold is None else cvfold
+    items = list(scenes_with_gt)
+    raws = dict(items)
+    ev = evaluation.InstanceEvaluator(classes=classes)
+    dev = next(model.parameters()).device
+    for name, cls, sc, masks, pick in predict_batches(model, items, batch_size, cvfold=cvfold, **kw):
+        if not torch.is_tensor(cls):
+            continue  # test.py: a scene without proposals is skipped
+        r = torch.as_tensor(np.asarray(raws[name]), device=dev)
+        gt = evaluation.gt_ids_from_labels(r[:, 6].long(), r[:, 7].long())
+        ev.add_scene(name, gt, evaluation.benchmark_label_ids(cls, cvfold), sc, masks, pick)
+    return ev.evaluate()

@@ -11,11 +11,7 @@
 //                      (proposals[i, fg_idxs[p]] = 1), no nonzero()/index_put round trip.
 // mask membership is  sigmoid(logit) >= logit_thresh  with sigmoid = 1 / (1 + expf(-x)), evaluated by the same
 // device function in both kernels.
-#include "common.h"
-
-#define PR_THREADS 1024
-
-__device__ __forceinline__ float pr_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
+#include "proposal_rows.h"
 
 __global__ __launch_bounds__(PR_THREADS) void k_proposal_stats(const float* __restrict__ logits,
                                                                const float* __restrict__ cls_logits,
@@ -26,76 +22,10 @@ __global__ __launch_bounds__(PR_THREADS) void k_proposal_stats(const float* __re
                                                                int* __restrict__ npoints_out,
                                                                float* __restrict__ scores_out,
                                                                int* __restrict__ final_out) {
-    __shared__ int s_cls;
-    __shared__ float s_cls_score;
-    __shared__ int r_cnt[PR_THREADS / 64];
-    __shared__ float r_prob[PR_THREADS / 64], r_sem[PR_THREADS / 64];
-    const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) {
-        // soft-max over the classes and its arg-max (first maximum), geoformer.py:215-216
-        const float* c = cls_logits + (size_t)q * ncls;
-        float mx = c[0];
-        int arg = 0;
-        for (int k = 1; k < ncls; k++)
-            if (c[k] > mx) {
-                mx = c[k];
-                arg = k;
-            }
-        float den = 0.f;
-        for (int k = 0; k < ncls; k++) den += expf(c[k] - mx);
-        s_cls = arg;
-        s_cls_score = 1.0f / den;  // exp(0) / sum
-    }
-    __syncthreads();
-    const int cls = s_cls;
-    const float* row = logits + (size_t)q * N;
-    const float* sem_row = sem_prob + (size_t)cls * N;  // class-major: the predicted class is one contiguous row
-    int cnt = 0;
-    float sp = 0.f, ss = 0.f;
-    // four independent points per thread and trip (loads of a trip go out together; the class probability is
-    // fetched for every point, from a clamped index, and selected afterwards)
-    for (int p0 = tid; p0 < N; p0 += 4 * PR_THREADS) {
-        float x[4], sv[4];
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-            const int p = p0 + e * PR_THREADS;
-            const int pc = p < N ? p : N - 1;
-            x[e] = row[pc];
-            sv[e] = sem_row[pc];
-        }
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-            const float pr = pr_sigmoid(x[e]);
-            const bool in = (p0 + e * PR_THREADS) < N && pr >= logit_thresh;
-            cnt += in ? 1 : 0;
-            sp += in ? pr : 0.f;
-            ss += in ? sv[e] : 0.f;
-        }
-    }
-    cnt = gf_wave_sum_i(cnt);  // (the __shfl_xor butterflies without the LDS crossbar: common.h)
-    sp = gf_wave_sum(sp);
-    ss = gf_wave_sum(ss);
-    if (lane == 0) {
-        r_cnt[wave] = cnt;
-        r_prob[wave] = sp;
-        r_sem[wave] = ss;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int n = 0;
-        float a = 0.f, b = 0.f;
-        for (int w = 0; w < PR_THREADS / 64; w++) {
-            n += r_cnt[w];
-            a += r_prob[w];
-            b += r_sem[w];
-        }
-        const float den = (float)n + 1e-6f;
-        const float mask_score = a / den, sem_score = b / den;
-        cls_pred_out[q] = cls;
-        npoints_out[q] = n;
-        scores_out[q] = mask_score * sqrtf(s_cls_score) * sem_score;
-        final_out[q] = (cls >= min_class) && (n >= npoint_thresh) && (mask_score >= score_thresh);
-    }
+    const int q = blockIdx.x;
+    pr_stats_row(logits + (size_t)q * N, cls_logits + (size_t)q * ncls, sem_prob, (size_t)N, N, ncls, logit_thresh,
+                 score_thresh, npoint_thresh, min_class, cls_pred_out + q, npoints_out + q, scores_out + q,
+                 final_out + q);
 }
 
 // Few-shot variant (GeoFormerFS.generate_proposal, model/geoformer/geoformer_fs.py:205-238): no class head -- the
@@ -327,36 +257,7 @@ __global__ __launch_bounds__(1024) void k_proposal_select(const int32_t* __restr
                                                           const float* __restrict__ scores, int nq,
                                                           int32_t* __restrict__ sel, long long* __restrict__ cls_out,
                                                           float* __restrict__ scores_out, int32_t* __restrict__ count) {
-    __shared__ int s_w[16];
-    __shared__ int s_run;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_run = 0;
-    __syncthreads();
-    for (int base = 0; base < nq; base += 1024) {
-        const int q = base + threadIdx.x;
-        const bool f = q < nq && final_[q] != 0;
-        const unsigned long long bal = __ballot(f);
-        if (lane == 0) s_w[wave] = __popcll(bal);
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < 16; w++) {
-            const int c = s_w[w];
-            if (w < wave) before += c;
-            total += c;
-        }
-        const int run = s_run;
-        if (f) {
-            const int pos = run + before + __popcll(bal & ((1ull << lane) - 1ull));
-            sel[pos] = q;
-            cls_out[pos] = cls_pred[q];
-            scores_out[pos] = scores[q];
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) s_run = run + total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *count = s_run;
+    pr_select_rows(final_, cls_pred, scores, nq, sel, cls_out, scores_out, count);
 }
 
 extern "C" int gf_proposal_select(const int32_t* final_, const int32_t* cls_pred, const float* scores, int nq,

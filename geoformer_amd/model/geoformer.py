@@ -222,6 +222,59 @@ class PendingProposals:
         return self.value
 
 
+class PendingBatchProposals:
+    """Proposals of every scene of a batched eval forward (forward(..., all_scenes=True, defer_proposals=True)) behind
+    ONE read-back: the per-scene accepted counts (and the kNN truncation flag) travel to a pinned buffer together;
+    ``get()`` waits for them, queues the packed membership scatter of all scenes (csrc/batch_post.hip) and returns a
+    list of B tuples (cls_final, scores_final, masks_final) -- ([], [], []) for a scene without proposals or without
+    foreground.  ``value`` given: nothing is in flight (every scene was empty)."""
+
+    def __init__(self, n_scenes, scene_ids=(), table=None, sel=None, cls=None, scores=None, counts=None, fg_idxs=None,
+                 logit_thresh=0.5, num_points=(), max_N=0, knn_flags=(), value=None):
+        self.value = value
+        if value is not None:
+            return
+        self.n_scenes, self.scene_ids, self.num_points, self.max_N = n_scenes, list(scene_ids), list(num_points), max_N
+        self.args = (table, sel, cls, scores, counts, fg_idxs, logit_thresh)
+        S = len(self.scene_ids)
+        self.stream = torch.cuda.current_stream(sel.device)
+        self.host = torch.zeros(S + 1, dtype=torch.int32).pin_memory()
+        self.host[:S].copy_(counts, non_blocking=True)
+        for f in knn_flags:
+            self.host[S:S + 1].copy_(f, non_blocking=True)
+        self.done = torch.cuda.Event()
+        self.done.record(self.stream)
+
+    def get(self):
+        if self.value is None:
+            from .. import postprocess
+
+            table, sel, cls, scores, counts, fg_idxs, logit_thresh = self.args
+            _lib.timed_wait(self.done)
+            S = len(self.scene_ids)
+            h = self.host.tolist()
+            counts_h, overflow = h[:S], h[S]
+            if overflow:
+                from .._lib import GeoFormerHipError
+
+                raise GeoFormerHipError("kNN graph: a point has more in-radius neighbours than the kernel's candidate list "
+                                        "holds (1024); its row is not the 64 nearest and the geodesic distances "
+                                        "would be wrong -- deduplicate the scene's points")
+            rows, elems = postprocess.packed_layout(counts_h, self.num_points)
+            out = [([], [], []) for _ in range(self.n_scenes)]
+            if rows[-1] > 0:
+                with torch.cuda.stream(self.stream):
+                    packed = pointops.proposal_scatter_batched(table, sel, counts, int(rows[-1]), int(elems[-1]),
+                                                               self.max_N, fg_idxs, logit_thresh)
+                masks = postprocess.split_packed(packed, counts_h, self.num_points)
+                for k, b in enumerate(self.scene_ids):
+                    c = counts_h[k]
+                    if c:
+                        out[b] = (cls[k, :c], scores[k, :c], masks[k])
+            self.value, self.args, self.host = out, None, None
+        return self.value
+
+
 class SplitForward:
     """Handle of GeoFormer.forward_split, a forward in three parts, all queued on the stream that is current when the
     handle is created (the scene's lane):
@@ -1159,14 +1212,51 @@ class GeoFormer(nn.Module):
         proposals[inst, fg_idxs[pts]] = 1
         return cls_pred[final], scores[final], proposals
 
+    def generate_proposals_batched(self, mask_logits, cls_logits, fg_idxs, batch_offsets, fg_offsets, scene_ids,
+                                   n_scenes, sem_prob, logit_thresh=0.5, score_thresh=0.5, npoint_thresh=100,
+                                   defer=False, knn_flags=()):
+        """generate_proposal for every scene of the batch (geoformer.py:193-262 with b = 0..B-1) in a fixed number of
+        launches (csrc/batch_post.hip): statistics over all (scene, query) pairs, per-scene selection, one read-back of
+        all counts, one packed membership scatter.  mask_logits: per kept scene [nq, N_b]; cls_logits [S, nq, ncls];
+        fg_offsets: host offsets of the kept scenes' foreground rows; scene_ids: the batch index of each kept scene;
+        sem_prob: (probabilities, class-major copy).  Returns the list of n_scenes tuples, or with defer a
+        PendingBatchProposals."""
+        from .. import postprocess
+
+        offs = _offsets_list(batch_offsets)
+        logits = [ml.contiguous() for ml in mask_logits]
+        nq = logits[0].shape[0]
+        starts = [offs[b] for b in scene_ids]
+        npts = [offs[b + 1] - offs[b] for b in scene_ids]
+        sem_t = sem_prob[1] if isinstance(sem_prob, tuple) else sem_prob.t().contiguous()
+        table = postprocess.proposal_scene_table([t.data_ptr() for t in logits], fg_offsets, starts, npts)
+        table_d = pointops._table_dev(table, fg_idxs.device)
+        cls_pred, _, scores, final = pointops.proposal_stats_batched(table_d, nq, cls_logits.contiguous(), sem_t,
+                                                                     logit_thresh, score_thresh, npoint_thresh,
+                                                                     min_class=4)
+        sel, cls, sc, counts = pointops.proposal_select_batched(final, cls_pred, scores)
+        pending = PendingBatchProposals(n_scenes, scene_ids, table_d, sel, cls, sc, counts, fg_idxs.contiguous(),
+                                        logit_thresh, npts, int(table[:, 1].max()), knn_flags)
+        pending.keep = logits  # (the scatter reads the logit rows through the table)
+        return pending if defer else pending.get()
+
     # -- forward --------------------------------------------------------------------------------
-    def forward(self, batch_input, epoch, training=True, defer_proposals=False):
+    def forward(self, batch_input, epoch, training=True, defer_proposals=False, all_scenes=False):
         """defer_proposals (GPU inference): everything is queued on the current stream and
         ``outputs["proposal_scores"]`` is a PendingProposals whose ``get()`` makes the forward's last read-back -- a
         serving loop can queue the next scene on another stream before it collects this one.  The in-flight side-stream
         state is kept per caller stream, so forwards issued on their own streams (from one host thread or several) do
-        not interfere; ``last_sampling_indices`` (a test hook) is the one attribute that is per model."""
-        steps = self._forward_steps(batch_input, epoch, training, defer_proposals, False)
+        not interfere; ``last_sampling_indices`` (a test hook) is the one attribute that is per model.
+
+        all_scenes (GPU inference): the proposals of EVERY scene of the batch, not only scene 0's (the reference's
+        "only batch 1 when test"): ``outputs["proposal_scores_per_scene"]`` is a list of B tuples (cls_final,
+        scores_final, masks_final) -- each what a forward of that scene alone returns, masks int32 [n_b, N_b] over the
+        scene's own points, ([], [], []) for a scene without proposals or without foreground -- in place of
+        ``proposal_scores``; with defer_proposals a PendingBatchProposals.  Scenes without foreground are dropped from
+        the batch after the foreground selection, so they do not stop the others."""
+        if all_scenes and (training or not batch_input["locs_float"].is_cuda):
+            raise ValueError("forward(all_scenes=True) is the batched eval forward on the GPU (training=False)")
+        steps = self._forward_steps(batch_input, epoch, training, defer_proposals, False, all_scenes)
         try:
             while True:
                 next(steps)
@@ -1183,7 +1273,7 @@ class GeoFormer(nn.Module):
         beside a BFS workgroup); values agree to rounding."""
         return SplitForward(self._forward_steps(batch_input, epoch, training, defer_proposals, True))
 
-    def _forward_steps(self, batch_input, epoch, training, defer_proposals, split):
+    def _forward_steps(self, batch_input, epoch, training, defer_proposals, split, all_scenes=False):
         """The forward as a generator: with ``split`` it yields an event behind the backbone + semantic head and the
         events behind the sampling / BFS stretch; returns the outputs."""
         cfg = self.cfg
@@ -1248,6 +1338,10 @@ class GeoFormer(nn.Module):
             if agree is not None:
                 agree(False, locs_float.device)
             outputs["mask_predictions"] = None
+            if all_scenes:
+                empty = [([], [], []) for _ in range(batch_size)]
+                outputs["proposal_scores_per_scene"] = PendingBatchProposals(batch_size, value=empty) \
+                    if defer_proposals else empty
             return outputs
         if not fused_fg:
             batch_idxs_ = batch_idxs[fg_idxs]
@@ -1257,6 +1351,15 @@ class GeoFormer(nn.Module):
         batch_offsets_ = get_batch_offsets(batch_idxs_, batch_size, host_only=fused_fg and not training)
         offs_ = _offsets_list(batch_offsets_)  # the only read-back of this stretch, before the heavy launches
         nonempty = min(offs_[b + 1] - offs_[b] for b in range(batch_size)) > 0
+        n_scenes, scene_ids = batch_size, list(range(batch_size))
+        if all_scenes and not nonempty:
+            # scenes without foreground leave the batch here (a forward of such a scene alone ends at this point too:
+            # no sampling draw, no proposals); the others go on as a batch of their own
+            scene_ids = [b for b in range(batch_size) if offs_[b + 1] > offs_[b]]
+            offs_ = [offs_[b] for b in scene_ids] + [offs_[-1]]
+            batch_offsets_ = torch.tensor(offs_, dtype=torch.int32, device=batch_offsets_.device)
+            pc_dims = [pc_dims[0][scene_ids], pc_dims[1][scene_ids]]
+            batch_size, nonempty = len(scene_ids), True
         if agree is not None and not agree(nonempty, locs_float.device):
             outputs["mask_predictions"] = None
             return outputs
@@ -1357,11 +1460,18 @@ class GeoFormer(nn.Module):
             preds = self.get_mask_prediction(geo_dists, dec_outputs, mask_features_, locs_float_, query_locs,
                                              batch_offsets_)
             outputs["mask_predictions"] = preds
-            outputs["proposal_scores"] = self.generate_proposal(
-                preds[-1]["mask_logits"], preds[-1]["cls_logits"], fg_idxs, batch_offsets, batch_offsets_,
-                semantic_scores_=semantic_scores_, logit_thresh=0.5, score_thresh=cfg.TEST_SCORE_THRESH,
-                npoint_thresh=cfg.TEST_NPOINT_THRESH, sem_prob=sem_prob, defer=defer_proposals,
-                knn_flags=[f for f in (knn_truncated(graphs),) if f is not None])
+            if all_scenes:
+                outputs["proposal_scores_per_scene"] = self.generate_proposals_batched(
+                    preds[-1]["mask_logits"], preds[-1]["cls_logits"], fg_idxs, batch_offsets, offs_, scene_ids,
+                    n_scenes, sem_prob, logit_thresh=0.5, score_thresh=cfg.TEST_SCORE_THRESH,
+                    npoint_thresh=cfg.TEST_NPOINT_THRESH, defer=defer_proposals,
+                    knn_flags=[f for f in (knn_truncated(graphs),) if f is not None])
+            else:
+                outputs["proposal_scores"] = self.generate_proposal(
+                    preds[-1]["mask_logits"], preds[-1]["cls_logits"], fg_idxs, batch_offsets, batch_offsets_,
+                    semantic_scores_=semantic_scores_, logit_thresh=0.5, score_thresh=cfg.TEST_SCORE_THRESH,
+                    npoint_thresh=cfg.TEST_NPOINT_THRESH, sem_prob=sem_prob, defer=defer_proposals,
+                    knn_flags=[f for f in (knn_truncated(graphs),) if f is not None])
         if locs_float.is_cuda:
             self._early().clear()
         return outputs

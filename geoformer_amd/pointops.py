@@ -1358,3 +1358,81 @@ def points_from_voxels(feats, p2v, v2p=None):
             and v2p.dtype == torch.int32 and v2p.is_contiguous() and v2p.shape[0] == feats.shape[0]):
         return _PointsFromVoxelsFn.apply(feats, p2v, v2p)
     return feats[p2v.long()]
+
+
+# ---- batched post-processing over a scene table (csrc/batch_post.hip) -----------------------------------------------
+def _table_dev(table, device):
+    """int64 scene table (numpy [S, F]) on the device: one small asynchronous upload from pinned memory."""
+    t = torch.from_numpy(np.ascontiguousarray(table, dtype=np.int64))
+    return t.pin_memory().to(device, non_blocking=True)
+
+
+def proposal_stats_batched(table, nq, cls_logits, sem_t, logit_thresh, score_thresh, npoint_thresh, min_class=4):
+    """proposal_stats of every (scene, query) in one launch: (cls_pred i32[S,nq], npoints i32[S,nq], scores f32[S,nq],
+    final i32[S,nq]).  table: device int64 [S, GF_PROP_SCENE_FIELDS] (postprocess.proposal_scene_table);
+    cls_logits fp32 [S, nq, ncls]; sem_t fp32 class-major [ncls, n_fg] over the batch's foreground points."""
+    _f32c(cls_logits, "cls_logits"), _f32c(sem_t, "sem_t")
+    S = table.shape[0]
+    ncls = cls_logits.shape[-1]
+    if cls_logits.shape != (S, nq, ncls) or sem_t.shape[0] != ncls:
+        raise RuntimeError(f"proposal_stats_batched: cls_logits {tuple(cls_logits.shape)} / sem_t {tuple(sem_t.shape)} "
+                           f"do not fit S={S} nq={nq}")
+    dev = cls_logits.device
+    ints = torch.empty((3, S, nq), dtype=torch.int32, device=dev)
+    scores = torch.empty((S, nq), dtype=torch.float32, device=dev)
+    check(_lib.load().gf_proposal_stats_batched(ptr(table), S, nq, ptr(cls_logits), ptr(sem_t), sem_t.shape[1], ncls,
+                                                float(logit_thresh), float(score_thresh), int(npoint_thresh),
+                                                int(min_class), ptr(ints[0]), ptr(ints[1]), ptr(scores), ptr(ints[2]),
+                                                stream_ptr()), "gf_proposal_stats_batched")
+    return ints[0], ints[1], scores, ints[2]
+
+
+def proposal_select_batched(final, cls_pred, scores):
+    """proposal_select per scene: (sel i32[S,nq], cls i64[S,nq], scores f32[S,nq], counts i32[S]); row b's first
+    counts[b] entries are valid."""
+    _i32c(final, "final"); _i32c(cls_pred, "cls_pred"); _f32c(scores, "scores")
+    S, nq = final.shape
+    dev = final.device
+    sel = torch.empty((S, nq), dtype=torch.int32, device=dev)
+    cls = torch.empty((S, nq), dtype=torch.int64, device=dev)
+    sc = torch.empty((S, nq), dtype=torch.float32, device=dev)
+    counts = torch.empty(S, dtype=torch.int32, device=dev)
+    check(_lib.load().gf_proposal_select_batched(ptr(final), ptr(cls_pred), ptr(scores), S, nq, ptr(sel), ptr(cls),
+                                                 ptr(sc), ptr(counts), stream_ptr()), "gf_proposal_select_batched")
+    return sel, cls, sc, counts
+
+
+def proposal_scatter_batched(table, sel, counts, total_rows, total_elems, max_N, fg_idxs, logit_thresh):
+    """Accepted rows of every scene as 0/1 int32 over the scene's own points, packed into one buffer of total_elems
+    (postprocess.packed_layout gives the blocks).  counts: the device counts of proposal_select_batched (their host
+    copy gave total_rows / total_elems)."""
+    _i32c(sel, "sel"); _i32c(counts, "counts")
+    if not (fg_idxs.is_cuda and fg_idxs.dtype == torch.int64 and fg_idxs.is_contiguous()):
+        raise RuntimeError("fg_idxs: expected a contiguous int64 tensor on the GPU")
+    out = torch.zeros(int(total_elems), dtype=torch.int32, device=sel.device)
+    check(_lib.load().gf_proposal_scatter_batched(ptr(table), table.shape[0], sel.shape[1], ptr(sel), ptr(counts),
+                                                  int(total_rows), int(max_N), ptr(fg_idxs), float(logit_thresh),
+                                                  ptr(out), stream_ptr()), "gf_proposal_scatter_batched")
+    return out
+
+
+def mask_intersections_batched(table, sizes):
+    """[n_b, n_b] intersection blocks of every scene, packed (table / sizes: postprocess.nms_scene_table)."""
+    dev = table.device
+    bits = torch.empty(max(int(sizes["bits"]), 1), dtype=torch.int64, device=dev)
+    inter = torch.empty(max(int(sizes["inter"]), 1), dtype=torch.int32, device=dev)
+    check(_lib.load().gf_mask_intersections_batched(ptr(table), table.shape[0], int(sizes["max_waves"]),
+                                                    int(sizes["max_pairs"]), ptr(bits), ptr(inter), stream_ptr()),
+          "gf_mask_intersections_batched")
+    return inter
+
+
+def matrix_nms_batched(table, inter, sizes, kernel, sigma, final_score_thresh):
+    """(picks i32 [sum n_b] packed at each scene's pick_off, pick_counts i32 [S]) of the fused matrix NMS."""
+    dev = table.device
+    picks = torch.empty(max(int(sizes["picks"]), 1), dtype=torch.int32, device=dev)
+    counts = torch.empty(table.shape[0], dtype=torch.int32, device=dev)
+    check(_lib.load().gf_matrix_nms_batched(ptr(table), table.shape[0], ptr(inter), int(kernel), float(sigma),
+                                            float(final_score_thresh), ptr(picks), ptr(counts), stream_ptr()),
+          "gf_matrix_nms_batched")
+    return picks, counts

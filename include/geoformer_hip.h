@@ -724,6 +724,52 @@ size_t gf_mask_intersections_scratch_bytes(int n, int N);
 int gf_mask_intersections(const int32_t* masks, int n, int N, void* scratch, int32_t* inter, void* stream);
 
 /* ===================================================================================
+ * Batched post-processing of an eval forward over S scenes (csrc/batch_post.hip): generate_proposal
+ * (model/geoformer/geoformer.py:193-262) and matrix NMS (util/utils_3d.py:95-141) once per scene, in a fixed number of
+ * launches.  Each call reads a device scene table of int64 rows.
+ * =================================================================================== */
+/* Proposal scene table, int64 [S, GF_PROP_SCENE_FIELDS], one row per scene:
+ *   {mask-logit pointer (fp32 [nq, N_b]), N_b (the scene's foreground points), fg_off (first column of the scene in
+ *    sem_prob / first entry in fg_idxs), pt_off (first point of the scene in the batch), num_points (the scene's
+ *    points), 0}. */
+#define GF_PROP_SCENE_FIELDS 6
+/* gf_proposal_stats per (scene, query): the same formula and workgroup shape (bit-identical per query).
+ *   cls_logits fp32 [S, nq, ncls], sem_prob fp32 CLASS-MAJOR [ncls, sem_stride] over the batch's foreground points;
+ *   outputs int32 / fp32 [S, nq]. */
+int gf_proposal_stats_batched(const long long* table, int S, int nq, const float* cls_logits, const float* sem_prob,
+                              long long sem_stride, int ncls, float logit_thresh, float score_thresh, int npoint_thresh,
+                              int min_class, int* cls_pred, int* npoints, float* scores, int* final_mask, void* stream);
+/* gf_proposal_select per scene: row b of sel / cls_out / scores_out ([S, nq]) holds scene b's accepted queries in
+ * ascending order, counts int32 [S] how many. */
+int gf_proposal_select_batched(const int32_t* final_, const int32_t* cls_pred, const float* scores, int S, int nq,
+                               int32_t* sel, long long* cls_out, float* scores_out, int32_t* counts, void* stream);
+/* gf_proposal_scatter of every scene into ONE zero-filled int32 buffer: scene b's block [counts[b], num_points_b]
+ * starts at element sum_{c<b} counts[c] * num_points_c; members go to column fg_idxs[fg_off + p] - pt_off (scene-local).
+ * total_rows = sum of counts (<= 65535), max_N = the largest N_b. */
+int gf_proposal_scatter_batched(const long long* table, int S, int nq, const int32_t* sel, const int32_t* counts,
+                                int total_rows, int max_N, const long long* fg_idxs, float logit_thresh, int* packed,
+                                void* stream);
+
+/* NMS scene table, int64 [S, GF_NMS_SCENE_FIELDS], one row per scene:
+ *   {masks pointer (int32 [n_b, N_b], nonzero = member), N_b, n_b, bits_off (uint64 words into the bits scratch,
+ *    n_b * ceil(N_b / 64) of them), inter_off (int32 elements into inter, n_b * n_b of them), scores pointer
+ *    (fp32 [n_b]), categories pointer (int64 [n_b]), pick_off (int32 elements into picks, n_b of them)}. */
+#define GF_NMS_SCENE_FIELDS 8
+#define GF_NMS_MAX_N 1024
+/* gf_mask_intersections per scene: inter + inter_off is scene b's [n_b, n_b] block.  max_waves / max_pairs: the
+ * largest n_b * ceil(N_b / 64) / n_b * n_b over the scenes. */
+int gf_mask_intersections_batched(const long long* table, int S, long long max_waves, long long max_pairs, void* bits,
+                                  int32_t* inter, void* stream);
+/* Matrix NMS per scene, one workgroup each (n_b <= GF_NMS_MAX_N), on the intersection blocks of
+ * gf_mask_intersections_batched.  Same [n, n] algebra as util/utils_3d.py:95-141 in fp32: proposals sorted by score,
+ * descending, EQUAL SCORES BY ASCENDING INDEX; iou = I / (d_i + d_j - I); compensation = max same-class IoU with a
+ * higher-ranked proposal; decay = min over rows of exp(-sigma iou^2) / exp(-sigma comp^2) (kernel 0, gaussian) or
+ * (1 - iou) / (1 - comp) (kernel 1, linear); kept where score * decay >= final_score_thresh.  picks + pick_off gets
+ * the kept proposals' indices in descending-score order, pick_counts int32 [S] how many. */
+int gf_matrix_nms_batched(const long long* table, int S, const int32_t* inter, int kernel, float sigma,
+                          float final_score_thresh, int32_t* picks, int32_t* pick_counts, void* stream);
+
+/* ===================================================================================
  * Overlap tables of the ScanNet instance evaluation for one scene (assign_instances_for_scan, util/eval.py:290-355,
  * with get_instances, util/utils_3d.py:18-73): everything the evaluation derives from the N points.
  *   masks int32 [n_rows,N] (gf_proposal_scatter layout; any nonzero is a member), rows int32 [n] (may be NULL: row i
