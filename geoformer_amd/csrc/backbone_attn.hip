@@ -286,6 +286,9 @@ __global__ __launch_bounds__(BT_THREADS) void k_bt_pre(const float* __restrict__
                           [&](int r, int cc, float v) { qkv_rows[(size_t)r * (3 * BT_D) + 2 * BT_D + cc] = v; });
 }
 
+// WIDE: c > BT_D, the output layer has more column tiles than waves (a separate instance, so that the narrow levels' kernel
+// stays what it was)
+template <bool WIDE>
 __global__ __launch_bounds__(BT_THREADS) void k_bt_layer(const int* __restrict__ scene_offsets,
                                                          const int* __restrict__ tile_scene,
                                                          const int* __restrict__ tile_first, int c, int li, BtParams P,
@@ -442,6 +445,12 @@ __global__ __launch_bounds__(BT_THREADS) void k_bt_layer(const int* __restrict__
         float* y = out + ((size_t)s0 + t0) * c;
         bt_tile_gemm_w<false>(&sT[0][0], BT_LD, nvalid, BT_D, c, wave, nw, lane, w_q,
                               [&](int r, int col, float v) { y[(size_t)r * c + col] = v; });
+        if (WIDE) {
+            // the registers held the output layer's first BT_D / 16 column tiles (one per wave); its rows BT_D .. c-1
+            // straight from memory
+            bt_tile_gemm<false>(&sT[0][0], BT_LD, nvalid, BT_D, P.aw + (size_t)BT_D * BT_D, P.ab + BT_D, c - BT_D, wave, nw,
+                                lane, [&](int r, int col, float v) { y[(size_t)r * c + BT_D + col] = v; });
+        }
     }
 }
 
@@ -494,7 +503,8 @@ int gf_backbone_transformer_prepared(const float* feats, const int* coords, cons
 }
 static int bt_forward(const float* feats, const int* coords, const int* scene_offsets, int n_scenes, int M, int c, int n_layers,
                       const float* const* params, void* scratch, float* out, void* stream, bool tables_ready) {
-    GF_CHECK_ARG(c > 0 && c % 16 == 0, "gf_backbone_transformer: channel width %d must be a multiple of 16", c);
+    GF_CHECK_ARG(c > 0 && c % 16 == 0 && c <= 3 * BT_D,
+                 "gf_backbone_transformer: channel width %d must be a multiple of 16, at most %d", c, 3 * BT_D);
     GF_CHECK_ARG(n_layers >= 1 && n_layers <= BT_MAXL, "gf_backbone_transformer: 1..%d layers, got %d", BT_MAXL,
                  n_layers);
     GF_CHECK_ARG(n_scenes >= 0 && n_scenes <= 4096 && M >= 0, "gf_backbone_transformer: bad sizes");
@@ -544,10 +554,11 @@ static int bt_forward(const float* feats, const int* coords, const int* scene_of
         hipLaunchKernelGGL(k_bt_tiles, dim3(1), dim3(64), 0, st, scene_offsets, n_scenes, max_tiles, tile_scene, tile_first);
     hipLaunchKernelGGL(k_bt_pre, dim3(max_tiles), dim3(BT_THREADS), 0, st, feats, coords, scene_offsets, tile_scene,
                        tile_first, c, P, sA);
+    auto layer_kernel = c > BT_D ? k_bt_layer<true> : k_bt_layer<false>;
     for (int l = 0; l < n_layers; l++) {
         float* in = (l & 1) ? sB : sA;
         float* ou = (l & 1) ? sA : sB;
-        hipLaunchKernelGGL(k_bt_layer, dim3(max_tiles), dim3(BT_THREADS), 0, st, scene_offsets, tile_scene, tile_first, c,
+        hipLaunchKernelGGL(layer_kernel, dim3(max_tiles), dim3(BT_THREADS), 0, st, scene_offsets, tile_scene, tile_first, c,
                            l, P, in, ou, out);
     }
     GF_CHECK_LAUNCH("gf_backbone_transformer");

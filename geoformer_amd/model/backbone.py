@@ -33,6 +33,12 @@ def _fusable(t, *bns):
         all(not bn.training for bn in bns)
 
 
+def _infer_transformer_ok(t, transformer):
+    from .. import pointops
+
+    return pointops.backbone_transformer_supported(t.features.shape[1], transformer)
+
+
 def _train_transformer_ok(t, transformer):
     from .. import pointops
 
@@ -184,7 +190,8 @@ class UBlock(nn.Module):
             dec = self.deconv(self.u(self.conv(output)))
             output.features = torch.cat((identity.features, dec.features), dim=1)
             output = self.blocks_tail(output)
-        if self.before_transformer_linear is not None and _fusable(output) and output.features.shape[1] % 16 == 0:
+        if self.before_transformer_linear is not None and _fusable(output) and \
+                _infer_transformer_ok(output, self.transformer):
             output.features = self._transformer_fused(output)
         elif self.before_transformer_linear is not None and torch.is_grad_enabled() and output.features.is_cuda and \
                 _train_transformer_ok(output, self.transformer):

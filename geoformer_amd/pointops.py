@@ -972,6 +972,17 @@ def backbone_transformer_params(before, transformer, after):
     return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts]), len(transformer.layers)
 
 
+BACKBONE_TRANSFORMER_MAX_C = 384  # csrc/backbone_attn.hip: 3 * BT_D, the widest level either form of the stack takes
+
+
+def backbone_transformer_supported(c, transformer):
+    """Whether gf_backbone_transformer (inference) takes a level of width c with this transformer: the native entry's
+    argument checks (bt_forward) plus the fixed shape of its kernels -- d_model 128, 4 heads, d_ff 64, 1..4 layers."""
+    return (c > 0 and c % 16 == 0 and c <= BACKBONE_TRANSFORMER_MAX_C and transformer.d_model == 128
+            and 1 <= len(transformer.layers) <= 4
+            and all(l.attn_1.h == 4 and l.ff.linear_1.out_features == 64 for l in transformer.layers))
+
+
 def backbone_transformer(feats, coords, scene_offsets, n_scenes, params, n_layers):
     """Fused before-linear -> per-scene voxel transformer -> after-linear: feats [M,c], coords int32 [M,4],
     scene_offsets int32 [n_scenes+1] on the device.  Returns [M,c]."""
@@ -1069,7 +1080,7 @@ class _VoxelTransformerTrainFn(torch.autograd.Function):
 
 def backbone_transformer_train_supported(feats, coords, transformer):
     return (feats.is_cuda and feats.dtype == torch.float32 and feats.shape[0] > 0 and feats.shape[1] % 16 == 0
-            and feats.shape[1] <= 384 and coords.dtype == torch.int32 and coords.is_contiguous()
+            and feats.shape[1] <= BACKBONE_TRANSFORMER_MAX_C and coords.dtype == torch.int32 and coords.is_contiguous()
             and transformer.d_model == 128 and 1 <= len(transformer.layers) <= 4
             and len({float(m.p) for m in transformer.modules() if isinstance(m, torch.nn.Dropout)}) == 1
             and all(l.attn_1.h == 4 and l.ff.linear_1.out_features == 64 for l in transformer.layers)

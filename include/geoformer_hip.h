@@ -795,7 +795,7 @@ int gf_instance_overlaps(const int32_t* masks, int n_rows, int N, const int32_t*
  * =================================================================================== */
 
 /* out = after(TransformerEncoder(xyz, before(feats))) per scene in n_layers + 2 launches (n_scenes <= 4096).
- *   feats fp32 [M,c] (c % 16 == 0), coords int32 [M,4] (b,x,y,z) with the rows of a scene contiguous,
+ *   feats fp32 [M,c] (c % 16 == 0, c <= 384), coords int32 [M,4] (b,x,y,z) with the rows of a scene contiguous,
  *   scene_offsets int32 [n_scenes+1] (device), out fp32 [M,c],
  *   scratch: gf_backbone_transformer_scratch_bytes(M) bytes,
  *   params: HOST array of gf_backbone_transformer_num_params(n_layers) DEVICE pointers, nn.Linear weights

@@ -80,7 +80,9 @@ def _reference(before, tr, after, feats, coords, n_scenes, seed, p):
 
 
 @pytest.mark.parametrize("lens,c,p,n_layers", [((37, 160, 5, 64), 96, 0.0, 2), ((37, 160, 5, 64), 112, 0.1, 2),
-                                               ((1, 300), 192, 0.1, 2), ((16, 0, 33), 96, 0.1, 1)])
+                                               ((1, 300), 192, 0.1, 2), ((16, 0, 33), 96, 0.1, 1),
+                                               ((15, 16, 17), 16, 0.1, 2), ((37, 160, 5, 64), 144, 0.1, 4),
+                                               ((1, 300), 384, 0.0, 2), ((40, 0, 33), 384, 0.1, 1)])
 def test_voxel_transformer_train_matches_modules_float64(lens, c, p, n_layers):
     from geoformer_amd import pointops
 

@@ -8,7 +8,8 @@ import pytest
 import torch
 
 
-def _setup(device, full=False, batch4=False):
+def _setup(device, full=False, batch4=False, width=None):
+    """width: the backbone width (STRUCTURE.m) in place of the yaml's 16."""
     from geoformer_amd import scene
     from geoformer_amd.model import GeoFormer, InstSetCriterion, load_config
     from tests.util import synthetic_state_dict
@@ -18,6 +19,8 @@ def _setup(device, full=False, batch4=False):
     else:
         cfg = load_config("geoformer_scannet.yaml", batch_size=2, dec_dropout=0.0, n_decode_point=128, n_query_points=16,
                           prepare_epochs=1)
+    if width is not None:
+        cfg.m = width
     torch.manual_seed(0)
     m = GeoFormer(cfg)
     m.load_state_dict(synthetic_state_dict(m.state_dict(), 1))
