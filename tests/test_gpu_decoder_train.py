@@ -41,9 +41,16 @@ def _ln(x, m):
     return F.layer_norm(x, (64,), m.weight.double(), m.bias.double(), m.eps)
 
 
-@pytest.mark.parametrize("B,T,p", [(2, 256, 0.0), (3, 100, 0.1), (1, 17, 0.1)])
+# (B, T) beyond the first three: one token (T = 1), the shipped training query count (T = 128) at batch 4 and at the
+# shipped batch 16, and more than 256 tokens (T = 300: the self-attention's keys span 19 tiles); each with and without dropout
+_TRAIN_STAGE_CASES = [(1, 1, 0.0), (1, 1, 0.1), (4, 128, 0.0), (4, 128, 0.1), (16, 128, 0.0), (16, 128, 0.1), (2, 300, 0.0),
+                      (2, 300, 0.1)]
+
+
+@pytest.mark.parametrize("B,T,p", [(2, 256, 0.0), (3, 100, 0.1), (1, 17, 0.1)] + _TRAIN_STAGE_CASES)
 def test_decoder_pre_stage_matches_float64(B, T, p):
     from geoformer_amd import pointops
+    from tests.util import decoder_pre_reference
 
     dev = torch.device("cuda", 0)
     layer, norm = _layer(1)
@@ -57,24 +64,12 @@ def test_decoder_pre_stage_matches_float64(B, T, p):
     t2n, q1 = pointops.decoder_pre_train(x, qpos, li, p, seed, pre)
     got = torch.autograd.grad((t2n * wa).sum() + (q1 * wb).sum(), [x, qpos] + pre)
     # float64 reference with the same masks
-    D = lambda t: t.double()
-    sa = layer.self_attn
     rows = (torch.arange(B, device=dev).view(B, 1) * T + torch.arange(T, device=dev).view(1, T))  # [B,T]
     ch = torch.arange(64, device=dev)
-    t2 = _ln(D(x), layer.norm1)
-    qk = t2 + D(qpos)
-    Wi, bi = D(sa.in_proj_weight), D(sa.in_proj_bias)
-    q = (qk @ Wi[:64].t() + bi[:64]).view(B, T, 4, 16).transpose(1, 2)
-    k = (qk @ Wi[64:128].t() + bi[64:128]).view(B, T, 4, 16).transpose(1, 2)
-    v = (t2 @ Wi[128:].t() + bi[128:]).view(B, T, 4, 16).transpose(1, 2)
-    s = torch.softmax((q * 0.25) @ k.transpose(2, 3), dim=-1)  # [B,4,T,T]
-    keep = pointops.dropout_keep_reference(seed, p, 8 * li + 0, rows.view(B, 1, T, 1).expand(B, 4, T, T),
-                                           torch.arange(T, device=dev).view(1, 1, 1, T) * 4 + torch.arange(4, device=dev).view(1, 4, 1, 1))
-    o = ((s * keep.double()) @ v).transpose(1, 2).reshape(B, T, 64)
-    att = o @ D(sa.out_proj.weight).t() + D(sa.out_proj.bias)
-    x1 = D(x) + att * pointops.dropout_keep_reference(seed, p, 8 * li + 1, rows.view(B, T, 1).expand(B, T, 64), ch.view(1, 1, 64)).double()
-    r_t2n = _ln(x1, layer.norm2)
-    r_q1 = r_t2n @ D(layer.attn_mlp[0].weight).t() + D(layer.attn_mlp[0].bias)
+    keep_attn = pointops.dropout_keep_reference(seed, p, 8 * li + 0, rows.view(B, 1, T, 1).expand(B, 4, T, T),
+                                                torch.arange(T, device=dev).view(1, 1, 1, T) * 4 + torch.arange(4, device=dev).view(1, 4, 1, 1))
+    keep_res = pointops.dropout_keep_reference(seed, p, 8 * li + 1, rows.view(B, T, 1).expand(B, T, 64), ch.view(1, 1, 64))
+    _, r_t2n, r_q1 = decoder_pre_reference(layer, x, qpos, keep_attn, keep_res)
     want = torch.autograd.grad((r_t2n * wa.double()).sum() + (r_q1 * wb.double()).sum(), [x, qpos] + pre)
     _close(t2n, r_t2n, "t2n")
     _close(q1, r_q1, "q1")
@@ -82,7 +77,8 @@ def test_decoder_pre_stage_matches_float64(B, T, p):
         _close(a, b, f"gradient {i}")
 
 
-@pytest.mark.parametrize("B,T,p,ff", [(2, 256, 0.0, 256), (3, 100, 0.1, 256), (1, 17, 0.1, 64)])
+@pytest.mark.parametrize("B,T,p,ff", [(2, 256, 0.0, 256), (3, 100, 0.1, 256), (1, 17, 0.1, 64)]
+                         + [(B, T, p, 256) for B, T, p in _TRAIN_STAGE_CASES])
 def test_decoder_post_stage_matches_float64(B, T, p, ff):
     from geoformer_amd import pointops
 

@@ -175,10 +175,12 @@ def test_proposal_stats_few_shot(hip, oracle, nq, N):
     assert (final != fin_t.numpy().astype(np.int32)).sum() <= 1
 
 
-@pytest.mark.parametrize("nq,nc,B,ff", [(256, 512, 1, 64), (100, 300, 2, 128), (16, 40, 1, 256)])
+@pytest.mark.parametrize("nq,nc,B,ff", [(256, 512, 1, 64), (100, 300, 2, 128), (16, 40, 1, 256), (300, 700, 2, 256),
+                                        (128, 2048, 2, 256)])
 def test_decoder_token_stages_fused(hip, nq, nc, B, ff):
     """Whole fused decoder (token stages + cross-attention launches) vs the layer-by-layer PyTorch modules
-    (transformer_detr.py:130-166, 425-463) around the same cross-attention kernel."""
+    (transformer_detr.py:130-166, 425-463) around the same cross-attention kernel.  nq = 300 runs stage B's online
+    soft-max loop (more than 16 key tiles), nq = 128 two_pass<8> with all eight tiles filled."""
     from geoformer_amd.model.layers import RelPosSpec, TransformerDecoder, TransformerDecoderLayer
 
     torch.manual_seed(nq + ff)

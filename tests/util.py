@@ -247,3 +247,32 @@ def _calibrated_benchmark_state(host_batch, nfg_frac, seed, cfg_name, mask_logit
             m.controller.weight.mul_(a)
             m.controller.bias.mul_(a)
         return {k: v.clone() for k, v in m.state_dict().items()}, scale
+
+
+def decoder_pre_reference(layer, x, qpos, keep_attn=None, keep_res=None):
+    """float64 restatement of the token side of TransformerDecoderLayer.forward_pre_rel before the cross-attention:
+    norm1 -> 4-head self-attention (d_k 16) -> out_proj + residual -> norm2 -> query half of attn_mlp[0].
+    x, qpos [B,T,64] (taken as float64, autograd flows through them); keep_attn [B,4,T,T] and keep_res [B,T,64] are
+    the dropout keep factors of the attention weights and of the residual branch (None: no dropout).
+    Returns (x1, t2n, q1): the updated target, norm2's output and the query half of the cross-attention's first linear."""
+    import torch
+    import torch.nn.functional as F
+
+    D = lambda t: t.double()  # noqa: E731
+    ln = lambda v, m: F.layer_norm(v, (64,), D(m.weight), D(m.bias), m.eps)  # noqa: E731
+    B, T, _ = x.shape
+    sa = layer.self_attn
+    t2 = ln(D(x), layer.norm1)
+    qk = t2 + D(qpos)
+    Wi, bi = D(sa.in_proj_weight), D(sa.in_proj_bias)
+    q = (qk @ Wi[:64].t() + bi[:64]).view(B, T, 4, 16).transpose(1, 2)
+    k = (qk @ Wi[64:128].t() + bi[64:128]).view(B, T, 4, 16).transpose(1, 2)
+    v = (t2 @ Wi[128:].t() + bi[128:]).view(B, T, 4, 16).transpose(1, 2)
+    s = torch.softmax((q * 0.25) @ k.transpose(2, 3), dim=-1)  # [B,4,T,T]
+    if keep_attn is not None:
+        s = s * D(keep_attn)
+    o = (s @ v).transpose(1, 2).reshape(B, T, 64)
+    att = o @ D(sa.out_proj.weight).t() + D(sa.out_proj.bias)
+    x1 = D(x) + (att if keep_res is None else att * D(keep_res))
+    t2n = ln(x1, layer.norm2)
+    return x1, t2n, t2n @ D(layer.attn_mlp[0].weight).t() + D(layer.attn_mlp[0].bias)
