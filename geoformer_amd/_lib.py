@@ -123,6 +123,7 @@ def _declare(lib):
         "gf_proposal_scatter_batched": (I, [P, I, I, P, P, I, I, P, F, P, P]),
         "gf_mask_intersections_batched": (I, [P, I, c_longlong, c_longlong, P, P, P]),
         "gf_matrix_nms_batched": (I, [P, I, P, I, F, F, P, P, P]),
+        "gf_label_map_batched": (I, [P, I, c_longlong, I, F, P, P, P, P, P, P, P, P, P]),
         "gf_instance_overlaps_scratch_bytes": (c_size_t, [I, I]),
         "gf_instance_overlaps": (I, [P, I, I, P, I, P, P, I, I, P, P, P, P, P, P]),
         "gf_voxelize_idx_scratch_bytes": (c_size_t, [I]),

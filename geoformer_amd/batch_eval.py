@@ -4,6 +4,8 @@
         ...                                   # masks int32 [n, N] over the scene's points, pick: the NMS result
     ap, avgs = evaluate(model, [(name, raw), ...], batch_size=4)
     print(evaluation.format_results(avgs))
+    for name, labels in label_batches(model, [(name, raw), ...], batch_size=4):
+        ...                                   # labels.ids / .owner [N], labels.table: one row per instance (host)
 
 A batch of raw scenes ([N, 8] = xyz, rgb, semantic label, instance label, as prepare_data_inst.py stores them) is
 collated on the host (scene.collate_raw), uploaded and voxelised on the GPU one batch ahead (feeder.DeviceFeeder), and
@@ -71,6 +73,41 @@ def predict_batches(model, raw_scenes, batch_size, *, epoch=300, spatial_shape=N
                                                kernel=nms_kernel, sigma=sigma, final_score_thresh=final_score_thresh)
         for (name, _), (cls, sc, masks), pick in zip(chunk, per, picks):
             yield name, cls, sc, masks, pick
+
+
+@torch.no_grad()
+def label_batches(model, raw_scenes, batch_size, *, min_score=postprocess.MIN_SCORE, keep_masks=False, **kw):
+    """Yields (name, SceneLabels) per scene, in input order, with the results on the host: the loop of predict_batches
+    with postprocess.label_points_batched once per batch of scenes.  Per scene the per-point maps (ids, owner) and the
+    instance table cross to the host; the picked masks [p, N] (rank order, SceneLabels.masks) only with keep_masks=True.
+    Keywords go to predict_batches."""
+    items = list(raw_scenes)
+    raws = dict(items)
+    dev = torch.device(kw["device"]) if kw.get("device") is not None else next(model.parameters()).device
+    pending = []
+
+    def flush():
+        cvfold = model.cfg.cvfold if kw.get("cvfold") is None else kw["cvfold"]
+        ids = [evaluation.benchmark_label_ids(c, cvfold) if torch.is_tensor(c) else [] for _, c, *_ in pending]
+        xyzs = [torch.as_tensor(np.asarray(raws[n])[:, :3].astype(np.float32)).to(dev, non_blocking=True)
+                for n, *_ in pending]
+        table, packed = postprocess._label_batch_packed([m for *_, m, _ in pending], [s for _, _, s, _, _ in pending],
+                                                        ids, [p for *_, p in pending], xyzs, min_score)
+        # the batch's maps and tables cross in three copies, whatever the number of scenes
+        out = postprocess._split_labels(table, *[b.cpu().numpy() for b in packed])
+        for (name, _, _, masks, pick), lab in zip(pending, out):
+            if keep_masks:
+                m = masks[pick].cpu().numpy() if torch.is_tensor(masks) else np.zeros((0, lab.owner.shape[0]), np.int32)
+                lab = lab._replace(masks=m)
+            yield name, lab
+        pending.clear()
+
+    for rec in predict_batches(model, items, batch_size, **kw):
+        pending.append(rec)
+        if len(pending) == batch_size:
+            yield from flush()
+    if pending:
+        yield from flush()
 
 
 @torch.no_grad()

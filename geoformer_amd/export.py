@@ -1,0 +1,82 @@
+"""Scene labels on disk: the ScanNet benchmark's instance-prediction files and one .npz per scene.
+
+    labels = postprocess.label_points(masks, scores, label_ids, pick, xyz)          # or batch_eval.label_batches
+    write_scannet_predictions("out", "scene0011_00", labels)                        # exclusive masks (owner == r)
+    label_ids, scores, masks = read_scannet_predictions("out", "scene0011_00")
+
+``<out_dir>/<name>.txt`` holds one ``predicted_masks/<name>_<rrr>.txt <label_id> <score>`` line per kept instance in
+rank order, the mask file one ``0`` / ``1`` per line for each of the scene's N points: the benchmark's submission format,
+and what util/visualize.py:212-227 reads (relative path, label, score).  Scores are printed as ``%.6f``.
+"""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+
+from .postprocess import InstanceTable, SceneLabels
+
+MASK_DIR = "predicted_masks"
+SCORE_FORMAT = "%.6f"
+_DIGITS = np.array([b"0\n", b"1\n"])
+
+
+def write_scannet_predictions(out_dir, name, labels, masks=None):
+    """Write scene `name`: the kept instances of labels (SceneLabels, host or device) in rank order.  masks None: the
+    exclusive masks owner == r (every point in at most one file); masks [p, N] in rank order (the picked masks, e.g.
+    SceneLabels.masks of label_batches(keep_masks=True)): the full ones.  Returns the path of the scene's .txt."""
+    labels = labels.to_host()
+    t = labels.table
+    owner = labels.owner
+    if masks is not None:
+        masks = masks.detach().cpu().numpy() if hasattr(masks, "detach") else np.asarray(masks)
+        if masks.shape != (len(t.kept), owner.shape[0]):
+            raise ValueError(f"write_scannet_predictions: masks {masks.shape} for {len(t.kept)} ranks over "
+                             f"{owner.shape[0]} points")
+    os.makedirs(os.path.join(out_dir, MASK_DIR), exist_ok=True)
+    lines = []
+    for r in np.nonzero(np.asarray(t.kept))[0]:
+        rel = f"{MASK_DIR}/{name}_{int(r):03d}.txt"
+        m = (owner == r) if masks is None else (masks[r] != 0)
+        with open(os.path.join(out_dir, rel), "wb") as f:
+            f.write(_DIGITS[m.astype(np.intp)].tobytes())
+        lines.append(f"{rel} {int(t.label_id[r])} {SCORE_FORMAT % float(t.score[r])}\n")
+    path = os.path.join(out_dir, f"{name}.txt")
+    with open(path, "w") as f:
+        f.writelines(lines)
+    return path
+
+
+def read_scannet_predictions(out_dir, name):
+    """(label_ids int64 [k], scores fp32 [k], masks uint8 [k, N]) of a written scene, in file order."""
+    with open(os.path.join(out_dir, f"{name}.txt")) as f:
+        rows = [line.rstrip().split() for line in f if line.strip()]
+    label_ids = np.array([int(r[1]) for r in rows], dtype=np.int64)
+    scores = np.array([float(r[2]) for r in rows], dtype=np.float32)
+    masks = []
+    for r in rows:
+        with open(os.path.join(out_dir, r[0]), "rb") as f:
+            raw = np.frombuffer(f.read(), dtype=np.uint8)
+        if raw.size % 2 or (raw[1::2] != ord("\n")).any() or ((raw[0::2] != ord("0")) & (raw[0::2] != ord("1"))).any():
+            raise ValueError(f"{r[0]}: not one 0 / 1 per line")
+        masks.append(raw[0::2] - ord("0"))
+    if masks and any(m.shape != masks[0].shape for m in masks):
+        raise ValueError(f"{name}: mask files of different lengths")
+    return label_ids, scores, (np.stack(masks) if masks else np.zeros((0, 0), np.uint8))
+
+
+def save_labels(path, labels):
+    """One .npz with ids, owner and the instance table (and the masks when the labels carry them)."""
+    labels = labels.to_host()
+    arrays = {"ids": labels.ids, "owner": labels.owner}
+    arrays.update({f"table_{k}": v for k, v in labels.table._asdict().items()})
+    if labels.masks is not None:
+        arrays["masks"] = labels.masks
+    np.savez_compressed(path, **arrays)
+
+
+def load_labels(path):
+    """SceneLabels of a save_labels file."""
+    with np.load(path) as z:
+        table = InstanceTable(*[z[f"table_{k}"] for k in InstanceTable._fields])
+        return SceneLabels(z["owner"], z["ids"], table, z["masks"] if "masks" in z.files else None)

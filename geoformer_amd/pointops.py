@@ -1447,3 +1447,24 @@ def matrix_nms_batched(table, inter, sizes, kernel, sigma, final_score_thresh):
                                             float(final_score_thresh), ptr(picks), ptr(counts), stream_ptr()),
           "gf_matrix_nms_batched")
     return picks, counts
+
+
+def label_map_batched(table, sizes, min_score):
+    """gf_label_map_batched on a device label scene table (postprocess.label_scene_table): (int32 [2, points] = owner,
+    ids; tab_i int32 [rows, GF_LBL_TABLE_INTS]; tab_f fp32 [rows, GF_LBL_TABLE_FLOATS])."""
+    from .postprocess import LBL_OWN_SPLIT, LBL_TABLE_FLOATS, LBL_TABLE_INTS
+
+    dev = table.device
+    bits = torch.empty(max(int(sizes["bits"]), 1), dtype=torch.int64, device=dev)
+    parts = max(int(sizes["parts"]), 1)
+    part_f = torch.empty((parts, 9), dtype=torch.float32, device=dev)
+    part_i = torch.empty(parts * (1 + LBL_OWN_SPLIT), dtype=torch.int32, device=dev)  # part_cnt, own_part
+    points, rows = int(sizes["points"]), int(sizes["rows"])
+    pts = torch.empty((2, max(points, 1)), dtype=torch.int32, device=dev)
+    tab_i = torch.empty((max(rows, 1), LBL_TABLE_INTS), dtype=torch.int32, device=dev)
+    tab_f = torch.empty((max(rows, 1), LBL_TABLE_FLOATS), dtype=torch.float32, device=dev)
+    check(_lib.load().gf_label_map_batched(ptr(table), table.shape[0], int(sizes["max_points"]), int(sizes["max_picks"]),
+                                           float(min_score), ptr(bits), ptr(part_f), ptr(part_i), ptr(part_i[parts:]),
+                                           ptr(pts[0]), ptr(pts[1]), ptr(tab_i), ptr(tab_f), stream_ptr()),
+          "gf_label_map_batched")
+    return pts[:, :points], tab_i[:rows], tab_f[:rows]

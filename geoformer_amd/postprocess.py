@@ -2,6 +2,8 @@
 test.py:88-93 right after the forward)."""
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import numpy as np
 import torch
 
@@ -150,3 +152,171 @@ def matrix_nms_batched(masks, scores, categories, kernel="gaussian", sigma=2.0, 
     counts_h = counts.cpu().tolist()
     picks = picks.long()
     return [picks[int(table[b, 7]):int(table[b, 7]) + counts_h[b]] for b in range(len(ns))]
+
+
+# ---- scene labelling (csrc/label_map.hip): one label per point, one table row per picked instance ---------------------
+LBL_SCENE_FIELDS = 12  # GF_LBL_SCENE_FIELDS
+LBL_CHUNK = 4096  # GF_LBL_CHUNK
+LBL_OWN_SPLIT = 4  # GF_LBL_OWN_SPLIT
+LBL_TABLE_INTS = 5  # GF_LBL_TABLE_INTS
+LBL_TABLE_FLOATS = 10  # GF_LBL_TABLE_FLOATS
+MIN_SCORE = 0.09  # util/visualize.py:221
+
+
+class InstanceTable(NamedTuple):
+    """One row per rank r of pick.  Geometry is over the whole mask (zeros when count == 0)."""
+    count: object  # int32 [p]: points of the mask
+    owned: object  # int32 [p]: points whose owner is r
+    label_id: object  # int32 [p]: label_ids[pick[r]]
+    index: object  # int32 [p]: pick[r], the original proposal
+    kept: object  # bool [p]: score >= min_score
+    score: object  # fp32 [p]
+    centroid: object  # fp32 [p, 3]
+    box_min: object  # fp32 [p, 3]
+    box_max: object  # fp32 [p, 3]
+
+
+class SceneLabels(NamedTuple):
+    owner: object  # int32 [N]: rank into pick of the instance that owns the point, -1 without one
+    ids: object  # int32 [N]: label_id * 1000 + owner + 1 (the val_gt encoding), 0 without an owner
+    table: InstanceTable
+    masks: object = None  # label_batches(keep_masks=True): the picked masks [p, N], rank order
+
+    def to_host(self):
+        """The same labels as numpy arrays."""
+        h = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else (None if a is None else np.asarray(a))  # noqa: E731
+        return SceneLabels(h(self.owner), h(self.ids), InstanceTable(*[h(c) for c in self.table]), h(self.masks))
+
+
+def _table_from_packed(ti, tf):
+    return InstanceTable(ti[:, 0], ti[:, 1], ti[:, 2], ti[:, 3], ti[:, 4] != 0, tf[:, 9], tf[:, 0:3], tf[:, 3:6], tf[:, 6:9])
+
+
+def _label_points_host(masks, scores, label_ids, pick, xyz, min_score):
+    """numpy path of label_points: the same integers as the kernels; centroid accumulated in float64."""
+    xyz = np.asarray(xyz, dtype=np.float32).reshape(-1, 3)
+    N = xyz.shape[0]
+    pick = np.asarray(pick, dtype=np.int64).reshape(-1)
+    p = pick.shape[0]
+    masks = np.asarray(masks).reshape(-1, N) if p else np.zeros((0, N), np.int32)
+    scores = np.asarray(scores, dtype=np.float32).reshape(-1)
+    label_ids = np.asarray(label_ids, dtype=np.int64).reshape(-1)
+    if p and (pick.min() < 0 or pick.max() >= masks.shape[0]):
+        raise ValueError("label_points: pick outside the masks")
+    if p > NMS_MAX_N:
+        raise ValueError(f"label_points: at most {NMS_MAX_N} picked instances per scene, got {p}")
+    m = masks[pick] != 0
+    sc = scores[pick]
+    kept = sc >= np.float32(min_score)
+    lab = label_ids[pick].astype(np.int32)
+    owner = np.full(N, -1, np.int32)
+    for r in np.nonzero(kept)[0]:
+        sel = m[r] & (owner < 0)
+        owner[sel] = r
+    own = np.maximum(owner, 0)
+    ids = np.where(owner >= 0, lab[own] * 1000 + owner + 1, 0).astype(np.int32) if p else np.zeros(N, np.int32)
+    count = m.sum(1).astype(np.int32)
+    owned = np.bincount(owner[owner >= 0], minlength=p).astype(np.int32)
+    centroid = np.zeros((p, 3), np.float32)
+    box_min = np.zeros((p, 3), np.float32)
+    box_max = np.zeros((p, 3), np.float32)
+    x64 = xyz.astype(np.float64)
+    for r in range(p):
+        if count[r]:
+            q = m[r]
+            centroid[r] = (x64[q].sum(0) / count[r]).astype(np.float32)
+            box_min[r], box_max[r] = xyz[q].min(0), xyz[q].max(0)
+    return SceneLabels(owner, ids, InstanceTable(count, owned, lab, pick.astype(np.int32), kept, sc, centroid, box_min,
+                                                 box_max))
+
+
+def label_scene_table(mask_ptrs, widths, ns, ps, pick_ptrs, score_ptrs, label_ptrs, xyz_ptrs):
+    """(int64 [S, LBL_SCENE_FIELDS] label scene table, sizes) for scenes of ps[b] picks out of ns[b] masks over widths[b]
+    points.  sizes: uint64 words of the packed bits ("bits"), partial records ("parts"), table rows ("rows"), points
+    ("points") in total, and the largest per-scene point / pick counts of the launches."""
+    N = np.asarray(widths, dtype=np.int64).reshape(-1)
+    n = np.asarray(ns, dtype=np.int64).reshape(-1)
+    p = np.asarray(ps, dtype=np.int64).reshape(-1)
+    if (n < 0).any() or (N < 0).any() or (p < 0).any():
+        raise ValueError("label_scene_table: negative size")
+    if (p > NMS_MAX_N).any():
+        raise ValueError(f"label_points: at most {NMS_MAX_N} picked instances per scene, got {int(p.max())}")
+    S = N.shape[0]
+    words = p * ((N + 63) // 64)
+    parts = p * ((N + LBL_CHUNK - 1) // LBL_CHUNK)
+    excl = lambda a: np.concatenate([[0], np.cumsum(a)[:-1]]) if S else []  # noqa: E731
+    t = np.zeros((S, LBL_SCENE_FIELDS), dtype=np.int64)
+    t[:, 0] = np.asarray(mask_ptrs, dtype=np.int64)
+    t[:, 1], t[:, 2], t[:, 3] = N, n, p
+    t[:, 4] = np.asarray(pick_ptrs, dtype=np.int64)
+    t[:, 5] = np.asarray(score_ptrs, dtype=np.int64)
+    t[:, 6] = np.asarray(label_ptrs, dtype=np.int64)
+    t[:, 7] = np.asarray(xyz_ptrs, dtype=np.int64)
+    t[:, 8], t[:, 9], t[:, 10], t[:, 11] = excl(words), excl(parts), excl(p), excl(N)
+    sizes = {"bits": int(words.sum()), "parts": int(parts.sum()), "rows": int(p.sum()), "points": int(N.sum()),
+             "max_points": int(N.max()) if S else 0, "max_picks": int(p.max()) if S else 0}
+    return t, sizes
+
+
+def _label_batch_packed(masks, scores, label_ids, picks, xyzs, min_score):
+    """The batch's launches: (scene table (host), packed device buffers of pointops.label_map_batched)."""
+    from . import pointops
+
+    S = len(xyzs)
+    if not (len(masks) == len(scores) == len(label_ids) == len(picks) == S):
+        raise ValueError("label_points_batched: one entry per scene in every list")
+    dev = next((x.device for x in xyzs if torch.is_tensor(x)), None)
+    if dev is None or dev.type != "cuda":
+        raise RuntimeError("label_points_batched: the kernels run on the GPU; label_points has the numpy path")
+    keep, rows, Ns, ns, ps = [], [], [], [], []
+    for m, s, l, pk, x in zip(masks, scores, label_ids, picks, xyzs):
+        x = torch.as_tensor(x, device=dev).to(torch.float32).reshape(-1, 3).contiguous()
+        N = x.shape[0]
+        pk = torch.as_tensor(pk, device=dev).to(torch.int64).reshape(-1).contiguous() if len(pk) else None
+        if not torch.is_tensor(m) or m.shape[0] == 0 or pk is None:
+            keep.append(x)
+            rows.append((0, 0, 0, 0, x.data_ptr())), Ns.append(N), ns.append(0), ps.append(0)
+            continue
+        m = (m if m.dtype == torch.int32 else (m != 0).int()).contiguous()
+        s = torch.as_tensor(s, device=dev).to(torch.float32).contiguous()
+        l = torch.as_tensor(l, device=dev).to(torch.int64).contiguous()
+        if m.dim() != 2 or m.shape[1] != N or s.shape != (m.shape[0],) or l.shape != (m.shape[0],):
+            raise ValueError("label_points: masks [n, N], scores [n], label_ids [n], xyz [N, 3]")
+        keep += [m, s, l, pk, x]
+        rows.append((m.data_ptr(), pk.data_ptr(), s.data_ptr(), l.data_ptr(), x.data_ptr()))
+        Ns.append(N), ns.append(m.shape[0]), ps.append(pk.shape[0])
+    table, sizes = label_scene_table([r[0] for r in rows], Ns, ns, ps, [r[1] for r in rows], [r[2] for r in rows],
+                                     [r[3] for r in rows], [r[4] for r in rows])
+    table_d = pointops._table_dev(table, dev)
+    return table, pointops.label_map_batched(table_d, sizes, min_score)
+
+
+def _split_labels(table, pts, ti, tf):
+    """One SceneLabels per row of the scene table: views of the packed buffers (device tensors or numpy arrays)."""
+    out = []
+    for t in table:
+        N, p, r, o = int(t[1]), int(t[3]), int(t[10]), int(t[11])
+        out.append(SceneLabels(pts[0, o:o + N], pts[1, o:o + N], _table_from_packed(ti[r:r + p], tf[r:r + p])))
+    return out
+
+
+def label_points_batched(masks, scores, label_ids, picks, xyzs, min_score=MIN_SCORE):
+    """label_points of several scenes at once on the GPU: lists with one entry per scene (a scene without proposals may
+    give [] for masks / scores / label_ids, as predict_batches yields it; xyz is always needed).  One table upload and the
+    three launches of gf_label_map_batched for the whole batch; returns one SceneLabels per scene, on the device (views of
+    the batch's buffers)."""
+    table, (pts, ti, tf) = _label_batch_packed(masks, scores, label_ids, picks, xyzs, min_score)
+    return _split_labels(table, pts, ti, tf)
+
+
+def label_points(masks, scores, label_ids, pick, xyz, min_score=MIN_SCORE):
+    """Per-point instance labels and the instance table of one scene from its picked masks: masks [n, N] 0/1, scores
+    [n], label_ids [n] (benchmark ids, evaluation.benchmark_label_ids), pick [p] rows of masks in descending score order
+    (the NMS result), xyz [N, 3].  The owner of a point is the lowest rank r in pick with score >= min_score whose mask
+    covers it (util/visualize.py:219-227 paints from the last to the first).  CUDA tensors take the kernels and the
+    results stay on the device; numpy arrays / CPU tensors take the numpy path.  A scene without proposals ([] for
+    masks) gives an all -1 / all 0 map and an empty table."""
+    if torch.is_tensor(xyz) and xyz.is_cuda:
+        return label_points_batched([masks], [scores], [label_ids], [pick], [xyz], min_score)[0]
+    h = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)  # noqa: E731
+    return _label_points_host(h(masks), h(scores), h(label_ids), h(pick), h(xyz), min_score)

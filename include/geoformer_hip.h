@@ -770,6 +770,35 @@ int gf_matrix_nms_batched(const long long* table, int S, const int32_t* inter, i
                           float final_score_thresh, int32_t* picks, int32_t* pick_counts, void* stream);
 
 /* ===================================================================================
+ * Scene labelling from the picked masks of S scenes (csrc/label_map.hip): one label per point and one table row per
+ * picked instance, as util/visualize.py:219-227 paints them (from the last pick to the first, score < min_score
+ * skipped, a later paint wins): the owner of a point is the LOWEST rank r in pick whose score is >= min_score and whose
+ * mask covers the point.  Three launches for any S, n, p; no read-back; no atomics in global memory (bit-identical
+ * results from call to call, and for a scene alone or in a batch).
+ * Label scene table, int64 [S, GF_LBL_SCENE_FIELDS], one row per scene:
+ *   {masks pointer (int32 [n_b, N_b], nonzero = member), N_b, n_b, p_b (<= GF_NMS_MAX_N), pick pointer (int64 [p_b],
+ *    rows of masks; a value outside [0, n_b) is an empty, not-kept row), scores pointer (fp32 [n_b]), label_ids pointer
+ *    (int64 [n_b]), xyz pointer (fp32 [N_b, 3]), bits_off (uint64 words into bits, p_b * ceil(N_b / 64) of them),
+ *    part_off (records into part_f / part_cnt / own_part, p_b * ceil(N_b / GF_LBL_CHUNK) of them), row_off (rows into
+ *    tab_i / tab_f, p_b of them), pt_off (elements into owner / ids, N_b of them)}.
+ * Scratch: bits, part_f fp32 [records, 9], part_cnt int32 [records], own_part int32 [GF_LBL_OWN_SPLIT * records].
+ * Outputs:
+ *   owner int32: rank into pick or -1;  ids int32: label_ids[pick[owner]] * 1000 + owner + 1, 0 without an owner;
+ *   tab_i int32 [rows, GF_LBL_TABLE_INTS]   = {count (points of the mask), owned (points with owner == r), label_id,
+ *                                              pick[r], kept (score >= min_score)};
+ *   tab_f fp32  [rows, GF_LBL_TABLE_FLOATS] = {centroid xyz, box_min xyz, box_max xyz (over the whole mask; zeros when
+ *                                              count == 0), score}.
+ * max_points / max_picks: the largest N_b / p_b over the scenes. */
+#define GF_LBL_SCENE_FIELDS 12
+#define GF_LBL_CHUNK 4096
+#define GF_LBL_OWN_SPLIT 4
+#define GF_LBL_TABLE_INTS 5
+#define GF_LBL_TABLE_FLOATS 10
+int gf_label_map_batched(const long long* table, int S, long long max_points, int max_picks, float min_score,
+                         void* bits, float* part_f, int32_t* part_cnt, int32_t* own_part, int32_t* owner, int32_t* ids,
+                         int32_t* tab_i, float* tab_f, void* stream);
+
+/* ===================================================================================
  * Overlap tables of the ScanNet instance evaluation for one scene (assign_instances_for_scan, util/eval.py:290-355,
  * with get_instances, util/utils_3d.py:18-73): everything the evaluation derives from the N points.
  *   masks int32 [n_rows,N] (gf_proposal_scatter layout; any nonzero is a member), rows int32 [n] (may be NULL: row i

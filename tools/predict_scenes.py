@@ -1,0 +1,110 @@
+"""Label maps and ScanNet benchmark files of scenes: the eval forward, matrix NMS and the scene labelling of
+batch_eval.label_batches, written with geoformer_amd.export.
+
+    python tools/predict_scenes.py --out out scene0011_00_inst_nostuff.npy ...      # [N, 8] as prepare_data_inst.py stores them
+    python tools/predict_scenes.py --out out --synthetic 8 --points 150000 --batch-size 4
+    python tools/predict_scenes.py --synthetic 8 --no-write                          # only the timing
+
+Per scene <out>/<name>.npz (ids, owner, instance table: export.load_labels) and, with --scannet, <out>/<name>.txt plus
+<out>/predicted_masks/ (exclusive masks; --full-masks writes the picked masks as they are).  Without --checkpoint the
+benchmark's synthetic model (bench.build_model) runs.  Prints one JSON line with the scenes per second of the
+label_batches loop, results on the host, for keep_masks off and on, beside the bare predict_batches loop (wall clock,
+host collate included, files not).
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("scenes", nargs="*", help="scene .npy files, [N, 8] = xyz, rgb, semantic label, instance label")
+    ap.add_argument("--synthetic", type=int, default=0, metavar="K", help="K synthetic scenes (scene.make_raw_scene)")
+    ap.add_argument("--points", type=int, default=150_000, help="points per synthetic scene")
+    ap.add_argument("--out", default="predictions")
+    ap.add_argument("--batch-size", type=int, default=4)
+    ap.add_argument("--min-score", type=float, default=None, help="default: postprocess.MIN_SCORE (0.09)")
+    ap.add_argument("--nms-score", type=float, default=None, help="final_score_thresh of the matrix NMS (default 0.5)")
+    ap.add_argument("--checkpoint", default=None, help="state dict (torch.save) of a GeoFormer of --config")
+    ap.add_argument("--config", default="test_geoformer_scannet.yaml")
+    ap.add_argument("--scannet", action="store_true", help="also write the benchmark's .txt files")
+    ap.add_argument("--full-masks", action="store_true", help="benchmark files hold the picked masks, not the exclusive ones")
+    ap.add_argument("--no-write", action="store_true")
+    ap.add_argument("--reps", type=int, default=3, help="timed passes per keep_masks setting")
+    args = ap.parse_args()
+
+    import geoformer_amd
+
+    geoformer_amd.configure_runtime()
+    import bench
+    from geoformer_amd import batch_eval, export, postprocess, scene
+    from geoformer_amd.model import GeoFormer, load_config
+
+    items = [(os.path.splitext(os.path.basename(p))[0], np.load(p)) for p in args.scenes]
+    items += [(f"synthetic{i:04d}", scene.make_raw_scene(args.points, 500 + i)) for i in range(args.synthetic)]
+    if not items:
+        ap.error("no scenes: give .npy files or --synthetic K")
+    for name, raw in items:
+        if raw.ndim != 2 or raw.shape[1] != 8:
+            ap.error(f"{name}: expected [N, 8], got {raw.shape}")
+    dev = torch.device("cuda")
+    if args.checkpoint:
+        model = GeoFormer(load_config(args.config))
+        sd = torch.load(args.checkpoint, map_location="cpu")
+        model.load_state_dict(sd.get("state_dict", sd) if isinstance(sd, dict) else sd)
+        model.to(dev)
+        model.eval()
+    else:
+        probe = scene.make_batch([batch_eval.scene_dict(items[0][1])])
+        model = bench.build_model(dev, probe_batch=bench.to_device(probe, dev), cfg_name=args.config)
+    kw = {"min_score": postprocess.MIN_SCORE if args.min_score is None else args.min_score}
+    if args.nms_score is not None:
+        kw["final_score_thresh"] = args.nms_score
+
+    def run(keep_masks):
+        np.random.seed(0)
+        return list(batch_eval.label_batches(model, items, args.batch_size, keep_masks=keep_masks, **kw))
+
+    results = run(args.full_masks)
+    if not args.no_write:
+        os.makedirs(args.out, exist_ok=True)
+        for name, lab in results:
+            export.save_labels(os.path.join(args.out, f"{name}.npz"), lab._replace(masks=None))
+            if args.scannet:
+                export.write_scannet_predictions(args.out, name, lab, lab.masks if args.full_masks else None)
+    pkw = {k: v for k, v in kw.items() if k != "min_score"}
+
+    def predict_only():  # the loop without the labelling and without any copy of a result, for comparison
+        np.random.seed(0)
+        n = sum(int(pick.numel()) for *_, pick in batch_eval.predict_batches(model, items, args.batch_size, **pkw))
+        torch.cuda.synchronize()
+        return n
+
+    rates = {}
+    for key, fn in (("predict_batches_only", predict_only), ("labels_only", lambda: run(False)),
+                    ("keep_masks", lambda: run(True))):
+        fn()  # (warm: allocator, launch plans)
+        best = []
+        for _ in range(args.reps):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            fn()
+            best.append(len(items) / (time.perf_counter() - t))
+        rates[key] = [round(x, 2) for x in sorted(best)]
+    kept = sum(int(np.sum(lab.table.kept)) for _, lab in results)
+    print(json.dumps({"scenes": len(items), "batch_size": args.batch_size, "min_score": kw["min_score"],
+                      "points": int(sum(r.shape[0] for _, r in items)),
+                      "picked": sum(len(lab.table.kept) for _, lab in results), "kept": kept,
+                      "labelled_points": sum(int((lab.owner >= 0).sum()) for _, lab in results),
+                      "scenes_per_s": rates, "out": None if args.no_write else args.out}))
+
+
+if __name__ == "__main__":
+    main()
