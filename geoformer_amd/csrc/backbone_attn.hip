@@ -20,10 +20,8 @@
 // query on the column, so the soft-max statistics are per-lane-column values and the accumulator of S^T is
 // directly the B operand of O^T = V^T P^T (online soft-max over 16-key tiles, one tile of look-ahead).
 // Norm = alpha * (x - mean) / (std_unbiased + eps) + bias  (transformer.py:62-76).
-#include "common.h"
+#include "tile_gemm.h"
 #include "train_common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define BT_D 128
 #define BT_H 4
@@ -43,112 +41,6 @@ struct BtParams {
     const float *na, *nb, *aw, *ab;
     int nl;
 };
-
-__device__ __forceinline__ f32x4 mfma4(float4 a, float4 b, f32x4 acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc, 0, 0, 0);
-    return acc;
-}
-
-// one 16-row tile: epi(r, col, act(sum_k A[r][k] W[col][k] + b[col]) (+ addend[r][col])) for the column tiles ct = wave,
-// wave+nw, ...  A in LDS or global memory (row stride lda); rows >= nvalid read as zero and are not emitted.  The bias and the
-// epilogue's global operand (`addend`, row stride add_ld) are requested before the products (decoder_layer.h: why).
-template <bool RELU, typename Epi>
-__device__ __forceinline__ void bt_tile_gemm(const float* A, int lda, int nvalid, int K, const float* __restrict__ W,
-                                             const float* __restrict__ bias, int N, int wave, int nwaves, int lane,
-                                             Epi epi, const float* __restrict__ addend = nullptr, int add_ld = 0) {
-    const int j = lane & 15, g = lane >> 4;
-    const int KC = K >> 4;
-    for (int ct = wave; ct < (N >> 4); ct += nwaves) {
-        const float* xa = A + (size_t)j * lda + 4 * g;
-        const float* wb = W + (size_t)(ct * 16 + j) * K + 4 * g;
-        const int col = ct * 16 + j;
-        const float bs = bias[col];
-        float ad[4] = {0.f, 0.f, 0.f, 0.f};
-        if (addend) {
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-                if (4 * g + i < nvalid) ad[i] = addend[(size_t)(4 * g + i) * add_ld + col];
-        }
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 8
-        for (int kc = 0; kc < KC; kc++) {
-            float4 a = j < nvalid ? *reinterpret_cast<const float4*>(xa + kc * 16) : make_float4(0.f, 0.f, 0.f, 0.f);
-            float4 b = *reinterpret_cast<const float4*>(wb + kc * 16);
-            acc = mfma4(a, b, acc);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const int r = 4 * g + i;
-            if (r >= nvalid) continue;
-            float v = acc[i] + bs;
-            if (RELU) v = fmaxf(v, 0.f);
-            if (addend) v += ad[i];
-            epi(r, col, v);
-        }
-    }
-}
-
-// The same product with its weight operands already in registers (decoder_layer.h, DlW: why): bt_w_load requests NT column
-// tiles per wave x KC 16-channel steps + bias ahead of the phase, bt_tile_gemm_w consumes them.  Same arithmetic and order.
-template <int NT, int KC>
-struct BtW {
-    float4 b[NT][KC];
-    float bias[NT];
-};
-template <int NT, int KC>
-__device__ __forceinline__ void bt_w_load(BtW<NT, KC>& w, const float* __restrict__ W, const float* __restrict__ bias, int N,
-                                          int K, int wave, int nwaves, int lane) {
-    const int j = lane & 15, g = lane >> 4;
-#pragma unroll
-    for (int t = 0; t < NT; t++) {
-        const int ct = wave + t * nwaves;
-        const bool on = ct < (N >> 4);
-        const float* wb = W + (size_t)((on ? ct : 0) * 16 + j) * K + 4 * g;
-        w.bias[t] = on ? bias[ct * 16 + j] : 0.f;
-#pragma unroll
-        for (int kc = 0; kc < KC; kc++)
-            w.b[t][kc] = (on && kc < (K >> 4)) ? *reinterpret_cast<const float4*>(wb + kc * 16) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-}
-template <bool RELU, int NT, int KC, typename Epi>
-__device__ __forceinline__ void bt_tile_gemm_w(const float* A, int lda, int nvalid, int K, int N, int wave, int nwaves, int lane,
-                                               const BtW<NT, KC>& w, Epi epi, const float* __restrict__ addend = nullptr,
-                                               int add_ld = 0) {
-    const int j = lane & 15, g = lane >> 4;
-    const float* xa = A + (size_t)j * lda + 4 * g;
-#pragma unroll
-    for (int t = 0; t < NT; t++) {
-        const int ct = wave + t * nwaves;
-        if (ct >= (N >> 4)) break;
-        const int col = ct * 16 + j;
-        float ad[4] = {0.f, 0.f, 0.f, 0.f};
-        if (addend) {
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-                if (4 * g + i < nvalid) ad[i] = addend[(size_t)(4 * g + i) * add_ld + col];
-        }
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kc = 0; kc < KC; kc++) {
-            if (kc < (K >> 4)) {
-                float4 a = j < nvalid ? *reinterpret_cast<const float4*>(xa + kc * 16) : make_float4(0.f, 0.f, 0.f, 0.f);
-                acc = mfma4(a, w.b[t][kc], acc);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const int r = 4 * g + i;
-            if (r >= nvalid) continue;
-            float v = acc[i] + w.bias[t];
-            if (RELU) v = fmaxf(v, 0.f);
-            if (addend) v += ad[i];
-            epi(r, col, v);
-        }
-    }
-}
 
 // Norm (transformer.py:62-76) of the rows of an LDS tile: one wave per row, two channels per lane
 struct BtNormP {  // a lane's two channels of a norm's alpha / bias (loaded ahead of the phase)
@@ -183,11 +75,11 @@ __device__ __forceinline__ void bt_tile_norm_p(const float (*S)[BT_LD], int nval
 // q, k, v of the tile from its normed rows (LDS) into the scene's QKV[T][384]
 __device__ __forceinline__ void bt_tile_qkv(const float (*S)[BT_LD], int nvalid, const BtLayer& L, float* qkv_rows,
                                             int wave, int nwaves, int lane) {
-    bt_tile_gemm<false>(&S[0][0], BT_LD, nvalid, BT_D, L.qw, L.qb, BT_D, wave, nwaves, lane,
+    gf_tile_gemm<false>(&S[0][0], BT_LD, nvalid, BT_D, L.qw, L.qb, BT_D, wave, nwaves, lane,
                         [&](int r, int c, float v) { qkv_rows[(size_t)r * (3 * BT_D) + c] = v; });
-    bt_tile_gemm<false>(&S[0][0], BT_LD, nvalid, BT_D, L.kw, L.kb, BT_D, wave, nwaves, lane,
+    gf_tile_gemm<false>(&S[0][0], BT_LD, nvalid, BT_D, L.kw, L.kb, BT_D, wave, nwaves, lane,
                         [&](int r, int c, float v) { qkv_rows[(size_t)r * (3 * BT_D) + BT_D + c] = v; });
-    bt_tile_gemm<false>(&S[0][0], BT_LD, nvalid, BT_D, L.vw, L.vb, BT_D, wave, nwaves, lane,
+    gf_tile_gemm<false>(&S[0][0], BT_LD, nvalid, BT_D, L.vw, L.vb, BT_D, wave, nwaves, lane,
                         [&](int r, int c, float v) { qkv_rows[(size_t)r * (3 * BT_D) + 2 * BT_D + c] = v; });
 }
 
@@ -207,15 +99,15 @@ __global__ __launch_bounds__(BT_THREADS) void k_bt_pre(const float* __restrict__
     float* X = scratch + (size_t)s0 * BT_SCRATCH_PER_TOKEN;
     float* QKV = X + (size_t)T * BT_D;
     const int* xyz = coords + (size_t)s0 * 4;
-    // every phase's weights, biases and norm parameters requested now (bt_w_load: why)
+    // every phase's weights, biases and norm parameters requested now (gf_tile_w_load: why)
     constexpr int KCI = 8;  // input widths up to 128 channels
-    BtW<1, KCI> w_b;
-    BtW<1, BT_D / 16> w_q, w_k, w_v;
-    bt_w_load(w_b, P.bw, P.bb, BT_D, c, wave, nw, lane);
+    GfTileW<1, KCI> w_b;
+    GfTileW<1, BT_D / 16> w_q, w_k, w_v;
+    gf_tile_w_load(w_b, P.bw, P.bb, BT_D, c, wave, nw, lane);
     const BtNormP np1 = bt_norm_load(P.L[0].n1a, P.L[0].n1b, lane);
-    bt_w_load(w_q, P.L[0].qw, P.L[0].qb, BT_D, BT_D, wave, nw, lane);
-    bt_w_load(w_k, P.L[0].kw, P.L[0].kb, BT_D, BT_D, wave, nw, lane);
-    bt_w_load(w_v, P.L[0].vw, P.L[0].vb, BT_D, BT_D, wave, nw, lane);
+    gf_tile_w_load(w_q, P.L[0].qw, P.L[0].qb, BT_D, BT_D, wave, nw, lane);
+    gf_tile_w_load(w_k, P.L[0].kw, P.L[0].kb, BT_D, BT_D, wave, nw, lane);
+    gf_tile_w_load(w_v, P.L[0].vw, P.L[0].vb, BT_D, BT_D, wave, nw, lane);
     // (... and what the first product's epilogue reads: the positional layer's column of this lane, its rows' coordinates)
     const int pcol = wave * 16 + (lane & 15);  // the one column tile of this wave (BT_D / 16 = nw tiles)
     const float pw0 = P.pw[pcol * 3], pw1 = P.pw[pcol * 3 + 1], pw2 = P.pw[pcol * 3 + 2], pbc = P.pb[pcol];
@@ -249,7 +141,7 @@ __global__ __launch_bounds__(BT_THREADS) void k_bt_pre(const float* __restrict__
     const float ft = (float)T;
     static_assert(BT_D / 16 == BT_THREADS / 64, "k_bt_pre: one column tile of the first product per wave");
     if (c <= KCI * 16) {
-        bt_tile_gemm_w<false>(feats + ((size_t)s0 + t0) * c, c, nvalid, c, BT_D, wave, nw, lane, w_b,
+        gf_tile_gemm_w<false>(feats + ((size_t)s0 + t0) * c, c, nvalid, c, BT_D, wave, nw, lane, w_b,
                               [&](int r, int col, float v) {
                                   const int i = r & 3;  // (r = 4 (lane >> 4) + i)
                                   const float r0 = (float)(T * tzr[i][0] - psum[0]) / ft;
@@ -260,7 +152,7 @@ __global__ __launch_bounds__(BT_THREADS) void k_bt_pre(const float* __restrict__
                               });
     } else {
         const int* tz = xyz + (size_t)t0 * 4;
-        bt_tile_gemm<false>(feats + ((size_t)s0 + t0) * c, c, nvalid, c, P.bw, P.bb, BT_D, wave, nw, lane,
+        gf_tile_gemm<false>(feats + ((size_t)s0 + t0) * c, c, nvalid, c, P.bw, P.bb, BT_D, wave, nw, lane,
                             [&](int r, int col, float v) {
                                 const float r0 = (float)(T * tz[r * 4 + 1] - psum[0]) / ft;
                                 const float r1 = (float)(T * tz[r * 4 + 2] - psum[1]) / ft;
@@ -278,11 +170,11 @@ __global__ __launch_bounds__(BT_THREADS) void k_bt_pre(const float* __restrict__
     });
     __syncthreads();
     float* qkv_rows = QKV + (size_t)t0 * (3 * BT_D);
-    bt_tile_gemm_w<false>(&sT[0][0], BT_LD, nvalid, BT_D, BT_D, wave, nw, lane, w_q,
+    gf_tile_gemm_w<false>(&sT[0][0], BT_LD, nvalid, BT_D, BT_D, wave, nw, lane, w_q,
                           [&](int r, int cc, float v) { qkv_rows[(size_t)r * (3 * BT_D) + cc] = v; });
-    bt_tile_gemm_w<false>(&sT[0][0], BT_LD, nvalid, BT_D, BT_D, wave, nw, lane, w_k,
+    gf_tile_gemm_w<false>(&sT[0][0], BT_LD, nvalid, BT_D, BT_D, wave, nw, lane, w_k,
                           [&](int r, int cc, float v) { qkv_rows[(size_t)r * (3 * BT_D) + BT_D + cc] = v; });
-    bt_tile_gemm_w<false>(&sT[0][0], BT_LD, nvalid, BT_D, BT_D, wave, nw, lane, w_v,
+    gf_tile_gemm_w<false>(&sT[0][0], BT_LD, nvalid, BT_D, BT_D, wave, nw, lane, w_v,
                           [&](int r, int cc, float v) { qkv_rows[(size_t)r * (3 * BT_D) + 2 * BT_D + cc] = v; });
 }
 
@@ -309,12 +201,12 @@ __global__ __launch_bounds__(BT_THREADS) void k_bt_layer(const int* __restrict__
     const BtLayer& L = P.L[li];
     // the weights of the phases behind the self-attention, requested now; those of the last phase (next layer's q / k / v or
     // the output layer: 96 registers) once the attention's own registers are free
-    BtW<1, BT_D / 16> w_o, w_f1;
-    BtW<1, BT_FF / 16> w_f2;
-    bt_w_load(w_o, L.ow, L.ob, BT_D, BT_D, wave, nw, lane);
+    GfTileW<1, BT_D / 16> w_o, w_f1;
+    GfTileW<1, BT_FF / 16> w_f2;
+    gf_tile_w_load(w_o, L.ow, L.ob, BT_D, BT_D, wave, nw, lane);
     const BtNormP np2 = bt_norm_load(L.n2a, L.n2b, lane);
-    bt_w_load(w_f1, L.f1w, L.f1b, BT_FF, BT_D, wave, nw, lane);
-    bt_w_load(w_f2, L.f2w, L.f2b, BT_D, BT_FF, wave, nw, lane);
+    gf_tile_w_load(w_f1, L.f1w, L.f1b, BT_FF, BT_D, wave, nw, lane);
+    gf_tile_w_load(w_f2, L.f2w, L.f2b, BT_D, BT_FF, wave, nw, lane);
     if (wave < BT_H) {
         // one wave per head: O[16 queries][32] over all keys of the scene
         const int h = wave;
@@ -355,8 +247,8 @@ __global__ __launch_bounds__(BT_THREADS) void k_bt_layer(const int* __restrict__
             float u0[4] = {0.f, 0.f, 0.f, 0.f}, u1[4] = {0.f, 0.f, 0.f, 0.f};
             if (kt + 1 < QT) fetch(kt + 1, n0, n1, u0, u1);
             f32x4 s = {0.f, 0.f, 0.f, 0.f};
-            s = mfma4(a0, bq0, s);
-            s = mfma4(a1, bq1, s);
+            s = gf_mfma4(a0, bq0, s);
+            s = gf_mfma4(a1, bq1, s);
             float scv[4];
 #pragma unroll
             for (int i = 0; i < 4; i++) scv[i] = (kt * 16 + 4 * g + i) < T ? s[i] * scale : -INFINITY;
@@ -395,18 +287,18 @@ __global__ __launch_bounds__(BT_THREADS) void k_bt_layer(const int* __restrict__
     }
     // (the last phase's operands: requested here, four phases ahead of their use)
     const bool more = li + 1 < P.nl;
-    BtW<1, BT_D / 16> w_q, w_k, w_v;
+    GfTileW<1, BT_D / 16> w_q, w_k, w_v;
     const BtLayer& Ln = P.L[more ? li + 1 : li];
     const BtNormP np3 = more ? bt_norm_load(Ln.n1a, Ln.n1b, lane) : bt_norm_load(P.na, P.nb, lane);
-    bt_w_load(w_q, more ? Ln.qw : P.aw, more ? Ln.qb : P.ab, more ? BT_D : c, BT_D, wave, nw, lane);
+    gf_tile_w_load(w_q, more ? Ln.qw : P.aw, more ? Ln.qb : P.ab, more ? BT_D : c, BT_D, wave, nw, lane);
     if (more) {
-        bt_w_load(w_k, Ln.kw, Ln.kb, BT_D, BT_D, wave, nw, lane);
-        bt_w_load(w_v, Ln.vw, Ln.vb, BT_D, BT_D, wave, nw, lane);
+        gf_tile_w_load(w_k, Ln.kw, Ln.kb, BT_D, BT_D, wave, nw, lane);
+        gf_tile_w_load(w_v, Ln.vw, Ln.vb, BT_D, BT_D, wave, nw, lane);
     }
     __syncthreads();
     // x += out(O)
     const float* xg = X + (size_t)t0 * BT_D;
-    bt_tile_gemm_w<false>(&sO[0][0], BT_LD, nvalid, BT_D, BT_D, wave, nw, lane, w_o,
+    gf_tile_gemm_w<false>(&sO[0][0], BT_LD, nvalid, BT_D, BT_D, wave, nw, lane, w_o,
                           [&](int r, int col, float v) { sX[r][col] = v; }, xg, BT_D);
     __syncthreads();
     bt_tile_norm_p(sX, nvalid, np2, wave, nw, lane, [&](int r, int c2, float v0, float v1) {
@@ -415,10 +307,10 @@ __global__ __launch_bounds__(BT_THREADS) void k_bt_layer(const int* __restrict__
     });
     __syncthreads();
     // x += ff2(relu(ff1(.)));  the hidden tile reuses sO
-    bt_tile_gemm_w<true>(&sT[0][0], BT_LD, nvalid, BT_D, BT_FF, wave, nw, lane, w_f1,
+    gf_tile_gemm_w<true>(&sT[0][0], BT_LD, nvalid, BT_D, BT_FF, wave, nw, lane, w_f1,
                          [&](int r, int col, float v) { sO[r][col] = v; });
     __syncthreads();
-    bt_tile_gemm_w<false>(&sO[0][0], BT_LD, nvalid, BT_FF, BT_D, wave, nw, lane, w_f2,
+    gf_tile_gemm_w<false>(&sO[0][0], BT_LD, nvalid, BT_FF, BT_D, wave, nw, lane, w_f2,
                           [&](int r, int col, float v) { sX[r][col] += v; });
     __syncthreads();
     if (more) {
@@ -430,11 +322,11 @@ __global__ __launch_bounds__(BT_THREADS) void k_bt_layer(const int* __restrict__
         });
         __syncthreads();
         float* qkv_rows = QKVo + (size_t)t0 * (3 * BT_D);
-        bt_tile_gemm_w<false>(&sT[0][0], BT_LD, nvalid, BT_D, BT_D, wave, nw, lane, w_q,
+        gf_tile_gemm_w<false>(&sT[0][0], BT_LD, nvalid, BT_D, BT_D, wave, nw, lane, w_q,
                               [&](int r, int cc, float v) { qkv_rows[(size_t)r * (3 * BT_D) + cc] = v; });
-        bt_tile_gemm_w<false>(&sT[0][0], BT_LD, nvalid, BT_D, BT_D, wave, nw, lane, w_k,
+        gf_tile_gemm_w<false>(&sT[0][0], BT_LD, nvalid, BT_D, BT_D, wave, nw, lane, w_k,
                               [&](int r, int cc, float v) { qkv_rows[(size_t)r * (3 * BT_D) + BT_D + cc] = v; });
-        bt_tile_gemm_w<false>(&sT[0][0], BT_LD, nvalid, BT_D, BT_D, wave, nw, lane, w_v,
+        gf_tile_gemm_w<false>(&sT[0][0], BT_LD, nvalid, BT_D, BT_D, wave, nw, lane, w_v,
                               [&](int r, int cc, float v) { qkv_rows[(size_t)r * (3 * BT_D) + 2 * BT_D + cc] = v; });
     } else {
         bt_tile_norm_p(sX, nvalid, np3, wave, nw, lane, [&](int r, int c2, float v0, float v1) {
@@ -443,12 +335,12 @@ __global__ __launch_bounds__(BT_THREADS) void k_bt_layer(const int* __restrict__
         });
         __syncthreads();
         float* y = out + ((size_t)s0 + t0) * c;
-        bt_tile_gemm_w<false>(&sT[0][0], BT_LD, nvalid, BT_D, c, wave, nw, lane, w_q,
+        gf_tile_gemm_w<false>(&sT[0][0], BT_LD, nvalid, BT_D, c, wave, nw, lane, w_q,
                               [&](int r, int col, float v) { y[(size_t)r * c + col] = v; });
         if (WIDE) {
             // the registers held the output layer's first BT_D / 16 column tiles (one per wave); its rows BT_D .. c-1
             // straight from memory
-            bt_tile_gemm<false>(&sT[0][0], BT_LD, nvalid, BT_D, P.aw + (size_t)BT_D * BT_D, P.ab + BT_D, c - BT_D, wave, nw,
+            gf_tile_gemm<false>(&sT[0][0], BT_LD, nvalid, BT_D, P.aw + (size_t)BT_D * BT_D, P.ab + BT_D, c - BT_D, wave, nw,
                                 lane, [&](int r, int col, float v) { y[(size_t)r * c + BT_D + col] = v; });
         }
     }
@@ -645,30 +537,6 @@ __global__ void k_bt_offsets_tiles(const int* __restrict__ coords, int M, int n_
     for (; t < max_tiles; t++) tile_scene[t] = -1;
 }
 
-// out[r][col] = sum_o A[r][o] W[o][col]: the product with a row-major nn.Linear weight [out, in] summed over its OUT
-// index (gradient towards a layer's input).  A: LDS tile of 16 rows (rows that do not exist hold zeros), K = number of
-// summed rows of W, N = columns produced (multiple of 16)
-template <typename Epi>
-__device__ __forceinline__ void bt_tile_gemm_t(const float* A, int lda, int K, const float* __restrict__ W, int ldw,
-                                               int N, int wave, int nwaves, int lane, Epi epi) {
-    const int j = lane & 15, g = lane >> 4;
-    const int KC = K >> 4;
-    for (int ct = wave; ct < (N >> 4); ct += nwaves) {
-        const float* xa = A + (size_t)j * lda + 4 * g;
-        const float* wb = W + (size_t)(4 * g) * ldw + ct * 16 + j;
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 2
-        for (int kc = 0; kc < KC; kc++) {
-            const float4 a = *reinterpret_cast<const float4*>(xa + kc * 16);
-            const float* w = wb + (size_t)kc * 16 * ldw;
-            const float4 b = make_float4(w[0], w[ldw], w[2 * (size_t)ldw], w[3 * (size_t)ldw]);
-            acc = mfma4(a, b, acc);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; i++) epi(4 * g + i, ct * 16 + j, acc[i]);
-    }
-}
-
 // backward of Norm over the rows of a tile: x, dy in LDS; out(r, c, dx_c, dx_c+1); the normalised rows go to XH
 // (zeros for rows that do not exist) for the alpha gradient
 template <typename Out>
@@ -751,7 +619,7 @@ __global__ __launch_bounds__(BT_THREADS) void k_bt_train_pre(const float* __rest
         const int r = threadIdx.x >> 4, a = threadIdx.x & 15;
         S.REL[((size_t)s0 + t0 + r) * BT_REL_LD + a] = a < 3 ? (float)(T * tz[r * 4 + 1 + a] - psum[a]) / ft : 0.f;
     }
-    bt_tile_gemm<false>(feats + ((size_t)s0 + t0) * c, c, nvalid, c, P.bw, P.bb, BT_D, wave, nw, lane,
+    gf_tile_gemm<false>(feats + ((size_t)s0 + t0) * c, c, nvalid, c, P.bw, P.bb, BT_D, wave, nw, lane,
                         [&](int r, int col, float v) {
                             const float r0 = (float)(T * tz[r * 4 + 1] - psum[0]) / ft;
                             const float r1 = (float)(T * tz[r * 4 + 2] - psum[1]) / ft;
@@ -814,8 +682,8 @@ __global__ __launch_bounds__(BT_THREADS) void k_bt_train_layer(int c, int li, Bt
                 v1[i] = key < T ? vp[16] : 0.f;
             }
             f32x4 s = {0.f, 0.f, 0.f, 0.f};
-            s = mfma4(a0, bq0, s);
-            s = mfma4(a1, bq1, s);
+            s = gf_mfma4(a0, bq0, s);
+            s = gf_mfma4(a1, bq1, s);
             float scv[4];
 #pragma unroll
             for (int i = 0; i < 4; i++) scv[i] = (kt * 16 + 4 * g + i) < T ? s[i] * scale : -INFINITY;
@@ -854,7 +722,7 @@ __global__ __launch_bounds__(BT_THREADS) void k_bt_train_layer(int c, int li, Bt
     }
     // x += dropout(out(O))
     const float* xg = S.X[li] + ((size_t)s0 + t0) * BT_D;
-    bt_tile_gemm<false>(&sO[0][0], BT_LD, nvalid, BT_D, L.ow, L.ob, BT_D, wave, nw, lane, [&](int r, int col, float v) {
+    gf_tile_gemm<false>(&sO[0][0], BT_LD, nvalid, BT_D, L.ow, L.ob, BT_D, wave, nw, lane, [&](int r, int col, float v) {
         sX[r][col] = xg[r * BT_D + col] + v * bt_keep(dr, site + 1, grow + r, col);
     });
     __syncthreads();
@@ -869,13 +737,13 @@ __global__ __launch_bounds__(BT_THREADS) void k_bt_train_layer(int c, int li, Bt
     __syncthreads();
     // x += dropout(ff2(dropout(relu(ff1(.)))));  the hidden tile reuses sO; H keeps the hidden layer before its dropout
     float* Hg = S.H[li] + ((size_t)s0 + t0) * BT_FF;
-    bt_tile_gemm<true>(&sT[0][0], BT_LD, nvalid, BT_D, L.f1w, L.f1b, BT_FF, wave, nw, lane,
+    gf_tile_gemm<true>(&sT[0][0], BT_LD, nvalid, BT_D, L.f1w, L.f1b, BT_FF, wave, nw, lane,
                        [&](int r, int col, float v) {
                            Hg[r * BT_FF + col] = v;
                            sO[r][col] = v * bt_keep(dr, site + 2, grow + r, col);
                        });
     __syncthreads();
-    bt_tile_gemm<false>(&sO[0][0], BT_LD, nvalid, BT_FF, L.f2w, L.f2b, BT_D, wave, nw, lane,
+    gf_tile_gemm<false>(&sO[0][0], BT_LD, nvalid, BT_FF, L.f2w, L.f2b, BT_D, wave, nw, lane,
                         [&](int r, int col, float v) { sX[r][col] += v * bt_keep(dr, site + 3, grow + r, col); });
     __syncthreads();
     {
@@ -896,7 +764,7 @@ __global__ __launch_bounds__(BT_THREADS) void k_bt_train_layer(int c, int li, Bt
         });
         __syncthreads();
         float* y = out + ((size_t)s0 + t0) * c;
-        bt_tile_gemm<false>(&sT[0][0], BT_LD, nvalid, BT_D, P.aw, P.ab, c, wave, nw, lane,
+        gf_tile_gemm<false>(&sT[0][0], BT_LD, nvalid, BT_D, P.aw, P.ab, c, wave, nw, lane,
                             [&](int r, int col, float v) { y[(size_t)r * c + col] = v; });
     }
 }
@@ -978,7 +846,7 @@ __global__ __launch_bounds__(BT_THREADS) void k_bt_bwd_tok(const float* __restri
         bt_tile_norm(sA, nvalid, P.na, P.nb, wave, nw, lane, [&](int r, int c2, float v0, float v1) {
             *reinterpret_cast<float2*>(&Wk.YN[(row0 + r) * BT_D + c2]) = make_float2(v0, v1);
         });
-        bt_tile_gemm_t(&sQ[0][0], BT_QLD, c, P.aw, BT_D, BT_D, wave, nw, lane, [&](int r, int col, float v) { sC[r][col] = v; });
+        gf_tile_gemm_t(&sQ[0][0], BT_QLD, c, P.aw, BT_D, BT_D, wave, nw, lane, [&](int r, int col, float v) { sC[r][col] = v; });
         __syncthreads();
         bt_tile_norm_bwd(sA, sC, sB, nvalid, P.na, wave, nw, lane, [&](int r, int c2, float d0, float d1) {
             sD[r][c2] = d0;
@@ -1000,9 +868,9 @@ __global__ __launch_bounds__(BT_THREADS) void k_bt_bwd_tok(const float* __restri
         bt_tile_norm(sA, nvalid, L.n1a, L.n1b, wave, nw, lane, [&](int r, int c2, float v0, float v1) {
             *reinterpret_cast<float2*>(&Wk.X2A[l][(row0 + r) * BT_D + c2]) = make_float2(v0, v1);
         });
-        bt_tile_gemm_t(&sQ[0][0], BT_QLD, BT_D, L.qw, BT_D, BT_D, wave, nw, lane, [&](int r, int col, float v) { sC[r][col] = v; });
-        bt_tile_gemm_t(&sQ[0][BT_D], BT_QLD, BT_D, L.kw, BT_D, BT_D, wave, nw, lane, [&](int r, int col, float v) { sC[r][col] += v; });
-        bt_tile_gemm_t(&sQ[0][2 * BT_D], BT_QLD, BT_D, L.vw, BT_D, BT_D, wave, nw, lane, [&](int r, int col, float v) { sC[r][col] += v; });
+        gf_tile_gemm_t(&sQ[0][0], BT_QLD, BT_D, L.qw, BT_D, BT_D, wave, nw, lane, [&](int r, int col, float v) { sC[r][col] = v; });
+        gf_tile_gemm_t(&sQ[0][BT_D], BT_QLD, BT_D, L.kw, BT_D, BT_D, wave, nw, lane, [&](int r, int col, float v) { sC[r][col] += v; });
+        gf_tile_gemm_t(&sQ[0][2 * BT_D], BT_QLD, BT_D, L.vw, BT_D, BT_D, wave, nw, lane, [&](int r, int col, float v) { sC[r][col] += v; });
         __syncthreads();
         bt_tile_norm_bwd(sA, sC, sB, nvalid, L.n1a, wave, nw, lane, [&](int r, int c2, float d0, float d1) {
             sD[r][c2] += d0;
@@ -1024,7 +892,7 @@ __global__ __launch_bounds__(BT_THREADS) void k_bt_bwd_tok(const float* __restri
             if (r < nvalid) Wk.DF[l][(row0 + r) * BT_D + col] = v;
         }
         __syncthreads();
-        bt_tile_gemm_t(&sA[0][0], BT_LD, BT_D, L.f2w, BT_FF, BT_FF, wave, nw, lane, [&](int r, int col, float v) { sB[r][col] = v; });
+        gf_tile_gemm_t(&sA[0][0], BT_LD, BT_D, L.f2w, BT_FF, BT_FF, wave, nw, lane, [&](int r, int col, float v) { sB[r][col] = v; });
         __syncthreads();
         for (int i = threadIdx.x; i < 16 * BT_FF; i += BT_THREADS) {
             const int r = i >> 6, col = i & 63;
@@ -1040,7 +908,7 @@ __global__ __launch_bounds__(BT_THREADS) void k_bt_bwd_tok(const float* __restri
         }
         load_tile(sA, S.XMID[l]);
         __syncthreads();
-        bt_tile_gemm_t(&sB[0][0], BT_LD, BT_FF, L.f1w, BT_D, BT_D, wave, nw, lane, [&](int r, int col, float v) { sC[r][col] = v; });
+        gf_tile_gemm_t(&sB[0][0], BT_LD, BT_FF, L.f1w, BT_D, BT_D, wave, nw, lane, [&](int r, int col, float v) { sC[r][col] = v; });
         bt_tile_norm(sA, nvalid, L.n2a, L.n2b, wave, nw, lane, [&](int r, int c2, float v0, float v1) {
             *reinterpret_cast<float2*>(&Wk.X2B[l][(row0 + r) * BT_D + c2]) = make_float2(v0, v1);
         });
@@ -1063,7 +931,7 @@ __global__ __launch_bounds__(BT_THREADS) void k_bt_bwd_tok(const float* __restri
             }
         }
         __syncthreads();
-        bt_tile_gemm_t(&sA[0][0], BT_LD, BT_D, L.ow, BT_D, BT_D, wave, nw, lane, [&](int r, int col, float v) { sC[r][col] = v; });
+        gf_tile_gemm_t(&sA[0][0], BT_LD, BT_D, L.ow, BT_D, BT_D, wave, nw, lane, [&](int r, int col, float v) { sC[r][col] = v; });
         __syncthreads();
         for (int r = wave; r < nvalid; r += nw) {
             const float2 d = *reinterpret_cast<const float2*>(&sC[r][2 * lane]);
@@ -1076,7 +944,7 @@ __global__ __launch_bounds__(BT_THREADS) void k_bt_bwd_tok(const float* __restri
         }
     } else {
         for (int i = threadIdx.x; i < nvalid * BT_D; i += BT_THREADS) Wk.DX0[row0 * BT_D + i] = sD[i >> 7][i & 127];
-        bt_tile_gemm_t(&sD[0][0], BT_LD, BT_D, P.bw, c, c, wave, nw, lane, [&](int r, int col, float v) {
+        gf_tile_gemm_t(&sD[0][0], BT_LD, BT_D, P.bw, c, c, wave, nw, lane, [&](int r, int col, float v) {
             if (r < nvalid) dfeats[(row0 + r) * c + col] = v;
         });
     }
@@ -1130,10 +998,10 @@ __global__ __launch_bounds__(BT_THREADS) void k_bt_bwd_attn(int li, BtSave S, Bt
                 k1[i] = key < T ? kp[16] : 0.f;
             }
             f32x4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-            s = mfma4(a0, bq0, s);
-            s = mfma4(a1, bq1, s);
-            dp = mfma4(va0, bd0, dp);
-            dp = mfma4(va1, bd1, dp);
+            s = gf_mfma4(a0, bq0, s);
+            s = gf_mfma4(a1, bq1, s);
+            dp = gf_mfma4(va0, bd0, dp);
+            dp = gf_mfma4(va1, bd1, dp);
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 const int key = kt * 16 + 4 * g + i;
@@ -1176,10 +1044,10 @@ __global__ __launch_bounds__(BT_THREADS) void k_bt_bwd_attn(int li, BtSave S, Bt
                 dd[i] = ok ? DD[(size_t)qr * BT_H + h] : 0.f;
             }
             f32x4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-            s = mfma4(aq0, bk0, s);
-            s = mfma4(aq1, bk1, s);
-            dp = mfma4(ad0, bv0, dp);
-            dp = mfma4(ad1, bv1, dp);
+            s = gf_mfma4(aq0, bk0, s);
+            s = gf_mfma4(aq1, bk1, s);
+            dp = gf_mfma4(ad0, bv0, dp);
+            dp = gf_mfma4(ad1, bv1, dp);
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 const int qr = qt * 16 + 4 * g + i;

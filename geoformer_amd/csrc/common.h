@@ -11,6 +11,8 @@
 
 #define GF_WAVE 64
 
+typedef float f32x4 __attribute__((ext_vector_type(4)));  // accumulator of v_mfma_f32_16x16x*
+
 // step table of the counted-loop conv kernel (spconv_rules.hip k_subm3 writes it, spconv_conv.hip reads it):
 // blocks of four steps per 16-row group; GF_STEP_BLKS * 4 >= 27 offsets; the first GF_STEP_PHA blocks always exist
 #define GF_STEP_BLKS 7

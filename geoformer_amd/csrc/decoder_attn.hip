@@ -28,8 +28,6 @@
 
 #include "common.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 #define DA_WAVES 16
 #define DA_D 64
 
@@ -264,32 +262,15 @@ __device__ __forceinline__ void da_split_pack(const float (&x)[4][4], DaPieces& 
                 P.p[h][piece][i] = __builtin_amdgcn_perm(pc[piece][2 * i + 1], pc[piece][2 * i], 0x07060302u);
     }
 }
-// acc += W_m[rb-block] . X over both K-steps, six piece pairs each, smallest first (Wp3: the block's 2 x 3 operands in LDS)
-__device__ __forceinline__ f32x4 da_gemm_bf3(const uint4* __restrict__ sW3, int m, int rb, int lane, const DaPieces& X, f32x4 acc) {
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-        const uint4* w = sW3 + (size_t)(((m * 4 + rb) * 2 + h) * 3) * 64 + lane;
-        const da_bf16x8 ah = __builtin_bit_cast(da_bf16x8, w[0]), am = __builtin_bit_cast(da_bf16x8, w[64]),
-                        al = __builtin_bit_cast(da_bf16x8, w[128]);
-        const da_bf16x8 xh = __builtin_bit_cast(da_bf16x8, X.p[h][0]), xm = __builtin_bit_cast(da_bf16x8, X.p[h][1]),
-                        xl = __builtin_bit_cast(da_bf16x8, X.p[h][2]);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, xh, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, xl, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, xm, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, xh, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, xm, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, xh, acc, 0, 0, 0);
-    }
-    return acc;
-}
 
 #ifndef DA_BF3_WAVES
 #define DA_BF3_WAVES 16
 #endif
 // NT tiles of 16 contexts per trip of a wave: every weight operand read from LDS serves NT products (a wave used to
 // re-read all 73 KB of packed weights for every tile: 2.9 GB of ds_read_b128 per launch, the LDS 43 % busy), and the NT
-// accumulator chains are independent, so consecutive MFMAs do not wait for each other.  <16, 1> is the round-4 shape
-// (128 registers, four waves per SIMD); <8, 2> holds two tiles' pieces (two waves per SIMD).
+// accumulator chains are independent, so consecutive MFMAs do not wait for each other.  The one shape in use is <16, 1>
+// (128 registers, four waves per SIMD).
+// acc[u] += W_m[rb-block] . X[u] over both K-steps, six piece pairs each (sW3: the block's 2 x 3 operands in LDS)
 template <int NT>
 __device__ __forceinline__ void da_gemm_bf3_n(const uint4* __restrict__ sW3, int m, int rb, int lane, const DaPieces (&X)[NT],
                                               f32x4 (&acc)[NT]) {

@@ -14,7 +14,7 @@
 // q/k/v projections; stage B is query-tile-parallel (a wave per head) and needs every token's K and V, which is why
 // the launch boundary sits there.  A 4-layer decoder is 4 cross-attention launches + 9 of these small ones
 // (~20 us each) instead of ~130.  All products are v_mfma_f32_16x16x4_f32 with operands loaded straight from
-// row-major activations (LDS tiles or global rows) and nn.Linear weights [out,in] (operand scheme of
+// row-major activations (LDS tiles or global rows) and nn.Linear weights [out,in] (tile_gemm.h, shared with
 // backbone_attn.hip).  Self-attention: 4 heads x 16 channels, S^T = K Q^T keeps the query on the MFMA column so
 // the online soft-max state is per lane column and P^T feeds V^T P^T directly; one key tile of look-ahead.
 #include "decoder_layer.h"
@@ -59,41 +59,41 @@ __global__ __launch_bounds__(DL_TILE_THREADS) void k_decoder_stage_a(const float
     const int lds = B * DL_D;  // row stride of the [T,B,64] tensors
     DL_STAMP(0);
     // every phase's weights, biases and norm parameters requested NOW (one wave per SIMD: 512 registers each, and no phase
-    // then opens with a fetch of its own -- decoder_layer.h)
+    // then opens with a fetch of its own -- tile_gemm.h)
     constexpr int NTF = DL_MAXFF / 16 / (DL_TILE_THREADS / 64);  // linear1's column tiles per wave at the widest FFN
-    DlW<1, DL_D / 16> w_om;
-    DlW<NTF, DL_D / 16> w_l1;
-    DlW<1, DL_MAXFF / 16> w_l2;
-    DlW<2, DL_D / 16> w_qk;
-    DlW<1, DL_D / 16> w_v;
+    GfTileW<1, DL_D / 16> w_om;
+    GfTileW<NTF, DL_D / 16> w_l1;
+    GfTileW<1, DL_MAXFF / 16> w_l2;
+    GfTileW<2, DL_D / 16> w_qk;
+    GfTileW<1, DL_D / 16> w_v;
     float n3w = 0.f, n3b = 0.f, fnw = 0.f, fnb = 0.f, n1w = 0.f, n1b = 0.f;
     if (has_post) {
-        dl_w_load(w_om, po.omw, po.omb, DL_D, DL_D, wave, nw, lane);
+        gf_tile_w_load(w_om, po.omw, po.omb, DL_D, DL_D, wave, nw, lane);
         n3w = po.n3w[lane]; n3b = po.n3b[lane];
-        dl_w_load(w_l1, po.l1w, po.l1b, ff, DL_D, wave, nw, lane);
-        dl_w_load(w_l2, po.l2w, po.l2b, DL_D, ff, wave, nw, lane);
+        gf_tile_w_load(w_l1, po.l1w, po.l1b, ff, DL_D, wave, nw, lane);
+        gf_tile_w_load(w_l2, po.l2w, po.l2b, DL_D, ff, wave, nw, lane);
         fnw = po.fnw[lane]; fnb = po.fnb[lane];
     }
     if (has_pre) {
         n1w = pr.n1w[lane]; n1b = pr.n1b[lane];
-        dl_w_load(w_qk, pr.ipw, pr.ipb, 2 * DL_D, DL_D, wave, nw, lane);
-        dl_w_load(w_v, pr.ipw + 2 * DL_D * DL_D, pr.ipb + 2 * DL_D, DL_D, DL_D, wave, nw, lane);
+        gf_tile_w_load(w_qk, pr.ipw, pr.ipb, 2 * DL_D, DL_D, wave, nw, lane);
+        gf_tile_w_load(w_v, pr.ipw + 2 * DL_D * DL_D, pr.ipb + 2 * DL_D, DL_D, DL_D, wave, nw, lane);
     }
     if (has_post) {
         // tgt = relu(out_mlp(attn)) + tgt2
         const float* tg = TGT2 + (size_t)t0 * DL_D;
-        dl_tile_gemm_w<true>(attn_out + ((size_t)b * T + t0) * DL_D, DL_D, nvalid, DL_D, DL_D, wave, nw, lane, w_om,
+        gf_tile_gemm_w<true>(attn_out + ((size_t)b * T + t0) * DL_D, DL_D, nvalid, DL_D, DL_D, wave, nw, lane, w_om,
                              [&](int r, int c, float v) { sX[r][c] = v; }, tg, DL_D);
         __syncthreads();
         DL_STAMP(1);
         dl_tile_layernorm_p(sX, nvalid, n3w, n3b, wave, nw, lane, [&](int r, int c, float v) { sT[r][c] = v; });
         __syncthreads();
         DL_STAMP(2);
-        dl_tile_gemm_w<true>(&sT[0][0], DL_LD, nvalid, DL_D, ff, wave, nw, lane, w_l1,
+        gf_tile_gemm_w<true>(&sT[0][0], DL_LD, nvalid, DL_D, ff, wave, nw, lane, w_l1,
                              [&](int r, int c, float v) { sH[r][c] = v; });
         __syncthreads();
         DL_STAMP(3);
-        dl_tile_gemm_w<false>(&sH[0][0], DL_LDH, nvalid, ff, DL_D, wave, nw, lane, w_l2,
+        gf_tile_gemm_w<false>(&sH[0][0], DL_LDH, nvalid, ff, DL_D, wave, nw, lane, w_l2,
                               [&](int r, int c, float v) { sX[r][c] += v; });
         __syncthreads();
         DL_STAMP(4);
@@ -119,10 +119,10 @@ __global__ __launch_bounds__(DL_TILE_THREADS) void k_decoder_stage_a(const float
     DL_STAMP(6);
     // in_proj: rows 0..127 of the packed weight -> q, k (from t2 + pos), rows 128..191 -> v (from t2)
     float* qkv = QKV + (size_t)t0 * (3 * DL_D);
-    dl_tile_gemm_w<false>(&sQ[0][0], DL_LD, nvalid, DL_D, 2 * DL_D, wave, nw, lane, w_qk,
+    gf_tile_gemm_w<false>(&sQ[0][0], DL_LD, nvalid, DL_D, 2 * DL_D, wave, nw, lane, w_qk,
                           [&](int r, int c, float v) { qkv[(size_t)r * (3 * DL_D) + c] = v; });
     DL_STAMP(7);
-    dl_tile_gemm_w<false>(&sT[0][0], DL_LD, nvalid, DL_D, DL_D, wave, nw, lane, w_v,
+    gf_tile_gemm_w<false>(&sT[0][0], DL_LD, nvalid, DL_D, DL_D, wave, nw, lane, w_v,
                           [&](int r, int c, float v) { qkv[(size_t)r * (3 * DL_D) + 2 * DL_D + c] = v; });
     DL_STAMP(8);
 }
@@ -150,7 +150,7 @@ __device__ __forceinline__ void dl_attn_two_pass(const float* __restrict__ QKV, 
 #pragma unroll
     for (int kt = 0; kt < QTN; kt++) {
         f32x4 s = {0.f, 0.f, 0.f, 0.f};
-        s = dl_mfma4(akt[kt], bq, s);  // (a clamped row beyond T: a finite product, masked below)
+        s = gf_mfma4(akt[kt], bq, s);  // (a clamped row beyond T: a finite product, masked below)
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             sc[kt][i] = (kt * 16 + 4 * g + i) < T ? s[i] * 0.25f : -INFINITY;  // 1/sqrt(16)
@@ -186,9 +186,9 @@ __global__ __launch_bounds__(DL_TILE_THREADS) void k_decoder_stage_b(int T, int 
     const float* QKV = TGT2 + (size_t)T * DL_D;
     DL_STAMP(16);
     // (the two products behind the self-attention: operands requested now)
-    DlW<1, DL_D / 16> w_op, w_w1;
-    dl_w_load(w_op, pr.opw, pr.opb, DL_D, DL_D, wave, nw, lane);
-    dl_w_load(w_w1, pr.w1w, pr.w1b, DL_D, DL_D, wave, nw, lane);
+    GfTileW<1, DL_D / 16> w_op, w_w1;
+    gf_tile_w_load(w_op, pr.opw, pr.opb, DL_D, DL_D, wave, nw, lane);
+    gf_tile_w_load(w_w1, pr.w1w, pr.w1b, DL_D, DL_D, wave, nw, lane);
     const float n2w = pr.n2w[lane], n2b = pr.n2b[lane];
     {
         const int h = wave;  // 4 waves = 4 heads
@@ -232,7 +232,7 @@ __global__ __launch_bounds__(DL_TILE_THREADS) void k_decoder_stage_b(int T, int 
                 }
             }
             f32x4 s = {0.f, 0.f, 0.f, 0.f};
-            s = dl_mfma4(ak, bq, s);
+            s = gf_mfma4(ak, bq, s);
             float sc[4];
 #pragma unroll
             for (int i = 0; i < 4; i++) sc[i] = (kt * 16 + 4 * g + i) < T ? s[i] * 0.25f : -INFINITY;  // 1/sqrt(16)
@@ -263,7 +263,7 @@ __global__ __launch_bounds__(DL_TILE_THREADS) void k_decoder_stage_b(int T, int 
     DL_STAMP(17);
     // tgt += out_proj(O)
     const float* xg = X + (size_t)t0 * DL_D;
-    dl_tile_gemm_w<false>(&sO[0][0], DL_LD, nvalid, DL_D, DL_D, wave, nw, lane, w_op,
+    gf_tile_gemm_w<false>(&sO[0][0], DL_LD, nvalid, DL_D, DL_D, wave, nw, lane, w_op,
                           [&](int r, int c, float v) { sX[r][c] = v; }, xg, DL_D);
     __syncthreads();
     DL_STAMP(18);
@@ -277,7 +277,7 @@ __global__ __launch_bounds__(DL_TILE_THREADS) void k_decoder_stage_b(int T, int 
     __syncthreads();
     DL_STAMP(19);
     float* q1 = q1_out + ((size_t)b * T + t0) * DL_D;
-    dl_tile_gemm_w<false>(&sT[0][0], DL_LD, nvalid, DL_D, DL_D, wave, nw, lane, w_w1,
+    gf_tile_gemm_w<false>(&sT[0][0], DL_LD, nvalid, DL_D, DL_D, wave, nw, lane, w_w1,
                           [&](int r, int c, float v) { q1[r * DL_D + c] = v; });
     DL_STAMP(20);
 }

@@ -29,28 +29,6 @@ struct DtPost {
     const float *omw, *omb, *n3w, *n3b, *l1w, *l1b, *l2w, *l2b, *fnw, *fnb;
 };
 
-// out[r][col] = sum_o A[r][o] W[o][col]: product with a row-major nn.Linear weight [out,in] summed over its OUT index
-template <typename Epi>
-__device__ __forceinline__ void dl_tile_gemm_t(const float* A, int lda, int K, const float* __restrict__ W, int ldw, int N,
-                                               int wave, int nwaves, int lane, Epi epi) {
-    const int j = lane & 15, g = lane >> 4;
-    const int KC = K >> 4;
-    for (int ct = wave; ct < (N >> 4); ct += nwaves) {
-        const float* xa = A + (size_t)j * lda + 4 * g;
-        const float* wb = W + (size_t)(4 * g) * ldw + ct * 16 + j;
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 2
-        for (int kc = 0; kc < KC; kc++) {
-            const float4 a = *reinterpret_cast<const float4*>(xa + kc * 16);
-            const float* w = wb + (size_t)kc * 16 * ldw;
-            const float4 b = make_float4(w[0], w[ldw], w[2 * (size_t)ldw], w[3 * (size_t)ldw]);
-            acc = dl_mfma4(a, b, acc);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; i++) epi(4 * g + i, ct * 16 + j, acc[i]);
-    }
-}
-
 // backward of torch.nn.LayerNorm over the rows of a tile (x, dy in LDS): out(r, c, dx); the normalised rows go to XH
 template <typename Out>
 __device__ __forceinline__ void dl_tile_layernorm_bwd(const float (*X)[DL_LD], const float (*G)[DL_LD], float (*XH)[DL_LD],
@@ -119,9 +97,9 @@ __global__ __launch_bounds__(DT_THREADS) void k_dt_pre_a(const float* __restrict
     });
     __syncthreads();
     float* qkv = QKV + row0 * (3 * DL_D);
-    dl_tile_gemm<false>(&sQ[0][0], DL_LD, nvalid, DL_D, pr.ipw, pr.ipb, 2 * DL_D, wave, nw, lane,
+    gf_tile_gemm<false>(&sQ[0][0], DL_LD, nvalid, DL_D, pr.ipw, pr.ipb, 2 * DL_D, wave, nw, lane,
                         [&](int r, int c, float v) { qkv[(size_t)r * (3 * DL_D) + c] = v; });
-    dl_tile_gemm<false>(&sT[0][0], DL_LD, nvalid, DL_D, pr.ipw + 2 * DL_D * DL_D, pr.ipb + 2 * DL_D, DL_D, wave, nw, lane,
+    gf_tile_gemm<false>(&sT[0][0], DL_LD, nvalid, DL_D, pr.ipw + 2 * DL_D * DL_D, pr.ipb + 2 * DL_D, DL_D, wave, nw, lane,
                         [&](int r, int c, float v) { qkv[(size_t)r * (3 * DL_D) + 2 * DL_D + c] = v; });
 }
 
@@ -155,7 +133,7 @@ __global__ __launch_bounds__(DT_THREADS) void k_dt_pre_b(const float* __restrict
                 v[i] = key < T ? QKV[(size_t)key * (3 * DL_D) + 2 * DL_D + h * DL_DK + j] : 0.f;
             }
             f32x4 s = {0.f, 0.f, 0.f, 0.f};
-            s = dl_mfma4(ak, bq, s);
+            s = gf_mfma4(ak, bq, s);
             float sc[4];
 #pragma unroll
             for (int i = 0; i < 4; i++) sc[i] = (kt * 16 + 4 * g + i) < T ? s[i] * 0.25f : -INFINITY;  // 1/sqrt(16)
@@ -185,7 +163,7 @@ __global__ __launch_bounds__(DT_THREADS) void k_dt_pre_b(const float* __restrict
     __syncthreads();
     for (int i = threadIdx.x; i < nvalid * DL_D; i += DT_THREADS) Oall[row0 * DL_D + i] = sO[i >> 6][i & 63];
     const float* xg = x + row0 * DL_D;
-    dl_tile_gemm<false>(&sO[0][0], DL_LD, nvalid, DL_D, pr.opw, pr.opb, DL_D, wave, nw, lane, [&](int r, int c, float v) {
+    gf_tile_gemm<false>(&sO[0][0], DL_LD, nvalid, DL_D, pr.opw, pr.opb, DL_D, wave, nw, lane, [&](int r, int c, float v) {
         sX[r][c] = xg[r * DL_D + c] + v * gf_drop_keep(dr, site + 1, grow + r, c);
     });
     __syncthreads();
@@ -197,7 +175,7 @@ __global__ __launch_bounds__(DT_THREADS) void k_dt_pre_b(const float* __restrict
     });
     __syncthreads();
     float* qo = q1 + row0 * DL_D;
-    dl_tile_gemm<false>(&sT[0][0], DL_LD, nvalid, DL_D, pr.w1w, pr.w1b, DL_D, wave, nw, lane,
+    gf_tile_gemm<false>(&sT[0][0], DL_LD, nvalid, DL_D, pr.w1w, pr.w1b, DL_D, wave, nw, lane,
                         [&](int r, int c, float v) { qo[r * DL_D + c] = v; });
 }
 
@@ -210,7 +188,7 @@ __global__ __launch_bounds__(DT_THREADS) void k_dt_post(const float* __restrict_
     const uint32_t site = 8u * layer;
     const float* tg = t2n + row0 * DL_D;
     float* yg = Y + row0 * DL_D;
-    dl_tile_gemm<true>(ca + row0 * DL_D, DL_D, nvalid, DL_D, po.omw, po.omb, DL_D, wave, nw, lane, [&](int r, int c, float v) {
+    gf_tile_gemm<true>(ca + row0 * DL_D, DL_D, nvalid, DL_D, po.omw, po.omb, DL_D, wave, nw, lane, [&](int r, int c, float v) {
         yg[r * DL_D + c] = v;
         sX[r][c] = v + tg[r * DL_D + c] * gf_drop_keep(dr, site + 2, grow + r, c);
     });
@@ -219,12 +197,12 @@ __global__ __launch_bounds__(DT_THREADS) void k_dt_post(const float* __restrict_
     dl_tile_layernorm(sX, nvalid, po.n3w, po.n3b, wave, nw, lane, [&](int r, int c, float v) { sT[r][c] = v; });
     __syncthreads();
     float* hg = H + row0 * ff;
-    dl_tile_gemm<true>(&sT[0][0], DL_LD, nvalid, DL_D, po.l1w, po.l1b, ff, wave, nw, lane, [&](int r, int c, float v) {
+    gf_tile_gemm<true>(&sT[0][0], DL_LD, nvalid, DL_D, po.l1w, po.l1b, ff, wave, nw, lane, [&](int r, int c, float v) {
         hg[(size_t)r * ff + c] = v;
         sH[r][c] = v * gf_drop_keep(dr, site + 3, grow + r, c);
     });
     __syncthreads();
-    dl_tile_gemm<false>(&sH[0][0], DL_LDH, nvalid, ff, po.l2w, po.l2b, DL_D, wave, nw, lane,
+    gf_tile_gemm<false>(&sH[0][0], DL_LDH, nvalid, ff, po.l2w, po.l2b, DL_D, wave, nw, lane,
                         [&](int r, int c, float v) { sX[r][c] += v * gf_drop_keep(dr, site + 4, grow + r, c); });
     __syncthreads();
     for (int i = threadIdx.x; i < nvalid * DL_D; i += DT_THREADS) x3[row0 * DL_D + i] = sX[i >> 6][i & 63];
@@ -264,7 +242,7 @@ __global__ __launch_bounds__(DT_THREADS) void k_dt_post_bwd(const float* __restr
         if (r < nvalid) W.DF[(row0 + r) * DL_D + c] = v;
     }
     __syncthreads();
-    dl_tile_gemm_t(&sA[0][0], DL_LD, DL_D, po.l2w, ff, ff, wave, nw, lane, [&](int r, int c, float v) { sH[r][c] = v; });
+    gf_tile_gemm_t(&sA[0][0], DL_LD, DL_D, po.l2w, ff, ff, wave, nw, lane, [&](int r, int c, float v) { sH[r][c] = v; });
     __syncthreads();
     for (int i = threadIdx.x; i < 16 * ff; i += DT_THREADS) {
         const int r = i / ff, c = i - r * ff;
@@ -280,7 +258,7 @@ __global__ __launch_bounds__(DT_THREADS) void k_dt_post_bwd(const float* __restr
     }
     dt_load_tile(sA, X2, row0, nvalid);
     __syncthreads();
-    dl_tile_gemm_t(&sH[0][0], DL_LDH, ff, po.l1w, DL_D, DL_D, wave, nw, lane, [&](int r, int c, float v) { sC[r][c] = v; });
+    gf_tile_gemm_t(&sH[0][0], DL_LDH, ff, po.l1w, DL_D, DL_D, wave, nw, lane, [&](int r, int c, float v) { sC[r][c] = v; });
     dl_tile_layernorm(sA, nvalid, po.n3w, po.n3b, wave, nw, lane,
                       [&](int r, int c, float v) { W.T3[(row0 + r) * DL_D + c] = v; });
     __syncthreads();
@@ -300,7 +278,7 @@ __global__ __launch_bounds__(DT_THREADS) void k_dt_post_bwd(const float* __restr
         sA[r][c] = dy;
     }
     __syncthreads();
-    dl_tile_gemm_t(&sA[0][0], DL_LD, DL_D, po.omw, DL_D, DL_D, wave, nw, lane, [&](int r, int c, float v) {
+    gf_tile_gemm_t(&sA[0][0], DL_LD, DL_D, po.omw, DL_D, DL_D, wave, nw, lane, [&](int r, int c, float v) {
         if (r < nvalid) d_ca[(row0 + r) * DL_D + c] = v;
     });
 }
@@ -322,7 +300,7 @@ __global__ __launch_bounds__(DT_THREADS) void k_dt_pre_bwd1(const float* __restr
     dt_load_tile(sC, d_t2n, row0, nvalid);
     dt_load_tile(sD, X1, row0, nvalid);
     __syncthreads();
-    dl_tile_gemm_t(&sA[0][0], DL_LD, DL_D, pr.w1w, DL_D, DL_D, wave, nw, lane, [&](int r, int c, float v) { sC[r][c] += v; });
+    gf_tile_gemm_t(&sA[0][0], DL_LD, DL_D, pr.w1w, DL_D, DL_D, wave, nw, lane, [&](int r, int c, float v) { sC[r][c] += v; });
     __syncthreads();
     dl_tile_layernorm_bwd(sD, sC, sB, nvalid, pr.n2w, wave, nw, lane, [&](int r, int c, float d) { sA[r][c] = d; });
     __syncthreads();
@@ -339,7 +317,7 @@ __global__ __launch_bounds__(DT_THREADS) void k_dt_pre_bwd1(const float* __restr
         sD[r][c] = v;
     }
     __syncthreads();
-    dl_tile_gemm_t(&sD[0][0], DL_LD, DL_D, pr.opw, DL_D, DL_D, wave, nw, lane, [&](int r, int c, float v) { sC[r][c] = v; });
+    gf_tile_gemm_t(&sD[0][0], DL_LD, DL_D, pr.opw, DL_D, DL_D, wave, nw, lane, [&](int r, int c, float v) { sC[r][c] = v; });
     __syncthreads();
     for (int r = wave; r < nvalid; r += nw) {
         const float d = sC[r][lane];
@@ -384,8 +362,8 @@ __global__ __launch_bounds__(512) void k_dt_attn_bwd(int T, GfDrop dr, int layer
                 kk[i] = key < T ? QKV[(size_t)key * (3 * DL_D) + DL_D + h * DL_DK + j] : 0.f;
             }
             f32x4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-            s = dl_mfma4(ak, bq, s);
-            dp = dl_mfma4(av, bd, dp);
+            s = gf_mfma4(ak, bq, s);
+            dp = gf_mfma4(av, bd, dp);
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 const int key = kt * 16 + 4 * g + i;
@@ -416,8 +394,8 @@ __global__ __launch_bounds__(512) void k_dt_attn_bwd(int T, GfDrop dr, int layer
                 dd[i] = ok ? DD[(size_t)qr * DL_H + h] : 0.f;
             }
             f32x4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-            s = dl_mfma4(aq, bk, s);
-            dp = dl_mfma4(ad, bv, dp);
+            s = gf_mfma4(aq, bk, s);
+            dp = gf_mfma4(ad, bv, dp);
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 const int qr = qt * 16 + 4 * g + i;
@@ -453,13 +431,13 @@ __global__ __launch_bounds__(DT_THREADS) void k_dt_pre_bwd2(const float* __restr
     dt_load_tile(sA, x, row0, nvalid);
     dt_load_tile(sD, W.DX1, row0, nvalid);
     __syncthreads();
-    dl_tile_gemm_t(&sQ[0][0], DT_QLD, DL_D, pr.ipw, DL_D, DL_D, wave, nw, lane, [&](int r, int c, float v) { sC[r][c] = v; });
-    dl_tile_gemm_t(&sQ[0][DL_D], DT_QLD, DL_D, pr.ipw + DL_D * DL_D, DL_D, DL_D, wave, nw, lane, [&](int r, int c, float v) {
+    gf_tile_gemm_t(&sQ[0][0], DT_QLD, DL_D, pr.ipw, DL_D, DL_D, wave, nw, lane, [&](int r, int c, float v) { sC[r][c] = v; });
+    gf_tile_gemm_t(&sQ[0][DL_D], DT_QLD, DL_D, pr.ipw + DL_D * DL_D, DL_D, DL_D, wave, nw, lane, [&](int r, int c, float v) {
         const float d = sC[r][c] + v;
         sC[r][c] = d;
         if (r < nvalid) dqpos[(row0 + r) * DL_D + c] = d;
     });
-    dl_tile_gemm_t(&sQ[0][2 * DL_D], DT_QLD, DL_D, pr.ipw + 2 * DL_D * DL_D, DL_D, DL_D, wave, nw, lane,
+    gf_tile_gemm_t(&sQ[0][2 * DL_D], DT_QLD, DL_D, pr.ipw + 2 * DL_D * DL_D, DL_D, DL_D, wave, nw, lane,
                    [&](int r, int c, float v) { sC[r][c] += v; });
     const float* qp = qpos + row0 * DL_D;
     dl_tile_layernorm(sA, nvalid, pr.n1w, pr.n1b, wave, nw, lane, [&](int r, int c, float v) {

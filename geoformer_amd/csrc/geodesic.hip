@@ -563,9 +563,6 @@ __global__ __launch_bounds__(THREADS) void k_geodesic_bfs_lds(const float* __res
                                                                   int2* __restrict__ queues, int qcap) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ int s_cnt[2];  // next-frontier counters of even / odd hops (reset a hop ahead: one barrier less)
-#ifdef BFS_PRIO
-    __builtin_amdgcn_s_setprio(BFS_PRIO);
-#endif
     const int nw = (n + 31) >> 5;
     unsigned* visited = reinterpret_cast<unsigned*>(smem);
     unsigned* touched = visited + nw;

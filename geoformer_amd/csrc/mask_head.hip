@@ -18,8 +18,6 @@
 // against 2*nq*N*(19*16+16) flops -> 80 flop/B: MFMA/VALU-bound, ~10 GFLOP per 150k-point scene.
 #include "common.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 #ifndef MH_Q
 #define MH_Q 2   // queries per wave: 2 at 3 workgroups per CU measured 209 us vs 262 us for 4 at 2 (S150k, nq=256)
 #endif
@@ -201,9 +199,6 @@ __global__ __launch_bounds__(256, MH_MINB) void k_mask_head(const float* __restr
                     rel = rel + ((cur.gd[t][tl] < 0.f && rel != 0.f) ? ms : 0.f);
                 }
                 f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#ifdef MH_EXP_NOMFMA  // dev experiment: the loop without its matrix instructions (results are garbage)
-                acc[0] = w5[t] * rel; acc[1] = wf[t][0] * cur.pc[tl]; acc[2] = wf[t][1] * cur.pc[tl]; acc[3] = wf[t][2] * cur.pc[tl];
-#else
                 acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w5[t], rel, acc, 0, 0, 0);
                 if constexpr (SPLIT) {  // the six piece pairs, smallest first, two per instruction
                     acc = mh_mfma2(wl[t], wh[t], cur.fh[tl], cur.fl[tl], acc);  // lo.hi + hi.lo
@@ -215,11 +210,6 @@ __global__ __launch_bounds__(256, MH_MINB) void k_mask_head(const float* __restr
                     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[t][2], cur.f[tl].z, acc, 0, 0, 0);
                     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[t][3], cur.f[tl].w, acc, 0, 0, 0);
                 }
-#endif
-#ifdef MH_EXP_NOVALU  // dev experiment: the loop without the activation / contraction arithmetic
-                part[tl] = acc[0];
-                continue;
-#endif
                 float s = 0.f;
                 // (mh_relu: ONE v_max; fmaxf costs a second instruction that canonicalises its operand first, 32 of the
                 // loop's ~290 vector instructions)

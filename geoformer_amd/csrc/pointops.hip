@@ -359,19 +359,13 @@ __device__ __forceinline__ void fps_static_for(F&& f) {
 #ifndef FPS_K
 #define FPS_K 16      // upper bound of the picks one exchange can deliver
 #endif
-#ifndef FPS_PIPE
-#define FPS_PIPE 1    // 1: wave 0 of a workgroup replays the exchanges and the point-holding waves absorb the picks of an
-#endif                //    exchange WHILE it does (below); the waves that share wave 0's SIMD (wave id % 4 == 0) hold no
-                      //    points: anything they issued would delay the replay's dependent chain by an issue slot per
-                      //    instruction (measured: 580 -> 950 cycles per pick).  0: every wave holds points, picks
-                      //    absorbed after the exchange.
-#define FPS_PW (FPS_PIPE ? FPS_WAVES - FPS_WAVES / 4 : FPS_WAVES)  // waves of a workgroup that hold points
+// wave 0 of a workgroup replays the exchanges and the point-holding waves absorb the picks of an exchange WHILE it does
+// (below); the waves that share wave 0's SIMD (wave id % 4 == 0) hold no points: anything they issued would delay the
+// replay's dependent chain by an issue slot per instruction (measured: 580 -> 950 cycles per pick)
+#define FPS_PW (FPS_WAVES - FPS_WAVES / 4)  // waves of a workgroup that hold points
 #ifndef FPS_POLL_SLEEP
 #define FPS_POLL_SLEEP 4  // x 64 cycles between two looks at the mailbox (1: the sampler alone 1 % faster, a search workgroup
                           // on the same compute unit 4 % slower -- and the search is the longer launch of the forward)
-#endif
-#ifndef FPS_PACKED
-#define FPS_PACKED 0  // 1: the absorb step on packed fp32 instructions (two points per instruction)
 #endif
 #define FPS_NG (FPS_MAXG * FPS_KPUB / 64)  // granules a lane gathers
 #define FPS_TAG (1ull << 63)
@@ -391,12 +385,6 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long c)
         ml = wave_max_u32(hi == md ? (unsigned)c : 0u);
     }
     return ((unsigned long long)md << 32) | ml;
-}
-__device__ __forceinline__ unsigned long long glt_lane_fix(const unsigned long long (&g)[8], int lane) {
-    unsigned long long v = g[0];
-#pragma unroll
-    for (int t = 1; t < 8; t++) v = lane == t ? g[t] : v;
-    return v;
 }
 __device__ __forceinline__ int fps_code_index(unsigned long long c) {
     return c ? (int)((FPS_KEY_NONE - (unsigned)((c >> 1) & 0x7fffffffull)) & 0x3fffffu) : 0;
@@ -426,70 +414,45 @@ extern "C" int gf_dev_fps_trace(void* p) {
 // a sorted prefix of its candidates with the last one flagged, and merging stops after consuming a
 // flagged entry (the source's next one is unknown), which keeps the result exact.
 // one pick absorbed by a lane's P points: tmp = min(tmp, |p - a|^2) in the reference's operation order
-// (dx*dx, then fma dy, then fma dz).  Two points per instruction where the ISA has packed fp32 (v_pk_add / v_pk_mul /
-// v_pk_fma_f32 are element-wise IEEE operations: same bits), the minimum per element.
+// (dx*dx, then fma dy, then fma dz).
 // LDS mailbox accesses of the pipelined absorb: relaxed workgroup-scope atomics keep the LDS address space (a volatile
 // access through a cast pointer becomes a FLAT instruction with sc0 sc1: +360 cycles per pick in the replay), the empty asm
 // keeps the compiler from reordering them, and the LDS executes one wave's instructions in order.
 #define FPS_LDS_ST(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
 #define FPS_LDS_LD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
 #define FPS_ORDER() asm volatile("" ::: "memory")
-typedef float fps_f2 __attribute__((ext_vector_type(2)));
 template <int P>
 __device__ __forceinline__ void fps_absorb(const float (&px)[P], const float (&py)[P], const float (&pz)[P], float (&tmp)[P],
                                            float ax, float ay, float az) {
-#if FPS_PACKED
-    const fps_f2 a2x = {ax, ax}, a2y = {ay, ay}, a2z = {az, az};
-#pragma unroll
-    for (int i = 0; i + 1 < P; i += 2) {
-        const fps_f2 dx = fps_f2{px[i], px[i + 1]} - a2x, dy = fps_f2{py[i], py[i + 1]} - a2y, dz = fps_f2{pz[i], pz[i + 1]} - a2z;
-        const fps_f2 d = __builtin_elementwise_fma(dz, dz, __builtin_elementwise_fma(dy, dy, dx * dx));
-        tmp[i] = fminf(d.x, tmp[i]);
-        tmp[i + 1] = fminf(d.y, tmp[i + 1]);
-    }
-    if (P & 1) {
-        const float dx = px[P - 1] - ax, dy = py[P - 1] - ay, dz = pz[P - 1] - az;
-        tmp[P - 1] = fminf(fmaf(dz, dz, fmaf(dy, dy, dx * dx)), tmp[P - 1]);
-    }
-#else
 #pragma unroll
     for (int i = 0; i < P; i++) {
         const float dx = px[i] - ax, dy = py[i] - ay, dz = pz[i] - az;
         tmp[i] = fminf(fmaf(dz, dz, fmaf(dy, dy, dx * dx)), tmp[i]);
     }
-#endif
 }
 
-#ifdef FPS_NUM_VGPR  // dev knob: a register cap, so that the workgroup fits beside another kernel's on its compute unit
-#define FPS_VGPR_CAP __attribute__((amdgpu_num_vgpr(FPS_NUM_VGPR)))
-#else
-#define FPS_VGPR_CAP
-#endif
 template <int P>
-__global__ __launch_bounds__(FPS_WAVES * 64) FPS_VGPR_CAP void k_fps(const float* __restrict__ xyz, int n, int m, int m0, int G,
+__global__ __launch_bounds__(FPS_WAVES * 64) void k_fps(const float* __restrict__ xyz, int n, int m, int m0, int G,
                                                         int bs_log2, int batch0,
                                                         unsigned long long* __restrict__ slots,
                                                         int32_t* __restrict__ idxs, int* __restrict__ err) {
     static_assert(FPS_NG >= 1 && FPS_NG * 64 == FPS_MAXG * FPS_KPUB && FPS_KPUB <= FPS_K && FPS_WAVES * 2 <= 64,
                   "lane mappings of the exchange");
     __shared__ unsigned long long s_part[2][FPS_WAVES * 2];
-    __shared__ int s_pick[2][FPS_K + 1];
     __shared__ float s_xyz[2][FPS_K * 3];
-    __shared__ unsigned s_prog[2];  // (FPS_PIPE) progress of the exchange being replayed: round << 8 | 0x80 (complete) | picks
+    __shared__ unsigned s_prog[2];  // progress of the exchange being replayed: round << 8 | 0x80 (complete) | picks
     const int bi = batch0 + blockIdx.y, wg = blockIdx.x;
     xyz += (size_t)bi * n * 3;
     idxs += (size_t)bi * m;
     slots += (size_t)bi * 2 * FPS_MAXG * FPS_KPUB;
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    // FPS_PIPE: wave 0 is the workgroup's coordinator (merge, exchange, replay) and owns no points
-    const bool holder = !FPS_PIPE || (wid & 3) != 0;
-    const int hid = FPS_PIPE ? wid - 1 - (wid >> 2) : wid;  // index among the workgroup's point-holding waves
+    // wave 0 is the workgroup's coordinator (merge, exchange, replay) and owns no points
+    const bool holder = (wid & 3) != 0;
+    const int hid = wid - 1 - (wid >> 2);  // index among the workgroup's point-holding waves
     const int gtid = (wg * FPS_PW + hid) * 64 + lane;
     const int stride = G * FPS_PW * 64;
-    if (FPS_PIPE) {
-        if (threadIdx.x < 2) s_prog[threadIdx.x] = 0u;
-        if (!holder && lane < 4) s_part[lane >> 1][wid * 2 + (lane & 1)] = 0ull;  // these waves never forward a candidate
-    }
+    if (threadIdx.x < 2) s_prog[threadIdx.x] = 0u;
+    if (!holder && lane < 4) s_part[lane >> 1][wid * 2 + (lane & 1)] = 0ull;  // these waves never forward a candidate
 
     float px[P], py[P], pz[P], tmp[P];
     unsigned key[P];
@@ -556,7 +519,6 @@ __global__ __launch_bounds__(FPS_WAVES * 64) FPS_VGPR_CAP void k_fps(const float
 #ifdef FPS_TRACE
     unsigned long long ftr[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #endif
-#if FPS_PIPE
     // The picks of an exchange are absorbed WHILE wave 0 replays it: wave 0 posts every accepted pick to LDS (coordinates,
     // then s_prog) and the point-holding waves, which used to idle at a barrier until the whole exchange was known and
     // then absorbed its ~12 picks on the critical path (17 % of the kernel + 20 % waiting for the slowest wave, by cycle
@@ -574,26 +536,15 @@ __global__ __launch_bounds__(FPS_WAVES * 64) FPS_VGPR_CAP void k_fps(const float
         __builtin_amdgcn_s_setprio(3);  // the replay is the kernel's serial chain
     }
     __syncthreads();  // (s_prog zeroed)
-#endif
     for (int round = 1; done < m; round++) {
         const int par = round & 1;
         const unsigned long long ft0 = FT();
-        // 1) absorb the new picks (FPS_PIPE: done already), track this lane's best
+        // 1) the new picks are absorbed already: track this lane's best
         unsigned bd = 0u, bk = FPS_KEY_NONE;
 #pragma unroll
         for (int i = 0; i < P; i++) {
             if (elig & (1u << i)) {
                 float d2 = tmp[i];
-#if !FPS_PIPE
-#pragma unroll
-                for (int a = 0; a < FPS_K; a++) {
-                    if (a < nnew) {
-                        const float dx = px[i] - nx[a], dy = py[i] - ny[a], dz = pz[i] - nz[a];
-                        d2 = fminf(fmaf(dz, dz, fmaf(dy, dy, dx * dx)), d2);
-                    }
-                }
-                tmp[i] = d2;
-#endif
                 const unsigned db = __float_as_uint(d2);
                 if (db > bd || (db == bd && key[i] < bk)) {
                     bd = db;
@@ -752,7 +703,6 @@ __global__ __launch_bounds__(FPS_WAVES * 64) FPS_VGPR_CAP void k_fps(const float
                 kz = keeper ? bz : kz;
                 kidx = keeper ? (int)((FPS_KEY_NONE - ((best_lo >> 1) & 0x7fffffffu)) & 0x3fffffu) : kidx;
                 if (lane == ol) alive = false;
-#if FPS_PIPE
                 if (lane == 0) {  // posted at once: the other waves absorb it while the replay goes on (LDS keeps a wave's order)
                     FPS_LDS_ST(&s_xyz[par][t * 3 + 0], bx);
                     FPS_LDS_ST(&s_xyz[par][t * 3 + 1], by);
@@ -760,7 +710,6 @@ __global__ __launch_bounds__(FPS_WAVES * 64) FPS_VGPR_CAP void k_fps(const float
                     FPS_ORDER();
                     FPS_LDS_ST(&s_prog[par], ((unsigned)round << 8) | (unsigned)(t + 1));
                 }
-#endif
                 const float dx = vx[0] - bx, dy = vy[0] - by, dz = vz[0] - bz;
                 cdist = fminf(cdist, fmaf(dz, dz, fmaf(dy, dy, dx * dx)));
             };
@@ -806,25 +755,14 @@ __global__ __launch_bounds__(FPS_WAVES * 64) FPS_VGPR_CAP void k_fps(const float
                     nacc = t + 1;
                 }
             }
-#if FPS_PIPE
             if (!direct && lane < nacc && wg == 0) idxs[done + lane] = kidx;
             FPS_ORDER();
             if (lane == 0) FPS_LDS_ST(&s_prog[par], ((unsigned)round << 8) | 0x80u | (unsigned)nacc);
             nnew = nacc;
-            (void)kx; (void)ky; (void)kz;
-#else
-            if (!direct && lane < nacc) {
-                s_xyz[par][lane * 3 + 0] = kx;
-                s_xyz[par][lane * 3 + 1] = ky;
-                s_xyz[par][lane * 3 + 2] = kz;
-                if (wg == 0) idxs[done + lane] = kidx;
-            }
-            if (lane == 0) s_pick[par][0] = nacc;
-#endif
+            (void)kx; (void)ky; (void)kz;  // (dead since take() posts the picks; kept: the register allocation depends on them)
             const unsigned long long ft7 = FT();
             FTA(6, ft6, ft7);
         }
-#if FPS_PIPE
         else if (holder) {
             // the point-holding waves follow the replay: absorb every pick as soon as wave 0 has posted it.  s_prog
             // carries the round, so a value two rounds old reads as "nothing yet"; wave 0 cannot start the next replay
@@ -840,11 +778,7 @@ __global__ __launch_bounds__(FPS_WAVES * 64) FPS_VGPR_CAP void k_fps(const float
                 for (int a = seen; a < cnt; a++) {
                     const float ax = FPS_LDS_LD(&s_xyz[par][a * 3 + 0]), ay = FPS_LDS_LD(&s_xyz[par][a * 3 + 1]),
                                 az = FPS_LDS_LD(&s_xyz[par][a * 3 + 2]);
-#ifndef FPS_EXP_NOABSORB  // dev experiment (wrong picks): what the absorbing waves cost a neighbour on the compute unit
                     fps_absorb<P>(px, py, pz, tmp, ax, ay, az);
-#else
-                    (void)ax; (void)ay; (void)az;
-#endif
                 }
                 seen = cnt;
                 if (cur && (c & 0x80u)) break;
@@ -862,20 +796,6 @@ __global__ __launch_bounds__(FPS_WAVES * 64) FPS_VGPR_CAP void k_fps(const float
             }
             nnew = (int)(c & 0x7fu);
         }
-        (void)s_pick;
-#else
-        const unsigned long long ft8 = FT();
-        __syncthreads();
-        const unsigned long long ft9 = FT();
-        FTA(7, ft8, ft9);
-        nnew = s_pick[par][0];
-#pragma unroll
-        for (int a = 0; a < FPS_K; a++) {
-            nx[a] = s_xyz[par][a * 3 + 0];
-            ny[a] = s_xyz[par][a * 3 + 1];
-            nz[a] = s_xyz[par][a * 3 + 2];
-        }
-#endif
         done += nnew;
 #ifdef FPS_TRACE
         ftr[8] += 1;

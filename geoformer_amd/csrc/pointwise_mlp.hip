@@ -8,9 +8,7 @@
 // the column): H^T = W . X^T -- the accumulator of one layer is directly the B operand of the next, so a point's
 // features are read once and its outputs written once.  Eval-mode BatchNorm and the bias are folded by the caller
 // into one per-channel (scale, shift) pair per layer.
-#include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "tile_gemm.h"
 
 #define PM_MAXL 4
 #define PM_MAXC 64  // channels per layer (4 tiles of 16)
@@ -97,10 +95,7 @@ __global__ __launch_bounds__(256) void k_pointwise_mlp(const float* __restrict__
                 for (int kc = 0; kc < PM_MAXC / 16; kc++) {
                     if (kc * 16 >= L.cin) continue;
                     const float4 a = *reinterpret_cast<const float4*>(wrow + kc * 16);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, h[kc].x, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, h[kc].y, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, h[kc].z, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, h[kc].w, acc, 0, 0, 0);
+                    acc = gf_mfma4(a, h[kc], acc);
                 }
                 // accumulator: channels ct*16 + 4g + i of point j; padded channels come out as 0 (scale = shift = 0)
                 const float4 sc = *reinterpret_cast<const float4*>(Sl + ct * 16 + 4 * g);
@@ -268,10 +263,7 @@ __global__ __launch_bounds__(256) void k_group_mlp_max(const float* __restrict__
                     for (int kc = 0; kc < PM_MAXC / 16; kc++) {
                         if (kc * 16 >= L.cin) continue;
                         const float4 a = *reinterpret_cast<const float4*>(wrow + kc * 16);
-                        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, h[kc].x, acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, h[kc].y, acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, h[kc].z, acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, h[kc].w, acc, 0, 0, 0);
+                        acc = gf_mfma4(a, h[kc], acc);
                     }
                     // padded channels: scale = shift = 0 -> 0 (also after the ReLU)
                     const float4 sc = *reinterpret_cast<const float4*>(Sl + ct * 16 + 4 * g);

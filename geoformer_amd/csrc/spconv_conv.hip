@@ -25,7 +25,6 @@
 #include "geoformer_hip_dev.h"
 #include "conv_pack.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define CONV_MAX_CIN 512
 
 extern "C" size_t gf_conv_packed_floats(int K, int Cin, int Cout) {
@@ -835,21 +834,10 @@ __global__ __launch_bounds__(256) void k_conv_g16(const float* __restrict__ in, 
         }
     }
 
-#ifdef CONV_G16_STRIP
-#if CONV_G16_STRIP == 0
-    return;
-#endif
-#endif
     for (int i = 0; i < gpw; i++) {
         const int g = (blockIdx.x * gpw + i) * 4 + w;
         if (g >= ngroups) break;
         const int row = g * 16 + r;
-#ifdef CONV_G16_STRIP
-#if CONV_G16_STRIP == 1  // stores only
-        if (row < M_out) *reinterpret_cast<float4*>(out + (size_t)row * 16 + 4 * q) = make_float4(0.f, 0.f, 0.f, 0.f);
-        continue;
-#endif
-#endif
         const int4* rec = steps + (size_t)g * (GF_STEP_BLKS * 16) + r;
         int4 ib[PHA];
 #pragma unroll
@@ -859,15 +847,6 @@ __global__ __launch_bounds__(256) void k_conv_g16(const float* __restrict__ in, 
         float4 resv = make_float4(0.f, 0.f, 0.f, 0.f);
         if (RES && row < M_out) resv = *reinterpret_cast<const float4*>(residual + (size_t)row * 16 + 4 * q);
         f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-#ifdef CONV_G16_STRIP
-#if CONV_G16_STRIP == 2  // index loads + mask + store
-        if (row < M_out) {
-            float4 v = make_float4((float)(ib[0].x + ib[1].y + ib[PHA - 1].z), (float)n, resv.x, 0.f);
-            *reinterpret_cast<float4*>(out + (size_t)row * 16 + 4 * q) = v;
-        }
-        continue;
-#endif
-#endif
 
         // ---- phase A: the first PHA blocks, every gather in flight at once ----
         u32x4 a[PHA * 4][NCH];
@@ -875,30 +854,9 @@ __global__ __launch_bounds__(256) void k_conv_g16(const float* __restrict__ in, 
         for (int s = 0; s < PHA * 4; s++) {
             const int idx = reinterpret_cast<const int*>(&ib[s >> 2])[s & 3];
             const unsigned voff = ((unsigned)idx << SHIFT) + lane_ch;  // idx == -1: beyond the descriptor, reads zeros
-#if defined(CONV_G16_STRIP) && CONV_G16_STRIP == 4  // no gathers: MFMA + weights on index-derived values
-#pragma unroll
-            for (int c = 0; c < NCH; c++) a[s][c] = (u32x4){voff, voff + 1u, voff + 2u, voff + 3u};
-#else
 #pragma unroll
             for (int c = 0; c < NCH; c++) a[s][c] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, voff, c * 64, 0);
-#endif
         }
-#ifdef CONV_G16_STRIP
-#if CONV_G16_STRIP == 3  // + gathers, summed on the VALU, no MFMA / weights
-        {
-            float4 v = resv;
-#pragma unroll
-            for (int s = 0; s < PHA * 4; s++)
-#pragma unroll
-                for (int c = 0; c < NCH; c++) {
-                    v.x += __uint_as_float(a[s][c][0]); v.y += __uint_as_float(a[s][c][1]);
-                    v.z += __uint_as_float(a[s][c][2]); v.w += __uint_as_float(a[s][c][3]);
-                }
-            if (row < M_out) *reinterpret_cast<float4*>(out + (size_t)row * 16 + 4 * q) = v;
-            continue;
-        }
-#endif
-#endif
 #pragma unroll
         for (int s = 0; s < PHA * 4; s++) {
             if (s < n) {
@@ -1005,15 +963,6 @@ __global__ __launch_bounds__(256) void k_conv_g16(const float* __restrict__ in, 
 // pipeline is issued unconditionally (a missing group or neighbour is index -1 = out of the descriptor's range, no
 // memory traffic), so the waits are exact counted vmcnt's instead of vmcnt(0).
 // ------------------------------------------------------------------------------------
-#ifdef CONV_TRACE
-// dev build: per-wave cycle stamps (s_memtime) of the pipelined kernel, written to a caller-set buffer
-__device__ unsigned long long* g_conv_trace = nullptr;
-extern "C" int gf_dev_conv_trace(void* p) {
-    GF_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_conv_trace), &p, sizeof(p)));
-    return GF_OK;
-}
-#define TR_NOW() __builtin_amdgcn_s_memtime()
-#endif
 #ifndef CONV_G16P_WAVES
 #define CONV_G16P_WAVES 2  // resident waves per SIMD the register budget is set for
 #endif
@@ -1043,9 +992,6 @@ __global__ __launch_bounds__(64 * WPB, CONV_G16P_WAVES) void k_conv_g16p(const f
     const __amdgpu_buffer_rsrc_t rs_st =
         __builtin_amdgcn_make_buffer_rsrc((void*)steps_raw, 0, (int)steps_bytes, 0x00020000);
     const int cw = blockIdx.x * WPB + w;
-#ifdef CONV_TRACE
-    unsigned long long tr[8] = {TR_NOW(), 0, 0, 0, 0, 0, 0, 0};  // start, after barrier, first data, [wait a0, mfma, tail] sums, end, groups
-#endif
     // the table's count and this wave's two boundaries as three INDEPENDENT loads (count -> boundaries was one more
     // dependent round trip in front of the first index load; the table's tail is sized for GF_CONV_CHUNKS_MAX entries)
     const int cwc = min(cw, GF_CONV_CHUNKS_MAX - 1);
@@ -1126,9 +1072,6 @@ __global__ __launch_bounds__(64 * WPB, CONV_G16P_WAVES) void k_conv_g16p(const f
     }
     if (g < gend) gather(aX, ibX, true, presX);
     if (LDSW) __syncthreads();
-#ifdef CONV_TRACE
-    tr[1] = TR_NOW();
-#endif
     if (g >= gend) return;
 
     // one group's MFMAs + store; `a` holds its gathered rows (in flight), `pres` its presence bits
@@ -1181,18 +1124,6 @@ __global__ __launch_bounds__(64 * WPB, CONV_G16P_WAVES) void k_conv_g16p(const f
             }
         };
         fetch_w(wq, ks[0]);
-#ifdef CONV_TRACE
-        const unsigned long long tc0 = TR_NOW();
-        {
-            // wait for the first gathered row of this group (and only for it)
-            float probe = __uint_as_float(a[0][0][0]);
-            asm volatile("v_mov_b32 %0, %0" : "+v"(probe));
-            a[0][0][0] = __float_as_uint(probe);
-        }
-        const unsigned long long tc1 = TR_NOW();
-        tr[3] += tc1 - tc0;
-        if (tr[2] == 0) tr[2] = tc1;
-#endif
 #pragma unroll
         for (int s = 0; s < NS; s++) {
             if (s + 1 < NS) fetch_w(wn, ks[s + 1]);
@@ -1236,11 +1167,6 @@ __global__ __launch_bounds__(64 * WPB, CONV_G16P_WAVES) void k_conv_g16p(const f
                 }
             }
         }
-#ifdef CONV_TRACE
-        const unsigned long long tc2 = TR_NOW();
-        tr[4] += tc2 - tc1;
-        tr[7] += 1;
-#endif
         if (row < M_out) {
             float4 v = make_float4(acc0[0] + acc1[0], acc0[1] + acc1[1], acc0[2] + acc1[2], acc0[3] + acc1[3]);
             if (RES) {
@@ -1258,9 +1184,6 @@ __global__ __launch_bounds__(64 * WPB, CONV_G16P_WAVES) void k_conv_g16p(const f
             }
             *reinterpret_cast<float4*>((out2 ? out2 : out) + (size_t)row * 16 + 4 * q) = v;
         }
-#ifdef CONV_TRACE
-        tr[5] += TR_NOW() - tc2;
-#endif
     };
 
     // steady state, unrolled by two so that the buffers keep static names:
@@ -1275,11 +1198,6 @@ __global__ __launch_bounds__(64 * WPB, CONV_G16P_WAVES) void k_conv_g16p(const f
         compute(aY, presY, g);
         if (++g >= gend) break;
     }
-#ifdef CONV_TRACE
-    tr[6] = TR_NOW();
-    if (g_conv_trace && lane == 0)
-        for (int i = 0; i < 8; i++) g_conv_trace[(size_t)cw * 8 + i] = tr[i];
-#endif
 }
 
 // ---- which kernel a call takes: conv_plan (a pure function of the call's sizes, tables, operands, pointer alignment

@@ -23,7 +23,6 @@
 #include "common.h"
 #include "geoformer_hip_dev.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 struct LwArgs {
@@ -260,11 +259,7 @@ __global__ __launch_bounds__(64 * WPB) void k_conv_lw(const LwArgs A) {
         for (int c = 0; c < NCH; c++)
 #pragma unroll
             for (int cb = 0; cb < NCB; cb++)
-#if defined(LW_STRIP) && LW_STRIP == 3  // no LDS weight reads
-                dst[c][cb] = make_float4(__uint_as_float(wb), 1.f, 2.f, (float)cb);
-#else
                 dst[c][cb] = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(s_w) + wb + (c * NCB + cb) * 1024);
-#endif
     };
     int kc = m ? __builtin_ctz(m) : 0;
     fetch_w(wv[0], kc);
@@ -292,11 +287,6 @@ __global__ __launch_bounds__(64 * WPB) void k_conv_lw(const LwArgs A) {
                         x.w = fmaxf(fmaf(x.w, sc[c].w, present ? sh[c].w : 0.f), 0.f);
                     }
                     const float4 (&wc)[NCB] = wv[d & 1][c];
-#if defined(LW_STRIP) && LW_STRIP == 1  // no MFMA
-#pragma unroll
-                    for (int cb = 0; cb < NCB; cb++) { acc[cb][0][0] += x.x * wc[cb].x; acc[cb][0][1] += x.y * wc[cb].y; }
-                    continue;
-#endif
 #pragma unroll
                     for (int cb = 0; cb < NCB; cb++) acc[cb][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wc[cb].x, x.x, acc[cb][0], 0, 0, 0);
 #pragma unroll
@@ -324,13 +314,8 @@ __global__ __launch_bounds__(64 * WPB) void k_conv_lw(const LwArgs A) {
                 const unsigned voff = __umul24((unsigned)idxr[d], row_bytes) + lane_c;
                 if (AFF) absent = (absent & ~(1u << d)) | (((unsigned)idxr[d] >> 31) << d);
                 const unsigned sb = s + d + D < total_steps ? 0u : 0x80000000u;
-#if defined(LW_STRIP) && LW_STRIP == 2  // no gathers
-#pragma unroll
-                for (int c = 0; c < NCH; c++) ring[d][c] = (u32x4){voff, sb, voff + 1u, (unsigned)c};
-#else
 #pragma unroll
                 for (int c = 0; c < NCH; c++) ring[d][c] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, voff, sb + c * 64, 0);
-#endif
                 idxr[d] = (int)__builtin_amdgcn_raw_buffer_load_b32(rs_st, lane_r, next_record(), 0);
                 LW_FENCE();
             }

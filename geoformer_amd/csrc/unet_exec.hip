@@ -16,7 +16,7 @@
 #include <time.h>
 #include <vector>
 
-#include "common.h"
+#include "tile_gemm.h"
 #include "geoformer_hip_dev.h"
 
 namespace {
@@ -46,7 +46,6 @@ __global__ void k_concat2(const float4* __restrict__ a, const float4* __restrict
 __global__ __launch_bounds__(256) void k_concat2_idn(const float* __restrict__ a, const float* __restrict__ b, int M, int C,
                                                      const float4* __restrict__ Wp, float* __restrict__ cat,
                                                      float* __restrict__ idn) {
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     const int lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
     const int ncb = C >> 4, nch = C >> 3, nc1 = C >> 4;  // column blocks, input chunks (2C / 16), chunks that come from a
     const int item = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -69,10 +68,7 @@ __global__ __launch_bounds__(256) void k_concat2_idn(const float* __restrict__ a
     for (int ch = 0; ch < IDC_MAXCH; ch++) {
         if (ch < nch) {
             if (cb == 0 && row < M) *reinterpret_cast<float4*>(cat + (size_t)row * 2 * C + ch * 16 + 4 * q) = x[ch];
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w[ch].x, x[ch].x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w[ch].y, x[ch].y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w[ch].z, x[ch].z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w[ch].w, x[ch].w, acc, 0, 0, 0);
+            acc = gf_mfma4(w[ch], x[ch], acc);
         }
     }
     if (row < M) *reinterpret_cast<float4*>(idn + (size_t)row * C + cb * 16 + 4 * q) = make_float4(acc[0], acc[1], acc[2], acc[3]);
