@@ -285,11 +285,13 @@ def resblock_fwd(x: torch.Tensor, wp0, wp1, wpi, nbr, gmask, K: int, M: int, ld:
     return buf[0]
 
 
-def conv_dgrad(grad_out: torch.Tensor, weight: torch.Tensor, bwd, M_in: int) -> torch.Tensor:
+def conv_dgrad(grad_out: torch.Tensor, weight: torch.Tensor, bwd, M_in: int, flat=None) -> torch.Tensor:
     """Input gradient = the forward kernel over the transposed relation.
     bwd = ("subm", (nbr, gmask, 27, M, ld)): same table, weights W[26-k]^T (the submanifold
     relation is symmetric: nbr[k][o] = i  <=>  nbr[26-k][i] = o);
-    bwd = ("table", (tbl, gmask, K, M_in, ld)): explicit transposed table, weights W[k]^T."""
+    bwd = ("table", (tbl, gmask, K, M_in, ld)): explicit transposed table, weights W[k]^T.
+    flat: optional flat step table of the SAME table (a submanifold relation is its own transpose, so the forward's
+    serves): the launch then goes through gf_conv_fwd_flat, as the training executor's does."""
     kind, spec = bwd
     tbl, gmask, K, M, ld = spec[:5]
     steps = spec[5] if len(spec) > 5 else None
@@ -300,7 +302,7 @@ def conv_dgrad(grad_out: torch.Tensor, weight: torch.Tensor, bwd, M_in: int) -> 
     wp = torch.empty(lib.gf_conv_packed_floats(K, Cout, Cin), dtype=torch.float32, device=w.device)
     check(lib.gf_conv_pack_weights_t(ptr(w), K, Cin, Cout, 1 if kind == "subm" else 0, ptr(wp), stream_ptr()),
           "gf_conv_pack_weights_t")
-    return conv_fwd(grad_out, None, tbl, gmask, K, M, ld, steps=steps, packed=(wp, Cout, Cin))
+    return conv_fwd(grad_out, None, tbl, gmask, K, M, ld, steps=steps, packed=(wp, Cout, Cin), flat=flat)
 
 
 def conv_wgrad(feats: torch.Tensor, grad_out: torch.Tensor, nbr, K: int, M_out: int, ld: int, gmask=None) -> torch.Tensor:

@@ -175,7 +175,10 @@ int gf_rules_flat_steps(const int32_t* nbr, const uint32_t* gmask, int K, int M,
  *   nbr may be NULL with K == 1 (identity map: plain GEMM, the k=1 "i_branch" conv)
  *   in_scale/in_shift  optional fp32 [Cin]: act(x) = max(x*scale + shift, 0) fused on the
  *                      gathered rows (eval-mode BatchNorm1d + ReLU, geoformer_modules.py:19-26)
- *   residual           optional fp32 [M_out,Cout] added in the epilogue (geoformer_modules.py:33)
+ *   residual           optional fp32 [M_out,Cout] added in the epilogue (geoformer_modules.py:33).  It may be `out`
+ *                      itself (in-place accumulation; the training executor's input gradients rely on it): in every
+ *                      launch shape each output element's residual is read by the lanes that write that element,
+ *                      before they write it.  `in` must not overlap `out`.
  *   out_scale/out_shift optional fp32 [Cout], 16-byte aligned: out = max(out*scale + shift, 0) in the epilogue (the
  *                      CONSUMER's BatchNorm + ReLU applied once per output element; gf_resblock_fwd uses it for bn1)
  *   steps              optional step table of the same relation (gf_rules_subm3); nbr may then be NULL for the
