@@ -32,20 +32,21 @@ import math
 import numpy as np
 import torch
 
-from . import _lib
+from . import _abi, _lib
 from ._lib import check, ptr
 
-# the per-scene record of include/geoformer_hip.h (64-bit words)
-REC = 320
+# the per-scene record of include/geoformer_hip.h (64-bit words).  Its sizes are the header's #defines; the R_* / H_* word
+# offsets and the ERR_* bits are enumerators there (GF_AUG_R_*, GF_AUG_H_*, GF_AUG_ERR_*), not #defines, and stay restated
+REC = _abi.const("GF_AUG_REC")
 R_M, R_SHIFT, R_FLIP, R_THETA, R_AMAX0, R_AMAX1 = 0, 9, 12, 13, 14, 17
 R_MIN, R_MAX, R_CHOSEN, R_ERR, R_CAP0, R_BASE0, R_CAP1, R_BASE1 = 20, 23, 26, 27, 28, 29, 30, 31
 R_PCMIN, R_PCMAX, R_NINST, R_IBASE, R_COUNTS, R_CROPU = 32, 35, 38, 39, 64, 128
 R_PBASE, R_CLASS, R_SUPID = 40, 41, 42
 R_BMIN, R_BMAX, R_BCNT, R_BLMAX = 43, 46, 49, 50
 H_N, H_NINST, H_ERR, H_SHAPE = 0, 1, 2, 6
-HEAD = 16
-MAX_INST = 4096
-MAX_CROP = 64
+HEAD = _abi.const("GF_AUG_HEAD")
+MAX_INST = _abi.const("GF_AUG_MAX_INST")
+MAX_CROP = _abi.const("GF_AUG_MAX_CROP")
 ERR_CELLS, ERR_INST, ERR_NOINST = 1, 2, 4
 NORMAL_MAX = 6.67  # |Box-Muller normal| from 32-bit uniforms: sqrt(2 ln 2^32) = 6.66
 

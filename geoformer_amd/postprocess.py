@@ -7,9 +7,11 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
-PROP_SCENE_FIELDS = 6  # GF_PROP_SCENE_FIELDS, include/geoformer_hip.h
-NMS_SCENE_FIELDS = 8  # GF_NMS_SCENE_FIELDS
-NMS_MAX_N = 1024  # GF_NMS_MAX_N
+from . import _abi
+
+PROP_SCENE_FIELDS = _abi.const("GF_PROP_SCENE_FIELDS")
+NMS_SCENE_FIELDS = _abi.const("GF_NMS_SCENE_FIELDS")
+NMS_MAX_N = _abi.const("GF_NMS_MAX_N")
 
 
 def matrix_non_max_suppression(proposals_pred, scores, categories, kernel="gaussian", sigma=2.0,
@@ -155,11 +157,11 @@ def matrix_nms_batched(masks, scores, categories, kernel="gaussian", sigma=2.0, 
 
 
 # ---- scene labelling (csrc/label_map.hip): one label per point, one table row per picked instance ---------------------
-LBL_SCENE_FIELDS = 12  # GF_LBL_SCENE_FIELDS
-LBL_CHUNK = 4096  # GF_LBL_CHUNK
-LBL_OWN_SPLIT = 4  # GF_LBL_OWN_SPLIT
-LBL_TABLE_INTS = 5  # GF_LBL_TABLE_INTS
-LBL_TABLE_FLOATS = 10  # GF_LBL_TABLE_FLOATS
+LBL_SCENE_FIELDS = _abi.const("GF_LBL_SCENE_FIELDS")
+LBL_CHUNK = _abi.const("GF_LBL_CHUNK")
+LBL_OWN_SPLIT = _abi.const("GF_LBL_OWN_SPLIT")
+LBL_TABLE_INTS = _abi.const("GF_LBL_TABLE_INTS")
+LBL_TABLE_FLOATS = _abi.const("GF_LBL_TABLE_FLOATS")
 MIN_SCORE = 0.09  # util/visualize.py:221
 
 

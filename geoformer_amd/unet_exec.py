@@ -13,26 +13,13 @@ import threading
 import torch
 import torch.nn as nn
 
-from . import _lib, sparse
+from . import _abi, _lib, sparse
 from ._lib import check, stream_ptr
 
-MAX_LEVELS = 8
-_FP = ctypes.c_void_p
-
-
-class ResBlockParams(ctypes.Structure):
-    _fields_ = [(n, _FP) for n in ("wp0", "wp1", "wpi", "s0", "t0", "s1", "t1")]
-
-
-class LevelParams(ctypes.Structure):
-    _fields_ = [("C", ctypes.c_int), ("tr_layers", ctypes.c_int), ("blocks", ResBlockParams * 2),
-                ("tail", ResBlockParams * 2), ("down_wp", _FP), ("down_s", _FP), ("down_t", _FP), ("up_wp", _FP),
-                ("up_s", _FP), ("up_t", _FP), ("tr_params", _FP)]
-
-
-class UnetParams(ctypes.Structure):
-    _fields_ = [("nlevels", ctypes.c_int), ("cin", ctypes.c_int), ("input_wp", _FP), ("out_s", _FP), ("out_t", _FP),
-                ("level", LevelParams * MAX_LEVELS)]
+MAX_LEVELS = _abi.const("GF_UNET_MAX_LEVELS")
+ResBlockParams = _abi.struct("GfResBlockParams")
+LevelParams = _abi.struct("GfUnetLevelParams")
+UnetParams = _abi.struct("GfUnetParams")
 
 
 def _levels(unet):

@@ -19,24 +19,11 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, pointops, sparse
+from . import _abi, _lib, pointops, sparse
 from ._lib import check, stream_ptr
 
-_FP = ctypes.c_void_p
-
-
-class TrainOp(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int) for n in ("kind", "level", "table", "src", "dst", "aux", "Cin", "Cout", "no_dgrad", "pad_")] + \
-        [(n, _FP) for n in ("w", "gamma", "beta", "running_mean", "running_var")] + \
-        [("eps", ctypes.c_float), ("momentum", ctypes.c_float)] + \
-        [(n, ctypes.c_longlong) for n in ("wp_off", "pgrad_off", "stats_off")]
-
-
-class TrainLevel(ctypes.Structure):
-    _fields_ = [("M", ctypes.c_int), ("ld", ctypes.c_int), ("nbr", _FP), ("gmask", _FP), ("steps", _FP),
-                ("M_coarse", ctypes.c_int), ("ld_down", ctypes.c_int), ("child", _FP), ("gmask_down", _FP),
-                ("ld_up", ctypes.c_int), ("pad_", ctypes.c_int), ("up", _FP), ("gmask_up", _FP), ("flat", _FP)]
-
+TrainOp = _abi.struct("GfTrainOp")
+TrainLevel = _abi.struct("GfTrainLevel")
 
 BN_RELU, CONV, CAT = 0, 1, 2
 T_1X1, T_SUBM, T_DOWN, T_UP = 0, 1, 2, 3
