@@ -4,6 +4,10 @@
         ...                                   # masks int32 [n, N] over the scene's points, pick: the NMS result
     ap, avgs = evaluate(model, [(name, raw), ...], batch_size=4)
     print(evaluation.format_results(avgs))
+    ev = evaluation.SemanticEvaluator(train_fold=model.cfg.train_fold)
+    ap, avgs = evaluate(model, [(name, raw), ...], batch_size=4, semantic=ev)    # AP and mIoU from one pass
+    res = evaluate_semantic(model, [(name, raw), ...], batch_size=4)             # backbone + semantic head only
+    print(evaluation.format_semantic_results(res))
     for name, labels in label_batches(model, [(name, raw), ...], batch_size=4):
         ...                                   # labels.ids / .owner [N], labels.table: one row per instance (host)
 
@@ -51,11 +55,14 @@ def collate_batches(raw_scenes, batch_size, spatial_shape=None, scale=50, full_s
 
 @torch.no_grad()
 def predict_batches(model, raw_scenes, batch_size, *, epoch=300, spatial_shape=None, nms_kernel="gaussian",
-                    sigma=2.0, final_score_thresh=NMS_FINAL_SCORE, cvfold=None, reserve=True, device=None):
+                    sigma=2.0, final_score_thresh=NMS_FINAL_SCORE, cvfold=None, reserve=True, device=None,
+                    semantic=None):
     """Yields (name, cls_final, scores_final, masks_final, pick) per scene, in input order.  raw_scenes: iterable of
     (name, raw [N, 8]).  The NMS categories are the benchmark label ids of the classes (evaluation.benchmark_label_ids
     with cvfold, default model.cfg.cvfold).  A scene without proposals yields ([], [], [], empty pick).  reserve: size
-    the allocator for the largest batch first (GeoFormer.reserve_for with the batch's total points)."""
+    the allocator for the largest batch first (GeoFormer.reserve_for with the batch's total points).  semantic: an
+    evaluation.SemanticEvaluator that is given every batch's semantic scores, labels, offsets and scene names (one
+    launch on the forward's stream before the NMS, nothing read back); None: nothing is added to the loop."""
     cvfold = model.cfg.cvfold if cvfold is None else cvfold
     dev = torch.device(device) if device is not None else next(model.parameters()).device
     model.eval()
@@ -65,8 +72,11 @@ def predict_batches(model, raw_scenes, batch_size, *, epoch=300, spatial_shape=N
     most = max(int(b["offsets"][-1]) for b in batches)
     if reserve:
         model.reserve_for(most)
-    for chunk, batch in zip(chunks, DeviceFeeder(batches, dev, reserve_points=most)):
+    for chunk, host, batch in zip(chunks, batches, DeviceFeeder(batches, dev, reserve_points=most)):
         out = model(batch, epoch, training=False, all_scenes=True)
+        if semantic is not None:
+            semantic.add_batch(out["semantic_scores"], batch["labels"], batch["offsets"], [n for n, _ in chunk],
+                               offsets_host=host["offsets"])
         per = out.get("proposal_scores_per_scene") or [([], [], []) for _ in chunk]
         labels = [evaluation.benchmark_label_ids(c, cvfold) if torch.is_tensor(c) else [] for c, _, _ in per]
         picks = postprocess.matrix_nms_batched([m for _, _, m in per], [s for _, s, _ in per], labels,
@@ -126,4 +136,47 @@ def evaluate(model, scenes_with_gt, batch_size, classes=0, *, cvfold=None, **kw)
         r = torch.as_tensor(np.asarray(raws[name]), device=dev)
         gt = evaluation.gt_ids_from_labels(r[:, 6].long(), r[:, 7].long())
         ev.add_scene(name, gt, evaluation.benchmark_label_ids(cls, cvfold), sc, masks, pick)
+    return ev.evaluate()
+
+
+@torch.no_grad()
+def semantic_batches(model, raw_scenes, batch_size, *, spatial_shape=None, reserve=True, device=None, evaluator=None):
+    """Yields (name, preds) per scene, in input order: preds int32 [N] on the device, a view of the batch's buffer -- the
+    semantic head's class of every point (the first maximal score, the rule of the forward's foreground selection).
+    Only the backbone and the semantic head run (forward_backbone with the fused voxel-row head; no arg-max by the
+    framework, no instance stage): the loop of the first ``prepare_epochs``.  evaluator: an evaluation.SemanticEvaluator
+    that counts every batch against its labels in the same launch."""
+    from . import pointops
+
+    dev = torch.device(device) if device is not None else next(model.parameters()).device
+    model.eval()
+    chunks, batches = collate_batches(raw_scenes, batch_size, spatial_shape)
+    if not batches:
+        return
+    most = max(int(b["offsets"][-1]) for b in batches)
+    if reserve:
+        model.reserve_for(most)
+    for chunk, host, batch in zip(chunks, batches, DeviceFeeder(batches, dev, reserve_points=most)):
+        _, scores, _ = model.forward_backbone(batch, len(chunk), want_preds=False)
+        scores = scores.contiguous()
+        if evaluator is not None:
+            preds = evaluator.add_batch(scores, batch["labels"], batch["offsets"], [n for n, _ in chunk],
+                                        offsets_host=host["offsets"])
+        else:
+            preds = pointops.semantic_confusion(scores, None, None, None)
+        off = host["offsets"].tolist()
+        for i, (name, _) in enumerate(chunk):
+            yield name, preds[off[i]:off[i + 1]]
+
+
+@torch.no_grad()
+def evaluate_semantic(model, scenes_with_gt, batch_size, **kw):
+    """mIoU / accuracy / foreground-filter quality of the semantic head over (name, raw [N, 8]) scenes whose column 6 is
+    the ground truth (raw dataset labels): evaluation.SemanticEvaluator.evaluate's dict, with the class count and the
+    train fold of model.cfg.  Keywords go to semantic_batches."""
+    ev = kw.pop("evaluator", None)
+    if ev is None:
+        ev = evaluation.SemanticEvaluator(n_classes=model.cfg.classes, train_fold=model.cfg.train_fold)
+    for _ in semantic_batches(model, scenes_with_gt, batch_size, evaluator=ev, **kw):
+        pass
     return ev.evaluate()

@@ -422,3 +422,277 @@ def compute_averages(aps, *, classes=0, overlaps=DEFAULT_OVERLAPS):
     """The summary dict of an AP array [1, C, n_overlaps] (evaluate_matches' shape)."""
     _, names = class_set(classes)
     return _averages(np.asarray(aps)[0], names, overlaps)
+
+
+# ---- semantic segmentation: predictions, confusion matrices, IoU -------------------------------------------------------
+# The semantic head is the model's foreground filter (geoformer.py:423-429: pred >= 4, or pred == 3 across folds) and the
+# only thing trained in the first prepare_epochs.  Its classes are the training labels of
+# datasets/scannetv2_inst.py:314-323: wall, floor, "unannotated" (raw -100, trained as a class), "candidate" (every
+# class of the other fold) and the train fold's nine classes.
+SEMANTIC_FG_CLASS = 4         # classes >= 4: the fold's instance classes
+SEMANTIC_CANDIDATE_CLASS = 3  # the other fold's classes
+DATASET_LABEL_NAMES = ("wall", "floor") + CLASS_NAMES  # raw dataset labels 0..19 (BENCHMARK_SEMANTIC_LABELS' order)
+IGNORE_LABEL = -100
+
+
+def semantic_label_lut(train_fold):
+    """(lut int32 [20], map_ignore, map_other) of raw ScanNet labels for a train fold, as
+    datasets/scannetv2_inst.py:314-323 relabels a scene: 0 -> 0, 1 -> 1, the fold's classes -> 4 + i, -100 -> 2
+    (map_ignore), everything else -> 3 (map_other)."""
+    fold = FOLD_SEMANTIC_LABELS[int(train_fold)]
+    lut = np.full(len(BENCHMARK_SEMANTIC_LABELS), SEMANTIC_CANDIDATE_CLASS, dtype=np.int32)
+    lut[0], lut[1] = 0, 1
+    for i, c in enumerate(fold):
+        lut[c] = SEMANTIC_FG_CLASS + i
+    return lut, 2, SEMANTIC_CANDIDATE_CLASS
+
+
+def SEMANTIC_CLASS_NAMES(train_fold):
+    """Names of the semantic head's 13 classes for a train fold, in class order."""
+    return ("wall", "floor", "unannotated", "candidate") + tuple(
+        DATASET_LABEL_NAMES[c] for c in FOLD_SEMANTIC_LABELS[int(train_fold)])
+
+
+def semantic_preds_host(scores):
+    """numpy statement of the native arg-max: the first maximal class of every row of scores [N, C] (start from class 0,
+    replace on strict '>' in ascending class order), int32 [N].  A NaN wins only in column 0.  On rows without ties or
+    NaNs this is scores.max(1)[1]."""
+    s = np.asarray(scores, dtype=np.float32)
+    if s.ndim != 2 or s.shape[1] < 1:
+        raise ValueError(f"scores {s.shape}: expected [N, C]")
+    mx = s[:, 0].copy()
+    arg = np.zeros(s.shape[0], dtype=np.int32)
+    for k in range(1, s.shape[1]):
+        w = s[:, k] > mx
+        mx[w] = s[w, k]
+        arg[w] = k
+    return arg
+
+
+def map_semantic_labels(labels, n_classes, lut=None, ignore_label=IGNORE_LABEL, map_ignore=-1, map_other=-1):
+    """The confusion matrix's row of every label, int64: map_ignore for ignore_label, lut[label] inside the table (the
+    identity over 0..n_classes-1 without one), map_other outside; a mapped value outside 0..n_classes-1 becomes
+    n_classes (ignored)."""
+    g = np.asarray(labels).astype(np.int64)
+    table = np.arange(n_classes, dtype=np.int64) if lut is None else np.asarray(lut, dtype=np.int64)
+    inside = (g >= 0) & (g < len(table))
+    m = np.full(g.shape, int(map_other), dtype=np.int64)
+    m[inside] = table[g[inside]]
+    m[g == ignore_label] = int(map_ignore)
+    m[(m < 0) | (m >= n_classes)] = n_classes
+    return m
+
+
+def semantic_confusion_host(scores, labels, offsets=None, *, lut=None, ignore_label=IGNORE_LABEL, map_ignore=-1,
+                            map_other=-1):
+    """numpy statement of gf_semantic_confusion: (preds int32 [N], conf int64 [S, C+1, C]) of S scenes packed one after
+    the other (offsets [S+1], default one scene); conf[s, row, pred] with row the mapped label, C for ignored ones."""
+    preds = semantic_preds_host(scores)
+    N, C = np.asarray(scores).shape
+    off = np.array([0, N], dtype=np.int64) if offsets is None else np.asarray(offsets).astype(np.int64)
+    if off.ndim != 1 or len(off) < 1 or off[0] != 0 or off[-1] != N or (np.diff(off) < 0).any():
+        raise ValueError(f"offsets {off.tolist()[:8]}...: ascending from 0 to N = {N}")
+    S = len(off) - 1
+    rows = map_semantic_labels(labels, C, lut, ignore_label, map_ignore, map_other)
+    if rows.shape != (N,):
+        raise ValueError(f"labels {rows.shape} against {N} points")
+    sc = np.repeat(np.arange(S, dtype=np.int64), np.diff(off))
+    bins = (C + 1) * C
+    conf = np.bincount(sc * bins + rows * C + preds, minlength=S * bins).reshape(S, C + 1, C).astype(np.int64)
+    return preds, conf
+
+
+def _ratio(a, b):
+    return float(a) / float(b) if b else float("nan")
+
+
+def _filter_quality(tp, n_pred, n_gt):
+    return {"precision": _ratio(tp, n_pred), "recall": _ratio(tp, n_gt), "iou": _ratio(tp, n_pred + n_gt - tp)}
+
+
+def semantic_metrics(conf, names=None, fg_class=SEMANTIC_FG_CLASS, candidate_class=SEMANTIC_CANDIDATE_CLASS):
+    """The summary of a confusion matrix [C+1, C] (row = ground truth, C = ignored; column = prediction).  Points whose
+    ground truth is ignored count nowhere (ScanNet's evaluate_semantic_label.py).  iou [C] = tp / (tp + fp + fn), nan
+    for a class in neither prediction nor ground truth; miou: nan-mean over all classes, miou_fold over fg_class..C-1;
+    acc = trace / points; macc: nan-mean of the per-class recall; foreground / candidate: precision, recall and IoU of
+    the model's two point filters, pred >= fg_class against gt >= fg_class and pred == candidate_class against gt ==
+    candidate_class (the recall is the share of those points the instance stage is shown)."""
+    conf = np.asarray(conf, dtype=np.int64)
+    C = conf.shape[1]
+    if conf.shape != (C + 1, C):
+        raise ValueError(f"confusion matrix {conf.shape}: expected [C+1, C]")
+    m = conf[:C]
+    tp = np.diag(m)
+    n_gt, n_pred = m.sum(1), m.sum(0)
+    denom = n_gt + n_pred - tp
+    with np.errstate(divide="ignore", invalid="ignore"):
+        iou = np.where(denom > 0, tp / denom, np.nan)
+        recall = np.where(n_gt > 0, tp / n_gt, np.nan)
+
+    def nanmean(v):
+        v = v[~np.isnan(v)]
+        return float(v.mean()) if v.size else float("nan")
+
+    names = [str(c) for c in range(C)] if names is None else list(names)
+    res = {"classes": {n: {"iou": float(iou[c]), "recall": float(recall[c]), "points": int(n_gt[c])}
+                       for c, n in enumerate(names)},
+           "iou": iou, "miou": nanmean(iou), "miou_fold": nanmean(iou[fg_class:]),
+           "acc": _ratio(tp.sum(), m.sum()), "macc": nanmean(recall),
+           "points": int(m.sum()), "ignored": int(conf[C].sum()),
+           "foreground": _filter_quality(m[fg_class:, fg_class:].sum(), m[:, fg_class:].sum(), m[fg_class:].sum())}
+    if 0 <= candidate_class < C:
+        c = candidate_class
+        res["candidate"] = _filter_quality(tp[c], n_pred[c], n_gt[c])
+    else:
+        res["candidate"] = _filter_quality(0, 0, 0)
+    return res
+
+
+def format_semantic_results(res):
+    """The summary as a printable table, in the style of format_results."""
+    lines = ["#" * 64, f"{'what':<15}:{'IoU':>15}{'recall':>15}{'points':>15}", "#" * 64]
+    for name, c in res["classes"].items():
+        lines.append(f"{name:<15}:{c['iou']:>15.3f}{c['recall']:>15.3f}{c['points']:>15d}")
+    lines.append("-" * 64)
+    lines.append(f"{'mIoU':<15}:{res['miou']:>15.3f}{'mAcc':>10}{res['macc']:>10.3f}{'acc':>5}{res['acc']:>10.3f}")
+    lines.append(f"{'mIoU (fold)':<15}:{res['miou_fold']:>15.3f}{'ignored':>15}{res['ignored']:>15d}")
+    lines.append(f"{'filter':<15}:{'precision':>15}{'recall':>15}{'IoU':>15}")
+    for key in ("foreground", "candidate"):
+        f = res[key]
+        lines.append(f"{key:<15}:{f['precision']:>15.3f}{f['recall']:>15.3f}{f['iou']:>15.3f}")
+    return "\n".join(lines)
+
+
+class SemanticEvaluator:
+    """mIoU / accuracy of the semantic head and the quality of its foreground filter over a set of scenes.
+
+        ev = SemanticEvaluator(n_classes=13, train_fold=0)
+        preds = ev.add_batch(outputs["semantic_scores"], batch["labels"], batch["offsets"], names)
+        res = ev.evaluate(); print(ev.format_results(res))
+
+    raw_labels: the labels are raw dataset labels (0..19, -100) and go through semantic_label_lut(train_fold); False:
+    they are training labels already (0..n_classes-1, -100 ignored).  Device tensors are counted by the native call
+    into matrices that stay on the device: nothing crosses to the host before evaluate() / confusion() /
+    scene_confusions().  Host arrays take the numpy path.  keep_scenes=False keeps the dataset total only."""
+
+    def __init__(self, n_classes=13, train_fold=0, raw_labels=True, keep_scenes=True, fg_class=SEMANTIC_FG_CLASS,
+                 candidate_class=SEMANTIC_CANDIDATE_CLASS):
+        self.n_classes = int(n_classes)
+        self.train_fold = int(train_fold)
+        self.raw_labels = bool(raw_labels)
+        self.keep_scenes = bool(keep_scenes)
+        self.fg_class, self.candidate_class = int(fg_class), int(candidate_class)
+        if self.raw_labels:
+            self.lut, self.map_ignore, self.map_other = semantic_label_lut(self.train_fold)
+        else:
+            self.lut, self.map_ignore, self.map_other = None, -1, -1
+        names = SEMANTIC_CLASS_NAMES(self.train_fold)
+        self.class_names = list(names) if len(names) == self.n_classes else [str(c) for c in range(self.n_classes)]
+        self.names = []      # scene names in the order added
+        self._host = []      # [S, C+1, C] per host batch (keep_scenes) ...
+        self._device = []    # ... (position in self.names, device tensor) per device batch
+        self._total_host = np.zeros((self.n_classes + 1, self.n_classes), dtype=np.int64)
+        self._total_dev = {}  # device -> running total (keep_scenes=False)
+        self._dev_lut = {}
+
+    def _map_kw(self):
+        return {"ignore_label": IGNORE_LABEL, "map_ignore": self.map_ignore, "map_other": self.map_other}
+
+    def add_batch(self, scores, labels, offsets=None, names=None, offsets_host=None):
+        """One batch of S scenes packed one after the other: scores [N, n_classes], labels [N], offsets [S+1] (default:
+        one scene), names: S scene names (default: their running numbers).  offsets_host: the caller's host copy of
+        device offsets (int32), which lets the native call refuse a malformed table before it launches.  Returns preds
+        int32 [N], where the scores live."""
+        S = 1 if offsets is None else int(offsets.shape[0]) - 1
+        names = [f"scene{len(self.names) + i:04d}" for i in range(S)] if names is None else list(names)
+        if len(names) != S:
+            raise ValueError(f"add_batch: {len(names)} names for {S} scenes")
+        if scores.shape[1] != self.n_classes:
+            raise ValueError(f"add_batch: scores {tuple(scores.shape)} for {self.n_classes} classes")
+        if _is_tensor(scores) and scores.is_cuda:
+            preds = self._add_device(scores, labels, offsets, offsets_host, S, len(self.names))
+        else:
+            host = [x.detach().cpu().numpy() if _is_tensor(x) else x for x in (scores, labels, offsets)]
+            preds, conf = semantic_confusion_host(host[0], host[1], host[2], lut=self.lut, **self._map_kw())
+            if self.keep_scenes:
+                self._host.append((len(self.names), conf))
+            else:
+                self._total_host += conf.sum(0)
+        self.names += names
+        return preds
+
+    def _add_device(self, scores, labels, offsets, offsets_host, S, at):
+        import torch
+
+        from . import pointops
+
+        dev = scores.device
+        lut = None
+        if self.lut is not None:
+            lut = self._dev_lut.get(dev)
+            if lut is None:
+                lut = self._dev_lut[dev] = torch.from_numpy(self.lut).to(dev)
+        if offsets is None:
+            offsets_host = torch.tensor([0, scores.shape[0]], dtype=torch.int32)
+            offsets = offsets_host.to(dev)
+        elif not offsets.is_cuda:
+            offsets_host = offsets.to(torch.int32).contiguous()
+            offsets = offsets_host.to(dev)
+        if offsets.dtype != torch.int32:
+            offsets = offsets.to(torch.int32)
+        labels = torch.as_tensor(labels).to(dev, torch.int64).contiguous()
+        conf = torch.zeros((S, self.n_classes + 1, self.n_classes), dtype=torch.int64, device=dev)
+        preds = pointops.semantic_confusion(scores.contiguous(), labels, offsets.contiguous(), conf, lut=lut,
+                                            offsets_host=offsets_host, **self._map_kw())
+        if self.keep_scenes:
+            self._device.append((at, conf))
+        elif dev in self._total_dev:
+            self._total_dev[dev] += conf.sum(0)
+        else:
+            self._total_dev[dev] = conf.sum(0)
+        return preds
+
+    def _collect(self):
+        """Every device matrix to the host (one copy per device), merged with the host ones in scene order."""
+        if self._device:
+            import torch
+
+            by_dev = {}
+            for at, conf in self._device:
+                by_dev.setdefault(conf.device, []).append((at, conf))
+            for items in by_dev.values():
+                h = torch.cat([c for _, c in items]).cpu().numpy()
+                k = 0
+                for at, c in items:
+                    self._host.append((at, h[k:k + c.shape[0]]))
+                    k += c.shape[0]
+            self._device = []
+            self._host.sort(key=lambda e: e[0])
+        for dev in list(self._total_dev):
+            self._total_host += self._total_dev.pop(dev).cpu().numpy()
+
+    def scene_confusions(self):
+        """{scene name: confusion matrix [C+1, C]} of the scenes added so far (keep_scenes=True)."""
+        if not self.keep_scenes:
+            raise ValueError("scene_confusions: the evaluator was made with keep_scenes=False")
+        self._collect()
+        out = {}
+        for at, conf in self._host:
+            for i in range(conf.shape[0]):
+                out[self.names[at + i]] = conf[i]
+        return out
+
+    def confusion(self):
+        """The dataset's confusion matrix [C+1, C]."""
+        self._collect()
+        total = self._total_host.copy()
+        for _, conf in self._host:
+            total += conf.sum(0)
+        return total
+
+    def evaluate(self):
+        """semantic_metrics of the dataset total (classes named by SEMANTIC_CLASS_NAMES(train_fold))."""
+        return semantic_metrics(self.confusion(), self.class_names, self.fg_class, self.candidate_class)
+
+    def format_results(self, res=None):
+        return format_semantic_results(self.evaluate() if res is None else res)

@@ -7,6 +7,9 @@
 ``<out_dir>/<name>.txt`` holds one ``predicted_masks/<name>_<rrr>.txt <label_id> <score>`` line per kept instance in
 rank order, the mask file one ``0`` / ``1`` per line for each of the scene's N points: the benchmark's submission format,
 and what util/visualize.py:212-227 reads (relative path, label, score).  Scores are printed as ``%.6f``.
+
+    write_scannet_semantic("out/semantic", "scene0011_00", preds, train_fold=0)     # one benchmark label id per point
+    label_ids = read_scannet_semantic("out/semantic", "scene0011_00")
 """
 from __future__ import annotations
 
@@ -63,6 +66,36 @@ def read_scannet_predictions(out_dir, name):
     if masks and any(m.shape != masks[0].shape for m in masks):
         raise ValueError(f"{name}: mask files of different lengths")
     return label_ids, scores, (np.stack(masks) if masks else np.zeros((0, 0), np.uint8))
+
+
+def semantic_benchmark_ids(train_fold):
+    """nyu40 id of each class of the semantic head (int64 [13]): wall 1, floor 2, the fold's nine classes their benchmark
+    ids, "unannotated" and "candidate" 0 (no benchmark class)."""
+    from .evaluation import BENCHMARK_SEMANTIC_LABELS, FOLD_SEMANTIC_LABELS
+
+    fold = FOLD_SEMANTIC_LABELS[int(train_fold)]
+    return np.array([BENCHMARK_SEMANTIC_LABELS[0], BENCHMARK_SEMANTIC_LABELS[1], 0, 0]
+                    + [BENCHMARK_SEMANTIC_LABELS[c] for c in fold], dtype=np.int64)
+
+
+def write_scannet_semantic(out_dir, name, preds, train_fold):
+    """Write ``<out_dir>/<name>.txt`` of the ScanNet semantic-label benchmark: one nyu40 label id per line for each of
+    the scene's points, from the semantic head's classes preds [N] (host or device) by semantic_benchmark_ids.  Returns
+    the path."""
+    preds = preds.detach().cpu().numpy() if hasattr(preds, "detach") else np.asarray(preds)
+    table = semantic_benchmark_ids(train_fold)
+    if preds.ndim != 1 or (preds.size and (preds.min() < 0 or preds.max() >= len(table))):
+        raise ValueError(f"write_scannet_semantic: classes 0..{len(table) - 1} of [N] points expected")
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, f"{name}.txt")
+    np.savetxt(path, table[preds.astype(np.int64)], fmt="%d")
+    return path
+
+
+def read_scannet_semantic(out_dir, name):
+    """The label ids int64 [N] of a write_scannet_semantic file."""
+    with open(os.path.join(out_dir, f"{name}.txt")) as f:
+        return np.array([int(line) for line in f if line.strip()], dtype=np.int64)
 
 
 def save_labels(path, labels):

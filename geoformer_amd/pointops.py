@@ -956,6 +956,47 @@ def instance_overlaps(masks, gt_ids, class_ids, rows=None, max_gt=256):
     return gt_id, gt_count, inter
 
 
+def semantic_confusion_limits():
+    """(largest class count, points per workgroup run) of gf_semantic_confusion."""
+    lib = _lib.load()
+    return lib.gf_semantic_confusion_max_classes(), lib.gf_semantic_confusion_run_points()
+
+
+def semantic_confusion(scores, labels, offsets, conf, *, lut=None, ignore_label=-100, map_ignore=-1, map_other=-1,
+                       want_preds=True, offsets_host=None):
+    """Per-point predictions and per-scene confusion matrices of a batch (gf_semantic_confusion), one launch on the
+    current stream, nothing read back.  scores fp32 [N, C]; labels int64 [N] or None (prediction only: conf is left as
+    it is); offsets int32 [S+1] on the device; conf int64 [S, C+1, C], ADDED to (row = mapped label, C = ignored; column
+    = prediction).  lut int32 [L] on the device: label -> class for 0..L-1, map_other outside, map_ignore for
+    ignore_label; None: the identity over 0..C-1.  offsets_host: a host int32 copy of offsets, checked by the native
+    call before it launches (without it a malformed table loses counts, nothing else).  Returns preds int32 [N] (the
+    first maximal class, select_foreground's rule), None with want_preds=False."""
+    _f32c(scores, "scores")
+    if scores.dim() != 2:
+        raise RuntimeError("scores: expected [N, C]")
+    N, C = scores.shape
+    S = 0
+    if labels is not None:
+        if not (labels.is_cuda and labels.dtype == torch.int64 and labels.is_contiguous() and labels.shape == (N,)):
+            raise RuntimeError(f"labels: expected a contiguous int64 [{N}] tensor on the GPU")
+        _i32c(offsets, "offsets")
+        S = offsets.shape[0] - 1
+        if not (conf.is_cuda and conf.dtype == torch.int64 and conf.is_contiguous() and conf.shape == (S, C + 1, C)):
+            raise RuntimeError(f"conf: expected a contiguous int64 [{S}, {C + 1}, {C}] tensor on the GPU")
+        if offsets_host is not None and not (offsets_host.device.type == "cpu" and offsets_host.dtype == torch.int32
+                                             and offsets_host.is_contiguous() and offsets_host.shape == (S + 1,)):
+            raise RuntimeError(f"offsets_host: expected a contiguous int32 [{S + 1}] host tensor")
+    if lut is not None:
+        _i32c(lut, "lut")
+    preds = torch.empty(N, dtype=torch.int32, device=scores.device) if want_preds else None
+    check(_lib.load().gf_semantic_confusion(
+        ptr(scores), ptr(labels), ptr(offsets) if labels is not None else None,
+        ptr(offsets_host) if labels is not None else None, S, N, C, ptr(lut), 0 if lut is None else lut.shape[0],
+        int(ignore_label), int(map_ignore), int(map_other), ptr(preds), ptr(conf) if labels is not None else None,
+        stream_ptr()), "gf_semantic_confusion")
+    return preds
+
+
 def backbone_transformer_params(before, transformer, after):
     """Device-pointer table of gf_backbone_transformer in the order include/geoformer_hip.h documents."""
     import ctypes

@@ -821,6 +821,34 @@ int gf_instance_overlaps(const int32_t* masks, int n_rows, int N, const int32_t*
                          int32_t* gt_count, int32_t* inter, void* stream);
 
 /* ===================================================================================
+ * Semantic-segmentation evaluation of a batch of S scenes packed one after the other: per-point prediction and
+ * per-scene confusion matrices from the forward's class scores (semantic_scores.max(1)[1], geoformer.py:423, counted
+ * as the benchmark's evaluate_semantic_label.py does).
+ *   scores fp32 [N,C] contiguous, 1 <= C <= gf_semantic_confusion_max_classes().
+ *   preds int32 [N] (may be NULL): the FIRST maximal class of each row -- start from class 0, replace on strict '>' in
+ *   ascending class order, exactly gf_fg_select's rule: a NaN wins only in column 0, and `preds >= 4` is the
+ *   foreground that call selects, ties and NaNs included.
+ *   labels int64 [N], or NULL for prediction only (conf is not touched, offsets / conf may be NULL).
+ *   offsets int32 [S+1] (device): ascending scene offsets, offsets[0] = 0, offsets[S] = N; a scene may be empty.
+ *   offsets_host: the same table in host memory, or NULL.  Given, it is checked before anything is launched
+ *   (offsets[0] != 0, a descending pair or offsets[S] != N is GF_ERR_INVALID_ARG).  Not given, nothing is read back:
+ *   the kernel never leaves [0,N) x [0,S) whatever the table holds, a malformed one only loses counts.
+ *   Label mapping: m = map_ignore when label == ignore_label; else lut[label] for 0 <= label < L (lut int32 [L],
+ *   device), map_other for every other label; lut NULL (L = 0): the identity over 0..C-1, map_other elsewhere.
+ *   m outside 0..C-1 means "ignored".
+ *   conf int64 [S, C+1, C]: conf[s, m, pred] for the points of scene s, row C for the ignored ones.  The call ADDS to
+ *   conf (the caller zeroes it): conf[s].sum() grows by exactly the scene's point count per call.
+ * One launch on `stream`, no host synchronisation: a workgroup owns gf_semantic_confusion_run_points() consecutive
+ * points, counts them per scene in an LDS table of (C+1)*C words and adds its non-zero bins with 64-bit integer
+ * atomics -- exact and independent of order. */
+int gf_semantic_confusion_max_classes(void);
+int gf_semantic_confusion_run_points(void);
+int gf_semantic_confusion(const float* scores, const long long* labels, const int32_t* offsets,
+                          const int32_t* offsets_host, int S, int N, int C, const int32_t* lut, int L,
+                          long long ignore_label, int map_ignore, int map_other, int32_t* preds, long long* conf,
+                          void* stream);
+
+/* ===================================================================================
  * Backbone voxel transformer of the two deepest U-Net levels, fused (inference)
  * (UBlock: model/geoformer/geoformer_modules.py:64-68,120-127; TransformerEncoder(d_model=128, N,
  *  heads=4, d_ff=64): model/transformer.py:62-188)

@@ -4,12 +4,15 @@ batch_eval.label_batches, written with geoformer_amd.export.
     python tools/predict_scenes.py --out out scene0011_00_inst_nostuff.npy ...      # [N, 8] as prepare_data_inst.py stores them
     python tools/predict_scenes.py --out out --synthetic 8 --points 150000 --batch-size 4
     python tools/predict_scenes.py --synthetic 8 --no-write                          # only the timing
+    python tools/predict_scenes.py --out out --semantic scene0011_00_inst_nostuff.npy   # + out/semantic/<name>.txt, mIoU
 
 Per scene <out>/<name>.npz (ids, owner, instance table: export.load_labels) and, with --scannet, <out>/<name>.txt plus
 <out>/predicted_masks/ (exclusive masks; --full-masks writes the picked masks as they are).  Without --checkpoint the
 benchmark's synthetic model (bench.build_model) runs.  Prints one JSON line with the scenes per second of the
 label_batches loop, results on the host, for keep_masks off and on, beside the bare predict_batches loop (wall clock,
-host collate included, files not).
+host collate included, files not).  --semantic (or the yaml's save_semantic) adds one pass of
+batch_eval.semantic_batches: <out>/semantic/<name>.txt, the ScanNet semantic benchmark's file (one label id per point),
+and, when the scenes carry labels, the mIoU table of evaluation.SemanticEvaluator before the JSON line.
 """
 import argparse
 import json
@@ -36,6 +39,7 @@ def main():
     ap.add_argument("--config", default="test_geoformer_scannet.yaml")
     ap.add_argument("--scannet", action="store_true", help="also write the benchmark's .txt files")
     ap.add_argument("--full-masks", action="store_true", help="benchmark files hold the picked masks, not the exclusive ones")
+    ap.add_argument("--semantic", action="store_true", help="also write <out>/semantic/<name>.txt and print the mIoU table")
     ap.add_argument("--no-write", action="store_true")
     ap.add_argument("--reps", type=int, default=3, help="timed passes per keep_masks setting")
     args = ap.parse_args()
@@ -79,6 +83,15 @@ def main():
             export.save_labels(os.path.join(args.out, f"{name}.npz"), lab._replace(masks=None))
             if args.scannet:
                 export.write_scannet_predictions(args.out, name, lab, lab.masks if args.full_masks else None)
+    if args.semantic or getattr(model.cfg, "save_semantic", False):
+        from geoformer_amd import evaluation
+
+        ev = evaluation.SemanticEvaluator(n_classes=model.cfg.classes, train_fold=model.cfg.train_fold)
+        for name, preds in batch_eval.semantic_batches(model, items, args.batch_size, evaluator=ev):
+            if not args.no_write:
+                export.write_scannet_semantic(os.path.join(args.out, "semantic"), name, preds, model.cfg.train_fold)
+        if any((raw[:, 6] != evaluation.IGNORE_LABEL).any() for _, raw in items):
+            print(ev.format_results())
     pkw = {k: v for k, v in kw.items() if k != "min_score"}
 
     def predict_only():  # the loop without the labelling and without any copy of a result, for comparison
