@@ -24,6 +24,7 @@
 #include <hip/hip_ext.h>
 #include "geoformer_hip_dev.h"
 #include "conv_pack.h"
+#include "conv_tile.h"
 
 #define CONV_MAX_CIN 512
 
@@ -77,19 +78,14 @@ extern "C" int gf_conv_pack_weights_t(const float* W, int K, int Cin, int Cout, 
 // Raw gather of this lane's 4 channels of row idx (zeros for a missing neighbour).  The fused
 // BatchNorm+ReLU is applied later (activate_a), next to the MFMAs, so that the gathers of a batch
 // are issued back to back instead of each waiting for its own data.
-template <bool VEC>
 __device__ __forceinline__ float4 load_a(const float* __restrict__ in, int idx, int Cin, int ch) {
     float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
     if (idx >= 0) {
         const float* src = in + (size_t)idx * Cin + ch;
-        if (VEC) {
-            a = *reinterpret_cast<const float4*>(src);
-        } else {
-            float* pa = reinterpret_cast<float*>(&a);
+        float* pa = reinterpret_cast<float*>(&a);
 #pragma unroll
-            for (int j = 0; j < 4; j++)
-                if (ch + j < Cin) pa[j] = src[j];
-        }
+        for (int j = 0; j < 4; j++)
+            if (ch + j < Cin) pa[j] = src[j];
     }
     return a;
 }
@@ -137,34 +133,6 @@ struct ConvPF {
     static constexpr int value = NCBW == 1 ? CONV_PF1 : (NCBW == 2 ? CONV_PF2 : CONV_PF3);
 };
 
-struct StepIter {
-    uint32_t m;  // offsets not yet visited
-    int k, c, nch;
-    __device__ __forceinline__ void init(uint32_t mask, int nch_) {
-        nch = nch_;
-        c = 0;
-        if (mask) {
-            k = __builtin_ctz(mask);
-            m = mask & (mask - 1);
-        } else {
-            k = -1;
-            m = 0;
-        }
-    }
-    __device__ __forceinline__ void next() {
-        if (k < 0) return;
-        if (++c == nch) {
-            c = 0;
-            if (m) {
-                k = __builtin_ctz(m);
-                m &= m - 1;
-            } else {
-                k = -1;
-            }
-        }
-    }
-};
-
 template <int NCBW, int SW, bool VEC>
 __global__ CONV_WPE_ATTR __launch_bounds__(SW > 8 ? 1024 : 256, (SW <= 8 && NCBW <= 2) ? 5 : 1) void k_conv_os(const float* __restrict__ in, const float4* __restrict__ Wp,
                                                  const int32_t* __restrict__ nbr, const uint32_t* __restrict__ gmask,
@@ -188,13 +156,9 @@ __global__ CONV_WPE_ATTR __launch_bounds__(SW > 8 ? 1024 : 256, (SW <= 8 && NCBW
     const int first = SPLIT ? blockIdx.x : ((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
     const int stride = SPLIT ? gridDim.x : ((gridDim.x * blockDim.x) >> 6);
     int* idx_l = s_idx[w];
-    // VEC path: gathers and weight loads go through buffer descriptors -- a 32-bit per-lane offset instead of
-    // 64-bit pointer arithmetic, a scalar offset for the (uniform) weight block, and the hardware range
-    // check turns "missing neighbour" (offset 0xffffffff) into zeros without a branch
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc((void*)in, 0, (int)in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w =
-        __builtin_amdgcn_make_buffer_rsrc((void*)Wp, 0, K * NCH * NCB * 1024, 0x00020000);
+    // VEC path: gathers and weight loads go through buffer descriptors (gf_buffer_rsrc)
+    const __amdgpu_buffer_rsrc_t rs_in = gf_buffer_rsrc(in, (int)in_bytes);
+    const __amdgpu_buffer_rsrc_t rs_w = gf_buffer_rsrc(Wp, K * NCH * NCB * 1024);
     const unsigned rowbytes = (unsigned)Cin * 4u;
     const float* sc_l = nullptr;
     const float* sh_l = nullptr;
@@ -330,21 +294,17 @@ __global__ CONV_WPE_ATTR __launch_bounds__(SW > 8 ? 1024 : 256, (SW <= 8 && NCBW
                     chv[j] = it.c * 16 + 4 * q;
                     if (VEC) {
                         const unsigned voff = present[j] ? (unsigned)idx * rowbytes + (unsigned)chv[j] * 4u : 0xffffffffu;
-                        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs_in, voff, 0, 0);
-                        a[j] = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]),
-                                           __uint_as_float(v[3]));
+                        a[j] = gf_as_float4(__builtin_amdgcn_raw_buffer_load_b128(rs_in, voff, 0, 0));
                     } else {
-                        a[j] = load_a<VEC>(in, idx, Cin, chv[j]);
+                        a[j] = load_a(in, idx, Cin, chv[j]);
                     }
                     if (VEC) {
                         const unsigned wblk = (unsigned)((it.k * NCH + it.c) * NCB + cb0);
 #pragma unroll
                         for (int cb = 0; cb < NCBW; cb++) {
                             // blocks past NCB fall outside the descriptor range and read as zeros
-                            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(
-                                rs_w, (unsigned)lane * 16u, (cb0 + cb < NCB) ? (wblk + cb) * 1024u : 0xfffffff0u, 0);
-                            b[j][cb] = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]),
-                                                   __uint_as_float(v[3]));
+                            b[j][cb] = gf_as_float4(__builtin_amdgcn_raw_buffer_load_b128(
+                                rs_w, (unsigned)lane * 16u, (cb0 + cb < NCB) ? (wblk + cb) * 1024u : 0xfffffff0u, 0));
                         }
                     } else {
 #pragma unroll
@@ -385,14 +345,7 @@ __global__ CONV_WPE_ATTR __launch_bounds__(SW > 8 ? 1024 : 256, (SW <= 8 && NCBW
                 if ((cb % NSW) != w) continue;
                 float4 t[NSW / 4 > 0 ? NSW / 4 : 1];
 #pragma unroll
-                for (int e = 0; e < NSW / 4; e++) {
-                    const float4 p0 = s_red[((4 * e + 0) * NCBW + cb) * 64 + lane];
-                    const float4 p1 = s_red[((4 * e + 1) * NCBW + cb) * 64 + lane];
-                    const float4 p2 = s_red[((4 * e + 2) * NCBW + cb) * 64 + lane];
-                    const float4 p3 = s_red[((4 * e + 3) * NCBW + cb) * 64 + lane];
-                    t[e] = make_float4((p0.x + p1.x) + (p2.x + p3.x), (p0.y + p1.y) + (p2.y + p3.y),
-                                       (p0.z + p1.z) + (p2.z + p3.z), (p0.w + p1.w) + (p2.w + p3.w));
-                }
+                for (int e = 0; e < NSW / 4; e++) t[e] = gf_lds_sum4(&s_red[(4 * e * NCBW + cb) * 64 + lane], NCBW * 64);
                 float4 sum = t[0];
 #pragma unroll
                 for (int e = 1; e < NSW / 4; e++)
@@ -438,6 +391,8 @@ __global__ CONV_WPE_ATTR __launch_bounds__(SW > 8 ? 1024 : 256, (SW <= 8 && NCBW
                            // batches of it cost every flat launch ~1 us (8.6 -> 9.6 us at level 5, PMC of round 4)
 // One convolution of the flat form.  `in2` (optional): the input rows are the CONCATENATION (in[:, :Cin1], in2[:, :Cin - Cin1])
 // -- the skip concatenation of UBlock.forward (geoformer_modules.py:116) read in place, Cin1 a multiple of 16.
+// (The only caller passes no `in2`, but the struct, the routine and the second-input path stay: the compiler cannot prove
+// that path dead, and folding them into the kernel changes k_conv_flat's machine code.)
 struct FlatOp {
     const float* in;
     const float* in2;
@@ -447,12 +402,10 @@ struct FlatOp {
     float* out;
     int K, M_out, ld, Cin, Cin1, Cout, NCH, NCB;
     unsigned in_bytes, in2_bytes;
-    int items, pad_;
 };
 template <int MAXB_>
 __device__ __forceinline__ void conv_flat_item(const FlatOp& A, int item, float4* s_red, float (*s_aff)[CONV_MAX_CIN]) {
     constexpr int PF = FLAT_PF, MAXB = MAXB_;
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     const float* __restrict__ in = A.in;
     const int K = A.K, M_out = A.M_out, ld = A.ld, Cin = A.Cin, Cout = A.Cout, NCH = A.NCH, NCB = A.NCB;
     const int32_t* __restrict__ nbr = A.nbr;
@@ -471,10 +424,9 @@ __device__ __forceinline__ void conv_flat_item(const FlatOp& A, int item, float4
     const int nsteps = K * NCH;
     const bool two = A.in2 != nullptr;
     const int nch1 = two ? A.Cin1 / 16 : NCH;  // chunks that come from `in`
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc((void*)in, 0, (int)A.in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_in2 =
-        __builtin_amdgcn_make_buffer_rsrc((void*)(two ? A.in2 : in), 0, (int)(two ? A.in2_bytes : A.in_bytes), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)A.Wp, 0, K * NCH * NCB * 1024, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = gf_buffer_rsrc(in, (int)A.in_bytes);
+    const __amdgpu_buffer_rsrc_t rs_in2 = gf_buffer_rsrc(two ? A.in2 : in, (int)(two ? A.in2_bytes : A.in_bytes));
+    const __amdgpu_buffer_rsrc_t rs_w = gf_buffer_rsrc(A.Wp, K * NCH * NCB * 1024);
     const unsigned rowbytes = (unsigned)(two ? A.Cin1 : Cin) * 4u, rowbytes2 = (unsigned)(Cin - (two ? A.Cin1 : 0)) * 4u;
     const unsigned inv_nch = (65536u + (unsigned)NCH - 1u) / (unsigned)NCH;  // s / NCH for s < 4096, NCH <= 16
 
@@ -521,8 +473,7 @@ __device__ __forceinline__ void conv_flat_item(const FlatOp& A, int item, float4
             const int e = bt * PF + j;
             const unsigned wblk = (unsigned)((kk[e] * NCH + cc[e]) * NCB + cb);
             // (a step past the wave's last one restates that one's block: loaded, never multiplied)
-            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs_w, (unsigned)lane * 16u, wblk * 1024u, 0);
-            b[bt & 1][j] = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
+            b[bt & 1][j] = gf_as_float4(__builtin_amdgcn_raw_buffer_load_b128(rs_w, (unsigned)lane * 16u, wblk * 1024u, 0));
         }
     };
     auto issue_a = [&](int bt) {  // gathers of batch bt (a missing neighbour is out of the descriptor's range: zeros)
@@ -537,7 +488,7 @@ __device__ __forceinline__ void conv_flat_item(const FlatOp& A, int item, float4
                 const unsigned voff = idx[e] >= 0 ? (unsigned)idx[e] * rowbytes2 + (unsigned)((cc[e] - nch1) * 64 + q * 16) : 0xffffffffu;
                 v = __builtin_amdgcn_raw_buffer_load_b128(rs_in2, voff, 0, 0);
             }
-            a[bt & 1][j] = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
+            a[bt & 1][j] = gf_as_float4(v);
         }
     };
     const int nb = w < nsteps ? ((nsteps - w + 15) / 16 + PF - 1) / PF : 0;  // batches of this wave (uniform)
@@ -585,16 +536,9 @@ __device__ __forceinline__ void conv_flat_item(const FlatOp& A, int item, float4
     // fixed-order sum over the sixteen waves; C/D layout: col = lane & 15, row = (lane >> 4) * 4 + j
     float4 t[4];
 #pragma unroll
-    for (int e = 0; e < 4; e++) {
-        const float4 p0 = s_red[(4 * e + 0) * 64 + lane];
-        const float4 p1 = s_red[(4 * e + 1) * 64 + lane];
-        const float4 p2 = s_red[(4 * e + 2) * 64 + lane];
-        const float4 p3 = s_red[(4 * e + 3) * 64 + lane];
-        t[e] = make_float4((p0.x + p1.x) + (p2.x + p3.x), (p0.y + p1.y) + (p2.y + p3.y), (p0.z + p1.z) + (p2.z + p3.z),
-                           (p0.w + p1.w) + (p2.w + p3.w));
-    }
-    const float v[4] = {(t[0].x + t[1].x) + (t[2].x + t[3].x), (t[0].y + t[1].y) + (t[2].y + t[3].y),
-                        (t[0].z + t[1].z) + (t[2].z + t[3].z), (t[0].w + t[1].w) + (t[2].w + t[3].w)};
+    for (int e = 0; e < 4; e++) t[e] = gf_lds_sum4(&s_red[4 * e * 64 + lane], 64);
+    const float4 sum = gf_sum4(t[0], t[1], t[2], t[3]);
+    const float v[4] = {sum.x, sum.y, sum.z, sum.w};
     if (col < Cout) {
 #pragma unroll
         for (int j = 0; j < 4; j++) {
@@ -619,7 +563,7 @@ __global__ __launch_bounds__(1024, 1) void k_conv_flat(const float* __restrict__
     __shared__ float4 s_red[16 * 64];
     __shared__ __attribute__((aligned(16))) float s_aff[2][CONV_MAX_CIN];
     const FlatOp A{in, nullptr, Wp, nbr, in_scale, in_shift, residual, out_scale, out_shift, out, K, M_out, ld, Cin, Cin, Cout,
-                   NCH, NCB, in_bytes, 0u, 0, 0};
+                   NCH, NCB, in_bytes, 0u};
     conv_flat_item<MAXB_>(A, (int)blockIdx.x, s_red, s_aff);
 }
 
@@ -634,6 +578,33 @@ __global__ __launch_bounds__(1024, 1) void k_conv_flat(const float* __restrict__
 #define CONV_PAIR_PF 2
 #endif
 #define CONV_PAIR_MISSING 0xfffff000u
+struct StepIter {
+    uint32_t m;  // offsets not yet visited
+    int k, c, nch;
+    __device__ __forceinline__ void init(uint32_t mask, int nch_) {
+        nch = nch_;
+        c = 0;
+        if (mask) {
+            k = __builtin_ctz(mask);
+            m = mask & (mask - 1);
+        } else {
+            k = -1;
+            m = 0;
+        }
+    }
+    __device__ __forceinline__ void next() {
+        if (k < 0) return;
+        if (++c == nch) {
+            c = 0;
+            if (m) {
+                k = __builtin_ctz(m);
+                m &= m - 1;
+            } else {
+                k = -1;
+            }
+        }
+    }
+};
 template <bool AFF>
 __global__ __launch_bounds__(256, 5) void k_conv_pair(const float* __restrict__ in, const float4* __restrict__ Wp,
                                                       const int32_t* __restrict__ nbr,
@@ -655,9 +626,8 @@ __global__ __launch_bounds__(256, 5) void k_conv_pair(const float* __restrict__ 
     const int first = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int stride = (gridDim.x * blockDim.x) >> 6;
     unsigned* off_l = s_off[w];
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc((void*)in, 0, (int)in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)Wp, 0, K * NCH * 1024, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = gf_buffer_rsrc(in, (int)in_bytes);
+    const __amdgpu_buffer_rsrc_t rs_w = gf_buffer_rsrc(Wp, K * NCH * 1024);
     const unsigned rowbytes = (unsigned)Cin * 4u;
     const unsigned lane_ch = 16u * (unsigned)q;  // byte offset of this lane's 4 channels inside a 16-channel chunk
     if (AFF) {
@@ -731,6 +701,7 @@ __global__ __launch_bounds__(256, 5) void k_conv_pair(const float* __restrict__ 
 #pragma unroll
             for (int j = 0; j < PF; j++) {
                 if (j < nv) {
+                    // (written out: through gf_as_float4 this kernel's code comes out differently)
                     float4 a0 = make_float4(__uint_as_float(x0[j][0]), __uint_as_float(x0[j][1]),
                                             __uint_as_float(x0[j][2]), __uint_as_float(x0[j][3]));
                     float4 a1 = make_float4(__uint_as_float(x1[j][0]), __uint_as_float(x1[j][1]),
@@ -804,15 +775,13 @@ __global__ __launch_bounds__(256) void k_conv_g16(const float* __restrict__ in, 
     constexpr int PHA = NCH == 1 ? GF_STEP_PHA : CONV_G16_PHA2;
     constexpr unsigned ROWB = NCH * 64u;  // bytes per input row
     constexpr int SHIFT = NCH == 1 ? 6 : 7;
-    extern __shared__ __attribute__((aligned(16))) float4 s_w[];
     __shared__ __attribute__((aligned(16))) float s_aff[2][NCH * 16];
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r = lane & 15, q = lane >> 4;
     const int ngroups = (M_out + 15) >> 4;
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc((void*)in, 0, (int)in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)Wp, 0, K * NCH * 1024, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = gf_buffer_rsrc(in, (int)in_bytes);
+    const __amdgpu_buffer_rsrc_t rs_w = gf_buffer_rsrc(Wp, K * NCH * 1024);
     if (LDSW) {
         const int total = K * NCH * 64;
         for (int t = threadIdx.x; t < total; t += 256) s_w[t] = Wp[t];
@@ -848,6 +817,23 @@ __global__ __launch_bounds__(256) void k_conv_g16(const float* __restrict__ in, 
         if (RES && row < M_out) resv = *reinterpret_cast<const float4*>(residual + (size_t)row * 16 + 4 * q);
         f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
 
+        // one step: the lowest offset still in m, its weights, the gathered rows `av` of neighbour `idx` (-1: missing)
+        auto step = [&](const u32x4 (&av)[NCH], int idx) {
+            const int k = __builtin_ctz(m);
+            m &= m - 1;
+            const bool present = idx >= 0;
+#pragma unroll
+            for (int c = 0; c < NCH; c++) {
+                float4 wv;
+                gf_conv_w<LDSW>(wv, rs_w, k * NCH + c, lane);
+                float4 x = gf_as_float4(av[c]);
+                if (AFF) x = gf_act_present(x, present, sc[c], sh[c]);
+                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wv.x, x.x, acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wv.y, x.y, acc1, 0, 0, 0);
+                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wv.z, x.z, acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wv.w, x.w, acc1, 0, 0, 0);
+            }
+        };
         // ---- phase A: the first PHA blocks, every gather in flight at once ----
         u32x4 a[PHA * 4][NCH];
 #pragma unroll
@@ -858,37 +844,8 @@ __global__ __launch_bounds__(256) void k_conv_g16(const float* __restrict__ in, 
             for (int c = 0; c < NCH; c++) a[s][c] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, voff, c * 64, 0);
         }
 #pragma unroll
-        for (int s = 0; s < PHA * 4; s++) {
-            if (s < n) {
-                const int k = __builtin_ctz(m);
-                m &= m - 1;
-                const bool present = reinterpret_cast<const int*>(&ib[s >> 2])[s & 3] >= 0;
-#pragma unroll
-                for (int c = 0; c < NCH; c++) {
-                    float4 wv;
-                    if (LDSW) {
-                        wv = s_w[(k * NCH + c) * 64 + lane];
-                    } else {
-                        const u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(rs_w, (unsigned)lane * 16u,
-                                                                              (unsigned)(k * NCH + c) * 1024u, 0);
-                        wv = make_float4(__uint_as_float(t[0]), __uint_as_float(t[1]), __uint_as_float(t[2]),
-                                         __uint_as_float(t[3]));
-                    }
-                    float4 x = make_float4(__uint_as_float(a[s][c][0]), __uint_as_float(a[s][c][1]),
-                                           __uint_as_float(a[s][c][2]), __uint_as_float(a[s][c][3]));
-                    if (AFF) {
-                        x.x = present ? fmaxf(fmaf(x.x, sc[c].x, sh[c].x), 0.f) : 0.f;
-                        x.y = present ? fmaxf(fmaf(x.y, sc[c].y, sh[c].y), 0.f) : 0.f;
-                        x.z = present ? fmaxf(fmaf(x.z, sc[c].z, sh[c].z), 0.f) : 0.f;
-                        x.w = present ? fmaxf(fmaf(x.w, sc[c].w, sh[c].w), 0.f) : 0.f;
-                    }
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wv.x, x.x, acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wv.y, x.y, acc1, 0, 0, 0);
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wv.z, x.z, acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wv.w, x.w, acc1, 0, 0, 0);
-                }
-            }
-        }
+        for (int s = 0; s < PHA * 4; s++)
+            if (s < n) step(a[s], reinterpret_cast<const int*>(&ib[s >> 2])[s & 3]);
         // ---- phase B: groups with more than 4*PHA present offsets, one block at a time ----
         for (int b = PHA; b * 4 < n; b++) {
             const int4 jb = rec[b * 16];
@@ -900,37 +857,8 @@ __global__ __launch_bounds__(256) void k_conv_g16(const float* __restrict__ in, 
                 for (int c = 0; c < NCH; c++) e[j][c] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, voff, c * 64, 0);
             }
 #pragma unroll
-            for (int j = 0; j < 4; j++) {
-                if (b * 4 + j < n) {
-                    const int k = __builtin_ctz(m);
-                    m &= m - 1;
-                    const bool present = reinterpret_cast<const int*>(&jb)[j] >= 0;
-#pragma unroll
-                    for (int c = 0; c < NCH; c++) {
-                        float4 wv;
-                        if (LDSW) {
-                            wv = s_w[(k * NCH + c) * 64 + lane];
-                        } else {
-                            const u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(rs_w, (unsigned)lane * 16u,
-                                                                                  (unsigned)(k * NCH + c) * 1024u, 0);
-                            wv = make_float4(__uint_as_float(t[0]), __uint_as_float(t[1]), __uint_as_float(t[2]),
-                                             __uint_as_float(t[3]));
-                        }
-                        float4 x = make_float4(__uint_as_float(e[j][c][0]), __uint_as_float(e[j][c][1]),
-                                               __uint_as_float(e[j][c][2]), __uint_as_float(e[j][c][3]));
-                        if (AFF) {
-                            x.x = present ? fmaxf(fmaf(x.x, sc[c].x, sh[c].x), 0.f) : 0.f;
-                            x.y = present ? fmaxf(fmaf(x.y, sc[c].y, sh[c].y), 0.f) : 0.f;
-                            x.z = present ? fmaxf(fmaf(x.z, sc[c].z, sh[c].z), 0.f) : 0.f;
-                            x.w = present ? fmaxf(fmaf(x.w, sc[c].w, sh[c].w), 0.f) : 0.f;
-                        }
-                        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wv.x, x.x, acc0, 0, 0, 0);
-                        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wv.y, x.y, acc1, 0, 0, 0);
-                        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wv.z, x.z, acc0, 0, 0, 0);
-                        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wv.w, x.w, acc1, 0, 0, 0);
-                    }
-                }
-            }
+            for (int j = 0; j < 4; j++)
+                if (b * 4 + j < n) step(e[j], reinterpret_cast<const int*>(&jb)[j]);
         }
         // transposed C/D layout: lane (r, q) holds channels 4q..4q+3 of row g*16 + r
         if (row < M_out) {
@@ -941,8 +869,7 @@ __global__ __launch_bounds__(256) void k_conv_g16(const float* __restrict__ in, 
             if (out_scale) {  // epilogue activation: the consumer's BatchNorm + ReLU, once per output element
                 const float4 os = *reinterpret_cast<const float4*>(out_scale + 4 * q);
                 const float4 ot = *reinterpret_cast<const float4*>(out_shift + 4 * q);
-                v.x = fmaxf(fmaf(v.x, os.x, ot.x), 0.f); v.y = fmaxf(fmaf(v.y, os.y, ot.y), 0.f);
-                v.z = fmaxf(fmaf(v.z, os.z, ot.z), 0.f); v.w = fmaxf(fmaf(v.w, os.w, ot.w), 0.f);
+                v = gf_relu_affine(v, os, ot);
             }
             *reinterpret_cast<float4*>(out + (size_t)row * 16 + 4 * q) = v;
         }
@@ -981,16 +908,13 @@ __global__ __launch_bounds__(64 * WPB, CONV_G16P_WAVES) void k_conv_g16p(const f
     constexpr int PHA = NCH == 1 ? GF_STEP_PHA : CONV_G16_PHA2;
     constexpr int NS = PHA * 4;  // steps of the pipelined part
     constexpr int SHIFT = NCH == 1 ? 6 : 7;
-    extern __shared__ __attribute__((aligned(16))) float4 s_w[];
     __shared__ __attribute__((aligned(16))) float s_aff[2][NCH * 16];
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r = lane & 15, q = lane >> 4;
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc((void*)in, 0, (int)in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)Wp, 0, K * NCH * 1024, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_st =
-        __builtin_amdgcn_make_buffer_rsrc((void*)steps_raw, 0, (int)steps_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = gf_buffer_rsrc(in, (int)in_bytes);
+    const __amdgpu_buffer_rsrc_t rs_w = gf_buffer_rsrc(Wp, K * NCH * 1024);
+    const __amdgpu_buffer_rsrc_t rs_st = gf_buffer_rsrc(steps_raw, (int)steps_bytes);
     const int cw = blockIdx.x * WPB + w;
     // the table's count and this wave's two boundaries as three INDEPENDENT loads (count -> boundaries was one more
     // dependent round trip in front of the first index load; the table's tail is sized for GF_CONV_CHUNKS_MAX entries)
@@ -1050,9 +974,7 @@ __global__ __launch_bounds__(64 * WPB, CONV_G16P_WAVES) void k_conv_g16p(const f
 #pragma unroll
             for (int j = 0; j < WST; j++) {
                 const int t = base + j * T + (int)threadIdx.x;
-                if (t < total)
-                    s_w[t] = make_float4(__uint_as_float(tmp[j][0]), __uint_as_float(tmp[j][1]), __uint_as_float(tmp[j][2]),
-                                         __uint_as_float(tmp[j][3]));
+                if (t < total) s_w[t] = gf_as_float4(tmp[j]);
             }
         }
     }
@@ -1095,28 +1017,13 @@ __global__ __launch_bounds__(64 * WPB, CONV_G16P_WAVES) void k_conv_g16p(const f
         float4 wq[NCH], wn[NCH];
         auto fetch_w = [&](float4 (&dst)[NCH], int k) {
 #pragma unroll
-            for (int c = 0; c < NCH; c++) {
-                if (LDSW) {
-                    dst[c] = s_w[(k * NCH + c) * 64 + lane];
-                } else {
-                    const u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(rs_w, (unsigned)lane * 16u,
-                                                                          (unsigned)(k * NCH + c) * 1024u, 0);
-                    dst[c] = make_float4(__uint_as_float(t[0]), __uint_as_float(t[1]), __uint_as_float(t[2]),
-                                         __uint_as_float(t[3]));
-                }
-            }
+            for (int c = 0; c < NCH; c++) gf_conv_w<LDSW>(dst[c], rs_w, k * NCH + c, lane);
         };
         auto mfma_step = [&](const u32x4 (&av)[NCH], const float4 (&wv)[NCH], bool present) {
 #pragma unroll
             for (int c = 0; c < NCH; c++) {
-                float4 x = make_float4(__uint_as_float(av[c][0]), __uint_as_float(av[c][1]), __uint_as_float(av[c][2]),
-                                       __uint_as_float(av[c][3]));
-                if (AFF) {
-                    x.x = present ? fmaxf(fmaf(x.x, sc[c].x, sh[c].x), 0.f) : 0.f;
-                    x.y = present ? fmaxf(fmaf(x.y, sc[c].y, sh[c].y), 0.f) : 0.f;
-                    x.z = present ? fmaxf(fmaf(x.z, sc[c].z, sh[c].z), 0.f) : 0.f;
-                    x.w = present ? fmaxf(fmaf(x.w, sc[c].w, sh[c].w), 0.f) : 0.f;
-                }
+                float4 x = gf_as_float4(av[c]);
+                if (AFF) x = gf_act_present(x, present, sc[c], sh[c]);
                 acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[c].x, x.x, acc0, 0, 0, 0);
                 acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[c].y, x.y, acc1, 0, 0, 0);
                 acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[c].z, x.z, acc0, 0, 0, 0);
@@ -1179,8 +1086,7 @@ __global__ __launch_bounds__(64 * WPB, CONV_G16P_WAVES) void k_conv_g16p(const f
                     // instead of one per GATHERED element (6-10 x more) in that convolution's prologue
                     *reinterpret_cast<float4*>(out + (size_t)row * 16 + 4 * q) = v;
                 }
-                v.x = fmaxf(fmaf(v.x, os.x, ot.x), 0.f); v.y = fmaxf(fmaf(v.y, os.y, ot.y), 0.f);
-                v.z = fmaxf(fmaf(v.z, os.z, ot.z), 0.f); v.w = fmaxf(fmaf(v.w, os.w, ot.w), 0.f);
+                v = gf_relu_affine(v, os, ot);
             }
             *reinterpret_cast<float4*>((out2 ? out2 : out) + (size_t)row * 16 + 4 * q) = v;
         }

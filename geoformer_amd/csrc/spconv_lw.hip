@@ -22,8 +22,7 @@
 // accumulators per column block.  More input chunks than fit are passes over channel windows (residual = the output).
 #include "common.h"
 #include "geoformer_hip_dev.h"
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+#include "conv_tile.h"
 
 struct LwArgs {
     const float* in;        // first channel of the window
@@ -57,7 +56,6 @@ __global__ __launch_bounds__(64 * WPB) void k_conv_lw(const LwArgs A) {
     constexpr int WPS = WPB / 4;     // waves per SIMD: they share one bin of the table, round j to wave j % WPS
     static_assert(NCB <= 2, "residual requests are written for one or two column blocks");
     static_assert(WPB % 4 == 0, "a workgroup is whole SIMD rounds");
-    extern __shared__ __attribute__((aligned(16))) float4 s_w[];
 #ifdef LW_TRACE
     const unsigned long long tr0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -74,12 +72,11 @@ __global__ __launch_bounds__(64 * WPB) void k_conv_lw(const LwArgs A) {
         if (j < rounds && bin < nbins)
             dsc = reinterpret_cast<const int4*>(flat + gf_flat_desc_at(ngroups))[(size_t)j * nbins + bin];
     }
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc((void*)A.in, 0, (int)A.in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_st =
-        __builtin_amdgcn_make_buffer_rsrc((void*)(flat + gf_flat_steps_at(ngroups, nbins)), 0, (int)A.steps_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = gf_buffer_rsrc(A.in, (int)A.in_bytes);
+    const __amdgpu_buffer_rsrc_t rs_st = gf_buffer_rsrc(flat + gf_flat_steps_at(ngroups, nbins), (int)A.steps_bytes);
     const unsigned out_bytes = (unsigned)A.M_out * (unsigned)A.Cout * 4u;
-    const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc((void*)A.out, 0, (int)out_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_out2 = __builtin_amdgcn_make_buffer_rsrc((void*)(A.out2 ? A.out2 : A.out), 0, (int)out_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_out = gf_buffer_rsrc(A.out, (int)out_bytes);
+    const __amdgpu_buffer_rsrc_t rs_out2 = gf_buffer_rsrc(A.out2 ? A.out2 : A.out, (int)out_bytes);
     const unsigned row_bytes = A.row_bytes;
     const unsigned lane_c = 16u * (unsigned)q;
     const unsigned lane_r = 4u * (unsigned)r;
@@ -224,6 +221,7 @@ __global__ __launch_bounds__(64 * WPB) void k_conv_lw(const LwArgs A) {
                     const u32x4 raw = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
                     __builtin_amdgcn_raw_buffer_store_b128(raw, rs_out, ooff, cb * 64, 0);
                 }
+                // (written out: through gf_relu_affine this kernel's code comes out differently)
                 v.x = fmaxf(fmaf(v.x, os[cb].x, ot[cb].x), 0.f); v.y = fmaxf(fmaf(v.y, os[cb].y, ot[cb].y), 0.f);
                 v.z = fmaxf(fmaf(v.z, os[cb].z, ot[cb].z), 0.f); v.w = fmaxf(fmaf(v.w, os[cb].w, ot[cb].w), 0.f);
             }
@@ -277,9 +275,8 @@ __global__ __launch_bounds__(64 * WPB) void k_conv_lw(const LwArgs A) {
                 fetch_w(wv[(d + 1) & 1], kc);
 #pragma unroll
                 for (int c = 0; c < NCH; c++) {
-                    float4 x = make_float4(__uint_as_float(ring[d][c][0]), __uint_as_float(ring[d][c][1]),
-                                           __uint_as_float(ring[d][c][2]), __uint_as_float(ring[d][c][3]));
-                    if (AFF) {
+                    float4 x = gf_as_float4(ring[d][c]);
+                    if (AFF) {  // (not gf_act_present: a missing row keeps the scale and drops the shift, max(0*sc + 0, 0))
                         const bool present = ((absent >> d) & 1u) == 0u;
                         x.x = fmaxf(fmaf(x.x, sc[c].x, present ? sh[c].x : 0.f), 0.f);
                         x.y = fmaxf(fmaf(x.y, sc[c].y, present ? sh[c].y : 0.f), 0.f);

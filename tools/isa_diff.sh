@@ -4,7 +4,8 @@
 # Compiles each source device-only to gfx950 assembly with the library's own flags (geoformer_amd/_build.py), once from
 # <parent-ref> (git archive into a temporary directory) and once from the working tree, drops the lines that hold the
 # per-compilation __hip_cuid_ symbol and compares.  The .amdhsa_* directives (registers, LDS, scratch) are part of the
-# text, so occupancy is covered.  Prints a verdict per file; exit status 1 if any file differs or fails to compile.
+# text, so occupancy is covered.  Prints a verdict per file, under a file that differs the kernels whose bodies differ
+# (needs c++filt); exit status 1 if any file differs or fails to compile.
 #   ISA_DIFF_KEEP=<dir>: keep the assembly there (<dir>/parent, <dir>/head) instead of a temporary directory
 #   ISA_DIFF_JOBS=<n>:   parallel compilations (default 6)
 set -u
@@ -34,6 +35,27 @@ for n in $names; do
     printf '%s\0%s\0%s\0' "$root" "$n" "$out/head/${n%.hip}.s"
 done | xargs -0 -n 3 -P "$jobs" bash -c 'asm "$0" "$1" "$2" || touch "$2.failed"'
 
+# The kernels of a file that differs, one line each: demangled name, lines before -> after, then the register / LDS /
+# scratch directives before -> after.  A kernel is its symbol's text from the `_Z...:` label to its .Lfunc_end (the
+# .amdhsa_* block lies in between), with the numbers of the local labels (.LBB, .Ltmp, .Lfunc_end) dropped.
+kernels_diff() {  # <parent.s> <head.s>
+    awk '
+        FNR == 1 { side++ }
+        /^_Z[A-Za-z0-9_.$]*:/ { sym = $1; sub(/:$/, "", sym); seen[sym]; next }
+        sym == "" { next }
+        /^\.Lfunc_end/ { sym = ""; next }
+        { l = $0; gsub(/\.L(BB|tmp|func_end)[0-9]+/, ".L", l); body[side, sym] = body[side, sym] l "\n"; n[side, sym]++ }
+        $1 ~ /^\.amdhsa_(next_free_[vs]gpr|accum_offset|(group|private)_segment_fixed_size)$/ { val[side, sym, $1] = $2 }
+        END {
+            split("next_free_vgpr accum_offset next_free_sgpr group_segment_fixed_size private_segment_fixed_size", key, " ")
+            for (s in seen) if (body[1, s] != body[2, s]) {
+                line = sprintf("    %s: %d -> %d lines;", s, n[1, s], n[2, s])
+                for (i = 1; i <= 5; i++) line = line sprintf(" %s %s -> %s%s", key[i], val[1, s, ".amdhsa_" key[i]], val[2, s, ".amdhsa_" key[i]], i < 5 ? "," : "")
+                print line
+            }
+        }' "$1" "$2" | c++filt -p | sort
+}
+
 bad=0
 for n in $names; do
     p=$out/parent/${n%.hip}.s; h=$out/head/${n%.hip}.s
@@ -43,6 +65,7 @@ for n in $names; do
         echo "identical  $n ($(wc -l < "$h") lines)"
     else
         echo "DIFFERENT  $n ($(diff "$p" "$h" | grep -c '^[<>]') differing lines of $(wc -l < "$h"))"; bad=1
+        kernels_diff "$p" "$h"
     fi
 done
 [ $bad -eq 0 ] && echo "same ISA in every file against $ref" || echo "ISA differs against $ref"
