@@ -15,8 +15,10 @@ A batch of raw scenes ([N, 8] = xyz, rgb, semantic label, instance label, as pre
 collated on the host (scene.collate_raw), uploaded and voxelised on the GPU one batch ahead (feeder.DeviceFeeder), and
 run through ONE eval forward with ``all_scenes=True``: every scene of the batch gets its proposals (the reference's
 forward keeps scene 0's only).  Matrix NMS of all scenes of the batch is one postprocess.matrix_nms_batched call, on the
-benchmark label ids of test.py:65-68 with final_score_thresh 0.5 (test.py:88-93).  A scene without proposals is left out
-of the evaluation, as test.py's ``continue`` does.
+benchmark label ids of test.py:65-68 with final_score_thresh 0.5 (test.py:88-93).  ``nms="greedy"`` takes the reference's
+other post-process instead (test.py:78-86): class-agnostic greedy NMS at ``cfg.TEST_NMS_THRESH``, one
+postprocess.greedy_nms_batched call per batch.  A scene without proposals is left out of the evaluation, as test.py's
+``continue`` does.
 """
 from __future__ import annotations
 
@@ -56,13 +58,19 @@ def collate_batches(raw_scenes, batch_size, spatial_shape=None, scale=50, full_s
 @torch.no_grad()
 def predict_batches(model, raw_scenes, batch_size, *, epoch=300, spatial_shape=None, nms_kernel="gaussian",
                     sigma=2.0, final_score_thresh=NMS_FINAL_SCORE, cvfold=None, reserve=True, device=None,
-                    semantic=None):
+                    semantic=None, nms="matrix", nms_thresh=None):
     """Yields (name, cls_final, scores_final, masks_final, pick) per scene, in input order.  raw_scenes: iterable of
     (name, raw [N, 8]).  The NMS categories are the benchmark label ids of the classes (evaluation.benchmark_label_ids
     with cvfold, default model.cfg.cvfold).  A scene without proposals yields ([], [], [], empty pick).  reserve: size
     the allocator for the largest batch first (GeoFormer.reserve_for with the batch's total points).  semantic: an
     evaluation.SemanticEvaluator that is given every batch's semantic scores, labels, offsets and scene names (one
-    launch on the forward's stream before the NMS, nothing read back); None: nothing is added to the loop."""
+    launch on the forward's stream before the NMS, nothing read back); None: nothing is added to the loop.  nms:
+    "matrix" (matrix NMS with nms_kernel / sigma / final_score_thresh) or "greedy" (class-agnostic greedy NMS at
+    nms_thresh, default model.cfg.TEST_NMS_THRESH; pick in pick order)."""
+    if nms not in ("matrix", "greedy"):
+        raise ValueError(f"predict_batches: nms must be 'matrix' or 'greedy', got {nms!r}")
+    if nms == "greedy" and nms_thresh is None:
+        nms_thresh = model.cfg.TEST_NMS_THRESH
     cvfold = model.cfg.cvfold if cvfold is None else cvfold
     dev = torch.device(device) if device is not None else next(model.parameters()).device
     model.eval()
@@ -78,9 +86,13 @@ def predict_batches(model, raw_scenes, batch_size, *, epoch=300, spatial_shape=N
             semantic.add_batch(out["semantic_scores"], batch["labels"], batch["offsets"], [n for n, _ in chunk],
                                offsets_host=host["offsets"])
         per = out.get("proposal_scores_per_scene") or [([], [], []) for _ in chunk]
-        labels = [evaluation.benchmark_label_ids(c, cvfold) if torch.is_tensor(c) else [] for c, _, _ in per]
-        picks = postprocess.matrix_nms_batched([m for _, _, m in per], [s for _, s, _ in per], labels,
-                                               kernel=nms_kernel, sigma=sigma, final_score_thresh=final_score_thresh)
+        if nms == "greedy":
+            picks = postprocess.greedy_nms_batched([m for _, _, m in per], [s for _, s, _ in per], nms_thresh)
+        else:
+            labels = [evaluation.benchmark_label_ids(c, cvfold) if torch.is_tensor(c) else [] for c, _, _ in per]
+            picks = postprocess.matrix_nms_batched([m for _, _, m in per], [s for _, s, _ in per], labels,
+                                                   kernel=nms_kernel, sigma=sigma,
+                                                   final_score_thresh=final_score_thresh)
         for (name, _), (cls, sc, masks), pick in zip(chunk, per, picks):
             yield name, cls, sc, masks, pick
 

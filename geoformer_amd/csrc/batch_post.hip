@@ -8,7 +8,9 @@
 //                      counts[b] x num_points[b] after the blocks of the scenes before it (offsets from the counts);
 //   k_bp_pack_bits /   grid (x, S): gf_mask_intersections' ballot packing and popcount pairs, one [n_b, n_b] block per
 //   k_bp_intersections scene;
-//   k_bp_matrix_nms    grid S: one workgroup per scene does the whole [n, n] algebra of matrix NMS in LDS.
+//   k_bp_matrix_nms    grid S: one workgroup per scene does the whole [n, n] algebra of matrix NMS in LDS;
+//   k_bp_greedy_nms /  grid S / 1: greedy NMS (util/utils_3d.py:76-93), one workgroup per scene walks the proposals in
+//   k_bp_greedy_ious   score order, one barrier per pick.
 #include "proposal_rows.h"
 
 #define BP_PROP_FIELDS GF_PROP_SCENE_FIELDS
@@ -309,5 +311,137 @@ extern "C" int gf_matrix_nms_batched(const long long* table, int S, const int32_
     hipLaunchKernelGGL(k_bp_matrix_nms, dim3(S), dim3(1024), 0, (hipStream_t)stream, table, inter, kernel, sigma,
                        final_score_thresh, picks, pick_counts);
     GF_CHECK_LAUNCH("gf_matrix_nms_batched");
+    return GF_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// Greedy NMS, one workgroup per scene (util/utils_3d.py:76-93).  Proposals ranked by score, descending, equal scores by
+// ascending index (the rule of k_bp_matrix_nms).  Walk the ranks: a rank still alive is picked and kills every later
+// rank j with iou[pick, j] > threshold (strict; the row is the pick; a NaN never kills; a dead rank kills nothing).
+// Thread j is rank j and keeps its own alive flag; the workgroup's view of the flags is one uint64 word per wave in LDS
+// (16 words = GF_NMS_MAX_N ranks).  Per PICK, not per rank: every thread finds the next alive rank from the words (dead
+// pivots cost nothing), the waves that still hold later ranks read their element of the pick's row, ballot the kills,
+// lane 0 clears them in the wave's word, one barrier.
+// The scan of the next iteration may overlap another wave's clears of that iteration.  That is harmless: pick q clears
+// only bits above q, bit q stays set, and the scan stops at the first set bit above the previous pick, which is q.
+// ------------------------------------------------------------------------------------
+template <bool FROM_INTER>
+__device__ __forceinline__ void bp_greedy_walk(const void* __restrict__ mat, const float* __restrict__ scores, int n,
+                                               float threshold, int32_t* __restrict__ out,
+                                               int32_t* __restrict__ count) {
+    __shared__ float s_score[BP_NMS_MAX_N], s_diag[BP_NMS_MAX_N];
+    __shared__ int s_ord[BP_NMS_MAX_N];
+    __shared__ unsigned long long s_alive[BP_NMS_MAX_N / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int32_t* inter = (const int32_t*)mat;
+    const float* ious = (const float*)mat;
+    // 1. rank = #(higher score, or equal score and lower index); slots a NaN leaves unwritten keep index 0 (in bounds)
+    if (tid < n) {
+        s_ord[tid] = 0;
+        s_score[tid] = scores[tid];
+    }
+    __syncthreads();
+    if (tid < n) {
+        const float si = s_score[tid];
+        int r = 0;
+        for (int j = 0; j < n; j++) {
+            const float sj = s_score[j];
+            r += (sj > si || (sj == si && j < tid)) ? 1 : 0;
+        }
+        if (r < n) s_ord[r] = tid;
+    }
+    __syncthreads();
+    bool alive = tid < n;
+    const int oj = alive ? s_ord[tid] : 0;
+    float dj = 0.f;
+    if (FROM_INTER) {
+        if (alive) dj = (float)inter[(size_t)oj * n + oj];
+        s_diag[tid] = dj;
+    }
+    {
+        const unsigned long long bal = __ballot(alive);
+        if (lane == 0) s_alive[wave] = bal;
+    }
+    __syncthreads();
+    // 2. the walk
+    int p = -1, cnt = 0;
+    while (true) {
+        int q = -1;
+        for (int w = (p + 1) >> 6; w < BP_NMS_MAX_N / 64; w++) {
+            unsigned long long m = s_alive[w];
+            if (w == ((p + 1) >> 6)) m &= ~0ull << ((p + 1) & 63);
+            if (m) {
+                q = w * 64 + __ffsll((long long)m) - 1;
+                break;
+            }
+        }
+        if (q < 0) break;  // (uniform: every thread read the same words, see above)
+        p = q;
+        const int op = s_ord[p];
+        if (tid == 0) out[cnt] = op;
+        cnt++;
+        if (wave * 64 + 63 > p) {  // wave-uniform: the wave holds ranks after the pick
+            bool kill = false;
+            if (alive && tid > p) {
+                float v;
+                if (FROM_INTER) {
+                    const float I = (float)inter[(size_t)op * n + oj];
+                    v = I / ((s_diag[p] + dj) - I);
+                } else {
+                    v = ious[(size_t)op * n + oj];
+                }
+                kill = v > threshold;
+            }
+            const unsigned long long bal = __ballot(kill);
+            alive = alive && !kill;
+            if (lane == 0 && bal) s_alive[wave] &= ~bal;
+        }
+        __syncthreads();
+    }
+    if (tid == 0) *count = cnt;
+}
+
+__global__ __launch_bounds__(1024) void k_bp_greedy_nms(const long long* __restrict__ table,
+                                                        const int32_t* __restrict__ inter_all, float threshold,
+                                                        int32_t* __restrict__ picks,
+                                                        int32_t* __restrict__ pick_counts) {
+    const long long* t = table + (size_t)blockIdx.x * BP_NMS_FIELDS;
+    const int n = (int)t[2];
+    if (n <= 0 || n > BP_NMS_MAX_N) {  // (the host rejects n > BP_NMS_MAX_N before the launch)
+        if (threadIdx.x == 0) pick_counts[blockIdx.x] = 0;
+        return;
+    }
+    bp_greedy_walk<true>(inter_all + t[4], (const float*)t[5], n, threshold, picks + t[7], pick_counts + blockIdx.x);
+}
+
+__global__ __launch_bounds__(1024) void k_bp_greedy_ious(const float* __restrict__ ious,
+                                                         const float* __restrict__ scores, int n, float threshold,
+                                                         int32_t* __restrict__ picks, int32_t* __restrict__ pick_count) {
+    bp_greedy_walk<false>(ious, scores, n, threshold, picks, pick_count);
+}
+
+extern "C" int gf_greedy_nms_batched(const long long* table, int S, const int32_t* inter, float threshold,
+                                     int32_t* picks, int32_t* pick_counts, void* stream) {
+    GF_CHECK_ARG(table && inter && picks && pick_counts, "gf_greedy_nms_batched: null argument");
+    GF_CHECK_ARG(S >= 0, "gf_greedy_nms_batched: bad arguments S=%d", S);
+    if (S == 0) return GF_OK;
+    hipLaunchKernelGGL(k_bp_greedy_nms, dim3(S), dim3(1024), 0, (hipStream_t)stream, table, inter, threshold, picks,
+                       pick_counts);
+    GF_CHECK_LAUNCH("gf_greedy_nms_batched");
+    return GF_OK;
+}
+
+extern "C" int gf_greedy_nms_ious(const float* ious, const float* scores, int n, float threshold, int32_t* picks,
+                                  int32_t* pick_count, void* stream) {
+    GF_CHECK_ARG(pick_count && n >= 0 && n <= BP_NMS_MAX_N, "gf_greedy_nms_ious: bad arguments n=%d (at most %d)", n,
+                 BP_NMS_MAX_N);
+    GF_CHECK_ARG(n == 0 || (ious && scores && picks), "gf_greedy_nms_ious: null argument");
+    if (n == 0) {
+        GF_TRY(hipMemsetAsync(pick_count, 0, sizeof(int32_t), (hipStream_t)stream));
+        return GF_OK;
+    }
+    hipLaunchKernelGGL(k_bp_greedy_ious, dim3(1), dim3(1024), 0, (hipStream_t)stream, ious, scores, n, threshold, picks,
+                       pick_count);
+    GF_CHECK_LAUNCH("gf_greedy_nms_ious");
     return GF_OK;
 }

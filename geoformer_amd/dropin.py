@@ -7,6 +7,10 @@
     pointnet2, pointnet2._ext       <- lib/pointnet2/_ext_src/src/bindings.cpp:8-21
     faiss, faiss.contrib.torch_utils<- geoformer.py:8-9,172-177; geodesic_utils.py:11-24
 
+``install(model=True)`` goes one level up and also registers the fused model, the device criteria and the native NMS
+(geoformer_amd.reference_names) as model.geoformer.geoformer, model.geoformer.geoformer_fs, criterion, criterion_fs and
+util.utils_3d: the reference's train.py / test.py / train_fs.py / test_fs.py then run this package's classes unchanged.
+
 Same function names, argument order and in-place/return conventions as the pybind modules, so
 ``lib/pointgroup_ops/functions/pointgroup_ops.py`` and ``lib/pointnet2/pointnet2_utils.py`` work on top
 unchanged.  Bad inputs raise ``RuntimeError`` (the reference's natives ``assert``/``exit(-1)``).
@@ -15,6 +19,7 @@ bfs_cluster, three_nn / three_interpolate) are bound as well, with the native ar
 """
 from __future__ import annotations
 
+import os
 import sys
 import types
 
@@ -247,8 +252,64 @@ class GpuIndexFlatL2:
         return D, I
 
 
-def install():
-    """Register the mirrors under the reference's import names.  Idempotent."""
+class _LatePath(list):
+    """``__path__`` of a stand-in package: the directories of that name on sys.path, looked up at every import, so a
+    driver tree put on sys.path after install(model=True) still serves its own submodules (util.config, ...)."""
+
+    def __init__(self, pkg):
+        super().__init__()
+        self._rel = pkg.replace(".", os.sep)
+
+    def __iter__(self):
+        dirs = (os.path.join(p or os.curdir, self._rel) for p in sys.path if isinstance(p, str))
+        return iter([d for d in dirs if os.path.isdir(d)])
+
+
+def _install_model_names():
+    """The second depth of install(): reference_names' modules under the reference's import names."""
+    import importlib
+
+    from . import reference_names as rn
+
+    taken = [n for n in rn.MODEL_NAMES if n in sys.modules and not rn.is_facade(sys.modules[n])]
+    if taken:
+        raise RuntimeError(f"install(model=True): {', '.join(taken)} already imported from "
+                           f"{getattr(sys.modules[taken[0]], '__file__', 'elsewhere')}; a driver that imported it holds "
+                           "the reference's own class.  Call install(model=True) before the driver's imports")
+    if all(n in sys.modules for n in rn.MODEL_NAMES):
+        return {n: sys.modules[n] for n in rn.MODEL_NAMES}  # a second call
+    # parent packages: the reference's own when its tree is on sys.path (its util.config, util.eval, ... stay its),
+    # otherwise empty stand-ins, so that `from model.geoformer.geoformer import GeoFormer` resolves without the tree
+    for pkg in rn.PARENT_PACKAGES:
+        if pkg not in sys.modules:
+            try:
+                importlib.import_module(pkg)
+            except ModuleNotFoundError as e:
+                if e.name != pkg:
+                    raise
+                stand_in = types.ModuleType(pkg)
+                stand_in.__path__ = _LatePath(pkg)
+                stand_in.__doc__ = "stand-in package of geoformer_amd.dropin.install(model=True)"
+                sys.modules[pkg] = stand_in
+                if "." in pkg:
+                    setattr(sys.modules[pkg.rpartition(".")[0]], pkg.rpartition(".")[2], stand_in)
+        if not hasattr(sys.modules[pkg], "__path__"):
+            raise RuntimeError(f"install(model=True): {pkg} is the module {getattr(sys.modules[pkg], '__file__', pkg)}, "
+                               "not a package; the reference's names cannot live under it")
+    mods = rn.build_modules()
+    for name, m in mods.items():
+        sys.modules[name] = m
+        parent, _, leaf = name.rpartition(".")
+        if parent:
+            setattr(sys.modules[parent], leaf, m)
+    return mods
+
+
+def install(model=False):
+    """Register the mirrors under the reference's import names.  Idempotent.  model=True: also the fused model, the
+    device criteria and the native post-processing (reference_names: model.geoformer.geoformer, model.geoformer.
+    geoformer_fs, criterion, criterion_fs, util.utils_3d), so that the reference's unmodified drivers build THIS
+    package's classes; it must run before the driver imports any of those names (RuntimeError otherwise)."""
     from . import spconv as sp
 
     sys.modules["spconv"] = sp
@@ -279,4 +340,7 @@ def install():
     if not hasattr(torch.cuda, "FloatTensor"):
         torch.cuda.FloatTensor = lambda *s: torch.empty(*s, dtype=torch.float32, device="cuda")
         torch.cuda.IntTensor = lambda *s: torch.empty(*s, dtype=torch.int32, device="cuda")
-    return {"spconv": sp, "PG_OP": pg, "pointnet2._ext": ext, "faiss": fa}
+    mods = {"spconv": sp, "PG_OP": pg, "pointnet2._ext": ext, "faiss": fa}
+    if model:
+        mods.update(_install_model_names())
+    return mods

@@ -1490,6 +1490,29 @@ def matrix_nms_batched(table, inter, sizes, kernel, sigma, final_score_thresh):
     return picks, counts
 
 
+def greedy_nms_batched(table, inter, sizes, threshold):
+    """(picks i32 [sum n_b] packed at each scene's pick_off, pick_counts i32 [S]) of the greedy NMS walk."""
+    dev = table.device
+    picks = torch.empty(max(int(sizes["picks"]), 1), dtype=torch.int32, device=dev)
+    counts = torch.empty(table.shape[0], dtype=torch.int32, device=dev)
+    check(_lib.load().gf_greedy_nms_batched(ptr(table), table.shape[0], ptr(inter), float(threshold), ptr(picks),
+                                            ptr(counts), stream_ptr()), "gf_greedy_nms_batched")
+    return picks, counts
+
+
+def greedy_nms_ious(ious, scores, threshold):
+    """(picks i32 [n], count i32 [1]) of the greedy NMS walk over a row-major fp32 [n, n] IoU matrix."""
+    _f32c(ious, "ious"), _f32c(scores, "scores")
+    n = scores.shape[0]
+    if ious.shape != (n, n):
+        raise RuntimeError(f"greedy_nms_ious: ious {tuple(ious.shape)} does not fit scores [{n}]")
+    picks = torch.empty(max(n, 1), dtype=torch.int32, device=scores.device)
+    count = torch.empty(1, dtype=torch.int32, device=scores.device)
+    check(_lib.load().gf_greedy_nms_ious(ptr(ious), ptr(scores), n, float(threshold), ptr(picks), ptr(count),
+                                         stream_ptr()), "gf_greedy_nms_ious")
+    return picks, count
+
+
 def label_map_batched(table, sizes, min_score):
     """gf_label_map_batched on a device label scene table (postprocess.label_scene_table): (int32 [2, points] = owner,
     ids; tab_i int32 [rows, GF_LBL_TABLE_INTS]; tab_f fp32 [rows, GF_LBL_TABLE_FLOATS])."""

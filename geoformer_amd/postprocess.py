@@ -1,5 +1,6 @@
 """Post-processing of the eval forward: matrix NMS over the proposals (util/utils_3d.py:95-141, called by
-test.py:88-93 right after the forward)."""
+test.py:88-93 right after the forward) and the reference's other post-process, class-agnostic greedy
+NMS (util/utils_3d.py:76-93, test.py:78-86 with cfg.TEST_NMS_THRESH)."""
 from __future__ import annotations
 
 from typing import NamedTuple
@@ -115,6 +116,44 @@ def nms_scene_table(mask_ptrs, widths, ns, score_ptrs, cat_ptrs):
     return t, sizes
 
 
+def _nms_batch_table(who, masks, scores, categories=None):
+    """(device, host scene table, device scene table, sizes, tensors to keep alive) of per-scene lists, for the batched
+    NMS kernels; device None: no scene has proposals.  categories None: the table's category pointers are 0."""
+    from . import pointops
+
+    categories = [None] * len(masks) if categories is None else categories
+    if not (len(masks) == len(scores) == len(categories)):
+        raise ValueError(f"{who}: masks, scores and categories need one entry per scene")
+    dev = next((m.device for m in masks if torch.is_tensor(m)), None)
+    if dev is None:
+        return None, None, None, None, []
+    if dev.type != "cuda":
+        raise RuntimeError(f"{who}: the batched kernels run on the GPU; "
+                           f"{'matrix_non_max_suppression' if who == 'matrix_nms_batched' else 'non_max_suppression_gpu'}"
+                           " is the CPU path")
+    keep, ms, ss, cs, ns, ws = [], [], [], [], [], []
+    for m, s, c in zip(masks, scores, categories):
+        if not torch.is_tensor(m) or m.shape[0] == 0:
+            ns.append(0), ws.append(0), ms.append(0), ss.append(0), cs.append(0)
+            continue
+        m = (m if m.dtype == torch.int32 else (m != 0).int()).contiguous()
+        s = s.to(torch.float32).contiguous()
+        c = c.to(torch.int64).contiguous() if c is not None else None
+        if s.shape != (m.shape[0],) or (c is not None and c.shape != (m.shape[0],)):
+            raise ValueError(f"{who}: scores / categories must be [n] for masks [n, N]")
+        keep += [m, s, c]
+        ns.append(m.shape[0]), ws.append(m.shape[1])
+        ms.append(m.data_ptr()), ss.append(s.data_ptr()), cs.append(c.data_ptr() if c is not None else 0)
+    table, sizes = nms_scene_table(ms, ws, ns, ss, cs)
+    return dev, table, pointops._table_dev(table, dev), sizes, keep
+
+
+def _split_picks(table, picks, counts):
+    counts_h = counts.cpu().tolist()  # the one read-back
+    picks = picks.long()
+    return [picks[int(table[b, 7]):int(table[b, 7]) + counts_h[b]] for b in range(table.shape[0])]
+
+
 def matrix_nms_batched(masks, scores, categories, kernel="gaussian", sigma=2.0, final_score_thresh=0.05):
     """matrix_non_max_suppression of several scenes at once on the GPU: lists of per-scene masks [n_b, N_b] (int32 0/1;
     other dtypes are converted), scores fp32 [n_b] and categories [n_b]; a scene without proposals may be given as
@@ -125,35 +164,71 @@ def matrix_nms_batched(masks, scores, categories, kernel="gaussian", sigma=2.0, 
 
     if kernel not in ("gaussian", "linear"):
         raise NotImplementedError(kernel)
-    if not (len(masks) == len(scores) == len(categories)):
-        raise ValueError("matrix_nms_batched: masks, scores and categories need one entry per scene")
-    dev = next((m.device for m in masks if torch.is_tensor(m)), None)
+    dev, table, table_d, sizes, _keep = _nms_batch_table("matrix_nms_batched", masks, scores, categories)
     if dev is None:  # no scene has proposals
         return [torch.zeros(0, dtype=torch.int64) for _ in masks]
-    if dev.type != "cuda":
-        raise RuntimeError("matrix_nms_batched: the batched kernels run on the GPU; matrix_non_max_suppression is the "
-                           "CPU path")
-    keep, ms, ss, cs, ns, ws = [], [], [], [], [], []
-    for m, s, c in zip(masks, scores, categories):
-        if not torch.is_tensor(m) or m.shape[0] == 0:
-            ns.append(0), ws.append(0), ms.append(0), ss.append(0), cs.append(0)
-            continue
-        m = (m if m.dtype == torch.int32 else (m != 0).int()).contiguous()
-        s = s.to(torch.float32).contiguous()
-        c = c.to(torch.int64).contiguous()
-        if s.shape != (m.shape[0],) or c.shape != (m.shape[0],):
-            raise ValueError("matrix_nms_batched: scores / categories must be [n] for masks [n, N]")
-        keep += [m, s, c]
-        ns.append(m.shape[0]), ws.append(m.shape[1])
-        ms.append(m.data_ptr()), ss.append(s.data_ptr()), cs.append(c.data_ptr())
-    table, sizes = nms_scene_table(ms, ws, ns, ss, cs)
-    table_d = pointops._table_dev(table, dev)
     inter = pointops.mask_intersections_batched(table_d, sizes)
     picks, counts = pointops.matrix_nms_batched(table_d, inter, sizes, 1 if kernel == "linear" else 0, sigma,
                                                 final_score_thresh)
-    counts_h = counts.cpu().tolist()
-    picks = picks.long()
-    return [picks[int(table[b, 7]):int(table[b, 7]) + counts_h[b]] for b in range(len(ns))]
+    return _split_picks(table, picks, counts)
+
+
+# ---- greedy NMS (csrc/batch_post.hip: k_bp_greedy_nms / k_bp_greedy_ious) ----------------------------------------------
+def greedy_nms_loop(ious, scores, threshold):
+    """The walk of non_max_suppression_gpu in framework operations, on the tensors' device: proposals in descending score
+    order (equal scores by ascending index); a proposal still alive is picked and suppresses every later proposal j
+    with ious[pick, j] > threshold.  One read-back per proposal: the CPU path, and what the kernel is measured against
+    on device tensors."""
+    n = scores.shape[0]
+    if n == 0:
+        return torch.zeros(0, dtype=torch.int64, device=scores.device)
+    order = torch.argsort(scores, descending=True, stable=True)
+    rows = ious[order][:, order]
+    alive = torch.ones(n, dtype=torch.bool, device=scores.device)
+    pick = []
+    for a in range(n):
+        if not bool(alive[a]):
+            continue
+        pick.append(a)
+        alive[a + 1:] &= ~(rows[a, a + 1:] > threshold)
+    return order[torch.tensor(pick, dtype=torch.int64, device=scores.device)]
+
+
+def non_max_suppression_gpu(ious, scores, threshold):
+    """Same signature and result as the reference (util/utils_3d.py:76-93): class-agnostic greedy NMS over a given
+    [n, n] IoU matrix; the picked indices in pick order, int64 on scores.device.  Equal scores are walked by ascending
+    index (torch.argsort gives no guarantee); the comparison is strict and the row is the pick, so a non-symmetric
+    matrix matters.  CUDA tensors: one launch of the walk kernel and one read-back (the count), n <= GF_NMS_MAX_N;
+    CPU tensors: greedy_nms_loop."""
+    n = scores.shape[0]
+    if ious.dim() != 2 or ious.shape[0] != n or ious.shape[1] != n:
+        raise ValueError(f"non_max_suppression_gpu: ious must be [n, n] for scores [n], got {tuple(ious.shape)}")
+    if not scores.is_cuda:
+        return greedy_nms_loop(ious, scores, threshold)
+    if n > NMS_MAX_N:
+        raise ValueError(f"greedy NMS: at most {NMS_MAX_N} proposals per scene, got {n}")
+    if n == 0:
+        return torch.zeros(0, dtype=torch.int64, device=scores.device)
+    from . import pointops
+
+    picks, count = pointops.greedy_nms_ious(ious.to(device=scores.device, dtype=torch.float32).contiguous(),
+                                            scores.to(torch.float32).contiguous(), threshold)
+    return picks[:int(count.item())].long()
+
+
+def greedy_nms_batched(masks, scores, threshold):
+    """Greedy NMS (non_max_suppression_gpu on IoUs of the masks, as test.py:78-86 builds them) of several scenes at once
+    on the GPU: lists of per-scene masks [n_b, N_b] (int32 0/1; other dtypes are converted) and scores fp32 [n_b]; a
+    scene without proposals may be given as [].  Returns one int64 tensor of picks per scene, in pick order.  Fixed
+    launches per batch (table upload, bit packing, intersections, the walk, one read-back of the counts)."""
+    from . import pointops
+
+    dev, table, table_d, sizes, _keep = _nms_batch_table("greedy_nms_batched", masks, scores)
+    if dev is None:  # no scene has proposals
+        return [torch.zeros(0, dtype=torch.int64) for _ in masks]
+    inter = pointops.mask_intersections_batched(table_d, sizes)
+    picks, counts = pointops.greedy_nms_batched(table_d, inter, sizes, threshold)
+    return _split_picks(table, picks, counts)
 
 
 # ---- scene labelling (csrc/label_map.hip): one label per point, one table row per picked instance ---------------------

@@ -771,6 +771,18 @@ int gf_mask_intersections_batched(const long long* table, int S, long long max_w
  * the kept proposals' indices in descending-score order, pick_counts int32 [S] how many. */
 int gf_matrix_nms_batched(const long long* table, int S, const int32_t* inter, int kernel, float sigma,
                           float final_score_thresh, int32_t* picks, int32_t* pick_counts, void* stream);
+/* Greedy NMS per scene (util/utils_3d.py:76-93), one workgroup each (n_b <= GF_NMS_MAX_N), on the same scene table
+ * (the categories pointer is not read and may be 0) and intersection blocks.  Proposals in descending score order, EQUAL
+ * SCORES BY ASCENDING INDEX; a proposal still alive is picked and suppresses every later proposal j with
+ * iou[pick, j] > threshold, iou = I / ((d_pick + d_j) - I) in fp32 (strict comparison; a NaN never suppresses; a
+ * suppressed proposal suppresses nothing).  picks + pick_off gets the picked indices in pick order, pick_counts int32
+ * [S] how many (0 for a scene with n_b == 0). */
+int gf_greedy_nms_batched(const long long* table, int S, const int32_t* inter, float threshold, int32_t* picks,
+                          int32_t* pick_counts, void* stream);
+/* The same walk over a caller-given row-major fp32 [n, n] matrix (the row is the pick: ious[pick * n + j]; it need not
+ * be symmetric), n <= GF_NMS_MAX_N: picks int32 [n], pick_count int32 [1]. */
+int gf_greedy_nms_ious(const float* ious, const float* scores, int n, float threshold, int32_t* picks,
+                       int32_t* pick_count, void* stream);
 
 /* ===================================================================================
  * Scene labelling from the picked masks of S scenes (csrc/label_map.hip): one label per point and one table row per

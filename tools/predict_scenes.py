@@ -1,5 +1,5 @@
-"""Label maps and ScanNet benchmark files of scenes: the eval forward, matrix NMS and the scene labelling of
-batch_eval.label_batches, written with geoformer_amd.export.
+"""Label maps and ScanNet benchmark files of scenes: the eval forward, matrix NMS (or, with --nms greedy, the reference's
+greedy NMS) and the scene labelling of batch_eval.label_batches, written with geoformer_amd.export.
 
     python tools/predict_scenes.py --out out scene0011_00_inst_nostuff.npy ...      # [N, 8] as prepare_data_inst.py stores them
     python tools/predict_scenes.py --out out --synthetic 8 --points 150000 --batch-size 4
@@ -35,6 +35,8 @@ def main():
     ap.add_argument("--batch-size", type=int, default=4)
     ap.add_argument("--min-score", type=float, default=None, help="default: postprocess.MIN_SCORE (0.09)")
     ap.add_argument("--nms-score", type=float, default=None, help="final_score_thresh of the matrix NMS (default 0.5)")
+    ap.add_argument("--nms", choices=("matrix", "greedy"), default="matrix",
+                    help="matrix NMS (test.py:88-93) or class-agnostic greedy NMS at the yaml's TEST_NMS_THRESH (test.py:78-86)")
     ap.add_argument("--checkpoint", default=None, help="state dict (torch.save) of a GeoFormer of --config")
     ap.add_argument("--config", default="test_geoformer_scannet.yaml")
     ap.add_argument("--scannet", action="store_true", help="also write the benchmark's .txt files")
@@ -71,6 +73,8 @@ def main():
     kw = {"min_score": postprocess.MIN_SCORE if args.min_score is None else args.min_score}
     if args.nms_score is not None:
         kw["final_score_thresh"] = args.nms_score
+    if args.nms != "matrix":
+        kw["nms"] = args.nms
 
     def run(keep_masks):
         np.random.seed(0)
