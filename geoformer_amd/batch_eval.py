@@ -10,6 +10,10 @@
     print(evaluation.format_semantic_results(res))
     for name, labels in label_batches(model, [(name, raw), ...], batch_size=4):
         ...                                   # labels.ids / .owner [N], labels.table: one row per instance (host)
+    for name, labels, pan in panoptic_batches(model, [(name, raw), ...], batch_size=4):
+        ...                                   # pan [N]: instance ids, 1000 wall, 2000 floor, 0 unlabelled (host)
+    res = evaluate_panoptic(model, [(name, raw), ...], batch_size=4)             # PQ / SQ / RQ
+    print(evaluation.format_panoptic_results(res))
 
 A batch of raw scenes ([N, 8] = xyz, rgb, semantic label, instance label, as prepare_data_inst.py stores them) is
 collated on the host (scene.collate_raw), uploaded and voxelised on the GPU one batch ahead (feeder.DeviceFeeder), and
@@ -97,16 +101,39 @@ def predict_batches(model, raw_scenes, batch_size, *, epoch=300, spatial_shape=N
             yield name, cls, sc, masks, pick
 
 
-@torch.no_grad()
-def label_batches(model, raw_scenes, batch_size, *, min_score=postprocess.MIN_SCORE, keep_masks=False, **kw):
-    """Yields (name, SceneLabels) per scene, in input order, with the results on the host: the loop of predict_batches
-    with postprocess.label_points_batched once per batch of scenes.  Per scene the per-point maps (ids, owner) and the
-    instance table cross to the host; the picked masks [p, N] (rank order, SceneLabels.masks) only with keep_masks=True.
-    Keywords go to predict_batches."""
+class _SemanticTap:
+    """Stands where predict_batches takes a SemanticEvaluator: keeps every batch's semantic classes (int32, device) per
+    scene name, and hands the batch on to the caller's own evaluator when there is one."""
+
+    def __init__(self, inner=None):
+        self.inner = inner
+        self.preds = {}
+
+    def add_batch(self, scores, labels, offsets, names, offsets_host=None):
+        from . import pointops
+
+        if self.inner is not None:
+            preds = self.inner.add_batch(scores, labels, offsets, names, offsets_host=offsets_host)
+        else:
+            preds = pointops.semantic_confusion(scores.contiguous(), None, None, None)
+        off = offsets_host.tolist()
+        for i, n in enumerate(names):
+            self.preds[n] = preds[off[i]:off[i + 1]]
+        return preds
+
+
+def _label_batches(model, raw_scenes, batch_size, min_score, keep_masks, panoptic, count_gt, kw):
+    """The loop of label_batches; yields (name, SceneLabels, pan).  panoptic: None (pan is None and nothing is added to
+    the loop) or an evaluation.PanopticEvaluator, whose class tables make the panoptic ids; with count_gt the
+    batch is also counted against the ground truth of the raw scenes' columns 6 / 7."""
     items = list(raw_scenes)
     raws = dict(items)
     dev = torch.device(kw["device"]) if kw.get("device") is not None else next(model.parameters()).device
     pending = []
+    tap = None
+    if panoptic is not None:
+        kw = dict(kw)
+        tap = kw["semantic"] = _SemanticTap(kw.get("semantic"))
 
     def flush():
         cvfold = model.cfg.cvfold if kw.get("cvfold") is None else kw["cvfold"]
@@ -115,13 +142,16 @@ def label_batches(model, raw_scenes, batch_size, *, min_score=postprocess.MIN_SC
                 for n, *_ in pending]
         table, packed = postprocess._label_batch_packed([m for *_, m, _ in pending], [s for _, _, s, _, _ in pending],
                                                         ids, [p for *_, p in pending], xyzs, min_score)
+        pans = [None] * len(pending)
+        if panoptic is not None:
+            pans = _panoptic_of_batch(panoptic, count_gt, [n for n, *_ in pending], raws, table, packed, tap, dev)
         # the batch's maps and tables cross in three copies, whatever the number of scenes
         out = postprocess._split_labels(table, *[b.cpu().numpy() for b in packed])
-        for (name, _, _, masks, pick), lab in zip(pending, out):
+        for (name, _, _, masks, pick), lab, pan in zip(pending, out, pans):
             if keep_masks:
                 m = masks[pick].cpu().numpy() if torch.is_tensor(masks) else np.zeros((0, lab.owner.shape[0]), np.int32)
                 lab = lab._replace(masks=m)
-            yield name, lab
+            yield name, lab, pan
         pending.clear()
 
     for rec in predict_batches(model, items, batch_size, **kw):
@@ -130,6 +160,70 @@ def label_batches(model, raw_scenes, batch_size, *, min_score=postprocess.MIN_SC
             yield from flush()
     if pending:
         yield from flush()
+
+
+def _panoptic_of_batch(ev, count_gt, names, raws, table, packed, tap, dev):
+    """Host panoptic ids of one labelled batch (one more copy); with count_gt the batch's tables go to `ev`."""
+    from . import pointops
+
+    pts, ti, _ = packed
+    sem = torch.cat([tap.preds.pop(n) for n in names]).contiguous()
+    off_h = torch.from_numpy(np.concatenate([[0], np.cumsum(table[:, 1])]).astype(np.int32))
+    P = int(table[:, 3].max()) if len(table) else 0
+    if count_gt:
+        gts = []
+        for n in names:
+            r = torch.as_tensor(np.asarray(raws[n])[:, 6:8], device=dev)
+            gts.append(evaluation.gt_ids_from_labels(r[:, 0].long(), r[:, 1].long()))
+        ti_h = ti.cpu().numpy()
+        label_ids = [ti_h[int(t[10]):int(t[10]) + int(t[3]), 2] for t in table]
+        pan = ev.add_batch(pts[0], pts[1], sem, torch.cat(gts), off_h.to(dev), label_ids, names, offsets_host=off_h)
+    else:
+        cls, st, sos = ev.device_tables(dev)
+        pan = pointops.panoptic_points(pts[0].contiguous(), pts[1].contiguous(), sem, off_h.to(dev), cls, st, sos,
+                                       ev.n_stuff, P)
+    pan = pan.cpu().numpy()
+    off = off_h.tolist()
+    return [pan[off[i]:off[i + 1]] for i in range(len(names))]
+
+
+@torch.no_grad()
+def label_batches(model, raw_scenes, batch_size, *, min_score=postprocess.MIN_SCORE, keep_masks=False, **kw):
+    """Yields (name, SceneLabels) per scene, in input order, with the results on the host: the loop of predict_batches
+    with postprocess.label_points_batched once per batch of scenes.  Per scene the per-point maps (ids, owner) and the
+    instance table cross to the host; the picked masks [p, N] (rank order, SceneLabels.masks) only with keep_masks=True.
+    Keywords go to predict_batches."""
+    for name, lab, _ in _label_batches(model, raw_scenes, batch_size, min_score, keep_masks, None, False, kw):
+        yield name, lab
+
+
+@torch.no_grad()
+def panoptic_batches(model, raw_scenes, batch_size, *, min_score=postprocess.MIN_SCORE, keep_masks=False, classes=None,
+                     stuff=evaluation.DEFAULT_STUFF_IDS, stuff_of_sem=None, evaluator=None, **kw):
+    """Yields (name, SceneLabels, pan) per scene, in input order, on the host: the loop of label_batches plus the
+    batch's semantic classes, joined by gf_panoptic_overlaps.  pan int32 [N]: the label map's id where a picked instance
+    owns the point, stuff id * 1000 (1000 wall, 2000 floor) where the semantic head says so, 0 elsewhere.  classes: the
+    thing classes (default: the model's cvfold); evaluator: an evaluation.PanopticEvaluator that also counts every
+    batch against the ground truth of the raw scenes' columns 6 / 7 (its class tables are used).  Other keywords go to
+    predict_batches."""
+    ev = evaluator
+    if ev is None:
+        ev = evaluation.PanopticEvaluator(model.cfg.cvfold if classes is None else classes, stuff, stuff_of_sem)
+    yield from _label_batches(model, raw_scenes, batch_size, min_score, keep_masks, ev, evaluator is not None, kw)
+
+
+@torch.no_grad()
+def evaluate_panoptic(model, scenes_with_gt, batch_size, classes=0, **kw):
+    """PQ / SQ / RQ of the model's panoptic labelling over (name, raw [N, 8]) scenes whose columns 6 / 7 are the ground
+    truth (evaluation.gt_ids_from_labels): evaluation.PanopticEvaluator.evaluate's dict.  Keywords go to
+    panoptic_batches."""
+    ev = kw.pop("evaluator", None)
+    if ev is None:
+        ev = evaluation.PanopticEvaluator(classes, kw.pop("stuff", evaluation.DEFAULT_STUFF_IDS),
+                                          kw.pop("stuff_of_sem", None))
+    for _ in panoptic_batches(model, scenes_with_gt, batch_size, evaluator=ev, **kw):
+        pass
+    return ev.evaluate()
 
 
 @torch.no_grad()

@@ -15,6 +15,7 @@ dataset-level matching and AP integration run on the host once per evaluation.
 from __future__ import annotations
 
 import warnings
+from typing import NamedTuple
 
 import numpy as np
 
@@ -696,3 +697,311 @@ class SemanticEvaluator:
 
     def format_results(self, res=None):
         return format_semantic_results(self.evaluate() if res is None else res)
+
+
+# ---- panoptic segmentation: things from the label map, stuff from the semantic head; PQ / SQ / RQ -------------------
+# Written from the published definition (Kirillov et al., "Panoptic Segmentation", CVPR 2019) and the matching rules of
+# its public evaluation: a predicted and a ground-truth segment of one class match iff their IoU, with the prediction's
+# void points taken out of the union, exceeds 0.5 (which makes the matching unique).  The per-scene contingency tables
+# come from gf_panoptic_overlaps (csrc/panoptic.hip) or from panoptic_overlaps_host, its numpy statement.
+DEFAULT_STUFF_IDS = (1, 2)  # nyu40 wall, floor: classes 0 and 1 of the semantic head
+STUFF_NAMES = {1: "wall", 2: "floor"}
+
+
+class PanopticTable(NamedTuple):
+    """One scene's contingency table.  Rows: the p thing rows (rank order of pick), one row per stuff class
+    (class_ids order), the unlabelled row; columns: the G ground-truth segments in ascending key order, void last."""
+    gt_id: object     # int64 [G]: the id of a thing instance, nyu40 id * 1000 of a stuff segment
+    inter: object     # int64 [p + n_stuff + 1, G + 1]
+    label_id: object  # int64 [p]: nyu40 class of every thing row
+    class_ids: object  # int64 [C]: the evaluated classes
+    is_stuff: object  # bool [C]
+
+
+def panoptic_class_tables(classes=0, stuff=DEFAULT_STUFF_IDS, stuff_of_sem=None):
+    """(class_ids int64 [C], is_stuff bool [C], stuff_of_sem int32 [L], names) of a panoptic class set: the stuff classes
+    first, then the thing classes of class_set(classes).  stuff_of_sem: semantic class -> index into class_ids of a stuff
+    class or -1; default: semantic class j is the j-th stuff class (wall, floor: the semantic head's classes 0, 1)."""
+    stuff = tuple(int(c) for c in stuff)
+    things, thing_names = class_set(classes)
+    ids = np.concatenate([np.asarray(stuff, dtype=np.int64), things])
+    if len(set(ids.tolist())) != len(ids) or (ids <= 0).any():
+        raise ValueError("panoptic classes: distinct positive nyu40 ids, no class both stuff and thing")
+    is_stuff = np.arange(len(ids)) < len(stuff)
+    sos = np.arange(len(stuff), dtype=np.int32) if stuff_of_sem is None else np.asarray(stuff_of_sem, dtype=np.int32)
+    names = [STUFF_NAMES.get(c, str(c)) for c in stuff] + list(thing_names)
+    return ids, is_stuff, sos, names
+
+
+def panoptic_overlaps_host(owner, sem, gt_ids, offsets=None, *, class_ids, is_stuff, stuff_of_sem, P, ids=None,
+                           max_gt=None):
+    """numpy statement of gf_panoptic_overlaps: (pan int32 [N] or None without ids, G int32 [S], gt_id int64 [S, max_gt],
+    inter int64 [S, R, max_gt + 1]) of S scenes packed one after the other (offsets [S+1], default one scene), with
+    R = P + n_stuff + 1 rows (things by owner, stuff classes in class_ids order, unlabelled) and the void points in the
+    last column.  max_gt: default the largest G of the batch; a scene with G > max_gt reports G alone (zeros)."""
+    owner = np.asarray(owner).astype(np.int64)
+    sem = np.asarray(sem).astype(np.int64)
+    gt = np.asarray(gt_ids).astype(np.int64)
+    N = owner.shape[0]
+    if owner.shape != (N,) or sem.shape != (N,) or gt.shape != (N,):
+        raise ValueError(f"owner {owner.shape}, sem {sem.shape}, gt_ids {gt.shape}: one value per point")
+    off = np.array([0, N], dtype=np.int64) if offsets is None else np.asarray(offsets).astype(np.int64)
+    if off.ndim != 1 or len(off) < 1 or off[0] != 0 or off[-1] != N or (np.diff(off) < 0).any():
+        raise ValueError(f"offsets {off.tolist()[:8]}...: ascending from 0 to N = {N}")
+    S = len(off) - 1
+    cls = np.asarray(class_ids, dtype=np.int64)
+    st = np.asarray(is_stuff).astype(bool)
+    sos = np.asarray(stuff_of_sem, dtype=np.int64).reshape(-1)
+    C, L, P = len(cls), len(sos), int(P)
+    n_stuff = int(st.sum())
+    R = P + n_stuff + 1
+    srank = np.where(st, np.cumsum(st) - 1, -1)  # rank among the stuff classes in class_ids order
+    # predicted rows
+    row = np.full(N, R - 1, dtype=np.int64)
+    label = np.zeros(N, dtype=np.int64)
+    thing = (owner >= 0) & (owner < P)
+    c = np.full(N, -1, dtype=np.int64)
+    ins = ~thing & (sem >= 0) & (sem < L)
+    c[ins] = sos[sem[ins]]
+    c[(c < 0) | (c >= C)] = -1
+    stuff = c >= 0
+    stuff[stuff] = srank[c[stuff]] >= 0
+    row[thing] = owner[thing]
+    row[stuff] = P + srank[c[stuff]]
+    label[stuff] = cls[c[stuff]] * 1000
+    pan = None
+    if ids is not None:
+        label[thing] = np.asarray(ids).astype(np.int64)[thing]
+        pan = label.astype(np.int32)
+    # ground-truth keys
+    q = gt // 1000
+    order = np.argsort(cls, kind="stable")
+    pos = np.searchsorted(cls[order], q)
+    hit = (pos < C) & (cls[order][np.minimum(pos, C - 1)] == q)
+    rank = np.where(hit, pos, -1)  # rank of q among the class ids
+    at = order[np.minimum(pos, C - 1)]  # index into class_ids
+    key = np.where(hit, rank * 1000 + np.where(st[at], 0, gt - q * 1000), -1)
+    sorted_cls = cls[order]
+    Gs = np.zeros(S, dtype=np.int32)
+    uniq, cols = [], []
+    for s in range(S):
+        k = key[off[s]:off[s + 1]]
+        u, inv = np.unique(k[k >= 0], return_inverse=True)
+        col = np.full(k.shape[0], -1, dtype=np.int64)
+        col[k >= 0] = inv
+        Gs[s] = len(u)
+        uniq.append(u)
+        cols.append(col)
+    max_gt = int(Gs.max()) if max_gt is None and S else int(max_gt or 0)
+    gt_id = np.zeros((S, max_gt), dtype=np.int64)
+    inter = np.zeros((S, R, max_gt + 1), dtype=np.int64)
+    for s in range(S):
+        G = int(Gs[s])
+        if G > max_gt:
+            continue
+        gt_id[s, :G] = sorted_cls[uniq[s] // 1000] * 1000 + uniq[s] % 1000
+        col = np.where(cols[s] >= 0, cols[s], max_gt)
+        inter[s] = np.bincount(row[off[s]:off[s + 1]] * (max_gt + 1) + col,
+                               minlength=R * (max_gt + 1)).reshape(R, max_gt + 1)
+    return pan, Gs, gt_id, inter
+
+
+def panoptic_tables(Gs, gt_id, inter, label_ids, class_ids, is_stuff, P):
+    """One PanopticTable per scene from the batch tables of gf_panoptic_overlaps / panoptic_overlaps_host: the thing
+    rows beyond a scene's own p = len(label_ids[s]) are dropped (points there mean an owner without a table row)."""
+    cls = np.asarray(class_ids, dtype=np.int64)
+    st = np.asarray(is_stuff).astype(bool)
+    out = []
+    for s in range(len(Gs)):
+        G = int(Gs[s])
+        lab = np.asarray(label_ids[s], dtype=np.int64).reshape(-1)
+        p = len(lab)
+        if p > P or inter[s, p:P].any():
+            raise ValueError(f"scene {s}: owners beyond its {p} picked instances")
+        it = np.asarray(inter[s], dtype=np.int64)
+        it = np.concatenate([it[:p], it[P:]])
+        out.append(PanopticTable(np.asarray(gt_id[s, :G], dtype=np.int64), np.concatenate([it[:, :G], it[:, -1:]], 1),
+                                 lab, cls, st))
+    return out
+
+
+def _panoptic_scene_counts(table):
+    """(tp, fp, fn int64 [C], iou float64 [C]) of one scene, per class of table.class_ids."""
+    cls = np.asarray(table.class_ids, dtype=np.int64)
+    st = np.asarray(table.is_stuff).astype(bool)
+    inter = np.asarray(table.inter, dtype=np.int64)
+    lab = np.asarray(table.label_id, dtype=np.int64)
+    C, p, G = len(cls), len(lab), inter.shape[1] - 1
+    if inter.shape[0] != p + int(st.sum()) + 1 or len(table.gt_id) != G:
+        raise ValueError(f"panoptic table {inter.shape} for {p} thing rows, {int(st.sum())} stuff classes, "
+                         f"{len(table.gt_id)} segments")
+    pred_cls = np.concatenate([lab, cls[st]])  # (the unlabelled row is no segment)
+    size_r = inter[:-1].sum(1)
+    void_r = inter[:-1, G]
+    size_g = inter[:, :G].sum(0)
+    gt_cls = np.asarray(table.gt_id, dtype=np.int64) // 1000
+    bad = (size_r[:p] > 0) & ~np.isin(lab, cls)
+    if bad.any():
+        raise ValueError(f"thing row {int(np.nonzero(bad)[0][0])} has class {int(lab[bad][0])}, outside the evaluated set")
+    I = inter[:-1, :G]
+    union = size_r[:, None] + size_g[None, :] - I - void_r[:, None]
+    match = (pred_cls[:, None] == gt_cls[None, :]) & (2 * I > union) & (size_r[:, None] > 0) & (size_g[None, :] > 0)
+    tp, fp, fn = (np.zeros(C, dtype=np.int64) for _ in range(3))
+    iou = np.zeros(C, dtype=np.float64)
+    index = {int(c): i for i, c in enumerate(cls)}
+    for r, g in zip(*np.nonzero(match)):
+        i = index[int(gt_cls[g])]
+        tp[i] += 1
+        iou[i] += float(I[r, g]) / float(union[r, g])
+    for g in np.nonzero((size_g > 0) & ~match.any(0))[0]:
+        fn[index[int(gt_cls[g])]] += 1
+    for r in np.nonzero((size_r > 0) & ~match.any(1) & ~(2 * void_r > size_r))[0]:
+        fp[index[int(pred_cls[r])]] += 1
+    return tp, fp, fn, iou
+
+
+def _pq_summary(tp, fp, fn, iou, class_ids, is_stuff, names=None):
+    tp, fp, fn = (np.asarray(a, dtype=np.int64) for a in (tp, fp, fn))
+    iou = np.asarray(iou, dtype=np.float64)
+    st = np.asarray(is_stuff).astype(bool)
+    denom = tp + 0.5 * fp + 0.5 * fn
+    seen = (tp + fp + fn) > 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        pq = np.where(seen, iou / denom, np.nan)
+        sq = np.where(seen, np.where(tp > 0, iou / np.maximum(tp, 1), 0.0), np.nan)
+        rq = np.where(seen, tp / denom, np.nan)
+
+    def mean(v, sel):
+        v = v[sel & seen]
+        return float(v.mean()) if v.size else float("nan")
+
+    names = [STUFF_NAMES.get(int(c), dict(zip(VALID_CLASS_IDS, CLASS_NAMES)).get(int(c), str(int(c))))
+             for c in class_ids] if names is None else list(names)
+    res = {"class_ids": np.asarray(class_ids, dtype=np.int64), "is_stuff": st, "tp": tp, "fp": fp, "fn": fn,
+           "iou_sum": iou, "classes": {}}
+    every = np.ones(len(st), dtype=bool)
+    for tag, sel in (("", every), ("_th", ~st), ("_st", st)):
+        res["pq" + tag], res["sq" + tag], res["rq" + tag] = mean(pq, sel), mean(sq, sel), mean(rq, sel)
+    for i, n in enumerate(names):
+        res["classes"][n] = {"pq": float(pq[i]), "sq": float(sq[i]), "rq": float(rq[i]), "tp": int(tp[i]),
+                             "fp": int(fp[i]), "fn": int(fn[i]), "stuff": bool(st[i])}
+    return res
+
+
+def panoptic_quality(tables, names=None):
+    """PQ / SQ / RQ of a set of scenes' PanopticTables (one class set): per class PQ = sum of the matched IoUs /
+    (TP + FP / 2 + FN / 2), SQ = that sum / TP (0 without a match), RQ = TP / (TP + FP / 2 + FN / 2); a class with no
+    TP, FP or FN is nan and left out of the means.  Keys: pq, sq, rq (all classes), *_th (things), *_st (stuff),
+    classes[name], and the per-class arrays tp, fp, fn, iou_sum.  A predicted segment more than half void is no FP; a
+    pair at IoU 0.5 exactly is no match (decided in integers)."""
+    tables = list(tables)
+    if not tables:
+        raise ValueError("panoptic_quality: no scene")
+    cls, st = np.asarray(tables[0].class_ids, dtype=np.int64), np.asarray(tables[0].is_stuff).astype(bool)
+    tot = [np.zeros(len(cls), dtype=np.int64) for _ in range(3)] + [np.zeros(len(cls), dtype=np.float64)]
+    for t in tables:
+        if not (np.array_equal(np.asarray(t.class_ids, dtype=np.int64), cls)
+                and np.array_equal(np.asarray(t.is_stuff).astype(bool), st)):
+            raise ValueError("panoptic_quality: the scenes' class sets differ")
+        for a, b in zip(tot, _panoptic_scene_counts(t)):
+            a += b
+    return _pq_summary(*tot, cls, st, names)
+
+
+def format_panoptic_results(res):
+    """The summary as a printable table, in the style of format_results."""
+    lines = ["#" * 64, f"{'what':<15}:{'PQ':>10}{'SQ':>10}{'RQ':>10}{'TP':>6}{'FP':>6}{'FN':>6}", "#" * 64]
+    for name, c in res["classes"].items():
+        lines.append(f"{name:<15}:{c['pq']:>10.3f}{c['sq']:>10.3f}{c['rq']:>10.3f}{c['tp']:>6d}{c['fp']:>6d}{c['fn']:>6d}")
+    lines.append("-" * 64)
+    for what, tag in (("all", ""), ("things", "_th"), ("stuff", "_st")):
+        lines.append(f"{what:<15}:{res['pq' + tag]:>10.3f}{res['sq' + tag]:>10.3f}{res['rq' + tag]:>10.3f}")
+    return "\n".join(lines)
+
+
+class PanopticEvaluator:
+    """PQ / SQ / RQ of panoptic labellings over a set of scenes.
+
+        ev = PanopticEvaluator(classes=0, stuff=(1, 2))
+        pan = ev.add_batch(owner, ids, sem, gt_ids, offsets, label_ids, names)   # S scenes packed one after the other
+        res = ev.evaluate(); print(ev.format_results(res))
+
+    classes: the thing classes (cvfold 0 / 1, "all" or nyu40 ids); stuff: the nyu40 ids of the stuff classes;
+    stuff_of_sem: semantic class -> index of its stuff class among `stuff`, or -1 (default: class j is stuff[j]).
+    Device tensors are counted by gf_panoptic_overlaps (one device-to-host copy of the tables per batch), host arrays
+    by panoptic_overlaps_host."""
+
+    def __init__(self, classes=0, stuff=DEFAULT_STUFF_IDS, stuff_of_sem=None):
+        self.class_ids, self.is_stuff, self.stuff_of_sem, self.class_names = panoptic_class_tables(classes, stuff,
+                                                                                                   stuff_of_sem)
+        self.n_stuff = int(self.is_stuff.sum())
+        self.max_gt = DEFAULT_MAX_GT
+        self.names = []
+        self.tables = []
+        self._dev = {}
+
+    def device_tables(self, dev):
+        """(class_ids, is_stuff, stuff_of_sem) as int32 tensors on `dev`."""
+        t = self._dev.get(dev)
+        if t is None:
+            import torch
+
+            t = self._dev[dev] = tuple(torch.as_tensor(np.asarray(a).astype(np.int32), device=dev)
+                                       for a in (self.class_ids, self.is_stuff, self.stuff_of_sem))
+        return t
+
+    def add_batch(self, owner, ids, sem, gt_ids, offsets=None, label_ids=None, names=None, offsets_host=None):
+        """One batch of S scenes packed one after the other: owner / ids [N] (the label map), sem [N] (the semantic
+        head's classes), gt_ids [N] (val_gt ids, gt_ids_from_labels), offsets [S+1] (default one scene), label_ids: per
+        scene the nyu40 class of every picked instance in rank order (InstanceTable.label_id).  Returns pan int32 [N],
+        where the inputs live."""
+        S = 1 if offsets is None else int(offsets.shape[0]) - 1
+        names = [f"scene{len(self.names) + i:04d}" for i in range(S)] if names is None else list(names)
+        label_ids = [np.asarray(l.detach().cpu() if _is_tensor(l) else l, dtype=np.int64).reshape(-1)
+                     for l in (label_ids if label_ids is not None else [[]] * S)]
+        if len(names) != S or len(label_ids) != S:
+            raise ValueError(f"add_batch: {len(names)} names and {len(label_ids)} label tables for {S} scenes")
+        if set(names) & set(self.names) or len(set(names)) != S:
+            raise ValueError("add_batch: a scene was added already")
+        P = max([len(l) for l in label_ids] + [0])
+        if _is_tensor(owner) and owner.is_cuda:
+            import torch
+
+            from . import pointops
+
+            dev = owner.device
+            cls, st, sos = self.device_tables(dev)
+            if offsets is None:
+                offsets_host = torch.tensor([0, owner.shape[0]], dtype=torch.int32)
+                offsets = offsets_host.to(dev)
+            elif not offsets.is_cuda:
+                offsets_host = offsets.to(torch.int32).contiguous()
+                offsets = offsets_host.to(dev)
+            i32 = lambda a: torch.as_tensor(a, device=dev).to(torch.int32).contiguous()  # noqa: E731
+            gt = torch.as_tensor(gt_ids, device=dev).to(torch.int64).contiguous()
+            pan, Gs, gt_id, inter, self.max_gt = pointops.panoptic_overlaps(
+                i32(owner), i32(ids), i32(sem), gt, i32(offsets), cls, st, sos, self.n_stuff, P, max_gt=self.max_gt,
+                offsets_host=offsets_host)
+        else:
+            h = lambda a: a.detach().cpu().numpy() if _is_tensor(a) else (None if a is None else np.asarray(a))  # noqa: E731
+            pan, Gs, gt_id, inter = panoptic_overlaps_host(h(owner), h(sem), h(gt_ids), h(offsets),
+                                                           class_ids=self.class_ids, is_stuff=self.is_stuff,
+                                                           stuff_of_sem=self.stuff_of_sem, P=P, ids=h(ids))
+        self.tables += panoptic_tables(Gs, gt_id, inter, label_ids, self.class_ids, self.is_stuff, P)
+        self.names += names
+        return pan
+
+    def add_scene(self, name, owner, ids, sem, gt_ids, label_id):
+        """One scene: add_batch with a single scene."""
+        return self.add_batch(owner, ids, sem, gt_ids, None, [label_id], [name])
+
+    def scene_tables(self):
+        """{scene name: PanopticTable} of the scenes added so far."""
+        return dict(zip(self.names, self.tables))
+
+    def evaluate(self):
+        """panoptic_quality of the scenes added so far."""
+        return panoptic_quality(self.tables, self.class_names)
+
+    def format_results(self, res=None):
+        return format_panoptic_results(self.evaluate() if res is None else res)

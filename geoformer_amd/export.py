@@ -98,10 +98,13 @@ def read_scannet_semantic(out_dir, name):
         return np.array([int(line) for line in f if line.strip()], dtype=np.int64)
 
 
-def save_labels(path, labels):
-    """One .npz with ids, owner and the instance table (and the masks when the labels carry them)."""
+def save_labels(path, labels, panoptic=None):
+    """One .npz with ids, owner and the instance table (and the masks when the labels carry them); panoptic: the
+    scene's panoptic ids [N] (batch_eval.panoptic_batches), stored as `panoptic` only when given."""
     labels = labels.to_host()
     arrays = {"ids": labels.ids, "owner": labels.owner}
+    if panoptic is not None:
+        arrays["panoptic"] = panoptic.detach().cpu().numpy() if hasattr(panoptic, "detach") else np.asarray(panoptic)
     arrays.update({f"table_{k}": v for k, v in labels.table._asdict().items()})
     if labels.masks is not None:
         arrays["masks"] = labels.masks

@@ -997,6 +997,102 @@ def semantic_confusion(scores, labels, offsets, conf, *, lut=None, ignore_label=
     return preds
 
 
+def panoptic_limits():
+    """(largest row count P + n_stuff + 1, points per workgroup run) of gf_panoptic_overlaps."""
+    lib = _lib.load()
+    return lib.gf_panoptic_max_rows(), lib.gf_panoptic_run_points()
+
+
+def panoptic_layout(S, R, max_gt):
+    """Word offsets (int32 words) of panoptic_overlaps_packed's buffer: G [S] at 0, gt_id (int64 [S, max_gt]) at `id`,
+    inter [S, R, max_gt + 1] at `inter`, `total` words."""
+    o_id = (S + 1) // 2 * 2
+    o_inter = o_id + 2 * S * max_gt
+    return {"id": o_id, "inter": o_inter, "total": o_inter + S * R * (max_gt + 1)}
+
+
+def _panoptic_args(owner, ids, sem, gt_ids, offsets, class_ids, is_stuff, stuff_of_sem, offsets_host):
+    _i32c(owner, "owner"); _i32c(sem, "sem"); _i32c(offsets, "offsets")
+    _i32c(class_ids, "class_ids"); _i32c(is_stuff, "is_stuff"); _i32c(stuff_of_sem, "stuff_of_sem")
+    N, S = owner.shape[0], offsets.shape[0] - 1
+    if ids is not None:
+        _i32c(ids, "ids")
+    for name, t in (("owner", owner), ("ids", ids), ("sem", sem), ("gt_ids", gt_ids)):
+        if t is not None and t.shape != (N,):
+            raise RuntimeError(f"{name}: expected [{N}], one value per point")
+    if gt_ids is not None and not (gt_ids.is_cuda and gt_ids.dtype == torch.int64 and gt_ids.is_contiguous()):
+        raise RuntimeError("gt_ids: expected a contiguous int64 vector on the GPU")
+    if class_ids.shape != is_stuff.shape or class_ids.dim() != 1:
+        raise RuntimeError("class_ids / is_stuff: expected two [C] vectors")
+    if offsets_host is not None and not (offsets_host.device.type == "cpu" and offsets_host.dtype == torch.int32
+                                         and offsets_host.is_contiguous() and offsets_host.shape == (S + 1,)):
+        raise RuntimeError(f"offsets_host: expected a contiguous int32 [{S + 1}] host tensor")
+    return N, S
+
+
+def panoptic_overlaps_packed(owner, ids, sem, gt_ids, offsets, class_ids, is_stuff, stuff_of_sem, n_stuff, P,
+                             max_gt=256, offsets_host=None, want_pan=True):
+    """One gf_panoptic_overlaps call into a single int32 device buffer laid out by panoptic_layout(S, R, max_gt), so
+    that one device-to-host copy brings every table back.  No synchronisation: a scene's G may exceed max_gt, in which
+    case only its G is meaningful.  Returns (pan int32 [N] or None, buf, layout)."""
+    N, S = _panoptic_args(owner, ids, sem, gt_ids, offsets, class_ids, is_stuff, stuff_of_sem, offsets_host)
+    if gt_ids is None:
+        raise RuntimeError("gt_ids: needed for the tables (panoptic_points gives the labels alone)")
+    C = class_ids.shape[0]
+    R = int(P) + int(n_stuff) + 1
+    lay = panoptic_layout(S, R, int(max_gt))
+    dev = owner.device
+    buf = torch.empty(lay["total"], dtype=torch.int32, device=dev)
+    pan = torch.empty(N, dtype=torch.int32, device=dev) if want_pan else None
+    lib = _lib.load()
+    ws = scratch("panoptic", lib.gf_panoptic_overlaps_scratch_bytes(S, N, C) // 4 + 1, torch.int32, dev)
+    base = buf.data_ptr()
+    check(lib.gf_panoptic_overlaps(ptr(owner), ptr(ids) if want_pan else None, ptr(sem), ptr(gt_ids), ptr(offsets),
+                                   ptr(offsets_host), S, N, ptr(class_ids), ptr(is_stuff), C, ptr(stuff_of_sem),
+                                   stuff_of_sem.shape[0], int(n_stuff), int(P), int(max_gt), ptr(ws), ptr(pan), base,
+                                   base + 4 * lay["id"], base + 4 * lay["inter"], stream_ptr()), "gf_panoptic_overlaps")
+    return pan, buf, lay
+
+
+def panoptic_unpack(h, lay, S, R, max_gt):
+    """(G int32 [S], gt_id int64 [S, max_gt], inter int32 [S, R, max_gt + 1]) of a host copy of the packed buffer."""
+    G = h[:S]
+    gt_id = h[lay["id"]:lay["id"] + 2 * S * max_gt].view(np.int64).reshape(S, max_gt)
+    inter = h[lay["inter"]:lay["inter"] + S * R * (max_gt + 1)].reshape(S, R, max_gt + 1)
+    return G, gt_id, inter
+
+
+def panoptic_overlaps(owner, ids, sem, gt_ids, offsets, class_ids, is_stuff, stuff_of_sem, n_stuff, P, max_gt=256,
+                      offsets_host=None, want_pan=True):
+    """Panoptic ids and contingency tables of a batch of S scenes packed one after the other (gf_panoptic_overlaps):
+    (pan int32 [N] on the device, G int32 [S], gt_id int64 [S, max_gt], inter int32 [S, R, max_gt + 1], max_gt) with the
+    tables on the host (numpy; one device-to-host copy per call).  owner / ids / sem int32 [N], gt_ids int64 [N],
+    offsets int32 [S+1], class_ids / is_stuff int32 [C], stuff_of_sem int32 [L]: device tensors.  Rows: P thing rows,
+    n_stuff stuff rows, the unlabelled row; columns: a scene's segments in ascending key order, void at max_gt.  When a
+    scene has more than max_gt segments the call is repeated with room for them: the returned max_gt is the one used."""
+    S, R = offsets.shape[0] - 1, int(P) + int(n_stuff) + 1
+    while True:
+        pan, buf, lay = panoptic_overlaps_packed(owner, ids, sem, gt_ids, offsets, class_ids, is_stuff, stuff_of_sem,
+                                                 n_stuff, P, max_gt, offsets_host, want_pan)
+        G, gt_id, inter = panoptic_unpack(buf.cpu().numpy(), lay, S, R, max_gt)
+        if S == 0 or int(G.max()) <= max_gt:
+            return pan, G, gt_id, inter, max_gt
+        max_gt = int(G.max())  # nothing was written past the capacities: run again with room
+
+
+def panoptic_points(owner, ids, sem, offsets, class_ids, is_stuff, stuff_of_sem, n_stuff, P):
+    """Panoptic id of every point (gf_panoptic_overlaps without ground truth: one launch, no table): ids where the
+    point has an owner in [0, P), class_ids[j] * 1000 where the semantic class names stuff class j, 0 elsewhere."""
+    N, S = _panoptic_args(owner, ids, sem, None, offsets, class_ids, is_stuff, stuff_of_sem, None)
+    pan = torch.empty(N, dtype=torch.int32, device=owner.device)
+    if N:
+        check(_lib.load().gf_panoptic_overlaps(ptr(owner), ptr(ids), ptr(sem), None, ptr(offsets), None, S, N,
+                                               ptr(class_ids), ptr(is_stuff), class_ids.shape[0], ptr(stuff_of_sem),
+                                               stuff_of_sem.shape[0], int(n_stuff), int(P), 0, None, ptr(pan), None,
+                                               None, None, stream_ptr()), "gf_panoptic_overlaps")
+    return pan
+
+
 def backbone_transformer_params(before, transformer, after):
     """Device-pointer table of gf_backbone_transformer in the order include/geoformer_hip.h documents."""
     import ctypes

@@ -397,3 +397,40 @@ def label_points(masks, scores, label_ids, pick, xyz, min_score=MIN_SCORE):
         return label_points_batched([masks], [scores], [label_ids], [pick], [xyz], min_score)[0]
     h = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)  # noqa: E731
     return _label_points_host(h(masks), h(scores), h(label_ids), h(pick), h(xyz), min_score)
+
+
+# ---- panoptic labels (csrc/panoptic.hip): things from the label map, stuff from the semantic head -------------------
+def panoptic_points_batched(labels, sems, stuff=(1, 2), stuff_of_sem=None):
+    """Panoptic id of every point of several scenes at once on the GPU: labels: one SceneLabels per scene (device,
+    label_points_batched), sems: per scene the semantic head's class of every point (int32 [N_b], device;
+    batch_eval.semantic_batches, pointops.semantic_confusion).  pan = ids where the point has an owner, stuff id * 1000
+    where the semantic class names a stuff class (stuff: their nyu40 ids; stuff_of_sem: semantic class -> index into
+    `stuff` or -1, default class j -> stuff[j]: wall, floor), 0 elsewhere.  One launch (gf_panoptic_overlaps without
+    ground truth); returns one int32 tensor per scene, views of the batch's buffer."""
+    from . import pointops
+
+    if len(labels) != len(sems):
+        raise ValueError("panoptic_points_batched: one entry per scene in both lists")
+    if not labels:
+        return []
+    dev = labels[0].owner.device if torch.is_tensor(labels[0].owner) else None
+    if dev is None or dev.type != "cuda":
+        raise RuntimeError("panoptic_points_batched: the kernel runs on the GPU; evaluation.panoptic_overlaps_host has "
+                           "the numpy path")
+    Ns = [int(l.owner.shape[0]) for l in labels]
+    if any(int(x.shape[0]) != n for x, n in zip(sems, Ns)):
+        raise ValueError("panoptic_points_batched: sems and labels differ in their point counts")
+    i32 = lambda ts: torch.cat([torch.as_tensor(t, device=dev).to(torch.int32).reshape(-1) for t in ts]).contiguous()  # noqa: E731
+    off = np.concatenate([[0], np.cumsum(Ns)]).astype(np.int32)
+    stuff = [int(c) for c in stuff]
+    sos = np.arange(len(stuff), dtype=np.int32) if stuff_of_sem is None else np.asarray(stuff_of_sem, dtype=np.int32)
+    t = lambda a: torch.as_tensor(np.asarray(a, dtype=np.int32), device=dev)  # noqa: E731
+    P = max(int(l.table.count.shape[0]) for l in labels)
+    pan = pointops.panoptic_points(i32([l.owner for l in labels]), i32([l.ids for l in labels]), i32(sems), t(off),
+                                   t(stuff), t(np.ones(len(stuff))), t(sos), len(stuff), P)
+    return [pan[off[i]:off[i + 1]] for i in range(len(Ns))]
+
+
+def panoptic_points(labels, sem, stuff=(1, 2), stuff_of_sem=None):
+    """panoptic_points_batched of one scene: SceneLabels and the semantic classes in, pan int32 [N] out (device)."""
+    return panoptic_points_batched([labels], [sem], stuff, stuff_of_sem)[0]

@@ -861,6 +861,44 @@ int gf_semantic_confusion(const float* scores, const long long* labels, const in
                           void* stream);
 
 /* ===================================================================================
+ * Panoptic labels and the tables of panoptic quality (Kirillov et al., "Panoptic Segmentation", CVPR 2019) of a batch
+ * of S scenes packed one after the other: things from the label map (gf_label_map_batched), stuff from the semantic
+ * head (gf_semantic_confusion's preds), against the ground truth of gf_instance_overlaps.
+ *   Per point: owner int32 (rank into pick, or -1), ids int32 (the label map's ids; may be NULL when pan is NULL),
+ *   sem int32 (the semantic class), gt_ids int64 (val_gt encoding nyu40_id * 1000 + inst + 1, 0 = unannotated).
+ *   offsets int32 [S+1] (device) and offsets_host (host copy or NULL): as gf_semantic_confusion; given, offsets_host
+ *   is checked before anything is launched.  Not given, nothing is read back: no index leaves [0,N) x [0,S).
+ *   class_ids int32 [C] the evaluated nyu40 ids (distinct, positive; 1 <= C <= 64), is_stuff int32 [C],
+ *   stuff_of_sem int32 [L]: semantic class -> index into class_ids of a stuff class, or -1; n_stuff = the number of
+ *   stuff classes; P = the largest pick count of the batch; R = P + n_stuff + 1 <= gf_panoptic_max_rows() rows.
+ *   Row of a point: owner when 0 <= owner < P; else P + (rank of class_ids[stuff_of_sem[sem]] among the stuff classes
+ *   in class_ids order) when 0 <= sem < L names a stuff class; else R - 1 (unlabelled).  An owner or a semantic class
+ *   outside its range is never an address.
+ *   Column of a point: q = floor(gt / 1000); q not among class_ids: void; a thing: key rank(q) * 1000 + (gt - q * 1000);
+ *   a stuff class: key rank(q) * 1000 (all its instances are ONE segment).  The scene's distinct keys in ascending
+ *   order are columns 0..G_s-1, the void column is the LAST one, index max_gt; columns G_s..max_gt-1 stay zero.
+ *   Outputs: d_G int32 [S]; gt_id int64 [S, max_gt] (the original id of a thing, nyu40_id * 1000 of a stuff segment;
+ *   zero past G_s); inter int32 [S, R, max_gt + 1]: inter[s, r, g] = points of scene s with row r and column g;
+ *   pan int32 [N] (may be NULL): ids[i] on a thing row, class_ids[j] * 1000 on a stuff row, 0 where unlabelled.
+ *   G_s > max_gt: only d_G[s] is meaningful for that scene (its part of inter is zero) and nothing is written past
+ *   the capacities; the other scenes are complete.  The caller grows max_gt and repeats the call.
+ *   Four commands on `stream` whatever S, N and P are (presence memset; keys + pan; one slot scan per scene; count),
+ *   no host synchronisation; owner, sem and gt_ids are read once.  The count: a workgroup owns
+ *   gf_panoptic_run_points() consecutive points, cut at the scene boundaries; a scene whose R * (G_s + 1) bins fit the
+ *   LDS table is counted there and flushed as one integer atomic per non-zero bin, a larger one by wave-aggregated
+ *   global integer atomics (one per distinct pair per wave).  Exact and independent of the schedule.
+ *   gt_ids NULL (pan given): the labels alone, one launch; scratch, d_G, gt_id and inter are not touched (may be NULL).
+ *   scratch: gf_panoptic_overlaps_scratch_bytes(S, N, C). */
+int gf_panoptic_max_rows(void);
+int gf_panoptic_run_points(void);
+size_t gf_panoptic_overlaps_scratch_bytes(int S, int N, int C);
+int gf_panoptic_overlaps(const int32_t* owner, const int32_t* ids, const int32_t* sem, const long long* gt_ids,
+                         const int32_t* offsets, const int32_t* offsets_host, int S, int N, const int32_t* class_ids,
+                         const int32_t* is_stuff, int C, const int32_t* stuff_of_sem, int L, int n_stuff, int P,
+                         int max_gt, void* scratch, int32_t* pan, int32_t* d_G, long long* gt_id, int32_t* inter,
+                         void* stream);
+
+/* ===================================================================================
  * Backbone voxel transformer of the two deepest U-Net levels, fused (inference)
  * (UBlock: model/geoformer/geoformer_modules.py:64-68,120-127; TransformerEncoder(d_model=128, N,
  *  heads=4, d_ff=64): model/transformer.py:62-188)

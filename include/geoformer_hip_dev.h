@@ -103,6 +103,11 @@ int gf_dev_cross_attn_bf3(int on);
  * set it so that scene-sized graphs exercise the queues' overflow into global memory. */
 int gf_dev_bfs_qcap_max(int qcap);
 
+/* Capacity in bins of gf_panoptic_overlaps' LDS table: a scene with more than `bins` (row, column) pairs is counted by
+ * wave-aggregated global atomics instead.  0 = never the LDS table, -1 = default (the table's size, also the largest
+ * value).  Process-wide; tests reset with -1. */
+int gf_dev_panoptic_lds_bins(int bins);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,6 +5,7 @@ greedy NMS) and the scene labelling of batch_eval.label_batches, written with ge
     python tools/predict_scenes.py --out out --synthetic 8 --points 150000 --batch-size 4
     python tools/predict_scenes.py --synthetic 8 --no-write                          # only the timing
     python tools/predict_scenes.py --out out --semantic scene0011_00_inst_nostuff.npy   # + out/semantic/<name>.txt, mIoU
+    python tools/predict_scenes.py --out out --panoptic scene0011_00_inst_nostuff.npy   # + `panoptic` in the .npz, PQ
 
 Per scene <out>/<name>.npz (ids, owner, instance table: export.load_labels) and, with --scannet, <out>/<name>.txt plus
 <out>/predicted_masks/ (exclusive masks; --full-masks writes the picked masks as they are).  Without --checkpoint the
@@ -12,7 +13,10 @@ benchmark's synthetic model (bench.build_model) runs.  Prints one JSON line with
 label_batches loop, results on the host, for keep_masks off and on, beside the bare predict_batches loop (wall clock,
 host collate included, files not).  --semantic (or the yaml's save_semantic) adds one pass of
 batch_eval.semantic_batches: <out>/semantic/<name>.txt, the ScanNet semantic benchmark's file (one label id per point),
-and, when the scenes carry labels, the mIoU table of evaluation.SemanticEvaluator before the JSON line.
+and, when the scenes carry labels, the mIoU table of evaluation.SemanticEvaluator before the JSON line.  --panoptic
+takes the label maps from batch_eval.panoptic_batches instead: <out>/<name>.npz also holds `panoptic` (the instance id,
+1000 wall, 2000 floor, 0 unlabelled per point), and, when the scenes carry labels, the PQ / SQ / RQ table of
+evaluation.PanopticEvaluator is printed before the JSON line.
 """
 import argparse
 import json
@@ -42,6 +46,8 @@ def main():
     ap.add_argument("--scannet", action="store_true", help="also write the benchmark's .txt files")
     ap.add_argument("--full-masks", action="store_true", help="benchmark files hold the picked masks, not the exclusive ones")
     ap.add_argument("--semantic", action="store_true", help="also write <out>/semantic/<name>.txt and print the mIoU table")
+    ap.add_argument("--panoptic", action="store_true",
+                    help="also store the panoptic ids (things + wall / floor) in <out>/<name>.npz and print the PQ table")
     ap.add_argument("--no-write", action="store_true")
     ap.add_argument("--reps", type=int, default=3, help="timed passes per keep_masks setting")
     args = ap.parse_args()
@@ -80,11 +86,23 @@ def main():
         np.random.seed(0)
         return list(batch_eval.label_batches(model, items, args.batch_size, keep_masks=keep_masks, **kw))
 
-    results = run(args.full_masks)
+    pans, pq = {}, None
+    if args.panoptic:
+        from geoformer_amd import evaluation
+
+        np.random.seed(0)
+        pq = evaluation.PanopticEvaluator(classes=model.cfg.cvfold)
+        results = []
+        for name, lab, pan in batch_eval.panoptic_batches(model, items, args.batch_size, keep_masks=args.full_masks,
+                                                          evaluator=pq, **kw):
+            results.append((name, lab))
+            pans[name] = pan
+    else:
+        results = run(args.full_masks)
     if not args.no_write:
         os.makedirs(args.out, exist_ok=True)
         for name, lab in results:
-            export.save_labels(os.path.join(args.out, f"{name}.npz"), lab._replace(masks=None))
+            export.save_labels(os.path.join(args.out, f"{name}.npz"), lab._replace(masks=None), pans.get(name))
             if args.scannet:
                 export.write_scannet_predictions(args.out, name, lab, lab.masks if args.full_masks else None)
     if args.semantic or getattr(model.cfg, "save_semantic", False):
@@ -96,6 +114,8 @@ def main():
                 export.write_scannet_semantic(os.path.join(args.out, "semantic"), name, preds, model.cfg.train_fold)
         if any((raw[:, 6] != evaluation.IGNORE_LABEL).any() for _, raw in items):
             print(ev.format_results())
+    if pq is not None and any((raw[:, 6] != -100).any() for _, raw in items):
+        print(pq.format_results())
     pkw = {k: v for k, v in kw.items() if k != "min_score"}
 
     def predict_only():  # the loop without the labelling and without any copy of a result, for comparison
