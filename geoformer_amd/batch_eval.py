@@ -42,10 +42,28 @@ def scene_dict(raw):
             "label": r[:, 6].astype(np.int64), "instance": r[:, 7].astype(np.int64)}
 
 
-def collate_batches(raw_scenes, batch_size, spatial_shape=None, scale=50, full_scale_min=128):
+def _scene_segments(segments, name, n):
+    """int32 [n] over-segment ids of scene `name` from the mapping (range-checked), -1 everywhere when it has none."""
+    seg = segments.get(name)
+    if seg is None:
+        return np.full(n, -1, np.int32)
+    seg = seg.detach().cpu().numpy() if torch.is_tensor(seg) else np.asarray(seg)
+    if seg.shape != (n,) or not np.issubdtype(seg.dtype, np.integer):
+        raise ValueError(f"segments[{name!r}]: expected an integer array [{n}], one id per point, got {seg.dtype} "
+                         f"{seg.shape}")
+    if n and (int(seg.max()) > np.iinfo(np.int32).max or int(seg.min()) < np.iinfo(np.int32).min):
+        raise ValueError(f"segments[{name!r}]: ids must fit int32 (at most 2^31 - 1), got {int(seg.min())} .. "
+                         f"{int(seg.max())}")
+    return seg.astype(np.int32)
+
+
+def collate_batches(raw_scenes, batch_size, spatial_shape=None, scale=50, full_scale_min=128, segments=None):
     """(chunks of (name, raw), host batch dicts): the scenes in order, batch_size per batch (the last may be short).
     spatial_shape: a lower bound on every batch's voxel grid (a scene's results depend on the grid it runs on: a
-    stride-2 convolution drops the voxels at an odd extent's edge)."""
+    stride-2 convolution drops the voxels at an odd extent's edge).  segments: a mapping scene name -> integer array
+    [N] of over-segment ids (scene-local, negative = none); given, every batch dict carries "segments" (int32 [N] over
+    the batch's points, -1 for a scene the mapping does not name) and the eval forward pools its mask logits over
+    them."""
     items = list(raw_scenes)
     if batch_size < 1:
         raise ValueError("batch_size >= 1")
@@ -55,6 +73,9 @@ def collate_batches(raw_scenes, batch_size, spatial_shape=None, scale=50, full_s
         b = scene.collate_raw([scene_dict(r) for _, r in chunk], scale, full_scale_min)
         if spatial_shape is not None:
             b["spatial_shape"] = np.maximum(b["spatial_shape"], np.asarray(spatial_shape, dtype=b["spatial_shape"].dtype))
+        if segments is not None:
+            b["segments"] = torch.from_numpy(np.concatenate(
+                [_scene_segments(segments, name, np.asarray(r).shape[0]) for name, r in chunk]))
         batches.append(b)
     return chunks, batches
 
@@ -62,7 +83,7 @@ def collate_batches(raw_scenes, batch_size, spatial_shape=None, scale=50, full_s
 @torch.no_grad()
 def predict_batches(model, raw_scenes, batch_size, *, epoch=300, spatial_shape=None, nms_kernel="gaussian",
                     sigma=2.0, final_score_thresh=NMS_FINAL_SCORE, cvfold=None, reserve=True, device=None,
-                    semantic=None, nms="matrix", nms_thresh=None):
+                    semantic=None, nms="matrix", nms_thresh=None, segments=None):
     """Yields (name, cls_final, scores_final, masks_final, pick) per scene, in input order.  raw_scenes: iterable of
     (name, raw [N, 8]).  The NMS categories are the benchmark label ids of the classes (evaluation.benchmark_label_ids
     with cvfold, default model.cfg.cvfold).  A scene without proposals yields ([], [], [], empty pick).  reserve: size
@@ -70,7 +91,9 @@ def predict_batches(model, raw_scenes, batch_size, *, epoch=300, spatial_shape=N
     evaluation.SemanticEvaluator that is given every batch's semantic scores, labels, offsets and scene names (one
     launch on the forward's stream before the NMS, nothing read back); None: nothing is added to the loop.  nms:
     "matrix" (matrix NMS with nms_kernel / sigma / final_score_thresh) or "greedy" (class-agnostic greedy NMS at
-    nms_thresh, default model.cfg.TEST_NMS_THRESH; pick in pick order)."""
+    nms_thresh, default model.cfg.TEST_NMS_THRESH; pick in pick order).  segments: collate_batches' mapping of
+    over-segment ids; the forward pools the mask logits over them (every mask is then constant over a segment's
+    foreground points); None: nothing is added to the loop."""
     if nms not in ("matrix", "greedy"):
         raise ValueError(f"predict_batches: nms must be 'matrix' or 'greedy', got {nms!r}")
     if nms == "greedy" and nms_thresh is None:
@@ -78,7 +101,7 @@ def predict_batches(model, raw_scenes, batch_size, *, epoch=300, spatial_shape=N
     cvfold = model.cfg.cvfold if cvfold is None else cvfold
     dev = torch.device(device) if device is not None else next(model.parameters()).device
     model.eval()
-    chunks, batches = collate_batches(raw_scenes, batch_size, spatial_shape)
+    chunks, batches = collate_batches(raw_scenes, batch_size, spatial_shape, segments=segments)
     if not batches:
         return
     most = max(int(b["offsets"][-1]) for b in batches)

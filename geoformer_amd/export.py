@@ -116,3 +116,18 @@ def load_labels(path):
     with np.load(path) as z:
         table = InstanceTable(*[z[f"table_{k}"] for k in InstanceTable._fields])
         return SceneLabels(z["owner"], z["ids"], table, z["masks"] if "masks" in z.files else None)
+
+
+def load_scannet_segments(path):
+    """The over-segmentation of a ScanNet scene: field ``segIndices`` of ``<scene>_vh_clean_2.0.010000.segs.json`` (what
+    data/scannetv2/prepare_data_inst.py:50-57 reads) as int32 [N], one segment id per mesh vertex."""
+    import json
+
+    with open(path) as f:
+        seg = np.asarray(json.load(f)["segIndices"])
+    if seg.ndim != 1 or not (seg.size == 0 or np.issubdtype(seg.dtype, np.integer)):
+        raise ValueError(f"{path}: segIndices is not a list of integers")
+    seg = seg.astype(np.int64)
+    if seg.size and (seg.max() > np.iinfo(np.int32).max or seg.min() < np.iinfo(np.int32).min):
+        raise ValueError(f"{path}: segment ids must fit int32")
+    return seg.astype(np.int32)

@@ -160,6 +160,19 @@ def _stream_key(device=None):
     return (st.device.index, st.cuda_stream)
 
 
+def _segments_arg(segments, n_points=None):
+    """The batch dict's "segments" (or None): int32 [N], one over-segment id per point of the batch."""
+    if segments is None:
+        return None
+    if not torch.is_tensor(segments) or segments.dtype != torch.int32:
+        raise TypeError(f'"segments": expected an int32 tensor [N], one id per point of the batch, got '
+                        f"{segments.dtype if torch.is_tensor(segments) else type(segments).__name__}")
+    if segments.dim() != 1 or (n_points is not None and segments.shape[0] != n_points):
+        raise ValueError(f'"segments": expected [{n_points if n_points is not None else "N"}], one id per point of the '
+                         f"batch, got {tuple(segments.shape)}")
+    return segments
+
+
 class PendingProposals:
     """The tail of generate_proposal (geoformer.py:236-262) behind the forward's last device->host read-back.  The
     accepted queries are compacted on the device (indices, classes, scores); only their NUMBER travels to a pinned
@@ -1147,11 +1160,15 @@ class GeoFormer(nn.Module):
 
     def generate_proposal(self, mask_logits, cls_logits, fg_idxs, batch_offsets, batch_offsets_,
                           semantic_scores_=None, logit_thresh=0.5, score_thresh=0.5, npoint_thresh=100, sem_prob=None,
-                          defer=False, knn_flags=()):
+                          defer=False, knn_flags=(), segments=None):
         """Batch-1 proposal extraction (geoformer.py:193-262): score = mean mask prob * sqrt(cls prob) *
         mean semantic prob of the predicted class over the mask.  defer: return a PendingProposals instead of
-        waiting for the device (GPU inference only)."""
+        waiting for the device (GPU inference only).  segments (int32 [N], one over-segment id per point of the batch,
+        negative = none; honoured without grad only): the mask logits are pooled over the segments' foreground points
+        (csrc/segment_pool.hip; postprocess.segment_pool_host on the CPU) and the pooled ones take the raw ones' place
+        in everything below; mask_logits itself is left as it is."""
         b = 0
+        segments = None if torch.is_grad_enabled() else _segments_arg(segments)
         if mask_logits[b].is_cuda and not torch.is_grad_enabled():
             # inference: two fused HIP launches (csrc/proposal.hip) instead of ~40 PyTorch ones; the acceptance flags
             # come back in one small copy and the row selection is made on the host (nonzero() on the device is six
@@ -1173,26 +1190,44 @@ class GeoFormer(nn.Module):
                 main = torch.cuda.current_stream(logits.device)
                 side = _SIDE_STREAMS.get((logits.device, main.cuda_stream, "aux"))
             cls_b, sem_c, fg_c = cls_logits[b].contiguous(), sem_t.contiguous(), fg_idxs.contiguous()
+
+            def pooled(raw):  # (queued on the stream of the statistics)
+                n_b = raw.shape[1]
+                seg_fg = segments[fg_c[offs_[b]:offs_[b] + n_b]]
+                return pointops.segment_pool_batched([raw], seg_fg, [0, n_b])[0]
+
             if side is not None:
                 ready = torch.cuda.Event()
                 ready.record(main)
                 side.wait_event(ready)
+                raw = logits
                 with torch.cuda.stream(side):
+                    if segments is not None:
+                        logits = pooled(raw)
                     cls_pred, _, scores, final = pointops.proposal_stats(logits, cls_b, sem_c, logit_thresh, score_thresh,
                                                                          npoint_thresh, min_class=4, class_major=True)
                     pending = PendingProposals(final, cls_pred, scores, logits, fg_c, logit_thresh, num_points,
                                                knn_flags=knn_flags)
                 pending.home = main
-                for t in (logits, cls_b, sem_c, fg_c) + tuple(knn_flags):
+                for t in (raw, cls_b, sem_c, fg_c) + tuple(knn_flags) + (() if segments is None else (segments,)):
                     t.record_stream(side)
                 return pending
+            if segments is not None:
+                logits = pooled(logits)
             cls_pred, _, scores, final = pointops.proposal_stats(logits, cls_b, sem_c, logit_thresh, score_thresh,
                                                                  npoint_thresh, min_class=4, class_major=True)
             pending = PendingProposals(final, cls_pred, scores, logits, fg_c, logit_thresh, num_points, knn_flags=knn_flags)
             return pending if defer else pending.get()
         sem = sem_prob if sem_prob is not None and not isinstance(sem_prob, tuple) else F.softmax(semantic_scores_, dim=1)
         num_points = int(batch_offsets[b + 1] - batch_offsets[b])
-        mask_prob = mask_logits[b].sigmoid()
+        logits = mask_logits[b]
+        if segments is not None:
+            from .. import postprocess
+
+            lo = int(batch_offsets_[b])
+            seg_fg = segments[fg_idxs[lo:lo + logits.shape[1]]]
+            logits = torch.from_numpy(postprocess.segment_pool_host(logits, seg_fg)).to(logits.device)
+        mask_prob = logits.sigmoid()
         cls_prob = F.softmax(cls_logits[b], dim=-1)
         cls_pred = torch.argmax(cls_logits[b], dim=-1)
         sem_b = sem[int(batch_offsets_[b]):int(batch_offsets_[b + 1])]
@@ -1214,17 +1249,21 @@ class GeoFormer(nn.Module):
 
     def generate_proposals_batched(self, mask_logits, cls_logits, fg_idxs, batch_offsets, fg_offsets, scene_ids,
                                    n_scenes, sem_prob, logit_thresh=0.5, score_thresh=0.5, npoint_thresh=100,
-                                   defer=False, knn_flags=()):
+                                   defer=False, knn_flags=(), segments=None):
         """generate_proposal for every scene of the batch (geoformer.py:193-262 with b = 0..B-1) in a fixed number of
         launches (csrc/batch_post.hip): statistics over all (scene, query) pairs, per-scene selection, one read-back of
         all counts, one packed membership scatter.  mask_logits: per kept scene [nq, N_b]; cls_logits [S, nq, ncls];
         fg_offsets: host offsets of the kept scenes' foreground rows; scene_ids: the batch index of each kept scene;
-        sem_prob: (probabilities, class-major copy).  Returns the list of n_scenes tuples, or with defer a
+        sem_prob: (probabilities, class-major copy).  segments: as generate_proposal's, pooled for all kept scenes in
+        one gf_segment_pool_batched call on this stream.  Returns the list of n_scenes tuples, or with defer a
         PendingBatchProposals."""
         from .. import postprocess
 
         offs = _offsets_list(batch_offsets)
         logits = [ml.contiguous() for ml in mask_logits]
+        segments = _segments_arg(segments)
+        if segments is not None:
+            logits = pointops.segment_pool_batched(logits, segments[fg_idxs], fg_offsets)
         nq = logits[0].shape[0]
         starts = [offs[b] for b in scene_ids]
         npts = [offs[b + 1] - offs[b] for b in scene_ids]
@@ -1284,6 +1323,10 @@ class GeoFormer(nn.Module):
         batch_size = len(batch_offsets) - 1
         assert batch_size > 0
         pc_dims = [batch_input["pc_maxs"], batch_input["pc_mins"]]  # swapped on purpose (geoformer.py:412-415)
+        # over-segment ids of the points (optional): the eval forward pools the mask logits over them before the proposals
+        segments = _segments_arg(batch_input.get("segments"), locs_float.shape[0])
+        if training or torch.is_grad_enabled():
+            segments = None
 
         # inference on the GPU: arg-max, foreground test, index list and the four gathers in three launches before
         # the one read-back (csrc/foreground.hip) instead of max / compare / nonzero() / four gathers around it
@@ -1465,13 +1508,13 @@ class GeoFormer(nn.Module):
                     preds[-1]["mask_logits"], preds[-1]["cls_logits"], fg_idxs, batch_offsets, offs_, scene_ids,
                     n_scenes, sem_prob, logit_thresh=0.5, score_thresh=cfg.TEST_SCORE_THRESH,
                     npoint_thresh=cfg.TEST_NPOINT_THRESH, defer=defer_proposals,
-                    knn_flags=[f for f in (knn_truncated(graphs),) if f is not None])
+                    knn_flags=[f for f in (knn_truncated(graphs),) if f is not None], segments=segments)
             else:
                 outputs["proposal_scores"] = self.generate_proposal(
                     preds[-1]["mask_logits"], preds[-1]["cls_logits"], fg_idxs, batch_offsets, batch_offsets_,
                     semantic_scores_=semantic_scores_, logit_thresh=0.5, score_thresh=cfg.TEST_SCORE_THRESH,
                     npoint_thresh=cfg.TEST_NPOINT_THRESH, sem_prob=sem_prob, defer=defer_proposals,
-                    knn_flags=[f for f in (knn_truncated(graphs),) if f is not None])
+                    knn_flags=[f for f in (knn_truncated(graphs),) if f is not None], segments=segments)
         if locs_float.is_cuda:
             self._early().clear()
         return outputs

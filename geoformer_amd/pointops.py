@@ -1628,3 +1628,72 @@ def label_map_batched(table, sizes, min_score):
                                            ptr(pts[0]), ptr(pts[1]), ptr(tab_i), ptr(tab_f), stream_ptr()),
           "gf_label_map_batched")
     return pts[:, :points], tab_i[:rows], tab_f[:rows]
+
+
+# ---- mask logits pooled over over-segments (csrc/segment_pool.hip) ----------------------------------------------------
+def segment_pool_limits():
+    """(int64 words per row of the segment scene table, sorted positions per workgroup) of gf_segment_pool_batched."""
+    lib = _lib.load()
+    return lib.gf_segment_pool_scene_fields(), lib.gf_segment_pool_chunk_points()
+
+
+def segment_pool_keys(seg_fg, fg_offsets):
+    """(keys_sorted int64 [n_fg], order int32 [n_fg]) for gf_segment_pool_batched: one key per foreground row of the
+    batch -- (scene, id) where the id is >= 0, (scene, 2^32 + the row's index in its scene) where it is negative, so such
+    a row is a run of its own -- in one stable sort.  Framework plumbing on the current stream, nothing read back."""
+    _i32c(seg_fg, "seg_fg")
+    off = [int(o) for o in fg_offsets]
+    n_fg, S = off[-1], len(off) - 1
+    if seg_fg.shape != (n_fg,):
+        raise RuntimeError(f"seg_fg: expected [{n_fg}], one id per foreground point, got {tuple(seg_fg.shape)}")
+    dev = seg_fg.device
+    pos = torch.arange(n_fg, dtype=torch.int64, device=dev)
+    if S > 1:
+        off_d = torch.tensor(off, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+        scene = torch.bucketize(pos, off_d[1:], right=True)
+        pos = pos - off_d[scene]
+    else:
+        scene = None
+    seg = seg_fg.long()
+    key = torch.where(seg >= 0, seg, pos + (1 << 32))
+    if scene is not None:
+        key = key + (scene << 33)
+    keys_sorted, order = torch.sort(key, stable=True)
+    return keys_sorted, order.int()
+
+
+def segment_pool_batched(logits_list, seg_fg, fg_offsets):
+    """Mask logits pooled over the scenes' over-segments (postprocess.segment_pool_host per scene): a list of new fp32
+    tensors [nq, N_b], every foreground point's logit replaced by the mean over the foreground points of its scene that
+    carry its segment id; a point with a negative id keeps its logit.  logits_list: fp32 [nq, N_b] per kept scene of
+    the forward; seg_fg int32 [n_fg] on the device, the ids of the batch's foreground points (scene-local: the same id
+    in two scenes names two segments); fg_offsets: host offsets [S + 1] of the scenes' foreground rows.  A fixed number
+    of launches on the current stream, no synchronisation; bit-identical from call to call and for a scene alone."""
+    from . import postprocess
+
+    S = len(logits_list)
+    off = [int(o) for o in fg_offsets]
+    if len(off) != S + 1:
+        raise RuntimeError(f"segment_pool_batched: {S} scenes need {S + 1} foreground offsets")
+    if S == 0:
+        return []
+    nq = logits_list[0].shape[0]
+    for b, t in enumerate(logits_list):
+        _f32c(t, "mask_logits")
+        if t.shape != (nq, off[b + 1] - off[b]):
+            raise RuntimeError(f"segment_pool_batched: scene {b}: logits {tuple(t.shape)}, expected "
+                               f"[{nq}, {off[b + 1] - off[b]}]")
+    outs = [torch.empty_like(t) for t in logits_list]
+    n_fg = off[-1]
+    if n_fg == 0:
+        _i32c(seg_fg, "seg_fg")
+        return outs
+    keys_sorted, order = segment_pool_keys(seg_fg, off)
+    table = postprocess.segment_scene_table([t.data_ptr() for t in logits_list], [t.data_ptr() for t in outs], off)
+    dev = seg_fg.device
+    table_d = _table_dev(table, dev)
+    lib = _lib.load()
+    ws = torch.empty(lib.gf_segment_pool_scratch_bytes(S, n_fg, nq) // 4 + 1, dtype=torch.int32, device=dev)
+    check(lib.gf_segment_pool_batched(ptr(table_d), table.ctypes.data, S, nq, ptr(keys_sorted), ptr(order), n_fg,
+                                      int(table[:, 2].max()), ptr(ws), stream_ptr()), "gf_segment_pool_batched")
+    return outs

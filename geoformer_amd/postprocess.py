@@ -434,3 +434,47 @@ def panoptic_points_batched(labels, sems, stuff=(1, 2), stuff_of_sem=None):
 def panoptic_points(labels, sem, stuff=(1, 2), stuff_of_sem=None):
     """panoptic_points_batched of one scene: SceneLabels and the semantic classes in, pan int32 [N] out (device)."""
     return panoptic_points_batched([labels], [sem], stuff, stuff_of_sem)[0]
+
+
+# ---- mask logits pooled over over-segments (csrc/segment_pool.hip): the host statement ----------------------------------
+def segment_pool_host(logits, seg_fg):
+    """One scene's mask logits pooled over its over-segments -- the statement gf_segment_pool_batched is tested against,
+    and the CPU path of GeoFormer.generate_proposal.  logits fp32 [nq, n] over the scene's foreground points, seg_fg
+    int [n]: pooled[q, p] = mean of logits[q, p'] over {p' : seg_fg[p'] == seg_fg[p]} where seg_fg[p] >= 0 (float64
+    inside, rounded once to fp32), logits[q, p] where it is negative.  A segment of one point keeps its logit bit for
+    bit."""
+    x = logits.detach().cpu().numpy() if torch.is_tensor(logits) else np.asarray(logits)
+    seg = seg_fg.detach().cpu().numpy() if torch.is_tensor(seg_fg) else np.asarray(seg_fg)
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim != 2 or seg.shape != (x.shape[1],) or not np.issubdtype(seg.dtype, np.integer):
+        raise ValueError(f"segment_pool_host: logits [nq, n] and integer seg_fg [n] expected, got {x.shape} / "
+                         f"{seg.dtype} {seg.shape}")
+    out = x.copy()
+    pooled = np.nonzero(seg >= 0)[0]
+    if pooled.size:
+        _, inv, counts = np.unique(seg[pooled], return_inverse=True, return_counts=True)
+        inv = inv.reshape(-1)
+        by_seg = pooled[np.argsort(inv, kind="stable")]  # the members of each segment next to each other
+        starts = np.concatenate([[0], np.cumsum(counts)[:-1]])
+        sums = np.add.reduceat(x[:, by_seg].astype(np.float64), starts, axis=1)
+        many = counts[inv] > 1  # (a segment of one point: the copy above, not a round trip through float64)
+        mean = (sums / counts[None, :]).astype(np.float32)
+        out[:, pooled[many]] = mean[:, inv[many]]
+    return out
+
+
+def segment_scene_table(in_ptrs, out_ptrs, fg_offsets):
+    """int64 [S, fields] segment scene table of gf_segment_pool_batched: scene b's logits at in_ptrs[b], the pooled ones
+    at out_ptrs[b] (both [nq, N_b]), its foreground rows fg_offsets[b]:fg_offsets[b+1] of the batch."""
+    from . import _lib
+
+    fo = np.asarray(fg_offsets, dtype=np.int64).reshape(-1)
+    S = len(in_ptrs)
+    if fo.shape != (S + 1,) or len(out_ptrs) != S:
+        raise ValueError(f"segment_scene_table: {S} scenes need S output pointers and S+1 foreground offsets")
+    t = np.zeros((S, _lib.load().gf_segment_pool_scene_fields()), dtype=np.int64)
+    t[:, 0] = np.asarray(in_ptrs, dtype=np.int64)
+    t[:, 1] = np.asarray(out_ptrs, dtype=np.int64)
+    t[:, 2] = np.diff(fo)
+    t[:, 3] = fo[:-1]
+    return t

@@ -198,3 +198,20 @@ def make_raw_scene(n_points: int = 150_000, seed: int = 1234, n_boxes=None, inst
     out[:, 3:6] = sc["rgb"]
     out[:, 6], out[:, 7] = lab, inst
     return out
+
+
+def grid_segments(raw, cell=0.25):
+    """A synthetic over-segmentation of a raw [N, 8] scene (make_raw_scene), standing where ScanNet's
+    ``*_vh_clean_2.0.010000.segs.json`` would: int32 [N], the dense rank (from 0) of (semantic label, instance,
+    floor(xyz / cell)) for an annotated point, -1 for an unannotated one (label < 0).  No segment mixes two instances
+    or two labels; the same input gives the same ids."""
+    r = np.asarray(raw)
+    lab, inst = r[:, 6].astype(np.int64), r[:, 7].astype(np.int64)
+    cells = np.floor(r[:, :3].astype(np.float64) / float(cell)).astype(np.int64)
+    keys = np.concatenate([lab[:, None], inst[:, None], cells], axis=1)
+    seg = np.full(r.shape[0], -1, np.int32)
+    ann = np.nonzero(lab >= 0)[0]
+    if ann.size:
+        _, inv = np.unique(keys[ann], axis=0, return_inverse=True)
+        seg[ann] = inv.reshape(-1).astype(np.int32)
+    return seg

@@ -899,6 +899,40 @@ int gf_panoptic_overlaps(const int32_t* owner, const int32_t* ids, const int32_t
                          void* stream);
 
 /* ===================================================================================
+ * Mask logits pooled over a scene's over-segments (superpoints; ScanNet's *.segs.json, field segIndices) for the S
+ * kept scenes of an eval forward (csrc/segment_pool.hip), between the mask head and gf_proposal_stats*:
+ *     out[q, p] = mean of in[q, p'] over the foreground points p' of the scene in p's segment
+ *   Segment scene table, int64 [S, gf_segment_pool_scene_fields()], one row per scene:
+ *     {logits in (fp32 [nq, N_b]), logits out (fp32 [nq, N_b]), N_b (the scene's foreground points), fg_off (the
+ *      scene's first foreground row in the batch; the rows of the scenes follow each other)}.
+ *   table (device) and table_host (the same rows on the host, or NULL): given, table_host is checked before anything
+ *   is launched -- out == in (the pooling is out of place), a NULL pointer with N_b > 0, N_b > max_N, rows that do not
+ *   follow each other or do not add up to n_fg are GF_ERR_INVALID_ARG.  Not given, nothing is read back and a scene
+ *   whose row fails these checks is skipped on the device: no address leaves its buffer.
+ *   keys_sorted int64 [n_fg], order int32 [n_fg]: the batch's foreground rows sorted STABLY by one key per row that
+ *   orders them by scene first (so scene b keeps the positions fg_off .. fg_off + N_b) and is equal for two rows exactly
+ *   when they are pooled together; order[j] = the foreground row at sorted position j.  A row without a segment has a
+ *   key of its own.  The run boundaries are found on the device from neighbouring keys.
+ *   nq < 1, a negative size, n_fg > 2^31 - 16 or a NULL pointer with n_fg > 0 is GF_ERR_INVALID_ARG; S == 0 or
+ *   n_fg == 0 succeeds with nothing launched.  max_N = the largest N_b.
+ *   Eight commands on `stream` whatever S, nq and the segments are (run flags; a three-launch scan; run table; pool;
+ *   combine; open runs), no host synchronisation.  The logits are read once and written once.  A workgroup owns
+ *   gf_segment_pool_chunk_points() consecutive sorted positions of ONE scene, counted from the scene's first, and 16
+ *   queries; a segment inside a chunk gets its mean in the launch that read it, a segment cut by chunk boundaries is
+ *   summed per chunk, its partial sums are added in chunk order by the chunk it begins in, and the result is written
+ *   by a last launch.  No floating-point atomics: every (query, segment) sum is formed once, in fp32, in an order that
+ *   depends only on the positions inside the scene, and every member receives that one word divided by the member
+ *   count -- bit-identical from call to call and for a scene alone or inside a batch; a segment of one row returns
+ *   its logit bit for bit.
+ *   scratch: gf_segment_pool_scratch_bytes(S, n_fg, nq). */
+int gf_segment_pool_scene_fields(void);
+int gf_segment_pool_chunk_points(void);
+size_t gf_segment_pool_scratch_bytes(int S, long long n_fg, int nq);
+int gf_segment_pool_batched(const long long* table, const long long* table_host, int S, int nq,
+                            const long long* keys_sorted, const int32_t* order, long long n_fg, long long max_N,
+                            void* scratch, void* stream);
+
+/* ===================================================================================
  * Backbone voxel transformer of the two deepest U-Net levels, fused (inference)
  * (UBlock: model/geoformer/geoformer_modules.py:64-68,120-127; TransformerEncoder(d_model=128, N,
  *  heads=4, d_ff=64): model/transformer.py:62-188)

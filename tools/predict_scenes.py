@@ -6,6 +6,7 @@ greedy NMS) and the scene labelling of batch_eval.label_batches, written with ge
     python tools/predict_scenes.py --synthetic 8 --no-write                          # only the timing
     python tools/predict_scenes.py --out out --semantic scene0011_00_inst_nostuff.npy   # + out/semantic/<name>.txt, mIoU
     python tools/predict_scenes.py --out out --panoptic scene0011_00_inst_nostuff.npy   # + `panoptic` in the .npz, PQ
+    python tools/predict_scenes.py --out out --segments segs scene0011_00_inst_nostuff.npy  # masks pooled over segs/<name>*.segs.json
 
 Per scene <out>/<name>.npz (ids, owner, instance table: export.load_labels) and, with --scannet, <out>/<name>.txt plus
 <out>/predicted_masks/ (exclusive masks; --full-masks writes the picked masks as they are).  Without --checkpoint the
@@ -16,7 +17,10 @@ batch_eval.semantic_batches: <out>/semantic/<name>.txt, the ScanNet semantic ben
 and, when the scenes carry labels, the mIoU table of evaluation.SemanticEvaluator before the JSON line.  --panoptic
 takes the label maps from batch_eval.panoptic_batches instead: <out>/<name>.npz also holds `panoptic` (the instance id,
 1000 wall, 2000 floor, 0 unlabelled per point), and, when the scenes carry labels, the PQ / SQ / RQ table of
-evaluation.PanopticEvaluator is printed before the JSON line.
+evaluation.PanopticEvaluator is printed before the JSON line.  --segments DIR pools every scene's mask logits over its
+over-segmentation before the proposals (csrc/segment_pool.hip): <DIR>/<name>*.segs.json (ScanNet's, field segIndices)
+or <DIR>/<name>.segs.npy, one id per point; for the --synthetic scenes scene.grid_segments stands in (DIR is not read).
+The JSON line's `segment_pooling` says whether the pooling ran.
 """
 import argparse
 import json
@@ -48,6 +52,9 @@ def main():
     ap.add_argument("--semantic", action="store_true", help="also write <out>/semantic/<name>.txt and print the mIoU table")
     ap.add_argument("--panoptic", action="store_true",
                     help="also store the panoptic ids (things + wall / floor) in <out>/<name>.npz and print the PQ table")
+    ap.add_argument("--segments", default=None, metavar="DIR",
+                    help="pool the mask logits over each scene's over-segmentation: DIR/<name>*.segs.json or "
+                         "DIR/<name>.segs.npy (synthetic scenes: scene.grid_segments)")
     ap.add_argument("--no-write", action="store_true")
     ap.add_argument("--reps", type=int, default=3, help="timed passes per keep_masks setting")
     args = ap.parse_args()
@@ -77,6 +84,25 @@ def main():
         probe = scene.make_batch([batch_eval.scene_dict(items[0][1])])
         model = bench.build_model(dev, probe_batch=bench.to_device(probe, dev), cfg_name=args.config)
     kw = {"min_score": postprocess.MIN_SCORE if args.min_score is None else args.min_score}
+    if args.segments is not None:
+        import glob
+
+        segs = {}
+        for i, (name, raw) in enumerate(items):
+            if i >= len(args.scenes):  # a synthetic scene
+                segs[name] = scene.grid_segments(raw)
+                continue
+            npy = os.path.join(args.segments, f"{name}.segs.npy")
+            found = sorted(glob.glob(os.path.join(glob.escape(args.segments), glob.escape(name) + "*.segs.json")))
+            if os.path.exists(npy):
+                segs[name] = np.load(npy)
+            elif found:
+                segs[name] = export.load_scannet_segments(found[0])
+            else:
+                ap.error(f"--segments: neither {npy} nor {name}*.segs.json in {args.segments}")
+            if segs[name].shape != (raw.shape[0],):
+                ap.error(f"--segments: {name}: {segs[name].shape[0]} ids for {raw.shape[0]} points")
+        kw["segments"] = segs
     if args.nms_score is not None:
         kw["final_score_thresh"] = args.nms_score
     if args.nms != "matrix":
@@ -140,6 +166,7 @@ def main():
                       "points": int(sum(r.shape[0] for _, r in items)),
                       "picked": sum(len(lab.table.kept) for _, lab in results), "kept": kept,
                       "labelled_points": sum(int((lab.owner >= 0).sum()) for _, lab in results),
+                      "segment_pooling": "segments" in kw,
                       "scenes_per_s": rates, "out": None if args.no_write else args.out}))
 
 
