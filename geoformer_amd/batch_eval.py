@@ -42,6 +42,44 @@ def scene_dict(raw):
             "label": r[:, 6].astype(np.int64), "instance": r[:, 7].astype(np.int64)}
 
 
+class GeometricSegments:
+    """``segments=GeometricSegments(radius=0.06)`` (or ``segments="geometric"`` for the defaults): the over-segments are
+    not looked up by scene name but computed from each scene's points (pointops.oversegment; keywords k, radius,
+    normal_deg, offset, flatness, min_points as postprocess.oversegment_host).  predict_batches computes them on the
+    device, per scene of the batch, from the batch's ``locs_float``; collate_batches on host batches computes them on the
+    host."""
+
+    def __init__(self, **params):
+        unknown = sorted(set(params) - set(postprocess.OVERSEGMENT_DEFAULTS))
+        if unknown:
+            raise TypeError(f"GeometricSegments: unknown parameter(s) {', '.join(unknown)}; known: "
+                            f"{', '.join(postprocess.OVERSEGMENT_DEFAULTS)}")
+        self.params = dict(postprocess.OVERSEGMENT_DEFAULTS, **params)
+
+    def __repr__(self):
+        return f"GeometricSegments({', '.join(f'{k}={v!r}' for k, v in self.params.items())})"
+
+    def of_batch(self, locs_float, offsets_host):
+        """int32 [N] ids of a batch's points: one pointops.oversegment per scene (scene-local ids), on locs_float's device
+        and the current stream."""
+        from . import pointops
+
+        off = [int(o) for o in offsets_host]
+        parts = [pointops.oversegment(locs_float[off[b]:off[b + 1]].contiguous(), **self.params)
+                 for b in range(len(off) - 1)]
+        return torch.cat(parts) if parts else torch.empty(0, dtype=torch.int32, device=locs_float.device)
+
+
+def _geometric(segments):
+    """The GeometricSegments `segments` stands for, or None where it is a mapping (or None)."""
+    if isinstance(segments, str):
+        if segments != "geometric":
+            raise ValueError(f"segments: a mapping scene name -> ids, a GeometricSegments or 'geometric', got "
+                             f"{segments!r}")
+        return GeometricSegments()
+    return segments if isinstance(segments, GeometricSegments) else None
+
+
 def _scene_segments(segments, name, n):
     """int32 [n] over-segment ids of scene `name` from the mapping (range-checked), -1 everywhere when it has none."""
     seg = segments.get(name)
@@ -63,7 +101,9 @@ def collate_batches(raw_scenes, batch_size, spatial_shape=None, scale=50, full_s
     stride-2 convolution drops the voxels at an odd extent's edge).  segments: a mapping scene name -> integer array
     [N] of over-segment ids (scene-local, negative = none); given, every batch dict carries "segments" (int32 [N] over
     the batch's points, -1 for a scene the mapping does not name) and the eval forward pools its mask logits over
-    them."""
+    them.  A GeometricSegments (or "geometric"): the ids are computed here, on the host, from the batch's locs_float
+    (predict_batches computes them on the device instead)."""
+    geo = _geometric(segments)
     items = list(raw_scenes)
     if batch_size < 1:
         raise ValueError("batch_size >= 1")
@@ -73,7 +113,9 @@ def collate_batches(raw_scenes, batch_size, spatial_shape=None, scale=50, full_s
         b = scene.collate_raw([scene_dict(r) for _, r in chunk], scale, full_scale_min)
         if spatial_shape is not None:
             b["spatial_shape"] = np.maximum(b["spatial_shape"], np.asarray(spatial_shape, dtype=b["spatial_shape"].dtype))
-        if segments is not None:
+        if geo is not None:
+            b["segments"] = geo.of_batch(b["locs_float"], b["offsets"])
+        elif segments is not None:
             b["segments"] = torch.from_numpy(np.concatenate(
                 [_scene_segments(segments, name, np.asarray(r).shape[0]) for name, r in chunk]))
         batches.append(b)
@@ -93,7 +135,10 @@ def predict_batches(model, raw_scenes, batch_size, *, epoch=300, spatial_shape=N
     "matrix" (matrix NMS with nms_kernel / sigma / final_score_thresh) or "greedy" (class-agnostic greedy NMS at
     nms_thresh, default model.cfg.TEST_NMS_THRESH; pick in pick order).  segments: collate_batches' mapping of
     over-segment ids; the forward pools the mask logits over them (every mask is then constant over a segment's
-    foreground points); None: nothing is added to the loop."""
+    foreground points); None: nothing is added to the loop.  A GeometricSegments (or "geometric"): the ids of every
+    batch are computed on the device from its locs_float once the feeder has delivered it (one pointops.oversegment per
+    scene, on the forward's stream, nothing read back) and stored as the batch's "segments"."""
+    geo = _geometric(segments)
     if nms not in ("matrix", "greedy"):
         raise ValueError(f"predict_batches: nms must be 'matrix' or 'greedy', got {nms!r}")
     if nms == "greedy" and nms_thresh is None:
@@ -101,13 +146,15 @@ def predict_batches(model, raw_scenes, batch_size, *, epoch=300, spatial_shape=N
     cvfold = model.cfg.cvfold if cvfold is None else cvfold
     dev = torch.device(device) if device is not None else next(model.parameters()).device
     model.eval()
-    chunks, batches = collate_batches(raw_scenes, batch_size, spatial_shape, segments=segments)
+    chunks, batches = collate_batches(raw_scenes, batch_size, spatial_shape, segments=None if geo else segments)
     if not batches:
         return
     most = max(int(b["offsets"][-1]) for b in batches)
     if reserve:
         model.reserve_for(most)
     for chunk, host, batch in zip(chunks, batches, DeviceFeeder(batches, dev, reserve_points=most)):
+        if geo is not None:
+            batch["segments"] = geo.of_batch(batch["locs_float"], host["offsets"])
         out = model(batch, epoch, training=False, all_scenes=True)
         if semantic is not None:
             semantic.add_batch(out["semantic_scores"], batch["labels"], batch["offsets"], [n for n, _ in chunk],

@@ -131,3 +131,15 @@ def load_scannet_segments(path):
     if seg.size and (seg.max() > np.iinfo(np.int32).max or seg.min() < np.iinfo(np.int32).min):
         raise ValueError(f"{path}: segment ids must fit int32")
     return seg.astype(np.int32)
+
+
+def save_scannet_segments(path, ids):
+    """Write an over-segmentation (int [N], one id per point, negative = none; pointops.oversegment's or any other) as
+    ``{"segIndices": [...]}``, the field load_scannet_segments reads back unchanged."""
+    import json
+
+    seg = ids.detach().cpu().numpy() if hasattr(ids, "detach") else np.asarray(ids)
+    if seg.ndim != 1 or not (seg.size == 0 or np.issubdtype(seg.dtype, np.integer)):
+        raise ValueError(f"save_scannet_segments: expected an integer array [N], got {seg.dtype} {seg.shape}")
+    with open(path, "w") as f:
+        json.dump({"segIndices": [int(v) for v in seg]}, f)

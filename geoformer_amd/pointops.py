@@ -1697,3 +1697,63 @@ def segment_pool_batched(logits_list, seg_fg, fg_offsets):
     check(lib.gf_segment_pool_batched(ptr(table_d), table.ctypes.data, S, nq, ptr(keys_sorted), ptr(order), n_fg,
                                       int(table[:, 2].max()), ptr(ws), stream_ptr()), "gf_segment_pool_batched")
     return outs
+
+
+# ---- geometric over-segmentation (csrc/oversegment.hip) -----------------------------------------------------------------
+def _knn_rows(xyz, I, deg, name):
+    _f32c(xyz, "xyz"); _i32c(I, "I"); _i32c(deg, "deg")
+    n = xyz.shape[0]
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or I.dim() != 2 or I.shape[0] != n or I.shape[1] < 1 or deg.shape != (n,):
+        raise RuntimeError(f"{name}: expected xyz [n, 3], I [n, k >= 1] and deg [n], got {tuple(xyz.shape)}, "
+                           f"{tuple(I.shape)}, {tuple(deg.shape)}")
+    return n, I.shape[1]
+
+
+def point_normals(xyz, I, deg):
+    """fp32 [n, 4] = (nx, ny, nz, sigma) per point of one scene from its kNN rows (knn_radius' I and deg): stage A of
+    postprocess.oversegment_host (point_normals_host), one launch on the current stream."""
+    n, k = _knn_rows(xyz, I, deg, "point_normals")
+    out = torch.empty((n, 4), dtype=torch.float32, device=xyz.device)
+    check(_lib.load().gf_point_normals(ptr(xyz), ptr(I), ptr(deg), n, k, ptr(out), stream_ptr()), "gf_point_normals")
+    return out
+
+
+def smooth_components(xyz, normals4, I, deg, normal_deg=15.0, offset=0.012, flatness=0.01, min_points=8):
+    """int32 [n] over-segment ids (the smallest point index of the segment, or -1) from ANY kNN rows and ANY normals4
+    (fp32 [n, 4]): stages B-D of postprocess.oversegment_host (smooth_components_host).  Five launches on the current
+    stream, nothing read back; bit-identical from call to call."""
+    n, k = _knn_rows(xyz, I, deg, "smooth_components")
+    _f32c(normals4, "normals4")
+    if normals4.shape != (n, 4):
+        raise RuntimeError(f"smooth_components: expected normals4 [{n}, 4], got {tuple(normals4.shape)}")
+    if min_points < 1:
+        raise RuntimeError(f"smooth_components: min_points = {min_points} (at least 1)")
+    lib = _lib.load()
+    ids = torch.empty(n, dtype=torch.int32, device=xyz.device)
+    ws = torch.empty(lib.gf_smooth_components_scratch_bytes(n) // 4 + 1, dtype=torch.int32, device=xyz.device)
+    check(lib.gf_smooth_components(ptr(xyz), ptr(normals4), ptr(I), ptr(deg), n, k,
+                                   float(np.float32(np.cos(np.radians(normal_deg)))), float(offset), float(flatness),
+                                   int(min_points), ptr(ids), ptr(ws), stream_ptr()), "gf_smooth_components")
+    return ids
+
+
+def oversegment(xyz, k=16, radius=0.07, normal_deg=15.0, offset=0.012, flatness=0.01, min_points=8, return_flag=False):
+    """Geometric over-segmentation of one scene (postprocess.oversegment_host): int32 [n] ids, the id space
+    segment_pool_batched and the batch key "segments" accept.  xyz fp32 [n, 3] on the GPU: knn_radius(k, radius),
+    point_normals and smooth_components on the current stream, nothing read back; return_flag: also knn_radius'
+    truncation flag (int32 [1], device).  A CPU tensor runs the host statement (the flag is then None)."""
+    if not xyz.is_cuda:
+        from . import postprocess
+
+        ids = torch.from_numpy(postprocess.oversegment_host(xyz, k=k, radius=radius, normal_deg=normal_deg,
+                                                            offset=offset, flatness=flatness, min_points=min_points))
+        return (ids, None) if return_flag else ids
+    _f32c(xyz, "xyz")
+    if min_points < 1:
+        raise RuntimeError(f"oversegment: min_points = {min_points} (at least 1)")
+    if xyz.shape[0] == 0:
+        ids = torch.empty(0, dtype=torch.int32, device=xyz.device)
+        return (ids, torch.zeros(1, dtype=torch.int32, device=xyz.device)) if return_flag else ids
+    _, I, deg, flag = knn_radius(xyz, k, radius, sqrt_out=False, return_flag=True)
+    ids = smooth_components(xyz, point_normals(xyz, I, deg), I, deg, normal_deg, offset, flatness, min_points)
+    return (ids, flag) if return_flag else ids

@@ -478,3 +478,169 @@ def segment_scene_table(in_ptrs, out_ptrs, fg_offsets):
     t[:, 2] = np.diff(fo)
     t[:, 3] = fo[:-1]
     return t
+
+
+# ---- geometric over-segmentation (csrc/oversegment.hip): the host statement ---------------------------------------------
+OVERSEGMENT_DEFAULTS = dict(k=16, radius=0.07, normal_deg=15.0, offset=0.012, flatness=0.01, min_points=8)
+_SIGN_EPS = 1e-6  # a normal's first component of magnitude above this is made positive
+
+
+def _np(t):
+    return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+
+
+def knn_radius_host(xyz, k, radius):
+    """(I int32 [n, k], deg int32 [n]) in the format of gf_knn_radius: per point the k nearest points with
+    sqrt(d2) <= radius in fp32, ordered by (d2, index), itself included, -1 where there are fewer; deg = valid entries
+    after column 0.  Brute force in blocks of rows (O(n^2)): the CPU path of small scenes and tests."""
+    x = np.ascontiguousarray(_np(xyz), dtype=np.float32).reshape(-1, 3)
+    n = x.shape[0]
+    I = np.full((n, k), -1, np.int32)
+    deg = np.zeros(n, np.int32)
+    r = np.float32(radius)
+    idx = np.arange(n, dtype=np.int64)
+    for lo in range(0, n, 512):
+        d = x[lo:lo + 512, None, :] - x[None, :, :]
+        d2 = d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1] + d[..., 2] * d[..., 2]  # fp32, as the kernel forms it
+        inside = np.sqrt(d2) <= r
+        key = np.where(inside, d2.view(np.int32).astype(np.int64) << 32 | idx[None, :], np.iinfo(np.int64).max)
+        kk = min(k, n)
+        part = np.argpartition(key, kk - 1, axis=1)[:, :kk] if kk < n else np.broadcast_to(idx, key.shape)
+        pk = np.take_along_axis(key, part, axis=1)
+        order = np.argsort(pk, axis=1, kind="stable")
+        cols = np.take_along_axis(part, order, axis=1)
+        ok = np.take_along_axis(pk, order, axis=1) != np.iinfo(np.int64).max
+        I[lo:lo + 512, :kk] = np.where(ok, cols, -1)
+        deg[lo:lo + 512] = np.maximum(ok.sum(axis=1) - 1, 0)
+    return I, deg
+
+
+def _valid_entries(I, deg, n):
+    """bool [n, k]: the row entries that count -- column c <= deg[i] with an index inside [0, n)."""
+    k = I.shape[1]
+    return (np.arange(k)[None, :] <= deg[:, None]) & (I >= 0) & (I < n)
+
+
+def point_normals_host(xyz, I, deg, return_eigenvalues=False):
+    """Stage A of oversegment_host in float64: [n, 4] = (nx, ny, nz, sigma) per point from the kNN rows (I, deg).
+    The neighbourhood of point i is the valid entries of row i (gf_knn_radius lists i itself).  C is the covariance of
+    the differences x_j - x_i about their mean; with fewer than 3 entries, or where C's trace is not positive (all
+    entries in one place), the point is invalid: normal 0, sigma -1.  Otherwise the normal is the unit eigenvector of
+    the smallest eigenvalue with its first component of magnitude > 1e-6 positive and sigma = max(l0, 0) /
+    (l0 + l1 + l2).  return_eigenvalues: also C's eigenvalues [n, 3], ascending (a test's measure of how well the normal
+    is determined)."""
+    x = np.ascontiguousarray(_np(xyz), dtype=np.float32).reshape(-1, 3).astype(np.float64)
+    I, deg = np.asarray(_np(I)), np.asarray(_np(deg))
+    n = x.shape[0]
+    out = np.zeros((n, 4), np.float64)
+    out[:, 3] = -1.0
+    if n == 0:
+        return (out, np.zeros((0, 3))) if return_eigenvalues else out
+    ok = _valid_entries(I, deg, n)
+    m = ok.sum(axis=1)
+    d = (x[np.where(ok, I, 0)] - x[:, None, :]) * ok[..., None]
+    mm = np.maximum(m, 1)[:, None]
+    mean = d.sum(axis=1) / mm
+    dc = (d - mean[:, None, :]) * ok[..., None]
+    C = np.einsum("nka,nkb->nab", dc, dc) / mm[..., None]
+    w, v = np.linalg.eigh(C)
+    nrm = v[:, :, 0]
+    nrm = nrm / np.maximum(np.linalg.norm(nrm, axis=1, keepdims=True), 1e-300)
+    big = np.abs(nrm) > _SIGN_EPS
+    first = np.take_along_axis(nrm, np.argmax(big, axis=1)[:, None], axis=1)[:, 0]
+    nrm = nrm * np.where(big.any(axis=1) & (first < 0), -1.0, 1.0)[:, None]
+    tr = w.sum(axis=1)
+    sigma = np.where(tr > 0, np.maximum(w[:, 0], 0.0) / np.where(tr > 0, tr, 1.0), -1.0)
+    valid = (m >= 3) & (tr > 0)
+    out[valid, :3] = nrm[valid]
+    out[valid, 3] = sigma[valid]
+    return (out, w) if return_eigenvalues else out
+
+
+def smooth_components_host(xyz, normals4, I, deg, *, normal_deg=15.0, offset=0.012, flatness=0.01, min_points=8,
+                           margins=None):
+    """Stages B-D of oversegment_host in float64 from ANY rows and ANY normals4: int32 [n] ids (the smallest point
+    index of the component, or -1).  margins = (on the dot product, on the offsets): also returns the number of edge
+    and attach decisions whose left side lies within the margin of its threshold."""
+    x = np.ascontiguousarray(_np(xyz), dtype=np.float32).reshape(-1, 3).astype(np.float64)
+    nrm4 = np.asarray(_np(normals4), dtype=np.float64).reshape(-1, 4)
+    I, deg = np.asarray(_np(I)), np.asarray(_np(deg))
+    n = x.shape[0]
+    if min_points < 1:
+        raise ValueError("smooth_components_host: min_points >= 1")
+    if n == 0:
+        ids = np.zeros(0, np.int32)
+        return (ids, 0) if margins is not None else ids
+    cos_t = float(np.float32(np.cos(np.radians(normal_deg))))  # the fp32 word the kernel compares with
+    off_t = float(np.float32(offset))
+    nv, sigma = nrm4[:, :3], nrm4[:, 3]
+    flat = (sigma >= 0) & (sigma <= float(np.float32(flatness)))
+    ok = _valid_entries(I, deg, n)
+    src, col = np.nonzero(ok)
+    dst = I[src, col].astype(np.int64)
+    ambiguous = 0
+    # stage B: the row entries that link two flat points
+    e = (dst != src) & flat[src] & flat[dst]
+    a, b = src[e], dst[e]
+    dot = np.abs(np.einsum("ij,ij->i", nv[a], nv[b]))
+    dist = np.abs(np.einsum("ij,ij->i", nv[a], x[b] - x[a]))
+    link = (dot >= cos_t) & (dist <= off_t)
+    if margins is not None:
+        ambiguous += int(((np.abs(dot - cos_t) <= margins[0]) | (np.abs(dist - off_t) <= margins[1])).sum())
+    a, b = a[link], b[link]
+    # stage C: components by hooking the larger root under the smaller and halving the paths, until nothing moves
+    parent = np.arange(n, dtype=np.int64)
+    while True:
+        ra, rb = parent[a], parent[b]
+        hi, lo = np.maximum(ra, rb), np.minimum(ra, rb)
+        if not (hi != lo).any():
+            break
+        np.minimum.at(parent, hi, lo)
+        while True:
+            nxt = parent[parent]
+            if (nxt == parent).all():
+                break
+            parent = nxt
+    ids = np.full(n, -1, np.int64)
+    ids[flat] = parent[flat]
+    size = np.bincount(ids[flat], minlength=n) if flat.any() else np.zeros(n, np.int64)
+    kept = flat & (size[np.maximum(ids, 0)] >= min_points)
+    ids[~kept] = -1
+    # stage D: a non-flat point takes the id of the first kept flat entry of its row whose plane it lies on
+    t = ~flat[src] & kept[dst]
+    s, c, j = src[t], col[t], dst[t]
+    dist = np.abs(np.einsum("ij,ij->i", nv[j], x[s] - x[j]))
+    if margins is not None:
+        ambiguous += int((np.abs(dist - off_t) <= margins[1]).sum())
+    hit = dist <= off_t
+    s, c, j = s[hit], c[hit], j[hit]
+    first = np.full(n, I.shape[1], np.int64)
+    np.minimum.at(first, s, c)
+    take = first[s] == c
+    ids[s[take]] = ids[j[take]]
+    ids = ids.astype(np.int32)
+    return (ids, ambiguous) if margins is not None else ids
+
+
+def oversegment_host(xyz, I=None, deg=None, *, k=16, radius=0.07, normal_deg=15.0, offset=0.012, flatness=0.01,
+                     min_points=8, return_ambiguous=False, margins=None):
+    """Geometric over-segmentation of one scene -- the statement gf_point_normals / gf_smooth_components are tested
+    against, and the CPU path of pointops.oversegment.  xyz [n, 3]; (I, deg): kNN rows as gf_knn_radius emits them, built
+    here (knn_radius_host(k, radius)) when not given.  int32 [n]: ids >= 0 (the smallest point index of the segment) or -1.
+      A  per point the normal and the surface variation sigma of its row's points (point_normals_host); a point is
+         FLAT when 0 <= sigma <= flatness.
+      B  a row entry (i, j), j != i, links i and j when both are flat, |n_i . n_j| >= cos(normal_deg) and
+         |n_i . (x_j - x_i)| <= offset; one passing direction suffices.
+      C  connected components of the flat points; one with fewer than min_points points is dissolved (-1).
+      D  a non-flat point takes the id of the first j of its row, in row order, that is flat and kept and has
+         |n_j . (x_i - x_j)| <= offset; -1 without one.
+    return_ambiguous: also the number of edge (B) and attach (D) decisions whose left side lies within margins =
+    (on the dot product, on the offsets; default (1e-5, 1e-5 * radius)) of its threshold."""
+    x = np.ascontiguousarray(_np(xyz), dtype=np.float32).reshape(-1, 3)
+    if I is None:
+        I, deg = knn_radius_host(x, k, radius)
+    if margins is None and return_ambiguous:
+        margins = (1e-5, 1e-5 * radius)
+    normals4 = point_normals_host(x, I, deg)
+    return smooth_components_host(x, normals4, I, deg, normal_deg=normal_deg, offset=offset, flatness=flatness,
+                                  min_points=min_points, margins=margins if return_ambiguous else None)

@@ -933,6 +933,36 @@ int gf_segment_pool_batched(const long long* table, const long long* table_host,
                             void* scratch, void* stream);
 
 /* ===================================================================================
+ * Geometric over-segmentation of one scene (csrc/oversegment.hip; the statement is postprocess.oversegment_host):
+ * the over-segment ids gf_segment_pool_batched pools over, from the points alone.  Both functions read kNN rows in
+ * gf_knn_radius' format -- I int32 [n,k], deg int32 [n] = valid entries after column 0 -- but accept ANY rows: only
+ * columns 0 .. min(deg[i], k - 1) of row i are read, and an entry outside [0, n) is skipped, never followed.
+ * n < 0, k < 1, a NULL pointer with n > 0 (and min_points < 1) are GF_ERR_INVALID_ARG before anything is launched;
+ * n == 0 succeeds with nothing launched.  Every launch goes on `stream`; no host synchronisation, no read-back.
+ *
+ * gf_point_normals (stage A, one launch, no scratch): out fp32 [n,4] = (nx, ny, nz, sigma), 16-byte aligned.  The
+ *   neighbourhood of point i is the row's entries that count (the row normally lists i itself).  Fewer than 3,
+ *   or all of them in one place (the covariance's trace is not positive): (0, 0, 0, -1).  Otherwise the fp32 covariance of
+ *   the differences x_j - x_i about their own mean, its eigenvectors by a fixed number of cyclic Jacobi sweeps, the unit
+ *   eigenvector of the smallest eigenvalue l0 with its first component of magnitude > 1e-6 made positive, and
+ *   sigma = max(l0, 0) / (l0 + l1 + l2).
+ *
+ * gf_smooth_components (stages B-D, five launches): ids_out int32 [n] from ANY rows and ANY normals4 (fp32 [n,4],
+ *   16-byte aligned).  A point is flat when 0 <= sigma <= flatness.  A row entry (i, j), j != i, links two flat points
+ *   when |n_i . n_j| >= cos_thresh and |n_i . (x_j - x_i)| <= offset (one direction suffices).  A connected component
+ *   of flat points gets its smallest point index as id; one with fewer than min_points points gets -1.  A non-flat
+ *   point takes the id of the first entry j of its row that is flat, kept and has |n_j . (x_i - x_j)| <= offset, else
+ *   -1.  Union-find over an int32 parent array, the larger root hooked under the smaller by atomicCAS; integer atomics
+ *   only.  The ids are a function of the inputs alone: bit-identical from call to call.
+ *   scratch: gf_smooth_components_scratch_bytes(n). */
+size_t gf_point_normals_scratch_bytes(int n);
+int gf_point_normals(const float* xyz, const int32_t* I, const int32_t* deg, int n, int k, float* out, void* stream);
+size_t gf_smooth_components_scratch_bytes(int n);
+int gf_smooth_components(const float* xyz, const float* normals4, const int32_t* I, const int32_t* deg, int n, int k,
+                         float cos_thresh, float offset, float flatness, int min_points, int32_t* ids_out,
+                         void* scratch, void* stream);
+
+/* ===================================================================================
  * Backbone voxel transformer of the two deepest U-Net levels, fused (inference)
  * (UBlock: model/geoformer/geoformer_modules.py:64-68,120-127; TransformerEncoder(d_model=128, N,
  *  heads=4, d_ff=64): model/transformer.py:62-188)

@@ -7,6 +7,7 @@ greedy NMS) and the scene labelling of batch_eval.label_batches, written with ge
     python tools/predict_scenes.py --out out --semantic scene0011_00_inst_nostuff.npy   # + out/semantic/<name>.txt, mIoU
     python tools/predict_scenes.py --out out --panoptic scene0011_00_inst_nostuff.npy   # + `panoptic` in the .npz, PQ
     python tools/predict_scenes.py --out out --segments segs scene0011_00_inst_nostuff.npy  # masks pooled over segs/<name>*.segs.json
+    python tools/predict_scenes.py --out out --geometric-segments scene0011_00_inst_nostuff.npy  # ... over segments made from the points
 
 Per scene <out>/<name>.npz (ids, owner, instance table: export.load_labels) and, with --scannet, <out>/<name>.txt plus
 <out>/predicted_masks/ (exclusive masks; --full-masks writes the picked masks as they are).  Without --checkpoint the
@@ -20,7 +21,9 @@ takes the label maps from batch_eval.panoptic_batches instead: <out>/<name>.npz 
 evaluation.PanopticEvaluator is printed before the JSON line.  --segments DIR pools every scene's mask logits over its
 over-segmentation before the proposals (csrc/segment_pool.hip): <DIR>/<name>*.segs.json (ScanNet's, field segIndices)
 or <DIR>/<name>.segs.npy, one id per point; for the --synthetic scenes scene.grid_segments stands in (DIR is not read).
-The JSON line's `segment_pooling` says whether the pooling ran.
+--geometric-segments (instead of --segments) computes the over-segmentation on the GPU from every scene's points
+(pointops.oversegment with its defaults, csrc/oversegment.hip), for given and synthetic scenes alike.
+The JSON line's `segment_pooling` says whether the pooling ran, `geometric_segments` where the segments came from.
 """
 import argparse
 import json
@@ -52,9 +55,13 @@ def main():
     ap.add_argument("--semantic", action="store_true", help="also write <out>/semantic/<name>.txt and print the mIoU table")
     ap.add_argument("--panoptic", action="store_true",
                     help="also store the panoptic ids (things + wall / floor) in <out>/<name>.npz and print the PQ table")
-    ap.add_argument("--segments", default=None, metavar="DIR",
-                    help="pool the mask logits over each scene's over-segmentation: DIR/<name>*.segs.json or "
-                         "DIR/<name>.segs.npy (synthetic scenes: scene.grid_segments)")
+    seg_from = ap.add_mutually_exclusive_group()
+    seg_from.add_argument("--geometric-segments", action="store_true",
+                          help="pool the mask logits over a geometric over-segmentation computed on the GPU from each "
+                               "scene's points (batch_eval.GeometricSegments with its defaults)")
+    seg_from.add_argument("--segments", default=None, metavar="DIR",
+                          help="pool the mask logits over each scene's over-segmentation: DIR/<name>*.segs.json or "
+                               "DIR/<name>.segs.npy (synthetic scenes: scene.grid_segments)")
     ap.add_argument("--no-write", action="store_true")
     ap.add_argument("--reps", type=int, default=3, help="timed passes per keep_masks setting")
     args = ap.parse_args()
@@ -103,6 +110,8 @@ def main():
             if segs[name].shape != (raw.shape[0],):
                 ap.error(f"--segments: {name}: {segs[name].shape[0]} ids for {raw.shape[0]} points")
         kw["segments"] = segs
+    if args.geometric_segments:
+        kw["segments"] = batch_eval.GeometricSegments()
     if args.nms_score is not None:
         kw["final_score_thresh"] = args.nms_score
     if args.nms != "matrix":
@@ -166,7 +175,7 @@ def main():
                       "points": int(sum(r.shape[0] for _, r in items)),
                       "picked": sum(len(lab.table.kept) for _, lab in results), "kept": kept,
                       "labelled_points": sum(int((lab.owner >= 0).sum()) for _, lab in results),
-                      "segment_pooling": "segments" in kw,
+                      "segment_pooling": "segments" in kw, "geometric_segments": args.geometric_segments,
                       "scenes_per_s": rates, "out": None if args.no_write else args.out}))
 
 
