@@ -819,6 +819,70 @@ extern "C" size_t gf_fps_scratch_bytes(int b) {
     return ((size_t)b * 2 * FPS_MAXG * FPS_KPUB + 8) * sizeof(unsigned long long);
 }
 
+// device flag set when an exchange gave up waiting for a workgroup (FPS_SPIN_LIMIT; the picks are then wrong)
+extern "C" const int32_t* gf_fps_error_flag(void* scratch, int b) {
+    return (const int32_t*)((unsigned long long*)scratch + (size_t)b * 2 * FPS_MAXG * FPS_KPUB);
+}
+
+// The launch geometry of one point-set size: the tie-break block, the cooperating workgroups, the points per lane, the
+// k_fps<inst> instantiation that holds them and the point sets per launch (gf_dev_fps_plan's outputs).  bad: the size
+// the kernel cannot take (the caller reports it).
+enum { FPS_PLAN_OK = 0, FPS_PLAN_INDEX, FPS_PLAN_POINTS };
+struct FpsPlan {
+    int bs_log2 = 0, G = 1, P = 1, inst = 1, per_launch = 1, bad = FPS_PLAN_OK;
+};
+#define FPS_MAX_P 22  // the largest instantiation
+#define FPS_CHECK_PLAN_INDEX(pl, n)                                                                                   \
+    GF_CHECK_ARG((pl).bad != FPS_PLAN_INDEX, "gf_furthest_point_sampling: n=%d exceeds the 22-bit index of the tie-break key", \
+                 n)
+#define FPS_CHECK_PLAN_POINTS(pl, n)                                                                     \
+    GF_CHECK_ARG((pl).bad != FPS_PLAN_POINTS, "gf_furthest_point_sampling: n=%d too large (max %d)", n, \
+                 FPS_MAXG * FPS_PW * 64 * FPS_MAX_P)
+
+static FpsPlan fps_plan(int n) {
+    FpsPlan pl;
+    if (n >= (1 << 22)) {
+        pl.bad = FPS_PLAN_INDEX;
+        return pl;
+    }
+    // reference launch geometry decides ties: bs = largest power of two <= n, capped at 512
+    while ((2 << pl.bs_log2) <= n && pl.bs_log2 < 9) pl.bs_log2++;
+    const int per_wg = FPS_PW * 64;  // lanes that hold points
+    int G = (2 * n + per_wg * 5 - 1) / (per_wg * 5);  // ~2.5 points per lane (40 000 points: 16 workgroups; 13 at 3 per lane cost the forward 1.8 %)
+    if (G < 1) G = 1;
+    if (G > FPS_MAXG) G = FPS_MAXG;
+    pl.G = G;
+    pl.P = (n + G * per_wg - 1) / (G * per_wg);
+    if (pl.P > FPS_MAX_P) {
+        pl.bad = FPS_PLAN_POINTS;
+        return pl;
+    }
+    static const int ladder[] = {1, 2, 3, 4, 5, 6, 8, 12, 16, 20, FPS_MAX_P};  // the instantiations the launch switches over
+    for (int inst : ladder) {
+        if (pl.P <= inst) {
+            pl.inst = inst;
+            break;
+        }
+    }
+    pl.per_launch = 1024 / (G * FPS_WAVES) > 0 ? 1024 / (G * FPS_WAVES) : 1;  // all cooperating waves resident
+    return pl;
+}
+
+// Dev hook (include/geoformer_hip_dev.h): the geometry gf_furthest_point_sampling launches with for n points
+extern "C" int gf_dev_fps_plan(int n, int* G, int* P, int* inst, int* bs_log2, int* per_launch) {
+    GF_CHECK_ARG(n >= 1, "gf_dev_fps_plan: bad size n=%d", n);
+    GF_CHECK_ARG(G && P && inst && bs_log2 && per_launch, "gf_dev_fps_plan: an output is null");
+    const FpsPlan pl = fps_plan(n);
+    FPS_CHECK_PLAN_INDEX(pl, n);
+    FPS_CHECK_PLAN_POINTS(pl, n);
+    *G = pl.G;
+    *P = pl.P;
+    *inst = pl.inst;
+    *bs_log2 = pl.bs_log2;
+    *per_launch = pl.per_launch;
+    return GF_OK;
+}
+
 extern "C" int gf_furthest_point_sampling_resume(const float* xyz, int b, int n, int m, int m_known, int32_t* idxs,
                                                  void* scratch, void* stream);
 
@@ -835,35 +899,30 @@ extern "C" int gf_furthest_point_sampling_resume(const float* xyz, int b, int n,
     GF_CHECK_ARG(m_known >= 0 && m_known <= m, "gf_furthest_point_sampling_resume: m_known=%d not in [0, m=%d]", m_known,
                  m);
     if (m_known == m && m > 0) return GF_OK;
-    GF_CHECK_ARG(n < (1 << 22), "gf_furthest_point_sampling: n=%d exceeds the 22-bit index of the tie-break key", n);
+    const FpsPlan pl = fps_plan(n);
+    FPS_CHECK_PLAN_INDEX(pl, n);
     if (b == 0 || m == 0) return GF_OK;
     hipStream_t st = (hipStream_t)stream;
-    // reference launch geometry decides ties: bs = largest power of two <= n, capped at 512
-    int bs_log2 = 0;
-    while ((2 << bs_log2) <= n && bs_log2 < 9) bs_log2++;
-    const int per_wg = FPS_PW * 64;  // lanes that hold points
-    int G = (2 * n + per_wg * 5 - 1) / (per_wg * 5);  // ~2.5 points per lane (40 000 points: 16 workgroups; 13 at 3 per lane cost the forward 1.8 %)
-    if (G < 1) G = 1;
-    if (G > FPS_MAXG) G = FPS_MAXG;
-    const int P = (n + G * per_wg - 1) / (G * per_wg);
-    GF_CHECK_ARG(P <= 22, "gf_furthest_point_sampling: n=%d too large (max %d)", n, FPS_MAXG * per_wg * 22);
+    FPS_CHECK_PLAN_POINTS(pl, n);
+    const int G = pl.G, bs_log2 = pl.bs_log2;
     unsigned long long* slots = (unsigned long long*)scratch;
     int* err = (int*)(slots + (size_t)b * 2 * FPS_MAXG * FPS_KPUB);
     GF_TRY(hipMemsetAsync(scratch, 0, gf_fps_scratch_bytes(b), st));
-    const int per_launch = 1024 / (G * FPS_WAVES) > 0 ? 1024 / (G * FPS_WAVES) : 1;  // all cooperating waves resident
-    for (int b0 = 0; b0 < b; b0 += per_launch) {
-        const int nb = (b - b0) < per_launch ? (b - b0) : per_launch;
-        if (P <= 1) launch_fps<1>(G, nb, st, xyz, n, m, m_known, bs_log2, b0, slots, idxs, err);
-        else if (P <= 2) launch_fps<2>(G, nb, st, xyz, n, m, m_known, bs_log2, b0, slots, idxs, err);
-        else if (P <= 3) launch_fps<3>(G, nb, st, xyz, n, m, m_known, bs_log2, b0, slots, idxs, err);
-        else if (P <= 4) launch_fps<4>(G, nb, st, xyz, n, m, m_known, bs_log2, b0, slots, idxs, err);
-        else if (P <= 5) launch_fps<5>(G, nb, st, xyz, n, m, m_known, bs_log2, b0, slots, idxs, err);
-        else if (P <= 6) launch_fps<6>(G, nb, st, xyz, n, m, m_known, bs_log2, b0, slots, idxs, err);
-        else if (P <= 8) launch_fps<8>(G, nb, st, xyz, n, m, m_known, bs_log2, b0, slots, idxs, err);
-        else if (P <= 12) launch_fps<12>(G, nb, st, xyz, n, m, m_known, bs_log2, b0, slots, idxs, err);
-        else if (P <= 16) launch_fps<16>(G, nb, st, xyz, n, m, m_known, bs_log2, b0, slots, idxs, err);
-        else if (P <= 20) launch_fps<20>(G, nb, st, xyz, n, m, m_known, bs_log2, b0, slots, idxs, err);
-        else launch_fps<22>(G, nb, st, xyz, n, m, m_known, bs_log2, b0, slots, idxs, err);
+    for (int b0 = 0; b0 < b; b0 += pl.per_launch) {
+        const int nb = (b - b0) < pl.per_launch ? (b - b0) : pl.per_launch;
+        switch (pl.inst) {
+        case 1: launch_fps<1>(G, nb, st, xyz, n, m, m_known, bs_log2, b0, slots, idxs, err); break;
+        case 2: launch_fps<2>(G, nb, st, xyz, n, m, m_known, bs_log2, b0, slots, idxs, err); break;
+        case 3: launch_fps<3>(G, nb, st, xyz, n, m, m_known, bs_log2, b0, slots, idxs, err); break;
+        case 4: launch_fps<4>(G, nb, st, xyz, n, m, m_known, bs_log2, b0, slots, idxs, err); break;
+        case 5: launch_fps<5>(G, nb, st, xyz, n, m, m_known, bs_log2, b0, slots, idxs, err); break;
+        case 6: launch_fps<6>(G, nb, st, xyz, n, m, m_known, bs_log2, b0, slots, idxs, err); break;
+        case 8: launch_fps<8>(G, nb, st, xyz, n, m, m_known, bs_log2, b0, slots, idxs, err); break;
+        case 12: launch_fps<12>(G, nb, st, xyz, n, m, m_known, bs_log2, b0, slots, idxs, err); break;
+        case 16: launch_fps<16>(G, nb, st, xyz, n, m, m_known, bs_log2, b0, slots, idxs, err); break;
+        case 20: launch_fps<20>(G, nb, st, xyz, n, m, m_known, bs_log2, b0, slots, idxs, err); break;
+        default: launch_fps<FPS_MAX_P>(G, nb, st, xyz, n, m, m_known, bs_log2, b0, slots, idxs, err); break;
+        }
     }
     GF_CHECK_LAUNCH("gf_furthest_point_sampling");
     return GF_OK;

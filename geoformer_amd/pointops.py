@@ -131,9 +131,10 @@ def ball_query(new_xyz, xyz, radius, nsample, grid=None):
     return idx
 
 
-def furthest_point_sampling(xyz, m, known=None):
+def furthest_point_sampling(xyz, m, known=None, check=False):
     """FPS indices [b,m] (int32).  known: the first picks [b,m0] of the same sequence from an earlier call with a
-    smaller m -- the draw continues from there (same result as one call with m)."""
+    smaller m -- the draw continues from there (same result as one call with m).  check: read the kernel's error word
+    back after the call (one synchronisation) and raise if it is set."""
     _f32c(xyz, "xyz")
     b, n, _ = xyz.shape
     lib = _lib.load()
@@ -144,8 +145,13 @@ def furthest_point_sampling(xyz, m, known=None):
         _i32c(known, "known")
         m0 = min(int(known.shape[1]), m)
         idx[:, :m0] = known[:, :m0]
-    check(lib.gf_furthest_point_sampling_resume(ptr(xyz), b, n, m, m0, ptr(idx), ptr(scratch), stream_ptr()),
-          "gf_furthest_point_sampling")
+    _lib.check(lib.gf_furthest_point_sampling_resume(ptr(xyz), b, n, m, m0, ptr(idx), ptr(scratch), stream_ptr()),
+               "gf_furthest_point_sampling")
+    if check and b > 0 and m0 < m:  # (otherwise nothing was launched and the scratch is as allocated)
+        off = (lib.gf_fps_error_flag(ptr(scratch), b) - scratch.data_ptr()) // 4
+        if int(scratch.view(torch.int32)[off].item()) != 0:
+            raise _lib.GeoFormerHipError("gf_furthest_point_sampling: an exchange gave up waiting for a workgroup of its "
+                                         "point set (picks wrong)")
     return idx
 
 

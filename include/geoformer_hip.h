@@ -474,9 +474,11 @@ int gf_ball_query(const float* new_xyz, const float* xyz, int b, int n, int m, f
                   void* stream);
 /* furthest_point_sampling (sampling_gpu.cu:72-232) incl. the |p|^2 <= 1e-3 skip, the m > n padding
  * and the launch-geometry tie-break of the reference.  xyz fp32 [b,n,3] -> idxs int32 [b,m].
- * scratch: gf_fps_scratch_bytes(b) bytes (zeroed by the call). */
+ * scratch: gf_fps_scratch_bytes(b) bytes (zeroed by the call); gf_fps_error_flag() points at a device int set to 1 when
+ * some exchange gave up waiting for a workgroup of its point set (picks then wrong). */
 size_t gf_fps_scratch_bytes(int b);
 int gf_furthest_point_sampling(const float* xyz, int b, int n, int m, int32_t* idxs, void* scratch, void* stream);
+const int32_t* gf_fps_error_flag(void* scratch, int b);
 /* Same sequence, continued: idxs[b, 0..m_known) already hold its first m_known picks (an earlier call with a
  * smaller m on the same points); fills idxs[b, m_known..m).  Lets a consumer of the first picks (the geodesic BFS
  * needs 256 of 2048) start while the rest is still being drawn. */

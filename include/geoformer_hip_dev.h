@@ -108,6 +108,12 @@ int gf_dev_bfs_qcap_max(int qcap);
  * value).  Process-wide; tests reset with -1. */
 int gf_dev_panoptic_lds_bins(int bins);
 
+/* The launch geometry gf_furthest_point_sampling uses for point sets of n points, without launching anything: G
+ * cooperating workgroups per point set, P points per lane, the k_fps<inst> instantiation that holds them (the smallest of
+ * 1, 2, 3, 4, 5, 6, 8, 12, 16, 20, 22 that is >= P), the tie-break block 1 << bs_log2 (the reference's launch geometry)
+ * and the point sets per launch.  Returns the status the sampling call would return for that n. */
+int gf_dev_fps_plan(int n, int* G, int* P, int* inst, int* bs_log2, int* per_launch);
+
 #ifdef __cplusplus
 }
 #endif

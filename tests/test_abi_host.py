@@ -84,6 +84,7 @@ EXPECTED = {
     "gf_index_scratch_bytes": (c_size_t, [c_size_t]),
     "gf_decoder_pre_grad_floats": (c_longlong, []),
     "gf_knn_error_flag": (P, [P, I]),  # returns const int32_t*
+    "gf_fps_error_flag": (P, [P, I]),  # the same shape
     "gf_feeder_create": (P, [I]),  # returns void*
     "gf_unet_train_bwd": (I, [P, I, I, P, P, P, P, P, P, P, P]),  # float* const*, float**, unsigned char*
     "gf_proposal_stats_batched": (I, [P, I, I, P, P, c_longlong, I, F, F, I, I, P, P, P, P, P]),
@@ -91,6 +92,7 @@ EXPECTED = {
     "gf_dev_host_wait_ns": (c_ulonglong, [I]),
     "gf_dev_event_create": (P, []),
     "gf_dev_conv_knobs": (I, [I, I, I, I, I]),
+    "gf_dev_fps_plan": (I, [I, P, P, P, P, P]),  # int n, five int* outputs
 }
 
 

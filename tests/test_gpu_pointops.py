@@ -100,8 +100,9 @@ def test_gather_group_and_grads(hip, oracle):
 
 
 @pytest.mark.parametrize("n,m0,m", [(5000, 256, 2048), (700, 1, 64), (300, 100, 512), (4096, 33, 34)])
-def test_fps_resume_equals_single_call(hip, n, m0, m):
-    """gf_furthest_point_sampling_resume: continuing from the first m0 picks gives the sequence of one call."""
+def test_fps_resume_equals_single_call(hip, oracle, n, m0, m):
+    """gf_furthest_point_sampling_resume: continuing from the first m0 picks gives the sequence of one call, which is
+    the oracle's."""
     from geoformer_amd import pointops
 
     rng = np.random.default_rng(n + m0)
@@ -113,6 +114,7 @@ def test_fps_resume_equals_single_call(hip, n, m0, m):
     assert (first == full[:, :m0]).all()
     cont = pointops.furthest_point_sampling(x, m, known=first)
     assert (cont == full).all()
+    assert (full.cpu().numpy() == oracle.fps(xyz, m)).all()
 
 
 @pytest.mark.parametrize("N,ncol,mode,span", [(20000, 4, 4, 40), (5000, 4, 3, 12), (3000, 3, 4, 9), (4000, 4, 1, 10),
