@@ -435,6 +435,18 @@ extern "C" const int32_t* gf_knn_error_flag(void* scratch, int n) {
     return (const int32_t*)scratch + 3 * (size_t)T + 1 + 2 * (size_t)nb;
 }
 
+// what build_point_grid and the two kernels that walk the grid use for a point set of n points (nothing is launched)
+extern "C" int gf_dev_point_grid_plan(int n, int* table_size, int* scan_blocks, int* knn_cap, int* bq_cap) {
+    GF_CHECK_ARG(n >= 1, "gf_dev_point_grid_plan: bad size n=%d", n);
+    GF_CHECK_ARG(table_size && scan_blocks && knn_cap && bq_cap, "gf_dev_point_grid_plan: an output is null");
+    const unsigned T = knn_table_size(n);
+    *table_size = (int)T;
+    *scan_blocks = gf_iscan_blocks((int)T);
+    *knn_cap = KNN_CAP;
+    *bq_cap = BQG_CAP;
+    return GF_OK;
+}
+
 // ------------------------------------------------------------------------------------
 // frontier BFS
 // ------------------------------------------------------------------------------------

@@ -114,6 +114,12 @@ int gf_dev_panoptic_lds_bins(int bins);
  * and the point sets per launch.  Returns the status the sampling call would return for that n. */
 int gf_dev_fps_plan(int n, int* G, int* P, int* inst, int* bs_log2, int* per_launch);
 
+/* The hash grid gf_knn_radius, gf_ball_query_grid and gf_point_grid_build make for a point set of n points, without
+ * launching anything: the number of buckets (a power of two), the workgroups of its prefix scan (more than 256 of them
+ * make the scan's top level loop with a carry), and the in-radius candidates per point that the kNN kernel's list holds
+ * (more: the error flag, rows truncated) and that the ball query's holds (more: its linear scan, same rows). */
+int gf_dev_point_grid_plan(int n, int* table_size, int* scan_blocks, int* knn_cap, int* bq_cap);
+
 #ifdef __cplusplus
 }
 #endif

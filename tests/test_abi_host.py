@@ -93,6 +93,7 @@ EXPECTED = {
     "gf_dev_event_create": (P, []),
     "gf_dev_conv_knobs": (I, [I, I, I, I, I]),
     "gf_dev_fps_plan": (I, [I, P, P, P, P, P]),  # int n, five int* outputs
+    "gf_dev_point_grid_plan": (I, [I, P, P, P, P]),  # int n, four int* outputs
 }
 
 
