@@ -1,9 +1,9 @@
 """The C ABI as ctypes sees it, read from include/geoformer_hip.h and include/geoformer_hip_dev.h.
 
 The two headers are the single source of every entry point's signature, every parameter struct's layout and every
-``GF_*`` integer the host code uses: nothing of them is restated in Python.  This is a regex pass over this project's
-own header style, not a C parser, and it is strict: a declaration it does not understand is a GeoFormerHipError naming
-the header line, never a default type.
+``GF_*`` integer (``#define`` or enumerator with a written value) the host code uses: nothing of them is restated in
+Python.  This is a regex pass over this project's own header style, not a C parser, and it is strict: a declaration
+it does not understand is a GeoFormerHipError naming the header line, never a default type.
 """
 from __future__ import annotations
 
@@ -83,7 +83,12 @@ def parse(text, label="<header>", abi=None):
         return _blank(m)
 
     text = re.sub(r"typedef\s+struct\s*\w*\s*\{(?P<body>[^{}]*)\}\s*(?P<name>\w+)\s*;", struct, text)
-    text = re.sub(r"(?:typedef\s+)?enum\s*\w*\s*\{[^{}]*\}\s*\w*\s*;", _blank, text)
+    def enum(m):  # enumerators with a written integer value are constants like the #defines
+        for e in re.finditer(r"\b(GF_\w+)\s*=\s*(-?(?:0[xX][0-9a-fA-F]+|\d+))\s*(?=[,}])", m[0]):
+            abi.consts[e[1]] = int(e[2], 0)
+        return _blank(m)
+
+    text = re.sub(r"(?:typedef\s+)?enum\s*\w*\s*\{[^{}]*\}\s*\w*\s*;", enum, text)
     text = re.sub(r"typedef\s+\w+\s*\(\s*\*\s*(\w+)\s*\)\s*\([^()]*\)\s*;", fnptr, text)
 
     # what is left is prototypes, one per ';'

@@ -80,6 +80,38 @@ def _geometric(segments):
     return segments if isinstance(segments, GeometricSegments) else None
 
 
+class MaskSplit:
+    """``split=MaskSplit(radius=0.08, min_points=100, mode="split")`` (or ``split="largest"`` / ``split="split"`` for the
+    defaults of that mode): every scene's picked masks are split into spatially connected clusters after the NMS
+    (postprocess.split_masks; keywords radius, k, min_samples, min_points, mode)."""
+
+    def __init__(self, **params):
+        unknown = sorted(set(params) - set(postprocess.SPLIT_DEFAULTS))
+        if unknown:
+            raise TypeError(f"MaskSplit: unknown parameter(s) {', '.join(unknown)}; known: "
+                            f"{', '.join(postprocess.SPLIT_DEFAULTS)}")
+        self.params = dict(postprocess.SPLIT_DEFAULTS, **params)
+        if self.params["mode"] not in postprocess.SPLIT_MODES:
+            raise ValueError(f"MaskSplit: mode must be one of {postprocess.SPLIT_MODES}, got {self.params['mode']!r}")
+
+    def __repr__(self):
+        return f"MaskSplit({', '.join(f'{k}={v!r}' for k, v in self.params.items())})"
+
+    def of_scene(self, cls, scores, masks, pick, xyz):
+        """(cls', scores', masks', pick') of one scene: postprocess.split_masks on the tensors' device and the current
+        stream."""
+        return postprocess.split_masks(masks, scores, cls, pick, xyz, **self.params)
+
+
+def _mask_split(split):
+    """The MaskSplit `split` stands for, or None."""
+    if split is None or isinstance(split, MaskSplit):
+        return split
+    if isinstance(split, str) and split in postprocess.SPLIT_MODES:
+        return MaskSplit(mode=split)
+    raise ValueError(f"split: None, a MaskSplit or one of {postprocess.SPLIT_MODES}, got {split!r}")
+
+
 def _scene_segments(segments, name, n):
     """int32 [n] over-segment ids of scene `name` from the mapping (range-checked), -1 everywhere when it has none."""
     seg = segments.get(name)
@@ -125,7 +157,7 @@ def collate_batches(raw_scenes, batch_size, spatial_shape=None, scale=50, full_s
 @torch.no_grad()
 def predict_batches(model, raw_scenes, batch_size, *, epoch=300, spatial_shape=None, nms_kernel="gaussian",
                     sigma=2.0, final_score_thresh=NMS_FINAL_SCORE, cvfold=None, reserve=True, device=None,
-                    semantic=None, nms="matrix", nms_thresh=None, segments=None):
+                    semantic=None, nms="matrix", nms_thresh=None, segments=None, split=None):
     """Yields (name, cls_final, scores_final, masks_final, pick) per scene, in input order.  raw_scenes: iterable of
     (name, raw [N, 8]).  The NMS categories are the benchmark label ids of the classes (evaluation.benchmark_label_ids
     with cvfold, default model.cfg.cvfold).  A scene without proposals yields ([], [], [], empty pick).  reserve: size
@@ -137,8 +169,13 @@ def predict_batches(model, raw_scenes, batch_size, *, epoch=300, spatial_shape=N
     over-segment ids; the forward pools the mask logits over them (every mask is then constant over a segment's
     foreground points); None: nothing is added to the loop.  A GeometricSegments (or "geometric"): the ids of every
     batch are computed on the device from its locs_float once the feeder has delivered it (one pointops.oversegment per
-    scene, on the forward's stream, nothing read back) and stored as the batch's "segments"."""
+    scene, on the forward's stream, nothing read back) and stored as the batch's "segments".  split: "largest", "split"
+    or a MaskSplit -- every scene's picked masks are split into spatially connected clusters after the NMS
+    (postprocess.split_masks on the forward's stream, with the scene's xyz from the batch's locs_float): "largest" keeps
+    the largest cluster of every picked mask (same shapes, nothing read back), "split" yields one row per kept cluster
+    (pick = arange; one read-back per scene); None: nothing is added to the loop."""
     geo = _geometric(segments)
+    splitter = _mask_split(split)
     if nms not in ("matrix", "greedy"):
         raise ValueError(f"predict_batches: nms must be 'matrix' or 'greedy', got {nms!r}")
     if nms == "greedy" and nms_thresh is None:
@@ -167,6 +204,14 @@ def predict_batches(model, raw_scenes, batch_size, *, epoch=300, spatial_shape=N
             picks = postprocess.matrix_nms_batched([m for _, _, m in per], [s for _, s, _ in per], labels,
                                                    kernel=nms_kernel, sigma=sigma,
                                                    final_score_thresh=final_score_thresh)
+        if splitter is not None:
+            per, picks = list(per), list(picks)
+            off = [int(o) for o in host["offsets"]]
+            for b, ((cls, sc, masks), pick) in enumerate(zip(per, picks)):
+                if torch.is_tensor(masks):
+                    cls, sc, masks, picks[b] = splitter.of_scene(cls, sc, masks, pick,
+                                                                 batch["locs_float"][off[b]:off[b + 1]].contiguous())
+                    per[b] = (cls, sc, masks)
         for (name, _), (cls, sc, masks), pick in zip(chunk, per, picks):
             yield name, cls, sc, masks, pick
 

@@ -13,7 +13,7 @@ import threading
 import numpy as np
 import torch
 
-from . import _lib
+from . import _abi, _lib
 from ._lib import check, ptr, stream_ptr
 
 
@@ -1763,3 +1763,90 @@ def oversegment(xyz, k=16, radius=0.07, normal_deg=15.0, offset=0.012, flatness=
     _, I, deg, flag = knn_radius(xyz, k, radius, sqrt_out=False, return_flag=True)
     ids = smooth_components(xyz, point_normals(xyz, I, deg), I, deg, normal_deg, offset, flatness, min_points)
     return (ids, flag) if return_flag else ids
+
+
+# ---- picked masks split into connected clusters (csrc/mask_split.hip) ----------------------------------------------------
+MSP_TABLE_INTS = _abi.const("GF_MSP_TABLE_INTS")
+NMS_MAX_N = _abi.const("GF_NMS_MAX_N")
+
+
+def _mask_rows(masks, pick, name):
+    _i32c(masks, "masks")
+    if not (pick.is_cuda and pick.dtype == torch.int64 and pick.is_contiguous()):
+        raise RuntimeError(f"{name}: pick: expected a contiguous int64 tensor on the GPU")
+    if masks.dim() != 2 or pick.dim() != 1:
+        raise RuntimeError(f"{name}: expected masks [n_rows, N] and pick [p], got {tuple(masks.shape)}, "
+                           f"{tuple(pick.shape)}")
+    if pick.shape[0] > NMS_MAX_N:
+        raise RuntimeError(f"{name}: {pick.shape[0]} picks (at most {NMS_MAX_N})")
+    return masks.shape[0], masks.shape[1], pick.shape[0]
+
+
+def mask_components(masks, pick, I, deg, min_samples=1, min_points=1):
+    """DBSCAN of the picked rows of masks (int32 [n_rows, N], nonzero = member; pick int64 [p]) over one scene's kNN rows
+    (knn_radius' I int32 [N, k] and deg int32 [N]), every mask restricting the graph to its own points:
+    postprocess.mask_components_host on the GPU.  Returns (comp int32 [p, N]: the cluster id -- its smallest core point
+    -- of every member point or -1, tab int32 [p, 5]: members, clusters kept, points in them, the largest cluster's id or
+    -1, its size).  Seven launches on the current stream, nothing read back; bit-identical from call to call."""
+    n_rows, N, p = _mask_rows(masks, pick, "mask_components")
+    _i32c(I, "I"); _i32c(deg, "deg")
+    if I.dim() != 2 or I.shape[0] != N or I.shape[1] < 1 or deg.shape != (N,):
+        raise RuntimeError(f"mask_components: expected I [{N}, k >= 1] and deg [{N}], got {tuple(I.shape)}, "
+                           f"{tuple(deg.shape)}")
+    if min_samples < 1 or min_points < 1:
+        raise RuntimeError(f"mask_components: min_samples = {min_samples}, min_points = {min_points} (at least 1)")
+    lib = _lib.load()
+    dev = masks.device
+    comp = torch.empty((p, N), dtype=torch.int32, device=dev)
+    if N == 0 or p == 0:  # nothing is launched: the rows of picks without points
+        return comp, torch.tensor([0, 0, 0, -1, 0], dtype=torch.int32, device=dev).repeat(p, 1)
+    tab = torch.empty((p, MSP_TABLE_INTS), dtype=torch.int32, device=dev)
+    ws = torch.empty(lib.gf_mask_components_scratch_bytes(N, p) // 8 + 1, dtype=torch.int64, device=dev)
+    check(lib.gf_mask_components(ptr(masks), n_rows, N, ptr(pick), p, ptr(I), ptr(deg), I.shape[1], int(min_samples),
+                                 int(min_points), ptr(comp), ptr(tab), ptr(ws), stream_ptr()), "gf_mask_components")
+    return comp, tab
+
+
+def mask_keep_largest(masks, pick, comp, tab):
+    """masks_out int32 [n_rows, N]: every picked row of masks cut down to its largest kept cluster (mask_components' comp
+    and tab; all zero without one), every other row copied.  One launch on the current stream, nothing read back."""
+    n_rows, N, p = _mask_rows(masks, pick, "mask_keep_largest")
+    _i32c(comp, "comp"); _i32c(tab, "tab")
+    if comp.shape != (p, N) or tab.shape != (p, MSP_TABLE_INTS):
+        raise RuntimeError(f"mask_keep_largest: expected comp [{p}, {N}] and tab [{p}, {MSP_TABLE_INTS}], got "
+                           f"{tuple(comp.shape)}, {tuple(tab.shape)}")
+    if p == 0 or n_rows == 0 or N == 0:
+        return masks.clone()
+    out = torch.empty_like(masks)
+    check(_lib.load().gf_mask_keep_largest(ptr(masks), n_rows, N, ptr(pick), p, ptr(comp), ptr(tab), ptr(out),
+                                           stream_ptr()), "gf_mask_keep_largest")
+    return out
+
+
+def dbscan(xyz, radius, min_samples=1, k=32, min_points=1, return_flag=False):
+    """DBSCAN of one point cloud: int32 [n] cluster ids (the smallest core point of the cluster) or -1 for noise and for
+    clusters of fewer than min_points points.  xyz fp32 [n, 3] on the GPU: knn_radius(k, radius) and mask_components
+    with one all-ones mask on the current stream, nothing read back.  The rows hold at most k - 1 neighbours: with every
+    in-radius neighbour in its row (deg < k - 1 everywhere) the result is sklearn.cluster.DBSCAN(radius, min_samples)
+    with the clusters named by their smallest core index; return_flag: also knn_radius' truncation flag (int32 [1],
+    device).  A CPU tensor runs the host statement (the flag is then None)."""
+    if min_samples < 1 or min_points < 1:
+        raise RuntimeError(f"dbscan: min_samples = {min_samples}, min_points = {min_points} (at least 1)")
+    if not xyz.is_cuda:
+        from . import postprocess
+
+        I, deg = postprocess.knn_radius_host(xyz, k, radius)
+        n = I.shape[0]
+        comp, _ = postprocess.mask_components_host(np.ones((1, n), np.int32), np.zeros(1, np.int64), I, deg,
+                                                   min_samples, min_points)
+        ids = torch.from_numpy(comp[0].copy())
+        return (ids, None) if return_flag else ids
+    _f32c(xyz, "xyz")
+    n = xyz.shape[0]
+    if n == 0:
+        ids = torch.empty(0, dtype=torch.int32, device=xyz.device)
+        return (ids, torch.zeros(1, dtype=torch.int32, device=xyz.device)) if return_flag else ids
+    _, I, deg, flag = knn_radius(xyz, k, radius, sqrt_out=False, return_flag=True)
+    comp, _ = mask_components(torch.ones((1, n), dtype=torch.int32, device=xyz.device),
+                              torch.zeros(1, dtype=torch.int64, device=xyz.device), I, deg, min_samples, min_points)
+    return (comp[0], flag) if return_flag else comp[0]

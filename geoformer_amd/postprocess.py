@@ -644,3 +644,151 @@ def oversegment_host(xyz, I=None, deg=None, *, k=16, radius=0.07, normal_deg=15.
     normals4 = point_normals_host(x, I, deg)
     return smooth_components_host(x, normals4, I, deg, normal_deg=normal_deg, offset=offset, flatness=flatness,
                                   min_points=min_points, margins=margins if return_ambiguous else None)
+
+
+# ---- picked masks split into connected clusters (csrc/mask_split.hip): the host statement -------------------------------
+MSP_TABLE_INTS = _abi.const("GF_MSP_TABLE_INTS")
+SPLIT_DEFAULTS = dict(radius=0.1, k=16, min_samples=1, min_points=50, mode="largest")
+SPLIT_MODES = ("largest", "split")
+
+
+def _min_index_components(n, a, b):
+    """int64 [n]: for every vertex the smallest index of its component under the edges (a[e], b[e]) -- the larger root
+    hooked under the smaller and the paths halved until nothing moves (stage C of smooth_components_host)."""
+    parent = np.arange(n, dtype=np.int64)
+    while True:
+        ra, rb = parent[a], parent[b]
+        hi, lo = np.maximum(ra, rb), np.minimum(ra, rb)
+        if not (hi != lo).any():
+            return parent
+        np.minimum.at(parent, hi, lo)
+        while True:
+            nxt = parent[parent]
+            if (nxt == parent).all():
+                break
+            parent = nxt
+
+
+def mask_components_host(masks, pick, I, deg, min_samples=1, min_points=1):
+    """DBSCAN of every picked mask over one scene's kNN rows -- the statement gf_mask_components is tested against, in
+    integers alone.  masks int32 [n_rows, N] (nonzero = member), pick int64 [p] rows of masks (a value outside
+    [0, n_rows) is an empty row), rows I int32 [N, k] / deg int32 [N] read as gf_smooth_components reads them: columns
+    0 .. min(deg[i], k - 1) of row i, an entry outside [0, N) skipped and never followed.  For pick rank r with member
+    set M:
+      cnt(i) = 1 + the read entries j of row i with j != i and j in M (a repeated entry counts each time);
+      i in M is a CORE point when cnt(i) >= min_samples;
+      a read entry (i, j) with both i and j core puts them in one cluster (one direction suffices), and a cluster's id
+      is the smallest index among its core points;
+      a member that is not core is a BORDER point: it takes the smallest cluster id among the core entries of its OWN
+      row, and is noise (-1) without one;
+      a cluster's size counts core and border points; one smaller than min_points is dissolved (all its points -1);
+      the largest cluster of a pick has the greatest size, ties go to the smaller id.
+    With min_samples = 1 this is connected components of the graph restricted to the mask; with complete symmetric
+    rows it is sklearn.cluster.DBSCAN(eps, min_samples) on the mask's points with the clusters named by their smallest
+    core index.  Returns (comp int32 [p, N]: the cluster id of every member point or -1, tab int32 [p, 5]: members,
+    clusters kept, points in kept clusters, id of the largest kept cluster or -1, its size)."""
+    masks = np.asarray(_np(masks))
+    pick = np.asarray(_np(pick)).astype(np.int64).reshape(-1)
+    I, deg = np.asarray(_np(I)), np.asarray(_np(deg))
+    if min_samples < 1 or min_points < 1:
+        raise ValueError("mask_components_host: min_samples >= 1 and min_points >= 1")
+    if masks.ndim != 2 or I.ndim != 2 or I.shape[0] != masks.shape[1] or deg.shape != (masks.shape[1],):
+        raise ValueError(f"mask_components_host: expected masks [n_rows, N], I [N, k] and deg [N], got {masks.shape}, "
+                         f"{I.shape}, {deg.shape}")
+    n_rows, N = masks.shape
+    p = pick.shape[0]
+    comp = np.full((p, N), -1, np.int32)
+    tab = np.zeros((p, MSP_TABLE_INTS), np.int32)
+    tab[:, 3] = -1
+    if N == 0 or p == 0:
+        return comp, tab
+    src, col = np.nonzero(_valid_entries(I, deg, N))
+    dst = I[src, col].astype(np.int64)
+    other = dst != src
+    src, dst = src[other], dst[other]
+    done = {}
+    for r, row in enumerate(pick.tolist()):
+        if not 0 <= row < n_rows:
+            continue
+        if row in done:  # (a row picked twice: the same statement, the same result)
+            comp[r], tab[r] = comp[done[row]], tab[done[row]]
+            continue
+        done[row] = r
+        M = masks[row] != 0
+        tab[r, 0] = M.sum()
+        inside = M[src] & M[dst]
+        cnt = 1 + np.bincount(src[inside], minlength=N)
+        core = M & (cnt >= min_samples)
+        both = core[src] & core[dst]
+        root = _min_index_components(N, src[both], dst[both])
+        ids = np.where(core, root, -1)
+        edge = M[src] & ~core[src] & core[dst]  # a border point's own row only
+        low = np.full(N, N, np.int64)
+        np.minimum.at(low, src[edge], root[dst[edge]])
+        border = M & ~core & (low < N)
+        ids[border] = low[border]
+        size = np.bincount(ids[ids >= 0], minlength=N)
+        ids[(ids >= 0) & (size[np.maximum(ids, 0)] < min_points)] = -1
+        comp[r] = ids
+        kept = np.unique(ids[ids >= 0])  # ascending: argmax takes the smaller id among equal sizes
+        tab[r, 1], tab[r, 2] = len(kept), (ids >= 0).sum()
+        if len(kept):
+            big = kept[np.argmax(size[kept])]
+            tab[r, 3], tab[r, 4] = big, size[big]
+    return comp, tab
+
+
+def mask_keep_largest_host(masks, pick, comp, tab):
+    """The statement of gf_mask_keep_largest: a copy of masks in which every picked row keeps its values at the points of
+    its largest kept cluster (mask_components_host's comp and tab) and is zero elsewhere."""
+    masks = np.asarray(_np(masks))
+    out = masks.copy()
+    for r, row in enumerate(np.asarray(_np(pick)).reshape(-1).tolist()):
+        if 0 <= row < masks.shape[0]:
+            big = int(tab[r, 3])
+            out[row] = np.where((comp[r] == big) & (big >= 0), masks[row], 0)
+    return out
+
+
+def split_masks(masks, scores, cls, pick, xyz, *, radius=0.1, k=16, min_samples=1, min_points=50, mode="largest"):
+    """Split the picked instance masks of one scene into spatially connected clusters (DBSCAN per mask, as query-based
+    3D instance segmenters post-process their masks): a mask that fires on two objects at once, or on an object plus
+    stray points far from it, is cleaned.  masks int32 [n, N], scores [n], cls [n], pick int64 [p] (the NMS result),
+    xyz fp32 [N, 3]; the graph is knn_radius(xyz, k, radius), the clusters those of mask_components_host(min_samples,
+    min_points).  Returns (cls', scores', masks', pick'):
+      mode="largest"  masks' [n, N] with every picked row cut down to its largest kept cluster (all zero without one);
+                      cls, scores and pick unchanged.  On the GPU nothing is read back.
+      mode="split"    every kept cluster becomes a row of masks' int32 [n_out, N], ordered by pick rank, then cluster
+                      id; scores' and cls' are those of the parent row, pick' = arange(n_out).  On the GPU the rows are
+                      built by framework operations from comp (one comparison per row), and the number of kept clusters
+                      is the one device-to-host read (torch.nonzero's).
+    GPU tensors run csrc/mask_split.hip (pointops.mask_components / mask_keep_largest) on the current stream, CPU
+    tensors the host statement.  A scene without proposals (masks = []) passes through."""
+    if mode not in SPLIT_MODES:
+        raise ValueError(f"split_masks: mode must be one of {SPLIT_MODES}, got {mode!r}")
+    if not torch.is_tensor(masks):
+        return cls, scores, masks, pick
+    pick = pick.to(torch.int64)
+    m32 = (masks if masks.dtype == torch.int32 else (masks != 0).int()).contiguous()
+    if masks.is_cuda:
+        from . import pointops
+
+        pick = pick.to(masks.device).contiguous()
+        _, I, deg = pointops.knn_radius(xyz.to(torch.float32).contiguous(), k, radius, sqrt_out=False)
+        comp, tab = pointops.mask_components(m32, pick, I, deg, min_samples, min_points)
+        if mode == "largest":
+            return cls, scores, pointops.mask_keep_largest(m32, pick, comp, tab), pick
+    else:
+        I, deg = knn_radius_host(xyz, k, radius)
+        comp, tab = mask_components_host(m32, pick, I, deg, min_samples, min_points)
+        if mode == "largest":
+            return cls, scores, torch.from_numpy(mask_keep_largest_host(m32, pick, comp, tab)), pick
+        comp = torch.from_numpy(comp)
+    # a kept cluster is named by its smallest core point, which carries its own index: one (rank, id) pair per cluster,
+    # and nonzero lists them by rank, then id
+    N = comp.shape[1]
+    found = (comp == torch.arange(N, dtype=torch.int32, device=comp.device)[None, :]).nonzero()
+    rank, ids = found[:, 0], found[:, 1]
+    parent = pick[rank]
+    out = (comp[rank] == ids[:, None].to(torch.int32)).to(torch.int32)
+    return cls[parent], scores[parent], out, torch.arange(rank.shape[0], dtype=torch.int64, device=comp.device)

@@ -965,6 +965,37 @@ int gf_smooth_components(const float* xyz, const float* normals4, const int32_t*
                          void* scratch, void* stream);
 
 /* ===================================================================================
+ * Picked instance masks split into spatially connected clusters (csrc/mask_split.hip; the statement is
+ * postprocess.mask_components_host): DBSCAN of every picked mask over ONE scene's radius graph, each mask restricting
+ * the graph to its own points.  masks int32 [n_rows, N] (nonzero = member), pick int64 [p] rows of masks (a value
+ * outside [0, n_rows) is an empty row), kNN rows I int32 [N,k] / deg int32 [N] read as gf_smooth_components reads them:
+ * columns 0 .. min(deg[i], k - 1) of row i, an entry outside [0, N) skipped and never followed.
+ *
+ * gf_mask_components (seven launches for any N, p, k): for pick rank r with member set M,
+ *   cnt(i) = 1 + the read entries j of row i with j != i and j in M (a repeated entry counts each time); i in M is a
+ *   CORE point when cnt(i) >= min_samples.  A read entry (i, j) with both ends core joins them (one direction
+ *   suffices); a cluster's id is its smallest core index.  A member that is not core (a BORDER point) takes the smallest
+ *   cluster id among the core entries of its own row, -1 without one.  A cluster of fewer than min_points points (core
+ *   and border) is dissolved to -1.
+ *   comp int32 [p, N]: the cluster id of every member point or -1;  tab int32 [p, GF_MSP_TABLE_INTS]: {members, clusters
+ *   kept, points in kept clusters, id of the largest kept cluster (ties: the smaller id) or -1, its size}.
+ *   Integer atomics only: comp and tab are a function of the inputs, bit-identical from call to call, and a pick's rows
+ *   are the same alone or among other picks.  scratch: gf_mask_components_scratch_bytes(N, p), 8-byte aligned.
+ * gf_mask_keep_largest (one launch): masks_out int32 [n_rows, N] (not overlapping masks) -- a picked row keeps its
+ *   values at the points of its largest kept cluster and is zero elsewhere (all zero without a kept cluster); every
+ *   other row is copied.
+ * N < 0, p < 0, p > GF_NMS_MAX_N, k < 1, min_samples < 1, min_points < 1, or a NULL pointer with N > 0 and p > 0, are
+ * GF_ERR_INVALID_ARG before anything is launched; N == 0 or p == 0 succeeds with nothing launched (masks_out is then
+ * not written).  Every launch goes on `stream`; no host synchronisation, no read-back. */
+enum { GF_MSP_TABLE_INTS = 5 }; /* columns of tab */
+size_t gf_mask_components_scratch_bytes(int N, int p);
+int gf_mask_components(const int32_t* masks, int n_rows, int N, const long long* pick, int p, const int32_t* I,
+                       const int32_t* deg, int k, int min_samples, int min_points, int32_t* comp, int32_t* tab,
+                       void* scratch, void* stream);
+int gf_mask_keep_largest(const int32_t* masks, int n_rows, int N, const long long* pick, int p, const int32_t* comp,
+                         const int32_t* tab, int32_t* masks_out, void* stream);
+
+/* ===================================================================================
  * Backbone voxel transformer of the two deepest U-Net levels, fused (inference)
  * (UBlock: model/geoformer/geoformer_modules.py:64-68,120-127; TransformerEncoder(d_model=128, N,
  *  heads=4, d_ff=64): model/transformer.py:62-188)

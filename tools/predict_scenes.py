@@ -8,6 +8,7 @@ greedy NMS) and the scene labelling of batch_eval.label_batches, written with ge
     python tools/predict_scenes.py --out out --panoptic scene0011_00_inst_nostuff.npy   # + `panoptic` in the .npz, PQ
     python tools/predict_scenes.py --out out --segments segs scene0011_00_inst_nostuff.npy  # masks pooled over segs/<name>*.segs.json
     python tools/predict_scenes.py --out out --geometric-segments scene0011_00_inst_nostuff.npy  # ... over segments made from the points
+    python tools/predict_scenes.py --out out --split-masks largest scene0011_00_inst_nostuff.npy  # picked masks cut to their largest connected cluster
 
 Per scene <out>/<name>.npz (ids, owner, instance table: export.load_labels) and, with --scannet, <out>/<name>.txt plus
 <out>/predicted_masks/ (exclusive masks; --full-masks writes the picked masks as they are).  Without --checkpoint the
@@ -24,6 +25,9 @@ or <DIR>/<name>.segs.npy, one id per point; for the --synthetic scenes scene.gri
 --geometric-segments (instead of --segments) computes the over-segmentation on the GPU from every scene's points
 (pointops.oversegment with its defaults, csrc/oversegment.hip), for given and synthetic scenes alike.
 The JSON line's `segment_pooling` says whether the pooling ran, `geometric_segments` where the segments came from.
+--split-masks largest|split splits every picked mask into spatially connected clusters after the NMS (DBSCAN per mask,
+batch_eval.MaskSplit with its defaults, csrc/mask_split.hip): `largest` keeps each mask's largest cluster, `split` makes
+every kept cluster an instance of its own.  The JSON line's `mask_split` names the mode (null without the flag).
 """
 import argparse
 import json
@@ -37,7 +41,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("scenes", nargs="*", help="scene .npy files, [N, 8] = xyz, rgb, semantic label, instance label")
     ap.add_argument("--synthetic", type=int, default=0, metavar="K", help="K synthetic scenes (scene.make_raw_scene)")
@@ -62,8 +66,16 @@ def main():
     seg_from.add_argument("--segments", default=None, metavar="DIR",
                           help="pool the mask logits over each scene's over-segmentation: DIR/<name>*.segs.json or "
                                "DIR/<name>.segs.npy (synthetic scenes: scene.grid_segments)")
+    ap.add_argument("--split-masks", choices=("largest", "split"), default=None,
+                    help="split every picked mask into spatially connected clusters after the NMS (batch_eval.MaskSplit "
+                         "with its defaults): keep the largest cluster, or make every kept cluster an instance")
     ap.add_argument("--no-write", action="store_true")
     ap.add_argument("--reps", type=int, default=3, help="timed passes per keep_masks setting")
+    return ap
+
+
+def main():
+    ap = build_parser()
     args = ap.parse_args()
 
     import geoformer_amd
@@ -116,6 +128,8 @@ def main():
         kw["final_score_thresh"] = args.nms_score
     if args.nms != "matrix":
         kw["nms"] = args.nms
+    if args.split_masks is not None:
+        kw["split"] = args.split_masks
 
     def run(keep_masks):
         np.random.seed(0)
@@ -176,6 +190,7 @@ def main():
                       "picked": sum(len(lab.table.kept) for _, lab in results), "kept": kept,
                       "labelled_points": sum(int((lab.owner >= 0).sum()) for _, lab in results),
                       "segment_pooling": "segments" in kw, "geometric_segments": args.geometric_segments,
+                      "mask_split": args.split_masks,
                       "scenes_per_s": rates, "out": None if args.no_write else args.out}))
 
 
