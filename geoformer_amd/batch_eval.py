@@ -14,6 +14,8 @@
         ...                                   # pan [N]: instance ids, 1000 wall, 2000 floor, 0 unlabelled (host)
     res = evaluate_panoptic(model, [(name, raw), ...], batch_size=4)             # PQ / SQ / RQ
     print(evaluation.format_panoptic_results(res))
+    for name, cls, scores, masks, pick in predict_batches(model, [(name, raw), ...], batch_size=4, tiles=Tiling(tile=4.0)):
+        ...                                   # a large scan runs as overlapping tiles; masks int32 [G, N], merged
 
 A batch of raw scenes ([N, 8] = xyz, rgb, semantic label, instance label, as prepare_data_inst.py stores them) is
 collated on the host (scene.collate_raw), uploaded and voxelised on the GPU one batch ahead (feeder.DeviceFeeder), and
@@ -112,6 +114,109 @@ def _mask_split(split):
     raise ValueError(f"split: None, a MaskSplit or one of {postprocess.SPLIT_MODES}, got {split!r}")
 
 
+class Tiling:
+    """``tiles=Tiling(tile=4.0, halo=0.5, max_points=400_000, iom=0.5, min_shared=20)``: every scene with more than
+    max_points points is run as the overlapping tiles of scene.tile_plan(xyz, tile, halo), and the picked instances of
+    its tiles are joined by postprocess.merge_tiles(iom, min_shared).  max_points is a starting point with no
+    measurement behind it."""
+
+    DEFAULTS = dict(tile=4.0, halo=0.5, max_points=400_000, **postprocess.TILE_DEFAULTS)
+
+    def __init__(self, **params):
+        unknown = sorted(set(params) - set(self.DEFAULTS))
+        if unknown:
+            raise TypeError(f"Tiling: unknown parameter(s) {', '.join(unknown)}; known: {', '.join(self.DEFAULTS)}")
+        self.params = dict(self.DEFAULTS, **params)
+        if not self.params["tile"] > 0 or not self.params["halo"] >= 0 or self.params["max_points"] < 0:
+            raise ValueError(f"Tiling: tile > 0, halo >= 0 and max_points >= 0, got {self!r}")
+
+    def __repr__(self):
+        return f"Tiling({', '.join(f'{k}={v!r}' for k, v in self.params.items())})"
+
+    def plan_of(self, raw):
+        """The scene.TilePlan of a raw [N, 8] scene, or None when it has at most max_points points."""
+        r = raw.detach().cpu().numpy() if torch.is_tensor(raw) else np.asarray(raw)
+        if r.shape[0] <= self.params["max_points"]:
+            return None
+        return scene.tile_plan(r[:, :3], self.params["tile"], self.params["halo"])
+
+    def merge(self, plan, per_tile):
+        """(cls, scores, masks [G, N], pick) of a scan from its tiles' results (postprocess.merge_tiles); a scan none
+        of whose tiles picked anything is a scene without proposals."""
+        cls, scores, masks, pick, _ = postprocess.merge_tiles(plan, per_tile, iom=self.params["iom"],
+                                                              min_shared=self.params["min_shared"])
+        if len(pick) == 0:
+            return [], [], [], pick
+        return cls, scores, masks, pick
+
+
+class TileName(tuple):
+    """(scene name, tile id): the name of a tile in tile_items' expanded list."""
+    __slots__ = ()
+
+    def __new__(cls, name, tile):
+        return super().__new__(cls, (name, int(tile)))
+
+
+def tile_items(items, tiling):
+    """(expanded items, plans): every (name, raw) whose scene has more than tiling's max_points points is replaced, in
+    place, by its non-empty tiles (TileName(name, tile id), the raw rows gathered through plan.index); plans: scene
+    name -> scene.TilePlan of the tiled scenes.  The other scenes pass through."""
+    out, plans = [], {}
+    for name, raw in items:
+        plan = tiling.plan_of(raw)
+        if plan is None:
+            out.append((name, raw))
+            continue
+        if name in plans:
+            raise ValueError(f"tile_items: two scenes are named {name!r}")
+        plans[name] = plan
+        r = raw.detach().cpu().numpy() if torch.is_tensor(raw) else np.asarray(raw)
+        out.extend((TileName(name, s), r[plan.points(s)]) for s in range(plan.T) if plan.offsets[s + 1] > plan.offsets[s])
+    return out, plans
+
+
+def _tiling(tiles):
+    if tiles is None or isinstance(tiles, Tiling):
+        return tiles
+    raise ValueError(f"tiles: None or a Tiling, got {tiles!r}")
+
+
+def _predict_tiled(model, raw_scenes, batch_size, tiling, kw):
+    """The loop of predict_batches over tile_items' expanded list; a tiled scene is yielded once, merged, when its last
+    tile has come out."""
+    if kw.get("semantic") is not None:
+        raise ValueError("predict_batches: semantic= is not supported with tiles yet")
+    items, plans = tile_items(list(raw_scenes), tiling)
+    segments = kw.get("segments")
+    if plans and segments is not None and _geometric(segments) is None:
+        # a mapping: a tiled scene's ids are sliced through the plan, per tile
+        sliced = {n: s for n, s in segments.items() if n not in plans}
+        for name, _ in items:
+            if isinstance(name, TileName) and name[0] in plans and segments.get(name[0]) is not None:
+                seg = segments[name[0]]
+                seg = seg.detach().cpu().numpy() if torch.is_tensor(seg) else np.asarray(seg)
+                if seg.shape != (plans[name[0]].N,):
+                    raise ValueError(f"segments[{name[0]!r}]: expected one id per point [{plans[name[0]].N}], got "
+                                     f"{seg.shape}")
+                sliced[name] = seg[plans[name[0]].points(name[1])]
+        kw = dict(kw, segments=sliced)
+    left = {n: int((np.diff(p.offsets) > 0).sum()) for n, p in plans.items()}
+    got = {n: {} for n in plans}
+    for name, cls, sc, masks, pick in predict_batches(model, items, batch_size, **kw):
+        if not (isinstance(name, TileName) and name[0] in plans):
+            yield name, cls, sc, masks, pick
+            continue
+        scan, s = name
+        got[scan][s] = (cls, sc, masks, pick)
+        left[scan] -= 1
+        if left[scan] == 0:
+            none = ([], [], [], torch.empty(0, dtype=torch.int64))
+            per_tile = [got[scan].get(t, none) for t in range(plans[scan].T)]
+            del got[scan]
+            yield (scan, *tiling.merge(plans[scan], per_tile))
+
+
 def _scene_segments(segments, name, n):
     """int32 [n] over-segment ids of scene `name` from the mapping (range-checked), -1 everywhere when it has none."""
     seg = segments.get(name)
@@ -157,7 +262,7 @@ def collate_batches(raw_scenes, batch_size, spatial_shape=None, scale=50, full_s
 @torch.no_grad()
 def predict_batches(model, raw_scenes, batch_size, *, epoch=300, spatial_shape=None, nms_kernel="gaussian",
                     sigma=2.0, final_score_thresh=NMS_FINAL_SCORE, cvfold=None, reserve=True, device=None,
-                    semantic=None, nms="matrix", nms_thresh=None, segments=None, split=None):
+                    semantic=None, nms="matrix", nms_thresh=None, segments=None, split=None, tiles=None):
     """Yields (name, cls_final, scores_final, masks_final, pick) per scene, in input order.  raw_scenes: iterable of
     (name, raw [N, 8]).  The NMS categories are the benchmark label ids of the classes (evaluation.benchmark_label_ids
     with cvfold, default model.cfg.cvfold).  A scene without proposals yields ([], [], [], empty pick).  reserve: size
@@ -173,7 +278,19 @@ def predict_batches(model, raw_scenes, batch_size, *, epoch=300, spatial_shape=N
     or a MaskSplit -- every scene's picked masks are split into spatially connected clusters after the NMS
     (postprocess.split_masks on the forward's stream, with the scene's xyz from the batch's locs_float): "largest" keeps
     the largest cluster of every picked mask (same shapes, nothing read back), "split" yields one row per kept cluster
-    (pick = arange; one read-back per scene); None: nothing is added to the loop."""
+    (pick = arange; one read-back per scene); None: nothing is added to the loop.  tiles: a Tiling -- every scene with
+    more than its max_points points is replaced in the item list by its non-empty tiles (tile_items), the loop runs over
+    the expanded list (same feeder, same batches of batch_size, segments= sliced or computed per tile, split= applied
+    per tile), and when a scene's last tile has come out postprocess.merge_tiles joins the tiles' picked instances: the
+    scene is yielded once, in input order, with masks int32 [G, N] over the whole scan holding the G merged instances
+    only, and pick their score order (one read-back per tiled scene).  semantic= with tiles is a ValueError; None:
+    nothing is added to the loop."""
+    if _tiling(tiles) is not None:
+        yield from _predict_tiled(model, raw_scenes, batch_size, tiles, dict(
+            epoch=epoch, spatial_shape=spatial_shape, nms_kernel=nms_kernel, sigma=sigma,
+            final_score_thresh=final_score_thresh, cvfold=cvfold, reserve=reserve, device=device, semantic=semantic,
+            nms=nms, nms_thresh=nms_thresh, segments=segments, split=split))
+        return
     geo = _geometric(segments)
     splitter = _mask_split(split)
     if nms not in ("matrix", "greedy"):

@@ -1850,3 +1850,115 @@ def dbscan(xyz, radius, min_samples=1, k=32, min_points=1, return_flag=False):
     comp, _ = mask_components(torch.ones((1, n), dtype=torch.int32, device=xyz.device),
                               torch.zeros(1, dtype=torch.int64, device=xyz.device), I, deg, min_samples, min_points)
     return (comp[0], flag) if return_flag else comp[0]
+
+
+# ---- instances joined across the tiles of a large scan (csrc/tile_merge.hip) ---------------------------------------------
+TILE_SCENE_FIELDS = _abi.const("GF_TILE_SCENE_FIELDS")
+TILE_MAX_ROWS = 4096   # gf_tile_merge_max_rows(): asserted against the library in tile_limits()
+TILE_MAX_PICKS = 256   # gf_tile_merge_max_picks()
+
+
+def tile_limits():
+    """(most rows in all, most picks in one tile) of the tile merge, from the library."""
+    lib = _lib.load()
+    lim = lib.gf_tile_merge_max_rows(), lib.gf_tile_merge_max_picks()
+    if lim != (TILE_MAX_ROWS, TILE_MAX_PICKS):
+        raise RuntimeError(f"tile merge: the library's limits {lim} are not {(TILE_MAX_ROWS, TILE_MAX_PICKS)}")
+    return lim
+
+
+def tile_check_caps(table_host):
+    """The caps of the tile merge on a host tile scene table (postprocess.tile_scene_table), before any launch."""
+    t = np.asarray(table_host)
+    if t.ndim != 2 or t.shape[1] != TILE_SCENE_FIELDS or t.dtype != np.int64:
+        raise RuntimeError(f"tile scene table: expected int64 [T, {TILE_SCENE_FIELDS}], got {t.dtype} {t.shape}")
+    most = int(t[:, 4].max()) if len(t) else 0
+    if most > TILE_MAX_PICKS:
+        raise RuntimeError(f"tile merge: {most} picks in tile {int(t[:, 4].argmax())} (at most {TILE_MAX_PICKS} per "
+                           f"tile)")
+    if int(t[:, 4].sum()) > TILE_MAX_ROWS:
+        raise RuntimeError(f"tile merge: {int(t[:, 4].sum())} picked rows over {len(t)} tiles (at most {TILE_MAX_ROWS})")
+    return int(t[:, 4].sum())
+
+
+def _tile_tables(table, table_host, tile_of, local_of, name):
+    P = tile_check_caps(table_host)
+    table_host = np.ascontiguousarray(table_host)
+    if not (table.is_cuda and table.dtype == torch.int64 and table.is_contiguous()
+            and tuple(table.shape) == table_host.shape):
+        raise RuntimeError(f"{name}: table: expected a contiguous int64 tensor {table_host.shape} on the GPU")
+    if tile_of is not None:
+        _i32c(tile_of, "tile_of"); _i32c(local_of, "local_of")
+        if tile_of.dim() != 2 or tile_of.shape[1] != 4 or local_of.shape != tile_of.shape:
+            raise RuntimeError(f"{name}: expected tile_of and local_of [N, 4], got {tuple(tile_of.shape)}, "
+                               f"{tuple(local_of.shape)}")
+    return table_host, P
+
+
+def tile_pack_picks(table, table_host, sizes):
+    """bits int32 [words]: per tile-local point the bitset of its memberships in the tile's picked masks, ceil(p_s / 32)
+    consecutive words (gf_tile_pack_picks; table / table_host / sizes: postprocess.tile_scene_table on the device and
+    on the host).  One launch on the current stream."""
+    table_host, P = _tile_tables(table, table_host, None, None, "tile_pack_picks")
+    bits = torch.empty(max(int(sizes["words"]), 1), dtype=torch.int32, device=table.device)
+    check(_lib.load().gf_tile_pack_picks(ptr(table), table_host.ctypes.data, table_host.shape[0], P, ptr(bits),
+                                         stream_ptr()), "gf_tile_pack_picks")
+    return bits
+
+
+def tile_overlaps(table, table_host, tile_of, local_of, bits, P):
+    """(inter int32 [P, P], shared int32 [P, T]) of postprocess.merge_tiles_host from the bitsets of tile_pack_picks and
+    the plan's point tables (int32 [N, 4] on the device): gf_tile_overlaps, one launch after two memsets on the current
+    stream, integer atomics only."""
+    table_host, rows = _tile_tables(table, table_host, tile_of, local_of, "tile_overlaps")
+    _i32c(bits, "bits")
+    if rows != P:
+        raise RuntimeError(f"tile_overlaps: the table holds {rows} rows, P = {P}")
+    T = table_host.shape[0]
+    inter = torch.empty((P, P), dtype=torch.int32, device=table.device)
+    shared = torch.empty((P, T), dtype=torch.int32, device=table.device)
+    check(_lib.load().gf_tile_overlaps(ptr(table), table_host.ctypes.data, T, ptr(tile_of), ptr(local_of),
+                                       tile_of.shape[0], ptr(bits), P, ptr(inter), ptr(shared), stream_ptr()),
+          "gf_tile_overlaps")
+    return inter, shared
+
+
+def tile_merge(inter, shared, cls, scores, row_tile, iom=0.5, min_shared=20):
+    """(comp int32 [P], members int32 [P], G int32 [1], cls int64 [P], scores fp32 [P]; the first G of the last two are
+    the instances') from the overlap tables: the connected components of postprocess.merge_tiles_host's edges, one
+    launch of one workgroup (gf_tile_merge).  cls int64 [P], scores fp32 [P], row_tile int32 [P]."""
+    _i32c(inter, "inter"); _i32c(shared, "shared"); _f32c(scores, "scores"); _i32c(row_tile, "row_tile")
+    P = scores.shape[0]
+    if P > TILE_MAX_ROWS:
+        raise RuntimeError(f"tile_merge: {P} rows (at most {TILE_MAX_ROWS})")
+    if not (cls.is_cuda and cls.dtype == torch.int64 and cls.is_contiguous()):
+        raise RuntimeError("tile_merge: cls: expected a contiguous int64 tensor on the GPU")
+    if inter.shape != (P, P) or shared.dim() != 2 or shared.shape[0] != P or cls.shape != (P,) or row_tile.shape != (P,):
+        raise RuntimeError(f"tile_merge: expected inter [{P}, {P}], shared [{P}, T], cls [{P}] and row_tile [{P}], got "
+                           f"{tuple(inter.shape)}, {tuple(shared.shape)}, {tuple(cls.shape)}, {tuple(row_tile.shape)}")
+    dev = scores.device
+    ints = torch.empty((2, max(P, 1)), dtype=torch.int32, device=dev)
+    d_G = torch.empty(1, dtype=torch.int32, device=dev)
+    inst_cls = torch.empty(max(P, 1), dtype=torch.int64, device=dev)
+    inst_scores = torch.empty(max(P, 1), dtype=torch.float32, device=dev)
+    check(_lib.load().gf_tile_merge(ptr(inter), ptr(shared), ptr(cls), ptr(scores), ptr(row_tile), P, shared.shape[1],
+                                    float(iom), int(min_shared), ptr(ints[0]), ptr(ints[1]), ptr(d_G), ptr(inst_cls),
+                                    ptr(inst_scores), stream_ptr()), "gf_tile_merge")
+    return ints[0, :P], ints[1, :P], d_G, inst_cls[:P], inst_scores[:P]
+
+
+def tile_assemble(table, table_host, tile_of, local_of, bits, members, G):
+    """(masks int32 [G, N], count int32 [G]): the union of the member rows of every instance over the scan's points,
+    scattered through the bitsets (gf_tile_assemble: two memsets and one launch on the current stream; the call zeroes
+    its outputs).  members int32 [P]: tile_merge's."""
+    table_host, P = _tile_tables(table, table_host, tile_of, local_of, "tile_assemble")
+    _i32c(bits, "bits"); _i32c(members, "members")
+    N = tile_of.shape[0]
+    if members.shape != (P,) or not 0 <= G <= P:
+        raise RuntimeError(f"tile_assemble: expected members [{P}] and 0 <= G <= {P}, got {tuple(members.shape)}, G = {G}")
+    masks = torch.empty((G, N), dtype=torch.int32, device=table.device)
+    count = torch.empty(G, dtype=torch.int32, device=table.device)
+    check(_lib.load().gf_tile_assemble(ptr(table), table_host.ctypes.data, table_host.shape[0], ptr(tile_of),
+                                       ptr(local_of), N, ptr(bits), ptr(members), P, int(G), ptr(masks), ptr(count),
+                                       stream_ptr()), "gf_tile_assemble")
+    return masks, count

@@ -792,3 +792,189 @@ def split_masks(masks, scores, cls, pick, xyz, *, radius=0.1, k=16, min_samples=
     parent = pick[rank]
     out = (comp[rank] == ids[:, None].to(torch.int32)).to(torch.int32)
     return cls[parent], scores[parent], out, torch.arange(rank.shape[0], dtype=torch.int64, device=comp.device)
+
+
+# ---- instances joined across the tiles of a large scan (csrc/tile_merge.hip): the host statement ------------------------
+TILE_SCENE_FIELDS = _abi.const("GF_TILE_SCENE_FIELDS")
+TILE_DEFAULTS = dict(iom=0.5, min_shared=20)
+
+
+def _tile_rows(plan, per_tile):
+    """The picked rows of all tiles, tile-major: per tile (masks int32 [n_rows, n_s] or None, pick int64 [p_s] on the
+    host or the device, cls, scores), with the shapes checked against the plan."""
+    T = plan.T
+    if len(per_tile) != T:
+        raise ValueError(f"merge_tiles: the plan has {T} tiles, got results of {len(per_tile)}")
+    out = []
+    for s, (cls, scores, masks, pick) in enumerate(per_tile):
+        n_s = int(plan.offsets[s + 1] - plan.offsets[s])
+        p_s = 0 if pick is None else int(len(pick))
+        if p_s == 0 or isinstance(masks, (list, tuple)):
+            if p_s:
+                raise ValueError(f"merge_tiles: tile {s} has {p_s} picks and no masks")
+            out.append((None, None, None, None))
+            continue
+        if masks.ndim != 2 or masks.shape[1] != n_s or len(cls) != masks.shape[0] or len(scores) != masks.shape[0]:
+            raise ValueError(f"merge_tiles: tile {s}: masks {tuple(masks.shape)}, {len(cls)} classes and {len(scores)} "
+                             f"scores do not fit the tile's {n_s} points")
+        out.append((masks, pick, cls, scores))
+    return out
+
+
+def merge_tiles_host(plan, per_tile, *, iom=0.5, min_shared=20, return_tables=False):
+    """Instances of a scan that was run as the tiles of `plan` (scene.tile_plan), joined across the tiles -- the
+    statement csrc/tile_merge.hip is tested against, in integers alone.  per_tile: per tile (cls, scores, masks int32
+    [n_rows_s, n_s], pick) as predict_batches yields them; a tile without picks may give [] for the first three.
+      Rows are the picked masks of all tiles, tile-major and then by rank in pick: P of them, row_tile[r] the tile.
+      inter[a, b], for rows of different tiles s, t: the points of the scan that lie in both tiles and in both masks.
+      shared[a, t], for t other than a's tile: the points of mask a that also lie in tile t.
+      Rows a, b are joined when cls[a] == cls[b], inter[a, b] >= min_shared and
+      float64(inter[a, b]) >= iom * float64(min(shared[a, t], shared[b, s])): intersection over the smaller side
+      WITHIN the region the two tiles share (not IoU: where a tile's border cuts an object, the part it holds must
+      match the whole as the neighbour sees it).
+      Instances are the connected components; the representative is the smallest row, global ids 0 .. G-1 follow the
+      representatives in ascending order; the class is the members' common class, the score the largest member score
+      (the same float), the mask the union of the members' masks over the scan's N points.
+    Returns (cls int64 [G], scores fp32 [G], masks int32 [G, N], pick int64 [G]: the stable argsort of -scores,
+    members int32 [P]: row -> global id); with return_tables also a dict of inter int32 [P, P], shared int32 [P, T],
+    comp int32 [P], count int32 [G] and row_tile int32 [P]."""
+    T, N = plan.T, plan.N
+    rows = _tile_rows(plan, per_tile)
+    A, row_tile, cls_all, sc_all, first = [], [], [], [], [0]
+    for s, (masks, pick, cls, scores) in enumerate(rows):
+        if masks is None:
+            A.append(np.zeros((0, int(plan.offsets[s + 1] - plan.offsets[s])), bool))
+        else:
+            pk = np.asarray(_np(pick)).astype(np.int64).reshape(-1)
+            m = np.asarray(_np(masks))
+            ok = (pk >= 0) & (pk < m.shape[0])  # a pick outside the masks is an empty row
+            a = np.zeros((pk.size, m.shape[1]), bool)
+            a[ok] = m[pk[ok]] != 0
+            A.append(a)
+            safe = np.where(ok, pk, 0)
+            cls_all.append(np.asarray(_np(cls)).astype(np.int64)[safe])
+            sc_all.append(np.asarray(_np(scores)).astype(np.float32)[safe])
+        row_tile += [s] * A[-1].shape[0]
+        first.append(first[-1] + A[-1].shape[0])
+    P = first[-1]
+    row_tile = np.asarray(row_tile, np.int32)
+    cls_all = np.concatenate(cls_all) if cls_all else np.zeros(0, np.int64)
+    sc_all = np.concatenate(sc_all) if sc_all else np.zeros(0, np.float32)
+    inter = np.zeros((P, P), np.int32)
+    shared = np.zeros((P, T), np.int32)
+    # the shared points of every pair of tiles, from the point tables: (s, t, index in s, index in t)
+    for i in range(4):
+        for j in range(i + 1, 4):
+            both = plan.tile_of[:, j] >= 0
+            s_, t_ = plan.tile_of[both, i].astype(np.int64), plan.tile_of[both, j].astype(np.int64)
+            la, lb = plan.local_of[both, i], plan.local_of[both, j]
+            key = s_ * T + t_
+            for k in np.unique(key):
+                sel = key == k
+                s, t = int(k) // T, int(k) % T
+                a, b = A[s][:, la[sel]], A[t][:, lb[sel]]
+                if a.shape[0]:
+                    shared[first[s]:first[s + 1], t] += a.sum(1, dtype=np.int32)
+                if b.shape[0]:
+                    shared[first[t]:first[t + 1], s] += b.sum(1, dtype=np.int32)
+                if a.shape[0] and b.shape[0]:
+                    blk = a.astype(np.int32) @ b.T.astype(np.int32)
+                    inter[first[s]:first[s + 1], first[t]:first[t + 1]] += blk
+                    inter[first[t]:first[t + 1], first[s]:first[s + 1]] += blk.T
+    a, b = np.nonzero(np.triu(row_tile[:, None] != row_tile[None, :], 1))
+    small = np.minimum(shared[a, row_tile[b]], shared[b, row_tile[a]])
+    edge = (cls_all[a] == cls_all[b]) & (inter[a, b] >= min_shared) & \
+           (inter[a, b].astype(np.float64) >= float(iom) * small.astype(np.float64))
+    comp = _min_index_components(P, a[edge], b[edge])
+    reps, members = np.unique(comp, return_inverse=True)
+    members = members.reshape(-1).astype(np.int32)
+    G = reps.size
+    scores = np.full(G, -np.inf, np.float32)
+    np.maximum.at(scores, members, sc_all)
+    masks = np.zeros((G, N), np.int32)
+    for s in range(T):
+        idx = plan.points(s)
+        for r in range(A[s].shape[0]):
+            masks[members[first[s] + r], idx[A[s][r]]] = 1
+    out = (cls_all[reps], scores, masks, np.argsort(-scores, kind="stable").astype(np.int64), members)
+    if return_tables:
+        out += (dict(inter=inter, shared=shared, comp=comp.astype(np.int32), count=masks.sum(1, dtype=np.int32),
+                     row_tile=row_tile),)
+    return out
+
+
+def tile_scene_table(plan, rows):
+    """(table int64 [T, GF_TILE_SCENE_FIELDS], sizes) of gf_tile_pack_picks / gf_tile_overlaps / gf_tile_assemble from
+    _tile_rows' device tensors: {masks pointer, n_rows, n_s, pick pointer, p_s, first row, first word}; sizes: P rows,
+    uint32 words of the bitsets, row_tile int32 [P]."""
+    T = plan.T
+    table = np.zeros((T, TILE_SCENE_FIELDS), np.int64)
+    row = word = 0
+    row_tile = []
+    for s, (masks, pick, _, _) in enumerate(rows):
+        n_s = int(plan.offsets[s + 1] - plan.offsets[s])
+        p_s = 0 if masks is None else int(pick.shape[0])
+        if p_s:
+            table[s] = (masks.data_ptr(), masks.shape[0], n_s, pick.data_ptr(), p_s, row, word)
+        else:
+            table[s] = (0, 0, n_s, 0, 0, row, word)
+        row += p_s
+        word += n_s * ((p_s + 31) // 32)
+        row_tile += [s] * p_s
+    return table, dict(rows=row, words=word, row_tile=np.asarray(row_tile, np.int32))
+
+
+def merge_tiles(plan, per_tile, *, iom=0.5, min_shared=20, return_tables=False):
+    """merge_tiles_host on the tensors' device and the current stream (csrc/tile_merge.hip: pointops.tile_pack_picks,
+    tile_overlaps, tile_merge, tile_assemble -- a fixed number of launches for any number of tiles and picks): the picked
+    instances of a scan's tiles joined into (cls [G], scores [G], masks int32 [G, N], pick, members), every output
+    bit-identical to the host statement and from call to call.  One device-to-host read, of G, sizes the dense output
+    (4 * G * N bytes).  More than pointops.TILE_MAX_PICKS picks in a tile or TILE_MAX_ROWS in all is an error before
+    anything is launched.  Host arrays (no tensor on a GPU among them) go to merge_tiles_host."""
+    dev = next((x.device for tile in per_tile for x in tile if torch.is_tensor(x) and x.is_cuda), None)
+    if dev is None:
+        out = merge_tiles_host(plan, per_tile, iom=iom, min_shared=min_shared, return_tables=return_tables)
+        if any(torch.is_tensor(x) for tile in per_tile for x in tile):
+            out = tuple(torch.from_numpy(x) for x in out[:5]) + out[5:]
+        return out
+    from . import pointops
+
+    T, N = plan.T, plan.N
+    rows = []
+    for masks, pick, cls, scores in _tile_rows(plan, per_tile):
+        if masks is not None:
+            masks = (masks if masks.dtype == torch.int32 else (masks != 0).int()).to(dev).contiguous()
+            pick = torch.as_tensor(pick).to(dev, torch.int64).contiguous()
+            cls, scores = torch.as_tensor(cls).to(dev, torch.int64), torch.as_tensor(scores).to(dev, torch.float32)
+        rows.append((masks, pick, cls, scores))
+    table, sizes = tile_scene_table(plan, rows)
+    pointops.tile_check_caps(table)
+    P = sizes["rows"]
+    if P == 0:
+        out = (torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.float32, device=dev),
+               torch.zeros((0, N), dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int64, device=dev),
+               torch.empty(0, dtype=torch.int32, device=dev))
+        if return_tables:
+            z = torch.zeros(0, dtype=torch.int32, device=dev)
+            out += (dict(inter=z.reshape(0, 0), shared=z.reshape(0, T), comp=z, count=z, row_tile=z),)
+        return out
+    # a pick outside the masks is an empty row: its class and score are those of row 0, as in the statement
+    with_picks = [r for r in rows if r[0] is not None]
+    safe = [torch.where((p >= 0) & (p < m.shape[0]), p, torch.zeros_like(p)) for m, p, _, _ in with_picks]
+    cls_all = torch.cat([c[p] for (_, _, c, _), p in zip(with_picks, safe)]).contiguous()
+    sc_all = torch.cat([s[p] for (_, _, _, s), p in zip(with_picks, safe)]).contiguous()
+    table_d = pointops._table_dev(table, dev)
+    tile_of = torch.from_numpy(plan.tile_of).to(dev, non_blocking=True)
+    local_of = torch.from_numpy(plan.local_of).to(dev, non_blocking=True)
+    row_tile = torch.from_numpy(sizes["row_tile"]).to(dev, non_blocking=True)
+    bits = pointops.tile_pack_picks(table_d, table, sizes)
+    inter, shared = pointops.tile_overlaps(table_d, table, tile_of, local_of, bits, P)
+    comp, members, d_G, inst_cls, inst_scores = pointops.tile_merge(inter, shared, cls_all, sc_all, row_tile, iom,
+                                                                    min_shared)
+    G = int(d_G.item())  # the one read-back: the dense output is sized by it
+    masks, count = pointops.tile_assemble(table_d, table, tile_of, local_of, bits, members, G)
+    scores = inst_scores[:G]
+    out = (inst_cls[:G], scores, masks, torch.sort(-scores, stable=True)[1], members)
+    if return_tables:
+        out += (dict(inter=inter, shared=shared, comp=comp, count=count, row_tile=row_tile),)
+    return out

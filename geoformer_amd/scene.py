@@ -10,6 +10,8 @@ resemble ``_vh_clean_2`` meshes.  The batch dict mirrors what
 """
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import numpy as np
 
 
@@ -215,3 +217,83 @@ def grid_segments(raw, cell=0.25):
         _, inv = np.unique(keys[ann], axis=0, return_inverse=True)
         seg[ann] = inv.reshape(-1).astype(np.int32)
     return seg
+
+
+# ---- tiles of a large scan (postprocess.merge_tiles joins the instances of the tiles) -----------------------------------
+class TilePlan(NamedTuple):
+    """tile_plan's result: integer tables over the scan's N points and its T = nx * ny tiles."""
+    tile_of: np.ndarray   # int32 [N, 4]: the point's tiles, ascending, -1 padded
+    local_of: np.ndarray  # int32 [N, 4]: the point's index inside that tile
+    core_of: np.ndarray   # int32 [N]: the tile whose core holds the point
+    offsets: np.ndarray   # int64 [T + 1]: start of each tile in index
+    index: np.ndarray     # int64 [offsets[-1]]: each tile's points (ids into the scan), ascending
+    nx: int
+    ny: int
+    size: tuple           # (tx, ty): the equalised tile widths in metres
+
+    @property
+    def T(self):
+        return self.nx * self.ny
+
+    @property
+    def N(self):
+        return self.tile_of.shape[0]
+
+    def points(self, s):
+        """int64 ids into the scan of tile s' points, ascending."""
+        return self.index[self.offsets[s]:self.offsets[s + 1]]
+
+
+def _tile_axis(v, tile, halo):
+    """One axis of tile_plan in float64: (n columns, width, core column [N], second column [N] or -1)."""
+    if v.size == 0:
+        return 1, 0.0, np.zeros(0, np.int64), np.full(0, -1, np.int64)
+    u = v - v.min()
+    e = float(u.max())
+    n = max(1, int(np.ceil(e / tile)))
+    t = e / n
+    if n > 1 and halo > t / 2:
+        raise ValueError(f"tile_plan: halo = {halo} exceeds half of the tile width {t:.6g} (extent {e:.6g} in {n} "
+                         f"tiles): a point would lie in more than two tiles of a row")
+    core = np.minimum(n - 1, np.floor(u / t)).astype(np.int64) if t > 0 else np.zeros(u.shape, np.int64)
+    lo = (core > 0) & (u - core * t < halo)
+    hi = (core < n - 1) & ((core + 1) * t - u <= halo)
+    other = np.where(lo, core - 1, np.where(hi, core + 1, -1))  # (halo <= t / 2: never both)
+    return n, t, core, other
+
+
+def tile_plan(xyz, tile=4.0, halo=0.5):
+    """Overlapping tiles of a scan in x / y (z is not cut) as integer tables: a TilePlan.  Per axis, with x0 the
+    minimum and ex the extent: nx = max(1, ceil(ex / tile)) columns of the equal width tx = ex / nx; the core column of
+    a point at u = x - x0 is ix = min(nx - 1, floor(u / tx)); the point also belongs to column ix - 1 when
+    u - ix * tx < halo and to column ix + 1 when (ix + 1) * tx - u <= halo, where that column exists.  A tile's id is
+    iy * nx + ix.  halo <= tx / 2 is required on an axis that is cut (ValueError otherwise), so a point lies in at most
+    4 tiles.  All arithmetic is float64 on the host; an empty tile stays in the plan with no points."""
+    x = np.asarray(xyz, dtype=np.float64)
+    if x.ndim != 2 or x.shape[1] < 2:
+        raise ValueError(f"tile_plan: expected xyz [N, >= 2], got {x.shape}")
+    tile, halo = float(tile), float(halo)
+    if not tile > 0 or not halo >= 0:
+        raise ValueError(f"tile_plan: tile = {tile} (positive), halo = {halo} (not negative)")
+    N = x.shape[0]
+    nx, tx, cx, ox = _tile_axis(x[:, 0], tile, halo)
+    ny, ty, cy, oy = _tile_axis(x[:, 1], tile, halo)
+    T = nx * ny
+    cols = np.stack([cx, ox], 1)  # [N, 2], -1 = none
+    rows = np.stack([cy, oy], 1)
+    cand = rows[:, :, None] * nx + cols[:, None, :]
+    cand = np.where((rows[:, :, None] >= 0) & (cols[:, None, :] >= 0), cand, T).reshape(N, 4)
+    cand.sort(axis=1)  # ascending, the missing ones (T) last
+    valid = cand < T
+    g, slot = np.nonzero(valid)  # row-major: g ascending
+    t = cand[g, slot]
+    order = np.argsort(t, kind="stable")  # by tile, then by point
+    counts = np.bincount(t, minlength=T)
+    offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    local = np.empty(order.size, np.int64)
+    local[order] = np.arange(order.size) - offsets[t[order]]
+    tile_of = np.where(valid, cand, -1).astype(np.int32)
+    local_of = np.zeros((N, 4), np.int32)
+    local_of[g, slot] = local
+    return TilePlan(tile_of, local_of, (cy * nx + cx).astype(np.int32), offsets, g[order].astype(np.int64), nx, ny,
+                    (tx, ty))

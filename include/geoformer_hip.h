@@ -996,6 +996,52 @@ int gf_mask_keep_largest(const int32_t* masks, int n_rows, int N, const long lon
                          const int32_t* tab, int32_t* masks_out, void* stream);
 
 /* ===================================================================================
+ * Instances of a scan that was run as T overlapping tiles, joined across the tiles (csrc/tile_merge.hip; the statement
+ * is postprocess.merge_tiles_host, the tile plan scene.tile_plan).  The device receives integer tables only:
+ *   tile_of, local_of int32 [N, 4], 16-byte aligned: the tiles of each of the scan's N points in ascending order, -1
+ *   padded, and the point's index inside each of them.
+ *   Tile scene table, int64 [T, GF_TILE_SCENE_FIELDS], one row per tile s (an empty tile has n_s = 0):
+ *     {masks pointer (int32 [n_rows, n_s], nonzero = member), n_rows, n_s, pick pointer (int64 [p_s], rows of masks; a
+ *      value outside [0, n_rows) is an empty row), p_s (<= gf_tile_merge_max_picks()), first row (the p_s of the tiles
+ *      before), first word (uint32 words into bits: the n * ceil(p / 32) of the tiles before)}.
+ *   table (device) and table_host (the same rows on the host): table_host is checked before anything is launched -- a
+ *   negative size, p_s over the cap, first row / first word that do not follow the tile before, picks that do not add
+ *   up to P, P > gf_tile_merge_max_rows() or T > 65535 are GF_ERR_INVALID_ARG.
+ * Rows 0 .. P-1 are the picked masks of all tiles, tile-major, then by rank in pick.
+ *
+ * gf_tile_pack_picks (one launch): bits uint32 -- per tile-local point j of tile s the ceil(p_s / 32) consecutive words
+ *   at first word + j * ceil(p_s / 32): bit k of word w is set when the mask of pick w * 32 + k holds the point.
+ * gf_tile_overlaps (two memsets, one launch): inter int32 [P, P] (symmetric) and shared int32 [P, T], zeroed by the
+ *   call; only entries across two tiles are written.  For rows a of tile s and b of tile t != s:
+ *   inter[a, b] = the points of the scan that lie in both tiles and in both masks; shared[a, t] = the points of mask a
+ *   that also lie in tile t.  One thread per point of the scan; a point in one tile costs the read of its tile_of row.
+ *   Integer atomics, one per distinct (tile pair, bitset pair) of a wave.
+ * gf_tile_merge (one launch of ONE workgroup of 1024 threads): rows a < b are joined when row_tile[a] != row_tile[b],
+ *   cls[a] == cls[b], inter[a, b] >= min_shared and (double)inter[a, b] >= iom * (double)min(shared[a, row_tile[b]],
+ *   shared[b, row_tile[a]]) (one double multiplication and a compare).  comp int32 [P]: the smallest row of each row's
+ *   connected component; members int32 [P]: the component's rank among the representatives (the global id);
+ *   d_G int32 [1] = G; inst_cls int64 [P], inst_scores fp32 [P] (first G valid): the representative's class and the
+ *   largest member score, the same word copied (integer-ordered maximum; the scores hold no NaN).
+ * gf_tile_assemble (two memsets, one launch): masks int32 [G, N] (0 / 1) and count int32 [G], zeroed by the call:
+ *   masks[members[r], g] = 1 for every row r and point g of its mask, through the bitsets; count = the points of each
+ *   instance (a word is counted by the atomicOr that finds it 0).  A member id outside [0, G) is skipped.
+ * Every output is a function of the inputs: bit-identical from call to call.  Every launch goes on `stream`; no host
+ * synchronisation, no read-back. */
+enum { GF_TILE_SCENE_FIELDS = 7 }; /* int64 words per row of the tile scene table */
+int gf_tile_merge_max_rows(void);
+int gf_tile_merge_max_picks(void);
+int gf_tile_pack_picks(const long long* table, const long long* table_host, int T, int P, uint32_t* bits, void* stream);
+int gf_tile_overlaps(const long long* table, const long long* table_host, int T, const int32_t* tile_of,
+                     const int32_t* local_of, long long N, const uint32_t* bits, int P, int32_t* inter, int32_t* shared,
+                     void* stream);
+int gf_tile_merge(const int32_t* inter, const int32_t* shared, const long long* cls, const float* scores,
+                  const int32_t* row_tile, int P, int T, double iom, int min_shared, int32_t* comp, int32_t* members,
+                  int32_t* d_G, long long* inst_cls, float* inst_scores, void* stream);
+int gf_tile_assemble(const long long* table, const long long* table_host, int T, const int32_t* tile_of,
+                     const int32_t* local_of, long long N, const uint32_t* bits, const int32_t* members, int P, int G,
+                     int32_t* masks, int32_t* count, void* stream);
+
+/* ===================================================================================
  * Backbone voxel transformer of the two deepest U-Net levels, fused (inference)
  * (UBlock: model/geoformer/geoformer_modules.py:64-68,120-127; TransformerEncoder(d_model=128, N,
  *  heads=4, d_ff=64): model/transformer.py:62-188)

@@ -9,6 +9,7 @@ greedy NMS) and the scene labelling of batch_eval.label_batches, written with ge
     python tools/predict_scenes.py --out out --segments segs scene0011_00_inst_nostuff.npy  # masks pooled over segs/<name>*.segs.json
     python tools/predict_scenes.py --out out --geometric-segments scene0011_00_inst_nostuff.npy  # ... over segments made from the points
     python tools/predict_scenes.py --out out --split-masks largest scene0011_00_inst_nostuff.npy  # picked masks cut to their largest connected cluster
+    python tools/predict_scenes.py --out out --tile 4 --halo 0.5 floor3.npy               # a large scan as overlapping 4 m tiles, instances joined
 
 Per scene <out>/<name>.npz (ids, owner, instance table: export.load_labels) and, with --scannet, <out>/<name>.txt plus
 <out>/predicted_masks/ (exclusive masks; --full-masks writes the picked masks as they are).  Without --checkpoint the
@@ -28,6 +29,9 @@ The JSON line's `segment_pooling` says whether the pooling ran, `geometric_segme
 --split-masks largest|split splits every picked mask into spatially connected clusters after the NMS (DBSCAN per mask,
 batch_eval.MaskSplit with its defaults, csrc/mask_split.hip): `largest` keeps each mask's largest cluster, `split` makes
 every kept cluster an instance of its own.  The JSON line's `mask_split` names the mode (null without the flag).
+--tile M runs every scene of more than --tile-max-points points as overlapping tiles of about M metres in x / y (halo
+--halo M on every side) and joins the instances of the tiles (batch_eval.Tiling, csrc/tile_merge.hip); it does not go
+with --panoptic.  The JSON line's `tiling` holds the parameters (null without the flag).
 """
 import argparse
 import json
@@ -69,6 +73,12 @@ def build_parser():
     ap.add_argument("--split-masks", choices=("largest", "split"), default=None,
                     help="split every picked mask into spatially connected clusters after the NMS (batch_eval.MaskSplit "
                          "with its defaults): keep the largest cluster, or make every kept cluster an instance")
+    ap.add_argument("--tile", type=float, default=None, metavar="M",
+                    help="run scenes of more than --tile-max-points points as overlapping tiles of about M metres and "
+                         "join the instances of the tiles (batch_eval.Tiling)")
+    ap.add_argument("--halo", type=float, default=None, metavar="M", help="overlap of the tiles on every side (default 0.5)")
+    ap.add_argument("--tile-max-points", type=int, default=None, metavar="N",
+                    help="scenes with at most N points run whole (default 400000)")
     ap.add_argument("--no-write", action="store_true")
     ap.add_argument("--reps", type=int, default=3, help="timed passes per keep_masks setting")
     return ap
@@ -130,6 +140,14 @@ def main():
         kw["nms"] = args.nms
     if args.split_masks is not None:
         kw["split"] = args.split_masks
+    tiling = None
+    if args.tile is not None:
+        if args.panoptic:
+            ap.error("--tile: --panoptic is not supported with tiles yet")
+        more = {k: v for k, v in (("halo", args.halo), ("max_points", args.tile_max_points)) if v is not None}
+        tiling = kw["tiles"] = batch_eval.Tiling(tile=args.tile, **more)
+    elif args.halo is not None or args.tile_max_points is not None:
+        ap.error("--halo and --tile-max-points go with --tile")
 
     def run(keep_masks):
         np.random.seed(0)
@@ -190,7 +208,7 @@ def main():
                       "picked": sum(len(lab.table.kept) for _, lab in results), "kept": kept,
                       "labelled_points": sum(int((lab.owner >= 0).sum()) for _, lab in results),
                       "segment_pooling": "segments" in kw, "geometric_segments": args.geometric_segments,
-                      "mask_split": args.split_masks,
+                      "mask_split": args.split_masks, "tiling": tiling.params if tiling else None,
                       "scenes_per_s": rates, "out": None if args.no_write else args.out}))
 
 
