@@ -22,13 +22,32 @@ class GeoFormerHipError(RuntimeError):
     pass
 
 
+class _Handle(ctypes.CDLL):
+    """The library's handle: an entry point gets its prototype from the headers (_abi.functions()) when it is first
+    looked up, and is then an attribute of the handle like any ctypes function.  A process pays for the entry points
+    it calls, not for every one the headers declare (about ten collector-tracked objects each).  The function object is
+    put on the handle only AFTER its prototype is set: forwards run on several host threads, and a thread that finds the
+    attribute another thread has just made must never call it without argtypes (ctypes would pass a pointer or a
+    long long as a C int).  Two threads that look a name up at the same time each bind an object of their own; either
+    may stay on the handle."""
+
+    def __getattr__(self, name):
+        if name.startswith("__") and name.endswith("__"):
+            raise AttributeError(name)  # (as ctypes.CDLL.__getattr__ does)
+        fn = self[name]  # a new function object, not yet visible to anyone; AttributeError for a missing export
+        sig = _abi.functions().get(name)
+        if sig is not None:
+            fn.restype, fn.argtypes = sig
+        setattr(self, name, fn)
+        return fn
+
+
 def _declare(lib):
-    """Bind every prototype of the headers (_abi.functions()) on the handle; returns that table."""
+    """Check that the library exports every prototype of the headers (_abi.functions()) -- AttributeError otherwise --
+    without keeping a function object for any of them; returns that table.  _Handle binds them on first use."""
     sig = _abi.functions()
-    for name, (res, args) in sig.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
+    for name in sig:
+        lib[name]
     return sig
 
 
@@ -68,7 +87,7 @@ def load():
     import torch  # noqa: F401  (loads libamdhip64 first; our library binds to the same SONAME)
 
     _check_hw_queues(torch)
-    lib = ctypes.CDLL(LIB_PATH)
+    lib = _Handle(LIB_PATH)
     EXPORTS = _declare(lib)
     if lib.gf_abi_version() != _abi.const("GF_ABI_VERSION"):
         raise GeoFormerHipError("libgeoformer_hip.so ABI version mismatch")

@@ -16,6 +16,9 @@
     print(evaluation.format_panoptic_results(res))
     for name, cls, scores, masks, pick in predict_batches(model, [(name, raw), ...], batch_size=4, tiles=Tiling(tile=4.0)):
         ...                                   # a large scan runs as overlapping tiles; masks int32 [G, N], merged
+    ap, avgs = evaluate(model, [(name, raw), ...], batch_size=4, tiles=Tiling(tile=4.0), stitch="core", semantic=ev)
+    res = evaluate_panoptic(model, [(name, raw), ...], batch_size=4, tiles=Tiling(tile=4.0), stitch="core")
+                                              # the tiles' semantic scores stitched per scan: "core" or "mean"
 
 A batch of raw scenes ([N, 8] = xyz, rgb, semantic label, instance label, as prepare_data_inst.py stores them) is
 collated on the host (scene.collate_raw), uploaded and voxelised on the GPU one batch ahead (feeder.DeviceFeeder), and
@@ -182,12 +185,69 @@ def _tiling(tiles):
     raise ValueError(f"tiles: None or a Tiling, got {tiles!r}")
 
 
-def _predict_tiled(model, raw_scenes, batch_size, tiling, kw):
+def _stitching(stitch, tiling, who):
+    """The checks of the stitch= keyword, before anything touches the model or the GPU."""
+    if stitch is not None and stitch not in postprocess.STITCH_MODES:
+        raise ValueError(f"{who}: stitch must be None or one of {postprocess.STITCH_MODES}, got {stitch!r}")
+    if stitch is not None and tiling is None:
+        raise ValueError(f"{who}: stitch= goes with tiles=")
+    return stitch
+
+
+def _tiled_raws(items, plans):
+    """{name: raw} of the tiled scenes, whose kept scores and labels go by name: a tiled scene that shares its name with
+    another scene of the list would be counted against the wrong labels, so that is a ValueError."""
+    names = [n for n, _ in items]
+    twice = sorted({str(n) for n in plans if names.count(n) > 1})
+    if twice:
+        raise ValueError(f"stitch=: the tiled scene(s) {', '.join(twice)} share their name with another scene")
+    return {n: r for n, r in items if n in plans}
+
+
+class _TileSemantics:
+    """Stands where predict_batches / semantic_batches take a SemanticEvaluator when scans run as tiles: a scene that is
+    no tile of a planned scan is handed on to `inner` at once, as a batch of one scene; the scores of a scan's tiles
+    are kept on the device (copies: nothing says that the next forward does not write the same buffer) until the scan's last
+    non-empty tile is in, then stitched (postprocess.stitch_tiles, one launch) and handed on once, under the scan's own
+    name with the scan's own labels (the raw scene's column 6).  A scan holds 4 * C * (the points of all its tiles)
+    bytes until then.  Nothing is read back."""
+
+    def __init__(self, inner, plans, raws, stitch):
+        self.inner, self.plans, self.raws, self.stitch = inner, plans, raws, stitch
+        self.left = {n: int((np.diff(p.offsets) > 0).sum()) for n, p in plans.items()}
+        self.kept = {}
+
+    def _hand_on(self, scores, labels, name):
+        off = torch.tensor([0, scores.shape[0]], dtype=torch.int32)
+        self.inner.add_batch(scores, labels, off.to(scores.device, non_blocking=True), [name], offsets_host=off)
+
+    def add_batch(self, scores, labels, offsets, names, offsets_host=None):
+        off = [int(o) for o in (offsets if offsets_host is None else offsets_host)]
+        for i, name in enumerate(names):
+            part = scores[off[i]:off[i + 1]]
+            if not (isinstance(name, TileName) and name[0] in self.plans):
+                self._hand_on(part, labels[off[i]:off[i + 1]], name)
+                continue
+            scan, s = name
+            plan = self.plans[scan]
+            self.kept.setdefault(scan, [None] * plan.T)[s] = part.clone(memory_format=torch.contiguous_format)
+            self.left[scan] -= 1
+            if self.left[scan] == 0:
+                stitched = postprocess.stitch_tiles(plan, self.kept.pop(scan), self.stitch)
+                lab = torch.from_numpy(scene_dict(self.raws[scan])["label"]).to(scores.device, non_blocking=True)
+                self._hand_on(stitched, lab, scan)
+
+
+def _predict_tiled(model, raw_scenes, batch_size, tiling, stitch, kw):
     """The loop of predict_batches over tile_items' expanded list; a tiled scene is yielded once, merged, when its last
-    tile has come out."""
+    tile has come out.  With stitch the semantic evaluator is given every tiled scene once too, stitched
+    (_TileSemantics), in the batch of the scene's last tile: before that batch's NMS and before the scene is yielded."""
+    if kw.get("semantic") is not None and stitch is None:
+        raise ValueError('predict_batches: semantic= is not supported with tiles yet without stitch="core" or "mean"')
+    raw_scenes = list(raw_scenes)
+    items, plans = tile_items(raw_scenes, tiling)
     if kw.get("semantic") is not None:
-        raise ValueError("predict_batches: semantic= is not supported with tiles yet")
-    items, plans = tile_items(list(raw_scenes), tiling)
+        kw = dict(kw, semantic=_TileSemantics(kw["semantic"], plans, _tiled_raws(raw_scenes, plans), stitch))
     segments = kw.get("segments")
     if plans and segments is not None and _geometric(segments) is None:
         # a mapping: a tiled scene's ids are sliced through the plan, per tile
@@ -262,7 +322,7 @@ def collate_batches(raw_scenes, batch_size, spatial_shape=None, scale=50, full_s
 @torch.no_grad()
 def predict_batches(model, raw_scenes, batch_size, *, epoch=300, spatial_shape=None, nms_kernel="gaussian",
                     sigma=2.0, final_score_thresh=NMS_FINAL_SCORE, cvfold=None, reserve=True, device=None,
-                    semantic=None, nms="matrix", nms_thresh=None, segments=None, split=None, tiles=None):
+                    semantic=None, nms="matrix", nms_thresh=None, segments=None, split=None, tiles=None, stitch=None):
     """Yields (name, cls_final, scores_final, masks_final, pick) per scene, in input order.  raw_scenes: iterable of
     (name, raw [N, 8]).  The NMS categories are the benchmark label ids of the classes (evaluation.benchmark_label_ids
     with cvfold, default model.cfg.cvfold).  A scene without proposals yields ([], [], [], empty pick).  reserve: size
@@ -283,10 +343,17 @@ def predict_batches(model, raw_scenes, batch_size, *, epoch=300, spatial_shape=N
     the expanded list (same feeder, same batches of batch_size, segments= sliced or computed per tile, split= applied
     per tile), and when a scene's last tile has come out postprocess.merge_tiles joins the tiles' picked instances: the
     scene is yielded once, in input order, with masks int32 [G, N] over the whole scan holding the G merged instances
-    only, and pick their score order (one read-back per tiled scene).  semantic= with tiles is a ValueError; None:
-    nothing is added to the loop."""
-    if _tiling(tiles) is not None:
-        yield from _predict_tiled(model, raw_scenes, batch_size, tiles, dict(
+    only, and pick their score order (one read-back per tiled scene); None: nothing is added to the loop.  stitch:
+    "core" or "mean", with tiles only -- how `semantic` is given a tiled scene: its tiles' scores are kept on the
+    device until the scene's last tile is in, stitched into one [N, C] (postprocess.stitch_tiles: each point's row from
+    its core tile, or the mean over the tiles that hold it) and counted once, under the scene's own name against the
+    scene's own labels, before the scene is yielded; there is no default because neither rule's effect on mIoU has been
+    measured.  With semantic=None there is nothing to stitch: stitch is checked and otherwise unused.  semantic= with
+    tiles and stitch=None is a ValueError; stitch without tiles is one too; so is, with semantic= and stitch, a tiled
+    scene whose name another scene of the list carries (the scores and labels of a scan are kept by its name)."""
+    _stitching(stitch, _tiling(tiles), "predict_batches")
+    if tiles is not None:
+        yield from _predict_tiled(model, raw_scenes, batch_size, tiles, stitch, dict(
             epoch=epoch, spatial_shape=spatial_shape, nms_kernel=nms_kernel, sigma=sigma,
             final_score_thresh=final_score_thresh, cvfold=cvfold, reserve=reserve, device=device, semantic=semantic,
             nms=nms, nms_thresh=nms_thresh, segments=segments, split=split))
@@ -477,15 +544,9 @@ def evaluate(model, scenes_with_gt, batch_size, classes=0, *, cvfold=None, **kw)
     return ev.evaluate()
 
 
-@torch.no_grad()
-def semantic_batches(model, raw_scenes, batch_size, *, spatial_shape=None, reserve=True, device=None, evaluator=None):
-    """Yields (name, preds) per scene, in input order: preds int32 [N] on the device, a view of the batch's buffer -- the
-    semantic head's class of every point (the first maximal score, the rule of the forward's foreground selection).
-    Only the backbone and the semantic head run (forward_backbone with the fused voxel-row head; no arg-max by the
-    framework, no instance stage): the loop of the first ``prepare_epochs``.  evaluator: an evaluation.SemanticEvaluator
-    that counts every batch against its labels in the same launch."""
-    from . import pointops
-
+def _semantic_forwards(model, raw_scenes, batch_size, spatial_shape, reserve, device):
+    """The forwards of semantic_batches: yields (chunk, host batch, device batch, scores fp32 [N, C] contiguous) per
+    batch."""
     dev = torch.device(device) if device is not None else next(model.parameters()).device
     model.eval()
     chunks, batches = collate_batches(raw_scenes, batch_size, spatial_shape)
@@ -496,7 +557,40 @@ def semantic_batches(model, raw_scenes, batch_size, *, spatial_shape=None, reser
         model.reserve_for(most)
     for chunk, host, batch in zip(chunks, batches, DeviceFeeder(batches, dev, reserve_points=most)):
         _, scores, _ = model.forward_backbone(batch, len(chunk), want_preds=False)
-        scores = scores.contiguous()
+        yield chunk, host, batch, scores.contiguous()
+
+
+@torch.no_grad()
+def semantic_batches(model, raw_scenes, batch_size, *, spatial_shape=None, reserve=True, device=None, evaluator=None,
+                     tiles=None, stitch=None):
+    """Yields (name, preds) per scene, in input order: preds int32 [N] on the device, a view of the batch's buffer -- the
+    semantic head's class of every point (the first maximal score, the rule of the forward's foreground selection).
+    Only the backbone and the semantic head run (forward_backbone with the fused voxel-row head; no arg-max by the
+    framework, no instance stage): the loop of the first ``prepare_epochs``.  evaluator: an evaluation.SemanticEvaluator
+    that counts every batch against its labels in the same launch.  tiles: a Tiling, with stitch "core" or "mean" (both
+    or neither: ValueError) -- every scene with more than max_points points runs as its non-empty tiles (tile_items), the
+    tiles' scores are kept on the device until the scene is complete and stitched (postprocess.stitch_tiles), and the
+    scene is counted and yielded once, under its own name, with preds int32 [N] over the whole scan."""
+    from . import pointops
+
+    tiling = _tiling(tiles)
+    _stitching(stitch, tiling, "semantic_batches")
+    if tiling is not None and stitch is None:
+        raise ValueError('semantic_batches: tiles= needs stitch="core" or "mean"')
+    if tiling is not None:
+        items = list(raw_scenes)
+        expanded, plans = tile_items(items, tiling)
+        tap = _SemanticTap(evaluator)
+        sem = _TileSemantics(tap, plans, _tiled_raws(items, plans), stitch)
+        for chunk, host, batch, scores in _semantic_forwards(model, expanded, batch_size, spatial_shape, reserve, device):
+            sem.add_batch(scores, batch["labels"], batch["offsets"], [n for n, _ in chunk], offsets_host=host["offsets"])
+            for name, _ in chunk:
+                # a scan is complete with its last tile, and is yielded in that tile's place
+                name = name[0] if isinstance(name, TileName) and name[0] in plans else name
+                if name in tap.preds:
+                    yield name, tap.preds.pop(name)
+        return
+    for chunk, host, batch, scores in _semantic_forwards(model, raw_scenes, batch_size, spatial_shape, reserve, device):
         if evaluator is not None:
             preds = evaluator.add_batch(scores, batch["labels"], batch["offsets"], [n for n, _ in chunk],
                                         offsets_host=host["offsets"])

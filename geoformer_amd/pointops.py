@@ -1962,3 +1962,49 @@ def tile_assemble(table, table_host, tile_of, local_of, bits, members, G):
                                        ptr(local_of), N, ptr(bits), ptr(members), P, int(G), ptr(masks), ptr(count),
                                        stream_ptr()), "gf_tile_assemble")
     return masks, count
+
+
+# ---- semantic scores stitched across the tiles of a large scan (csrc/tile_stitch.hip) ------------------------------------
+TILE_SCORE_FIELDS = _abi.const("GF_TILE_SCORE_FIELDS")
+TILE_STITCH_MODES = {"core": _abi.const("GF_TILE_STITCH_CORE"), "mean": _abi.const("GF_TILE_STITCH_MEAN")}
+TILE_STITCH_MAX_CLASSES = 64  # gf_tile_stitch_max_classes(): asserted against the library in tile_stitch_limits()
+
+
+def tile_stitch_limits():
+    """The largest class count of the tile stitch, from the library (that of gf_semantic_confusion)."""
+    cap = _lib.load().gf_tile_stitch_max_classes()
+    if cap != TILE_STITCH_MAX_CLASSES:
+        raise RuntimeError(f"tile stitch: the library's cap {cap} is not {TILE_STITCH_MAX_CLASSES}")
+    return cap
+
+
+def tile_stitch_scores(table, table_host, tile_of, local_of, core_of, C, mode):
+    """out fp32 [N, C]: the scan's per-point scores from its tiles' (gf_tile_stitch_scores, the statement is
+    postprocess.stitch_tiles_host): one launch on the current stream, no memset, no atomics, nothing read back.  table /
+    table_host: int64 [T, GF_TILE_SCORE_FIELDS] = {scores pointer fp32 [n_s, C], n_s} on the device and on the host;
+    tile_of, local_of int32 [N, 4] and core_of int32 [N] on the device: the plan's point tables; mode "core" or "mean".
+    Shapes that disagree or C above the cap raise before anything is launched."""
+    if mode not in TILE_STITCH_MODES:
+        raise ValueError(f"tile_stitch_scores: mode must be one of {tuple(TILE_STITCH_MODES)}, got {mode!r}")
+    t = np.asarray(table_host)
+    if t.ndim != 2 or t.shape[1] != TILE_SCORE_FIELDS or t.dtype != np.int64 or t.shape[0] < 1:
+        raise RuntimeError(f"tile_stitch_scores: table_host: expected int64 [T >= 1, {TILE_SCORE_FIELDS}], got {t.dtype} "
+                           f"{t.shape}")
+    table_host = np.ascontiguousarray(t)
+    if not (table.is_cuda and table.dtype == torch.int64 and table.is_contiguous()
+            and tuple(table.shape) == table_host.shape):
+        raise RuntimeError(f"tile_stitch_scores: table: expected a contiguous int64 tensor {table_host.shape} on the GPU")
+    _i32c(tile_of, "tile_of"); _i32c(local_of, "local_of"); _i32c(core_of, "core_of")
+    if tile_of.dim() != 2 or tile_of.shape[1] != 4 or local_of.shape != tile_of.shape \
+            or core_of.shape != (tile_of.shape[0],):
+        raise RuntimeError(f"tile_stitch_scores: expected tile_of and local_of [N, 4] and core_of [N], got "
+                           f"{tuple(tile_of.shape)}, {tuple(local_of.shape)}, {tuple(core_of.shape)}")
+    C = int(C)
+    if not 1 <= C <= TILE_STITCH_MAX_CLASSES:
+        raise RuntimeError(f"tile_stitch_scores: C = {C} classes (1 to {TILE_STITCH_MAX_CLASSES})")
+    N = tile_of.shape[0]
+    out = torch.empty((N, C), dtype=torch.float32, device=table.device)
+    check(_lib.load().gf_tile_stitch_scores(ptr(table), table_host.ctypes.data, table_host.shape[0], ptr(tile_of),
+                                            ptr(local_of), ptr(core_of), N, C, TILE_STITCH_MODES[mode], ptr(out),
+                                            stream_ptr()), "gf_tile_stitch_scores")
+    return out

@@ -978,3 +978,105 @@ def merge_tiles(plan, per_tile, *, iom=0.5, min_shared=20, return_tables=False):
     if return_tables:
         out += (dict(inter=inter, shared=shared, comp=comp, count=count, row_tile=row_tile),)
     return out
+
+
+# ---- semantic scores stitched across the tiles of a large scan (csrc/tile_stitch.hip): the host statement ----------------
+TILE_SCORE_FIELDS = _abi.const("GF_TILE_SCORE_FIELDS")
+STITCH_MODES = ("core", "mean")
+
+
+def _stitch_tiles_checked(plan, per_tile_scores, mode, who):
+    """(C, the tiles' scores with None for every empty tile) of stitch_tiles / stitch_tiles_host, with the mode, the
+    shapes against the plan and the dtype checked (ValueError); nothing is copied or moved."""
+    if mode not in STITCH_MODES:
+        raise ValueError(f"{who}: mode must be one of {STITCH_MODES}, got {mode!r}")
+    if len(per_tile_scores) != plan.T:
+        raise ValueError(f"{who}: the plan has {plan.T} tiles, got scores of {len(per_tile_scores)}")
+    C, out = None, []
+    for s, x in enumerate(per_tile_scores):
+        n_s = int(plan.offsets[s + 1] - plan.offsets[s])
+        if x is None:
+            if n_s:
+                raise ValueError(f"{who}: tile {s} holds {n_s} points and has no scores")
+            out.append(None)
+            continue
+        f32 = x.dtype == torch.float32 if torch.is_tensor(x) else getattr(x, "dtype", None) == np.float32
+        if not f32:
+            raise ValueError(f"{who}: tile {s}: expected float32 scores, got {getattr(x, 'dtype', type(x).__name__)}")
+        if x.ndim != 2 or x.shape[0] != n_s or x.shape[1] < 1:
+            raise ValueError(f"{who}: tile {s}: expected scores [{n_s}, C], got {tuple(x.shape)}")
+        if C is not None and x.shape[1] != C:
+            raise ValueError(f"{who}: tile {s} has {x.shape[1]} classes, the tiles before {C}")
+        C = int(x.shape[1])
+        out.append(x if n_s else None)
+    if C is None:
+        raise ValueError(f"{who}: no tile gives the number of classes")
+    return C, out
+
+
+def stitch_tiles_host(plan, per_tile_scores, mode):
+    """Per-point semantic scores fp32 [N, C] of a scan that was run as the tiles of `plan` (scene.tile_plan) -- the
+    statement csrc/tile_stitch.hip is tested against, in exact float32.  per_tile_scores[s]: float32 [n_s, C], tile s'
+    scores in the tile's own point order (plan.points(s)); None or [0, C] for an empty tile.
+      A slot j of point g counts when tile_of[g, j] lies in [0, T) and local_of[g, j] in [0, n_s) of that tile (every
+      slot with tile_of >= 0 of a plan made by scene.tile_plan); its row is per_tile_scores[tile_of[g, j]][local_of[g, j]].
+      "core": out[g] = the row of the first slot j with tile_of[g, j] == core_of[g], the same words.  The core tile is
+        the one that shows the point the most context: the point is at least halo away from that tile's outer edge and
+        at most halo away from the outer edge of every other tile that holds it.
+      "mean": over the slots j = 0..3 in that order (ascending tile id) that count: acc = row for the first one, then
+        acc = acc + row in float32, one add per slot; out[g] = acc / float32(count), the IEEE division (exact for the
+        counts 1, 2 and 4 that scene.tile_plan makes; correctly rounded for the 3 of a hand-built table).
+      A point without such a slot (hand-built tables only) gets zeros.
+    ValueError for scores that are not float32 [n_s, C] with one C, and for a mode outside the two."""
+    C, tiles = _stitch_tiles_checked(plan, per_tile_scores, mode, "stitch_tiles_host")
+    N, T = plan.N, plan.T
+    flat = np.concatenate([np.zeros((0, C), np.float32)] + [np.asarray(_np(x)) for x in tiles if x is not None])
+    n = np.diff(plan.offsets).astype(np.int64)  # (the row of (s, l) in flat is offsets[s] + l)
+    tile_of, local_of = plan.tile_of.astype(np.int64), plan.local_of.astype(np.int64)
+    safe = np.clip(tile_of, 0, T - 1)
+    ok = (tile_of >= 0) & (tile_of < T) & (local_of >= 0) & (local_of < n[safe])
+    row = np.where(ok, plan.offsets[safe] + local_of, 0)
+    out = np.zeros((N, C), np.float32)
+    if mode == "core":
+        match = tile_of == plan.core_of.astype(np.int64)[:, None]
+        g, j = np.nonzero(match & (np.cumsum(match, 1) == 1) & ok)
+        out[g] = flat[row[g, j]]
+        return out
+    cnt = np.zeros(N, np.int64)
+    for j in range(4):
+        g = np.nonzero(ok[:, j])[0]
+        v = flat[row[g, j]]
+        out[g] = np.where((cnt[g] == 0)[:, None], v, out[g] + v)
+        cnt[g] += 1
+    g = np.nonzero(cnt)[0]
+    out[g] = out[g] / cnt[g].astype(np.float32)[:, None]
+    return out
+
+
+def stitch_tiles(plan, per_tile_scores, mode):
+    """stitch_tiles_host on the tensors' device and the current stream (csrc/tile_stitch.hip, one launch of
+    pointops.tile_stitch_scores for any number of tiles): fp32 [N, C], bit-identical to the host statement and from call
+    to call; nothing is read back.  The tiles' tensors must be float32 [n_s, C], contiguous and on one device (checked
+    on the host against the plan, ValueError, before anything is launched; C above pointops.TILE_STITCH_MAX_CLASSES is
+    pointops' RuntimeError).  Host arrays (no tensor on a GPU among them) go to stitch_tiles_host."""
+    dev = next((x.device for x in per_tile_scores if torch.is_tensor(x) and x.is_cuda), None)
+    if dev is None:
+        out = stitch_tiles_host(plan, per_tile_scores, mode)
+        return torch.from_numpy(out) if any(torch.is_tensor(x) for x in per_tile_scores) else out
+    from . import pointops
+
+    C, tiles = _stitch_tiles_checked(plan, per_tile_scores, mode, "stitch_tiles")
+    table = np.zeros((plan.T, TILE_SCORE_FIELDS), np.int64)
+    for s, x in enumerate(tiles):
+        if x is None:
+            continue
+        if not (torch.is_tensor(x) and x.device == dev and x.is_contiguous()):
+            raise ValueError(f"stitch_tiles: tile {s}: expected a contiguous float32 tensor on {dev}")
+        table[s] = (x.data_ptr(), x.shape[0])
+    if plan.N == 0:
+        return torch.empty((0, C), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        return pointops.tile_stitch_scores(pointops._table_dev(table, dev),
+                                           table, torch.from_numpy(plan.tile_of).to(dev, non_blocking=True),
+                                           torch.from_numpy(plan.local_of).to(dev, non_blocking=True),
+                                           torch.from_numpy(plan.core_of).to(dev, non_blocking=True), C, mode)

@@ -1041,6 +1041,28 @@ int gf_tile_assemble(const long long* table, const long long* table_host, int T,
                      const int32_t* local_of, long long N, const uint32_t* bits, const int32_t* members, int P, int G,
                      int32_t* masks, int32_t* count, void* stream);
 
+/* Per-point semantic scores of a scan stitched from the scores of its T tiles (csrc/tile_stitch.hip; the statement is
+ * postprocess.stitch_tiles_host).  tile_of, local_of as above; core_of int32 [N]: the tile whose core holds the point.
+ *   Tile score table, int64 [T, GF_TILE_SCORE_FIELDS], one row per tile s (an empty tile has n_s = 0):
+ *     {scores pointer (fp32 [n_s, C], contiguous, the tile's points in the tile's own order), n_s}.
+ *   table (device) and table_host (the same rows on the host): table_host is checked before the launch -- a negative
+ *   n_s, a NULL pointer with n_s > 0, T outside 1..65535, C outside 1..gf_tile_stitch_max_classes(), a mode other than
+ *   the two below or N < 0 are GF_ERR_INVALID_ARG; N == 0 succeeds with nothing launched.
+ * gf_tile_stitch_scores (one launch, no memset: every cell of out is written): out fp32 [N, C].
+ *   GF_TILE_STITCH_CORE: out[g] = the row of g in tile core_of[g] (the first slot j with tile_of[g, j] == core_of[g]),
+ *     the same words copied; zeros when there is no such slot.
+ *   GF_TILE_STITCH_MEAN: over the slots j = 0..3 in that order whose tile holds the point: acc = the row of the first
+ *     one, then acc = acc + row (fp32, one add per slot, no multiplication), and out[g] = acc / (float)count, the
+ *     correctly rounded division (exact for the counts 1, 2 and 4 of scene.tile_plan); zeros without a slot.
+ *   A tile id outside [0, T) or a local index outside [0, n_s) contributes nothing and is never an address.  No
+ *   atomics: bit-identical from call to call.  The launch goes on `stream`; no host synchronisation, no read-back. */
+enum { GF_TILE_SCORE_FIELDS = 2 }; /* int64 words per row of the tile score table */
+enum { GF_TILE_STITCH_CORE = 0, GF_TILE_STITCH_MEAN = 1 };
+int gf_tile_stitch_max_classes(void); /* = gf_semantic_confusion_max_classes(): the scores only ever go there */
+int gf_tile_stitch_scores(const long long* table, const long long* table_host, int T, const int32_t* tile_of,
+                          const int32_t* local_of, const int32_t* core_of, long long N, int C, int mode, float* out,
+                          void* stream);
+
 /* ===================================================================================
  * Backbone voxel transformer of the two deepest U-Net levels, fused (inference)
  * (UBlock: model/geoformer/geoformer_modules.py:64-68,120-127; TransformerEncoder(d_model=128, N,

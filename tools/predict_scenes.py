@@ -10,6 +10,7 @@ greedy NMS) and the scene labelling of batch_eval.label_batches, written with ge
     python tools/predict_scenes.py --out out --geometric-segments scene0011_00_inst_nostuff.npy  # ... over segments made from the points
     python tools/predict_scenes.py --out out --split-masks largest scene0011_00_inst_nostuff.npy  # picked masks cut to their largest connected cluster
     python tools/predict_scenes.py --out out --tile 4 --halo 0.5 floor3.npy               # a large scan as overlapping 4 m tiles, instances joined
+    python tools/predict_scenes.py --out out --tile 4 --tile-stitch core --panoptic floor3.npy  # ... and the tiles' semantics stitched: PQ of the scan
 
 Per scene <out>/<name>.npz (ids, owner, instance table: export.load_labels) and, with --scannet, <out>/<name>.txt plus
 <out>/predicted_masks/ (exclusive masks; --full-masks writes the picked masks as they are).  Without --checkpoint the
@@ -30,8 +31,11 @@ The JSON line's `segment_pooling` says whether the pooling ran, `geometric_segme
 batch_eval.MaskSplit with its defaults, csrc/mask_split.hip): `largest` keeps each mask's largest cluster, `split` makes
 every kept cluster an instance of its own.  The JSON line's `mask_split` names the mode (null without the flag).
 --tile M runs every scene of more than --tile-max-points points as overlapping tiles of about M metres in x / y (halo
---halo M on every side) and joins the instances of the tiles (batch_eval.Tiling, csrc/tile_merge.hip); it does not go
-with --panoptic.  The JSON line's `tiling` holds the parameters (null without the flag).
+--halo M on every side) and joins the instances of the tiles (batch_eval.Tiling, csrc/tile_merge.hip).  --tile-stitch
+core|mean also stitches the tiles' semantic scores per scan (batch_eval's stitch=, csrc/tile_stitch.hip): each point's
+scores from its core tile, or the mean over the tiles that hold it; --panoptic goes with --tile only then, and the
+--semantic pass then runs over the tiles too (without it that pass runs every scan whole).  The JSON line's `tiling`
+holds the parameters and `stitch` (null without --tile).
 """
 import argparse
 import json
@@ -79,6 +83,9 @@ def build_parser():
     ap.add_argument("--halo", type=float, default=None, metavar="M", help="overlap of the tiles on every side (default 0.5)")
     ap.add_argument("--tile-max-points", type=int, default=None, metavar="N",
                     help="scenes with at most N points run whole (default 400000)")
+    ap.add_argument("--tile-stitch", choices=("core", "mean"), default=None,
+                    help="with --tile: stitch the tiles' semantic scores per scan, each point from its core tile or the "
+                         "mean over the tiles that hold it (batch_eval's stitch=); needed for --tile --panoptic")
     ap.add_argument("--no-write", action="store_true")
     ap.add_argument("--reps", type=int, default=3, help="timed passes per keep_masks setting")
     return ap
@@ -142,12 +149,14 @@ def main():
         kw["split"] = args.split_masks
     tiling = None
     if args.tile is not None:
-        if args.panoptic:
-            ap.error("--tile: --panoptic is not supported with tiles yet")
+        if args.panoptic and args.tile_stitch is None:
+            ap.error("--tile: --panoptic is not supported with tiles yet without --tile-stitch core|mean")
         more = {k: v for k, v in (("halo", args.halo), ("max_points", args.tile_max_points)) if v is not None}
         tiling = kw["tiles"] = batch_eval.Tiling(tile=args.tile, **more)
-    elif args.halo is not None or args.tile_max_points is not None:
-        ap.error("--halo and --tile-max-points go with --tile")
+        if args.tile_stitch is not None:
+            kw["stitch"] = args.tile_stitch
+    elif args.halo is not None or args.tile_max_points is not None or args.tile_stitch is not None:
+        ap.error("--halo, --tile-max-points and --tile-stitch go with --tile")
 
     def run(keep_masks):
         np.random.seed(0)
@@ -176,7 +185,8 @@ def main():
         from geoformer_amd import evaluation
 
         ev = evaluation.SemanticEvaluator(n_classes=model.cfg.classes, train_fold=model.cfg.train_fold)
-        for name, preds in batch_eval.semantic_batches(model, items, args.batch_size, evaluator=ev):
+        skw = {"tiles": tiling, "stitch": args.tile_stitch} if args.tile_stitch is not None else {}
+        for name, preds in batch_eval.semantic_batches(model, items, args.batch_size, evaluator=ev, **skw):
             if not args.no_write:
                 export.write_scannet_semantic(os.path.join(args.out, "semantic"), name, preds, model.cfg.train_fold)
         if any((raw[:, 6] != evaluation.IGNORE_LABEL).any() for _, raw in items):
@@ -208,7 +218,7 @@ def main():
                       "picked": sum(len(lab.table.kept) for _, lab in results), "kept": kept,
                       "labelled_points": sum(int((lab.owner >= 0).sum()) for _, lab in results),
                       "segment_pooling": "segments" in kw, "geometric_segments": args.geometric_segments,
-                      "mask_split": args.split_masks, "tiling": tiling.params if tiling else None,
+                      "mask_split": args.split_masks, "tiling": dict(tiling.params, stitch=args.tile_stitch) if tiling else None,
                       "scenes_per_s": rates, "out": None if args.no_write else args.out}))
 
 
