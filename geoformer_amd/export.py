@@ -10,6 +10,9 @@ and what util/visualize.py:212-227 reads (relative path, label, score).  Scores 
 
     write_scannet_semantic("out/semantic", "scene0011_00", preds, train_fold=0)     # one benchmark label id per point
     label_ids = read_scannet_semantic("out/semantic", "scene0011_00")
+
+    write_png("out/render/scene0011_00_input_0.png", image[0])                      # uint8 [H, W, 3] of render.render
+    write_ply("out/scene0011_00.ply", xyz, rgb)                                     # the coloured points, for a viewer
 """
 from __future__ import annotations
 
@@ -116,6 +119,124 @@ def load_labels(path):
     with np.load(path) as z:
         table = InstanceTable(*[z[f"table_{k}"] for k in InstanceTable._fields])
         return SceneLabels(z["owner"], z["ids"], table, z["masks"] if "masks" in z.files else None)
+
+
+_PNG_MAGIC = b"\x89PNG\r\n\x1a\n"
+
+
+def _host_array(a):
+    return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+
+
+def write_png(path, image, level=6):
+    """Write image uint8 [H, W, 3] (host or device; render.render's, one view) as an 8-bit RGB PNG: IHDR, one IDAT of
+    the rows with filter 0, IEND, written with zlib and struct alone.  Returns the path."""
+    import struct
+    import zlib
+
+    im = _host_array(image)
+    if im.ndim != 3 or im.shape[2] != 3 or im.dtype != np.uint8 or 0 in im.shape:
+        raise ValueError(f"write_png: expected uint8 [H, W, 3], got {im.dtype} {im.shape}")
+    H, W = im.shape[:2]
+    rows = np.zeros((H, 1 + 3 * W), np.uint8)  # a filter byte (0: none) ahead of every row
+    rows[:, 1:] = im.reshape(H, 3 * W)
+
+    def chunk(kind, data):
+        return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xFFFFFFFF)
+
+    with open(path, "wb") as f:
+        f.write(_PNG_MAGIC + chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 2, 0, 0, 0))
+                + chunk(b"IDAT", zlib.compress(rows.tobytes(), level)) + chunk(b"IEND", b""))
+    return path
+
+
+def read_png(path):
+    """uint8 [H, W, 3] of an 8-bit RGB PNG without interlacing (what write_png writes; all five row filters are
+    understood).  Every chunk's CRC is checked."""
+    import struct
+    import zlib
+
+    with open(path, "rb") as f:
+        data = f.read()
+    if data[:8] != _PNG_MAGIC:
+        raise ValueError(f"{path}: not a PNG file")
+    at, head, idat, ended = 8, None, [], False
+    while at + 12 <= len(data) and not ended:
+        n, kind = struct.unpack(">I4s", data[at:at + 8])
+        body = data[at + 8:at + 8 + n]
+        if len(body) != n or struct.unpack(">I", data[at + 8 + n:at + 12 + n])[0] != zlib.crc32(kind + body) & 0xFFFFFFFF:
+            raise ValueError(f"{path}: chunk {kind!r} is truncated or fails its CRC")
+        if kind == b"IHDR":
+            head = struct.unpack(">IIBBBBB", body)
+        elif kind == b"IDAT":
+            idat.append(body)
+        ended = kind == b"IEND"
+        at += 12 + n
+    if head is None or not ended:
+        raise ValueError(f"{path}: no IHDR or no IEND")
+    W, H, depth, colour, _, _, interlace = head
+    if (depth, colour, interlace) != (8, 2, 0):
+        raise ValueError(f"{path}: only 8-bit RGB without interlacing is read (depth {depth}, colour type {colour})")
+    raw = np.frombuffer(zlib.decompress(b"".join(idat)), np.uint8)
+    if raw.size != H * (1 + 3 * W):
+        raise ValueError(f"{path}: {raw.size} bytes of image data for {W} x {H}")
+    raw = raw.reshape(H, 1 + 3 * W)
+    if not raw[:, 0].any():
+        return raw[:, 1:].reshape(H, W, 3).copy()
+    out = np.zeros((H + 1, 3 * W + 3), np.int64)  # a row above and a pixel to the left, zeros
+    for y in range(H):
+        ft, row, cur, up = int(raw[y, 0]), raw[y, 1:].astype(np.int64), out[y + 1], out[y]
+        if ft in (0, 2):
+            cur[3:] = (row + (up[3:] if ft == 2 else 0)) & 255
+            continue
+        if ft not in (1, 3, 4):
+            raise ValueError(f"{path}: row filter {ft}")
+        for i in range(3 * W):
+            a, b, c = cur[i], up[i + 3], up[i]
+            if ft == 1:
+                pred = a
+            elif ft == 3:
+                pred = (a + b) >> 1
+            else:
+                p = a + b - c
+                pa, pb, pc = abs(p - a), abs(p - b), abs(p - c)
+                pred = a if pa <= pb and pa <= pc else (b if pb <= pc else c)
+            cur[i + 3] = (row[i] + pred) & 255
+    return out[1:, 3:].astype(np.uint8).reshape(H, W, 3)
+
+
+def write_ply(path, xyz, rgb):
+    """Write the points as a binary little-endian PLY vertex cloud (x y z float32, red green blue uchar), for a viewer.
+    xyz [N, 3], rgb uint8 [N, 3], host or device.  Returns the path."""
+    p = _host_array(xyz).astype("<f4").reshape(-1, 3)
+    c = _host_array(rgb)
+    if c.dtype != np.uint8 or c.shape != p.shape:
+        raise ValueError(f"write_ply: rgb: expected uint8 {p.shape}, got {c.dtype} {c.shape}")
+    rec = np.zeros(p.shape[0], dtype=[("xyz", "<f4", 3), ("rgb", "u1", 3)])
+    rec["xyz"], rec["rgb"] = p, c
+    head = ("ply\nformat binary_little_endian 1.0\n" f"element vertex {p.shape[0]}\n"
+            "property float x\nproperty float y\nproperty float z\n"
+            "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n")
+    with open(path, "wb") as f:
+        f.write(head.encode("ascii") + rec.tobytes())
+    return path
+
+
+def read_ply(path):
+    """(xyz float32 [N, 3], rgb uint8 [N, 3]) of a write_ply file."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header\n")
+    lines = data[:end].decode("ascii", "replace").split("\n") if end >= 0 else []
+    props = [ln.split()[1:] for ln in lines if ln.startswith("property ")]
+    want = [["float", "x"], ["float", "y"], ["float", "z"], ["uchar", "red"], ["uchar", "green"], ["uchar", "blue"]]
+    count = [int(ln.split()[2]) for ln in lines if ln.startswith("element vertex ")]
+    if lines[:2] != ["ply", "format binary_little_endian 1.0"] or props != want or len(count) != 1:
+        raise ValueError(f"{path}: not a binary little-endian PLY of x y z red green blue vertices")
+    rec = np.frombuffer(data[end + len(b"end_header\n"):], dtype=[("xyz", "<f4", 3), ("rgb", "u1", 3)])
+    if rec.shape[0] != count[0]:
+        raise ValueError(f"{path}: {rec.shape[0]} vertices in the body, {count[0]} in the header")
+    return rec["xyz"].astype(np.float32), rec["rgb"].copy()
 
 
 def load_scannet_segments(path):

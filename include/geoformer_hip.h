@@ -1064,6 +1064,61 @@ int gf_tile_stitch_scores(const long long* table, const long long* table_host, i
                           void* stream);
 
 /* ===================================================================================
+ * Headless rendering of a scene's points to images (csrc/render.hip; stands where util/visualize.py opens a viewer;
+ * the statement is render.splat_host / render.resolve_host): a z-buffered point splat with 64-bit atomicMin, then a
+ * resolve pass.  A whole call is memset (the caller's), splat, resolve: three stream operations for any V.
+ * =================================================================================== */
+
+/* Limits, as functions: the width of a camera record in floats (20), the views of one call (64), the side of an
+ * image in pixels (4096), the disc radius in sub-pixels (16) and the supersampling factor (4). */
+int gf_render_camera_floats(void);
+int gf_render_max_views(void);
+int gf_render_max_side(void);
+int gf_render_max_radius(void);
+int gf_render_max_supersample(void);
+
+/* gf_render_splat: keys [V, Hs, Ws] (64-bit, preset by the caller to all-ones = background with one asynchronous memset
+ * of 0xFF bytes on `stream`) <- min over the points whose disc covers the sub-pixel of (depthkey << 32 | point index).
+ *   xyz fp32 [N, 3]; keep uint8 [N] or NULL (NULL: every point; 0 drops the point); cams fp32 [V, 20], per view
+ *     {eye[3], R[9] row-major (rows: image right, image down, forward), kind (0 orthographic, 1 perspective),
+ *      scale (orthographic: sub-pixels per metre; perspective: focal length in sub-pixels), cx, cy, near, spx, rmin,
+ *      rmax}; Ws x Hs: the sub-pixel grid (each 1 .. gf_render_max_side() * gf_render_max_supersample());
+ *   max_radius: 0 .. gf_render_max_radius(), the caller's bound on every record's rmax: radii are clamped to it, and it
+ *     picks the launch shape (<= 3: a thread per (point, view); above: a wave per 64 points, lanes over each footprint).
+ *   Per (view, point), float32, every operation rounded on its own, in this order:
+ *     d = p - eye; xc = (R00 d0 + R01 d1) + R02 d2, yc and zc with rows 1 and 2;
+ *     orthographic: u = xc scale + cx, v = yc scale + cy, r = rmin;
+ *     perspective: culled when !(zc >= near); u = (xc scale) / zc + cx, v = (yc scale) / zc + cy;
+ *       r = min(rmax, max(rmin, floor(spx / zc)));
+ *       (as compares: r = rmin; if (q > r) r = q; if (r > rmax) r = rmax; if (!(r >= 0)) r = 0, with rmax taken as
+ *       max_radius when it is not <= max_radius, so a NaN q leaves rmin and no record makes a larger disc);
+ *     culled when u is NaN or outside [-(rmax + 1), Ws + rmax + 1) (v: Hs), before any conversion to an integer;
+ *     (iu, iv) = (floor u, floor v); r as an integer;
+ *     depthkey = zc's bits, all flipped when negative, the sign bit flipped otherwise (ascending with zc);
+ *     atomicMin of the key on every sub-pixel (iu + dx, iv + dy) inside the image with dx^2 + dy^2 <= r^2 + r.
+ *   Equal depths resolve to the lower point index: the result does not depend on the order of arrival, bit-identical
+ *   from call to call.  No footprint leaves the image whatever the records hold.  N == 0 succeeds with nothing
+ *   launched; NULL xyz / cams / keys, N < 0 or N >= 2^31, V outside 1 .. gf_render_max_views(), a side or max_radius
+ *   outside its range are GF_ERR_INVALID_ARG with nothing launched. */
+int gf_render_splat(const float* xyz, const unsigned char* keep, long long N, const float* cams, int V, int Ws, int Hs,
+                    int max_radius, long long* keys, void* stream);
+
+/* gf_render_resolve (one launch, no memset: every cell of image and index is written): keys [V, H S, W S] as
+ * gf_render_splat left them -> index int32 [V, H S, W S], the winning point of every sub-pixel (-1: background), and
+ * image uint8 [V, H, W, 3].  rgb uint8 [N, 3]; ids int32 [N] or NULL; h_lut: HOST, 9 int32 in 0..256 (Q8, 256 =
+ * unchanged); stride 1..16 sub-pixels; background, outline: 0xRRGGBB.  Per foreground sub-pixel with point i, depth z
+ * (recovered exactly from the key's high word): o = the number of its 8 neighbours at (+-stride, +-stride) inside
+ * the image that are foreground with z_nb + dz < z (one fp32 add, one compare); colour = (rgb[i] * lut[o] + 128) >> 8
+ * per channel; with ids, the outline colour instead when the right or the lower neighbour (inside the image) is
+ * background or holds a point of another id.  Background sub-pixels take the background colour.  A pixel is the
+ * integer mean (sum + S S / 2) / (S S) per channel over its S x S block.  A key whose index is not in [0, N) counts as
+ * background.  W, H outside 1 .. gf_render_max_side(), S outside 1 .. gf_render_max_supersample(), V as above, a bad
+ * table, stride or colour, N < 0 or a NULL pointer (ids aside; rgb may be NULL when N == 0) are GF_ERR_INVALID_ARG. */
+int gf_render_resolve(const long long* keys, int V, int W, int H, int S, const unsigned char* rgb, const int32_t* ids,
+                      long long N, const int32_t* h_lut, int stride, float dz, int background, int outline,
+                      unsigned char* image, int32_t* index, void* stream);
+
+/* ===================================================================================
  * Backbone voxel transformer of the two deepest U-Net levels, fused (inference)
  * (UBlock: model/geoformer/geoformer_modules.py:64-68,120-127; TransformerEncoder(d_model=128, N,
  *  heads=4, d_ff=64): model/transformer.py:62-188)

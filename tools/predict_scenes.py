@@ -11,6 +11,7 @@ greedy NMS) and the scene labelling of batch_eval.label_batches, written with ge
     python tools/predict_scenes.py --out out --split-masks largest scene0011_00_inst_nostuff.npy  # picked masks cut to their largest connected cluster
     python tools/predict_scenes.py --out out --tile 4 --halo 0.5 floor3.npy               # a large scan as overlapping 4 m tiles, instances joined
     python tools/predict_scenes.py --out out --tile 4 --tile-stitch core --panoptic floor3.npy  # ... and the tiles' semantics stitched: PQ of the scan
+    python tools/predict_scenes.py --out out --render turntable:4 scene0011_00_inst_nostuff.npy  # + out/render/<name>_instance_pred_<view>.png
 
 Per scene <out>/<name>.npz (ids, owner, instance table: export.load_labels) and, with --scannet, <out>/<name>.txt plus
 <out>/predicted_masks/ (exclusive masks; --full-masks writes the picked masks as they are).  Without --checkpoint the
@@ -36,6 +37,10 @@ core|mean also stitches the tiles' semantic scores per scan (batch_eval's stitch
 scores from its core tile, or the mean over the tiles that hold it; --panoptic goes with --tile only then, and the
 --semantic pass then runs over the tiles too (without it that pass runs every scan whole).  The JSON line's `tiling`
 holds the parameters and `stitch` (null without --tile).
+--render top|turntable:K draws every scene on the GPU (geoformer_amd.render, csrc/render.hip) from above or from K views
+around it, --render-size WxH pixels, in the colours of --render-task (input, semantic_gt, semantic_pred, instance_gt,
+instance_pred; semantic_pred takes the classes of the --semantic pass, which it switches on):
+<out>/render/<name>_<task>_<view>.png, 8-bit RGB.
 """
 import argparse
 import json
@@ -47,6 +52,52 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def parse_views(text):
+    """top -> ("top", 1); turntable:K -> ("turntable", K)."""
+    if text == "top":
+        return ("top", 1)
+    kind, _, k = text.partition(":")
+    if kind != "turntable" or not k.isdigit() or int(k) < 1:
+        raise argparse.ArgumentTypeError(f"expected top or turntable:K with K >= 1, got {text!r}")
+    return ("turntable", int(k))
+
+
+def parse_size(text):
+    w, _, h = text.lower().partition("x")
+    if not (w.isdigit() and h.isdigit() and int(w) >= 1 and int(h) >= 1):
+        raise argparse.ArgumentTypeError(f"expected WxH, got {text!r}")
+    return (int(w), int(h))
+
+
+RENDER_TASKS = ("input", "semantic_gt", "semantic_pred", "instance_gt", "instance_pred")
+
+
+def cameras_of(views, xyz, size):
+    from geoformer_amd import render
+
+    bounds = render.bounds_of(xyz)
+    return [render.top_down(bounds, size)] if views[0] == "top" else render.turntable(bounds, views[1], 30.0, size)
+
+
+def write_renders(out_dir, results, raws, views, size, task, semantic=None, device="cuda"):
+    """<out_dir>/render/<name>_<task>_<view>.png of every (name, SceneLabels) of results, drawn on the device with
+    render.render's defaults; raws: name -> raw [N, 8]; semantic: name -> classes [N] (for semantic_pred).  Returns the
+    paths."""
+    from geoformer_amd import export, render
+
+    os.makedirs(os.path.join(out_dir, "render"), exist_ok=True)
+    paths = []
+    for name, lab in results:
+        raw = np.asarray(raws[name])
+        xyz = torch.as_tensor(raw[:, :3].astype(np.float32), device=device)
+        rgb, ids, keep = render.colors_for(task, raw_scene=raw, labels=lab, semantic=(semantic or {}).get(name),
+                                           device=device)
+        image, _ = render.render(xyz, rgb, cameras_of(views, xyz, size), size, ids=ids, keep=keep)
+        for v, im in enumerate(image.cpu().numpy()):
+            paths.append(export.write_png(os.path.join(out_dir, "render", f"{name}_{task}_{v}.png"), im))
+    return paths
 
 
 def build_parser():
@@ -86,6 +137,10 @@ def build_parser():
     ap.add_argument("--tile-stitch", choices=("core", "mean"), default=None,
                     help="with --tile: stitch the tiles' semantic scores per scan, each point from its core tile or the "
                          "mean over the tiles that hold it (batch_eval's stitch=); needed for --tile --panoptic")
+    ap.add_argument("--render", type=parse_views, default=None, metavar="top|turntable:K",
+                    help="draw every scene on the GPU from above, or from K views around it: <out>/render/*.png")
+    ap.add_argument("--render-size", type=parse_size, default=(1024, 768), metavar="WxH")
+    ap.add_argument("--render-task", choices=RENDER_TASKS, default="instance_pred", help="what the colours show")
     ap.add_argument("--no-write", action="store_true")
     ap.add_argument("--reps", type=int, default=3, help="timed passes per keep_masks setting")
     return ap
@@ -181,7 +236,8 @@ def main():
             export.save_labels(os.path.join(args.out, f"{name}.npz"), lab._replace(masks=None), pans.get(name))
             if args.scannet:
                 export.write_scannet_predictions(args.out, name, lab, lab.masks if args.full_masks else None)
-    if args.semantic or getattr(model.cfg, "save_semantic", False):
+    sem_preds = {}
+    if args.semantic or getattr(model.cfg, "save_semantic", False) or (args.render and args.render_task == "semantic_pred"):
         from geoformer_amd import evaluation
 
         ev = evaluation.SemanticEvaluator(n_classes=model.cfg.classes, train_fold=model.cfg.train_fold)
@@ -189,10 +245,14 @@ def main():
         for name, preds in batch_eval.semantic_batches(model, items, args.batch_size, evaluator=ev, **skw):
             if not args.no_write:
                 export.write_scannet_semantic(os.path.join(args.out, "semantic"), name, preds, model.cfg.train_fold)
+            if args.render and args.render_task == "semantic_pred":
+                sem_preds[name] = preds.clone()  # (a view of the batch's buffer)
         if any((raw[:, 6] != evaluation.IGNORE_LABEL).any() for _, raw in items):
             print(ev.format_results())
     if pq is not None and any((raw[:, 6] != -100).any() for _, raw in items):
         print(pq.format_results())
+    if args.render and not args.no_write:
+        write_renders(args.out, results, dict(items), args.render, args.render_size, args.render_task, sem_preds, dev)
     pkw = {k: v for k, v in kw.items() if k != "min_score"}
 
     def predict_only():  # the loop without the labelling and without any copy of a result, for comparison
