@@ -19,6 +19,8 @@
     ap, avgs = evaluate(model, [(name, raw), ...], batch_size=4, tiles=Tiling(tile=4.0), stitch="core", semantic=ev)
     res = evaluate_panoptic(model, [(name, raw), ...], batch_size=4, tiles=Tiling(tile=4.0), stitch="core")
                                               # the tiles' semantic scores stitched per scan: "core" or "mean"
+    for name, cls, scores, masks, pick in predict_batches(model, [(name, raw), ...], batch_size=4, density=Density()):
+        ...                                   # a dense scan runs on one point per 2 cm cell; masks still int32 [n, N]
 
 A batch of raw scenes ([N, 8] = xyz, rgb, semantic label, instance label, as prepare_data_inst.py stores them) is
 collated on the host (scene.collate_raw), uploaded and voxelised on the GPU one batch ahead (feeder.DeviceFeeder), and
@@ -30,6 +32,8 @@ postprocess.greedy_nms_batched call per batch.  A scene without proposals is lef
 ``continue`` does.
 """
 from __future__ import annotations
+
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -277,6 +281,130 @@ def _predict_tiled(model, raw_scenes, batch_size, tiling, stitch, kw):
             yield (scan, *tiling.merge(plans[scan], per_tile))
 
 
+class Density:
+    """``density=Density(cell=0.02, mode="center")``: every scene is run on one representative point per occupied cell of
+    a grid of `cell` metres (pointops.grid_subsample; mode "center": the point nearest the cell's centre, "first": the
+    cell's first point) and every result is put back on the scene's own points.  cell=None: 1 / scale of the collate,
+    0.02 m -- one representative per voxel-sized cell."""
+
+    DEFAULTS = dict(cell=None, mode="center")
+
+    def __init__(self, **params):
+        unknown = sorted(set(params) - set(self.DEFAULTS))
+        if unknown:
+            raise TypeError(f"Density: unknown parameter(s) {', '.join(unknown)}; known: {', '.join(self.DEFAULTS)}")
+        self.params = dict(self.DEFAULTS, **params)
+        if self.params["cell"] is not None and not (self.params["cell"] > 0 and np.isfinite(self.params["cell"])):
+            raise ValueError(f"Density: cell > 0 (or None), got {self!r}")
+        if self.params["mode"] not in postprocess.GRID_MODES:
+            raise ValueError(f"Density: mode must be one of {postprocess.GRID_MODES}, got {self.params['mode']!r}")
+
+    def __repr__(self):
+        return f"Density({', '.join(f'{k}={v!r}' for k, v in self.params.items())})"
+
+    def cell(self, scale=50):
+        """The cell in metres: the parameter, or 1 / scale of the collate."""
+        return 1.0 / scale if self.params["cell"] is None else float(self.params["cell"])
+
+
+class DensityMap(NamedTuple):
+    """A subsampled scene's way back: rep int64 [n] (host) -- the scene's rows that were kept, in order -- and cell_of
+    int32 [N] (device) -- for every point of the scene the row of the subsampled scene that stands for it."""
+    rep: np.ndarray
+    cell_of: torch.Tensor
+
+
+def _density(density):
+    if density is None or isinstance(density, Density):
+        return density
+    raise ValueError(f"density: None or a Density, got {density!r}")
+
+
+def density_items(items, density, device):
+    """(subsampled items, maps): every (name, raw) becomes (name, raw[rep]) with (rep, cell_of, _) =
+    pointops.grid_subsample of its xyz on `device` (one launch sequence and one two-word read-back per scene); maps:
+    scene name -> DensityMap.  A scene that keeps every point (M == N) passes through with no map.  A subsampled scene
+    that shares its name with another scene of the list is a ValueError (its map goes by its name)."""
+    from . import pointops
+
+    items = list(items)
+    dev = torch.device(device)
+    out, maps = [], {}
+    for name, raw in items:
+        r = raw.detach().cpu().numpy() if torch.is_tensor(raw) else np.asarray(raw)
+        xyz = torch.from_numpy(np.ascontiguousarray(r[:, :3], dtype=np.float32)).to(dev)
+        rep, cell_of, _ = pointops.grid_subsample(xyz, density.cell(), density.params["mode"])
+        if rep.shape[0] == r.shape[0]:
+            out.append((name, raw))
+            continue
+        if name in maps:
+            raise ValueError(f"density=: two scenes are named {name!r}")
+        rep = rep.cpu().numpy().astype(np.int64)
+        maps[name] = DensityMap(rep, cell_of)
+        out.append((name, r[rep]))
+    names = [n for n, _ in items]
+    twice = sorted({str(n) for n in maps if names.count(n) > 1})
+    if twice:
+        raise ValueError(f"density=: the subsampled scene(s) {', '.join(twice)} share their name with another scene")
+    return out, maps
+
+
+def _hand_on(inner, scores, labels, name):
+    """One scene to a semantic evaluator, as a batch of one."""
+    off = torch.tensor([0, scores.shape[0]], dtype=torch.int32)
+    return inner.add_batch(scores, labels, off.to(scores.device, non_blocking=True), [name], offsets_host=off)
+
+
+class _DensitySemantics:
+    """Stands where the loops take a SemanticEvaluator when scenes run subsampled: every scene is handed on to `inner` as
+    a batch of one -- a subsampled scene with its scores put back on the scene's own points through cell_of (a copy of
+    rows: every point takes its representative's scores) and with the scene's own labels (the raw scene's column 6), any
+    other scene as it came.  With tiles, _TileSemantics stands in front and this object is given the stitched scan."""
+
+    def __init__(self, inner, maps, raws):
+        self.inner, self.maps, self.raws = inner, maps, raws
+
+    def add_batch(self, scores, labels, offsets, names, offsets_host=None):
+        off = [int(o) for o in (offsets if offsets_host is None else offsets_host)]
+        for i, name in enumerate(names):
+            part, lab = scores[off[i]:off[i + 1]], labels[off[i]:off[i + 1]]
+            if not isinstance(name, TileName) and name in self.maps:
+                part = postprocess.expand_rows(part, self.maps[name].cell_of)
+                lab = torch.from_numpy(scene_dict(self.raws[name])["label"]).to(scores.device, non_blocking=True)
+            _hand_on(self.inner, part.contiguous(), lab, name)
+
+
+def _density_segments(segments, maps):
+    """The segments= mapping of the subsampled list: a subsampled scene's ids gathered through rep."""
+    if segments is None or _geometric(segments) is not None:
+        return segments
+    out = dict(segments)
+    for name, m in maps.items():
+        if segments.get(name) is not None:
+            seg = segments[name]
+            seg = seg.detach().cpu().numpy() if torch.is_tensor(seg) else np.asarray(seg)
+            if seg.shape != (m.cell_of.shape[0],):
+                raise ValueError(f"segments[{name!r}]: expected one id per point [{m.cell_of.shape[0]}], got "
+                                 f"{seg.shape}")
+            out[name] = seg[m.rep]
+    return out
+
+
+def _predict_dense(model, raw_scenes, batch_size, density, kw):
+    """The loop of predict_batches over density_items' subsampled list: everything else (segments=, split=, tiles= /
+    stitch=) sees the subsampled scenes, and the masks of a subsampled scene are put back on its own points last."""
+    items = list(raw_scenes)
+    dev = torch.device(kw["device"]) if kw.get("device") is not None else next(model.parameters()).device
+    sub, maps = density_items(items, density, dev)
+    kw = dict(kw, segments=_density_segments(kw.get("segments"), maps))
+    if kw.get("semantic") is not None and maps:
+        kw["semantic"] = _DensitySemantics(kw["semantic"], maps, {n: r for n, r in items if n in maps})
+    for name, cls, sc, masks, pick in predict_batches(model, sub, batch_size, **kw):
+        if name in maps and torch.is_tensor(masks):
+            masks = postprocess.expand_masks(masks, maps[name].cell_of)
+        yield name, cls, sc, masks, pick
+
+
 def _scene_segments(segments, name, n):
     """int32 [n] over-segment ids of scene `name` from the mapping (range-checked), -1 everywhere when it has none."""
     seg = segments.get(name)
@@ -322,7 +450,8 @@ def collate_batches(raw_scenes, batch_size, spatial_shape=None, scale=50, full_s
 @torch.no_grad()
 def predict_batches(model, raw_scenes, batch_size, *, epoch=300, spatial_shape=None, nms_kernel="gaussian",
                     sigma=2.0, final_score_thresh=NMS_FINAL_SCORE, cvfold=None, reserve=True, device=None,
-                    semantic=None, nms="matrix", nms_thresh=None, segments=None, split=None, tiles=None, stitch=None):
+                    semantic=None, nms="matrix", nms_thresh=None, segments=None, split=None, tiles=None, stitch=None,
+                    density=None):
     """Yields (name, cls_final, scores_final, masks_final, pick) per scene, in input order.  raw_scenes: iterable of
     (name, raw [N, 8]).  The NMS categories are the benchmark label ids of the classes (evaluation.benchmark_label_ids
     with cvfold, default model.cfg.cvfold).  A scene without proposals yields ([], [], [], empty pick).  reserve: size
@@ -350,8 +479,22 @@ def predict_batches(model, raw_scenes, batch_size, *, epoch=300, spatial_shape=N
     scene's own labels, before the scene is yielded; there is no default because neither rule's effect on mIoU has been
     measured.  With semantic=None there is nothing to stitch: stitch is checked and otherwise unused.  semantic= with
     tiles and stitch=None is a ValueError; stitch without tiles is one too; so is, with semantic= and stitch, a tiled
-    scene whose name another scene of the list carries (the scores and labels of a scan are kept by its name)."""
+    scene whose name another scene of the list carries (the scores and labels of a scan are kept by its name).
+    density: a Density -- subsample first: every scene is replaced by one representative point per occupied cell
+    (density_items; pointops.grid_subsample on the device, one two-word read-back per scene), everything above --
+    segments= (a mapping's ids gathered through the representatives), split=, tiles= / stitch= -- sees the subsampled
+    scene, and expansion comes last: the scene is yielded once under its own name with masks int32 [R, N] over its own
+    points (every point takes its representative's column) and `semantic` is given its scores on all N points against
+    its own labels.  A scene that keeps every point runs exactly as without density=; a subsampled scene whose name
+    another scene carries is a ValueError; None: nothing is added to the loop.  What subsampling does to AP or mIoU has
+    not been measured."""
     _stitching(stitch, _tiling(tiles), "predict_batches")
+    if _density(density) is not None:
+        yield from _predict_dense(model, raw_scenes, batch_size, density, dict(
+            epoch=epoch, spatial_shape=spatial_shape, nms_kernel=nms_kernel, sigma=sigma,
+            final_score_thresh=final_score_thresh, cvfold=cvfold, reserve=reserve, device=device, semantic=semantic,
+            nms=nms, nms_thresh=nms_thresh, segments=segments, split=split, tiles=tiles, stitch=stitch))
+        return
     if tiles is not None:
         yield from _predict_tiled(model, raw_scenes, batch_size, tiles, stitch, dict(
             epoch=epoch, spatial_shape=spatial_shape, nms_kernel=nms_kernel, sigma=sigma,
@@ -562,7 +705,7 @@ def _semantic_forwards(model, raw_scenes, batch_size, spatial_shape, reserve, de
 
 @torch.no_grad()
 def semantic_batches(model, raw_scenes, batch_size, *, spatial_shape=None, reserve=True, device=None, evaluator=None,
-                     tiles=None, stitch=None):
+                     tiles=None, stitch=None, density=None):
     """Yields (name, preds) per scene, in input order: preds int32 [N] on the device, a view of the batch's buffer -- the
     semantic head's class of every point (the first maximal score, the rule of the forward's foreground selection).
     Only the backbone and the semantic head run (forward_backbone with the fused voxel-row head; no arg-max by the
@@ -570,18 +713,29 @@ def semantic_batches(model, raw_scenes, batch_size, *, spatial_shape=None, reser
     that counts every batch against its labels in the same launch.  tiles: a Tiling, with stitch "core" or "mean" (both
     or neither: ValueError) -- every scene with more than max_points points runs as its non-empty tiles (tile_items), the
     tiles' scores are kept on the device until the scene is complete and stitched (postprocess.stitch_tiles), and the
-    scene is counted and yielded once, under its own name, with preds int32 [N] over the whole scan."""
+    scene is counted and yielded once, under its own name, with preds int32 [N] over the whole scan.  density: a Density
+    -- every scene runs subsampled (density_items; tiles= then cuts the subsampled scene), its scores -- stitched, when
+    tiled -- are put back on its own points through cell_of, and it is counted against its own labels and yielded with
+    preds int32 [N]."""
     from . import pointops
 
     tiling = _tiling(tiles)
     _stitching(stitch, tiling, "semantic_batches")
     if tiling is not None and stitch is None:
         raise ValueError('semantic_batches: tiles= needs stitch="core" or "mean"')
-    if tiling is not None:
+    if tiling is not None or _density(density) is not None:
         items = list(raw_scenes)
-        expanded, plans = tile_items(items, tiling)
-        tap = _SemanticTap(evaluator)
-        sem = _TileSemantics(tap, plans, _tiled_raws(items, plans), stitch)
+        sem = tap = _SemanticTap(evaluator)
+        plans = {}
+        if density is not None:
+            dev = torch.device(device) if device is not None else next(model.parameters()).device
+            raws = items
+            items, maps = density_items(raws, density, dev)
+            sem = _DensitySemantics(tap, maps, {n: r for n, r in raws if n in maps})
+        expanded = items
+        if tiling is not None:
+            expanded, plans = tile_items(items, tiling)
+            sem = _TileSemantics(sem, plans, _tiled_raws(items, plans), stitch)
         for chunk, host, batch, scores in _semantic_forwards(model, expanded, batch_size, spatial_shape, reserve, device):
             sem.add_batch(scores, batch["labels"], batch["offsets"], [n for n, _ in chunk], offsets_host=host["offsets"])
             for name, _ in chunk:

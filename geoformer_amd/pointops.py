@@ -2008,3 +2008,97 @@ def tile_stitch_scores(table, table_host, tile_of, local_of, core_of, C, mode):
                                             ptr(local_of), ptr(core_of), N, C, TILE_STITCH_MODES[mode], ptr(out),
                                             stream_ptr()), "gf_tile_stitch_scores")
     return out
+
+
+# ---- scans of any density: grid subsample and nearest point (csrc/resample.hip) ------------------------------------------
+GRID_MODES = {"first": 0, "center": 1}  # gf_grid_subsample's mode
+RESAMPLE_MAX_POINTS = 1 << 29           # gf_resample_max_points(): asserted against the library in resample_limits()
+GRID_AXIS_CELLS = 1 << 21               # gf_grid_subsample_max_cells()
+NEAREST_MAX_CELLS = float(1 << 30)      # gf_nearest_point_max_cells()
+
+
+def resample_limits():
+    """(most points of a set, cells per axis of the subsample, cells per axis the nearest-point walk is proven for), from
+    the library."""
+    lib = _lib.load()
+    lim = lib.gf_resample_max_points(), lib.gf_grid_subsample_max_cells(), lib.gf_nearest_point_max_cells()
+    assert lim == (RESAMPLE_MAX_POINTS, GRID_AXIS_CELLS, NEAREST_MAX_CELLS), lim
+    return lim
+
+
+def _xyz3(t, name, device=None):
+    if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3 or not t.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous float32 tensor [n, 3], got "
+                         f"{(t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__}")
+    if device is not None and t.device != device:
+        raise ValueError(f"{name}: expected a tensor on {device}, got {t.device}")
+    if t.shape[0] > RESAMPLE_MAX_POINTS:
+        raise ValueError(f"{name}: {t.shape[0]} points (at most {RESAMPLE_MAX_POINTS})")
+    return t
+
+
+def grid_subsample(xyz, cell, mode="center", origin=None):
+    """(rep int32 [M], cell_of int32 [N], count int32 [M]) of postprocess.grid_subsample_host on xyz's device: one
+    representative -- a real point -- per occupied cell of a grid of `cell` metres, the cells numbered in order of first
+    occurrence.  xyz fp32 [N, 3]; origin: fp32 [3] tensor on the same device (None: the minimum corner, found on the
+    device).  On the GPU: gf_grid_subsample on the current stream, bit-identical to the statement and from call to call;
+    the two words {M, invalid} are read back once (the only synchronisation) and an invalid point -- not finite, below
+    the origin, or 2^21 cells or more from it -- is a ValueError, as in the statement.  A CPU tensor runs the
+    statement."""
+    from . import postprocess
+
+    _xyz3(xyz, "grid_subsample: xyz")
+    c = postprocess._grid_args(cell, mode, "grid_subsample")
+    if origin is not None and not (torch.is_tensor(origin) and origin.dtype == torch.float32 and origin.shape == (3,)
+                                   and origin.is_contiguous() and origin.device == xyz.device):
+        raise ValueError(f"grid_subsample: origin: expected a contiguous float32 tensor [3] on {xyz.device}")
+    if not xyz.is_cuda:
+        return tuple(torch.from_numpy(a) for a in postprocess.grid_subsample_host(xyz, c, mode, origin))
+    N, dev = xyz.shape[0], xyz.device
+    if N == 0:
+        return tuple(torch.empty(0, dtype=torch.int32, device=dev) for _ in range(3))
+    lib = _lib.load()
+    out = torch.empty((3, N), dtype=torch.int32, device=dev)
+    words = torch.empty(2, dtype=torch.int32, device=dev)
+    ws = torch.empty(lib.gf_grid_subsample_scratch_bytes(N) // 8 + 1, dtype=torch.int64, device=dev)
+    check(lib.gf_grid_subsample(ptr(xyz), N, float(c), GRID_MODES[mode], ptr(origin) if origin is not None else None,
+                                ptr(ws), ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(words), stream_ptr()),
+          "gf_grid_subsample")
+    M, invalid = words.tolist()
+    if invalid:
+        raise ValueError(f"grid_subsample: a point lies outside the grid (not finite, below the origin or "
+                         f"{GRID_AXIS_CELLS} cells or more from it)")
+    return out[0, :M], out[1], out[2, :M]
+
+
+def nearest_point(query, xyz, max_dist, check=True, return_flag=False):
+    """(idx int32 [Q], d2 fp32 [Q]) of postprocess.nearest_point_host on the tensors' device: for every query the point
+    of xyz minimising (d2, index) among those within max_dist, (-1, inf) without one.  On the GPU: gf_nearest_point on
+    the current stream (a hash grid over xyz, 27 cells walked per query), bit-identical to the statement and from call
+    to call.  The walk is proven complete while xyz's bounding box spans fewer than 2^30 cells of max_dist * 1.001 on
+    every axis; the kernel raises a device flag beyond that, which `check` reads here (one read-back) and turns into a
+    ValueError.  return_flag: also the flag (int32 [1], device; None on the CPU) for a caller who folds it into a
+    read-back of their own -- with check=False nothing is read back.  A CPU tensor runs the statement."""
+    from . import postprocess
+
+    _xyz3(query, "nearest_point: query")
+    _xyz3(xyz, "nearest_point: xyz", query.device)
+    md = np.float32(max_dist)
+    if not (md > 0 and np.isfinite(md)):
+        raise ValueError(f"nearest_point: max_dist must be positive and finite in float32, got {max_dist!r}")
+    if not query.is_cuda:
+        idx, d2 = (torch.from_numpy(a) for a in postprocess.nearest_point_host(query, xyz, md))
+        return (idx, d2, None) if return_flag else (idx, d2)
+    Q, n, dev = query.shape[0], xyz.shape[0], query.device
+    idx = torch.empty(Q, dtype=torch.int32, device=dev)
+    d2 = torch.empty(Q, dtype=torch.float32, device=dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    if Q:
+        lib = _lib.load()
+        ws = torch.empty(lib.gf_nearest_point_scratch_bytes(n) // 8 + 1, dtype=torch.int64, device=dev)
+        _lib.check(lib.gf_nearest_point(ptr(query), Q, ptr(xyz) if n else None, n, float(md), ptr(ws), ptr(idx), ptr(d2),
+                                        ptr(flag), stream_ptr()), "gf_nearest_point")
+        if check and int(flag.item()):
+            raise ValueError(f"nearest_point: the points span {int(NEAREST_MAX_CELLS)} cells of max_dist or more on an "
+                             f"axis, beyond the range the search is proven complete for")
+    return (idx, d2, flag) if return_flag else (idx, d2)

@@ -1080,3 +1080,151 @@ def stitch_tiles(plan, per_tile_scores, mode):
                                            table, torch.from_numpy(plan.tile_of).to(dev, non_blocking=True),
                                            torch.from_numpy(plan.local_of).to(dev, non_blocking=True),
                                            torch.from_numpy(plan.core_of).to(dev, non_blocking=True), C, mode)
+
+
+# ---- scans of any density: grid subsample, labels carried back (csrc/resample.hip) ---------------------------------------
+GRID_MODES = ("first", "center")
+GRID_AXIS_CELLS = 1 << 21  # gf_grid_subsample_max_cells(): asserted against the library in pointops.resample_limits()
+
+
+def _xyz3(xyz, name):
+    x = _np(xyz)
+    if x.ndim != 2 or x.shape[1] != 3:
+        raise ValueError(f"{name}: expected [n, 3], got {x.shape}")
+    return np.ascontiguousarray(x, dtype=np.float32)
+
+
+def _grid_args(cell, mode, who):
+    if mode not in GRID_MODES:
+        raise ValueError(f"{who}: mode must be one of {GRID_MODES}, got {mode!r}")
+    c = np.float32(cell)
+    if not (c > 0 and np.isfinite(c)):
+        raise ValueError(f"{who}: cell must be positive and finite in float32, got {cell!r}")
+    return c
+
+
+def grid_subsample_host(xyz, cell, mode="center", origin=None):
+    """(rep int32 [M], cell_of int32 [N], count int32 [M]): one representative point per occupied cell of a grid of
+    `cell` metres -- the statement gf_grid_subsample is held to, bit for bit.  All arithmetic is float32, in the order
+    written.  xyz float32 [N, 3]; origin float32 [3], default xyz.min(0).  t = (xyz - origin) / cell, c = floor(t); a
+    point is valid when t is finite and 0 <= c < 2^21 on every axis, and any invalid point is a ValueError.  Cells (key
+    cx | cy << 21 | cz << 42) are numbered in ascending order of their lowest point index -- the order of first
+    occurrence, in both modes.  mode "first": rep[m] is that lowest index; "center": the point of the cell minimising
+    (d2, index) with ctr = origin + (c + 0.5) * cell, d = xyz - ctr, d2 = (dx dx + dy dy) + dz dz.  Representatives are
+    real points: every column of a scene goes through by one gather, nothing is averaged.  cell_of[rep[m]] == m,
+    count.sum() == N, rep ascends in "first" mode; N = 0 gives empty outputs."""
+    x = _xyz3(xyz, "grid_subsample_host: xyz")
+    cell = _grid_args(cell, mode, "grid_subsample_host")
+    N = x.shape[0]
+    if origin is not None:
+        origin = np.ascontiguousarray(_np(origin), dtype=np.float32)
+        if origin.shape != (3,):
+            raise ValueError(f"grid_subsample_host: origin: expected [3], got {origin.shape}")
+    if N == 0:
+        return np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.int32)
+    with np.errstate(all="ignore"):
+        if origin is None:
+            origin = x.min(0)
+        t = (x - origin) / cell
+        c = np.floor(t)
+        bad = ~(np.isfinite(t) & (c >= 0) & (c < GRID_AXIS_CELLS)).all(1)
+    if bad.any():
+        raise ValueError(f"grid_subsample_host: {int(bad.sum())} point(s) outside the grid (not finite, below the origin "
+                         f"or {GRID_AXIS_CELLS} cells or more from it); the first is point {int(np.nonzero(bad)[0][0])}")
+    ci = c.astype(np.int64)
+    key = ci[:, 0] | ci[:, 1] << 21 | ci[:, 2] << 42
+    order = np.argsort(key, kind="stable")           # groups of equal keys, each in ascending point order
+    head = np.r_[True, key[order][1:] != key[order][:-1]]
+    lowest = order[head]                             # a group's lowest point index
+    M = lowest.shape[0]
+    number = np.empty(M, np.int64)
+    number[np.argsort(lowest)] = np.arange(M)        # groups numbered by ascending lowest index
+    cell_of = np.empty(N, np.int32)
+    cell_of[order] = number[np.cumsum(head) - 1]
+    count = np.bincount(cell_of, minlength=M).astype(np.int32)
+    if mode == "first":
+        return np.sort(lowest).astype(np.int32), cell_of, count
+    with np.errstate(all="ignore"):
+        d = x - (origin + (c + np.float32(0.5)) * cell)
+        d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+    by = np.lexsort((np.arange(N), d2, cell_of))     # per cell, ascending (d2, index)
+    rep = by[np.r_[True, cell_of[by][1:] != cell_of[by][:-1]]]
+    return rep.astype(np.int32), cell_of, count
+
+
+def nearest_point_host(query, xyz, max_dist, chunk_elems=1 << 22):
+    """(idx int32 [Q], d2 float32 [Q]): for every query the point of xyz minimising (d2, index) among those with
+    d2 <= r2 -- the statement gf_nearest_point is held to, bit for bit.  float32 throughout: r2 = max_dist * max_dist,
+    d2 = (dx dx + dy dy) + dz dz of d = query - point.  (-1, inf) with no candidate or for a query with a non-finite
+    coordinate; a point with a non-finite coordinate is never a candidate.  Brute force, in chunks of queries."""
+    q = _xyz3(query, "nearest_point_host: query")
+    p = _xyz3(xyz, "nearest_point_host: xyz")
+    md = np.float32(max_dist)
+    if not (md > 0 and np.isfinite(md)):
+        raise ValueError(f"nearest_point_host: max_dist must be positive and finite in float32, got {max_dist!r}")
+    Q, n = q.shape[0], p.shape[0]
+    idx = np.full(Q, -1, np.int32)
+    out = np.full(Q, np.inf, np.float32)
+    if Q == 0 or n == 0:
+        return idx, out
+    none = np.uint32(0xFFFFFFFF)
+    with np.errstate(all="ignore"):
+        r2 = md * md
+        p_ok = np.isfinite(p).all(1)
+        step = max(1, chunk_elems // n)
+        for lo in range(0, Q, step):
+            qs = q[lo:lo + step]
+            d = qs[:, None, :] - p[None, :, :]
+            d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+            cand = (d2 <= r2) & p_ok[None, :] & np.isfinite(qs).all(1)[:, None]
+            bits = np.where(cand, d2.view(np.uint32), none)  # d2 >= +0: the bit patterns ascend with the values
+            j = bits.argmin(1)                               # the first minimum: the lowest index
+            b = bits[np.arange(qs.shape[0]), j]
+            hit = b != none
+            idx[lo:lo + step] = np.where(hit, j, -1)
+            out[lo:lo + step] = np.where(hit, b, np.uint32(0x7F800000)).astype(np.uint32).view(np.float32)
+    return idx, out
+
+
+def _parent(parent, n, who):
+    if not torch.is_tensor(parent) or parent.dim() != 1 or parent.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{who}: parent: expected an int32 or int64 tensor [N]")
+    if parent.numel() and int(parent.max()) >= n:
+        raise ValueError(f"{who}: parent holds {int(parent.max())}, the source has {n} rows")
+    return parent.long()
+
+
+def expand_rows(rows, parent, fill=0):
+    """out [N, C] (or [N]) = rows[parent] with `fill` where parent < 0: the rows [n, C] (or [n]) of a subsampled scene
+    (or of another point set) on the N points whose parent is given -- grid_subsample's cell_of, nearest_point's idx.  A
+    pure copy (one gather) on rows' device."""
+    if not torch.is_tensor(rows) or rows.dim() not in (1, 2):
+        raise ValueError("expand_rows: rows: expected a tensor [n, C] or [n]")
+    p = _parent(parent, rows.shape[0], "expand_rows").to(rows.device)
+    if rows.shape[0] == 0:
+        return rows.new_full((p.shape[0], *rows.shape[1:]), fill)
+    lost = p < 0
+    return rows[p.clamp(min=0)].masked_fill_(lost if rows.dim() == 1 else lost[:, None], fill)
+
+
+def expand_masks(masks, parent):
+    """masks int32 [R, N] over the N points of a scan from masks [R, n] over its subsampled points: column g is column
+    parent[g], zero where parent < 0.  A pure copy."""
+    if not torch.is_tensor(masks) or masks.dim() != 2:
+        raise ValueError("expand_masks: masks: expected a tensor [R, n]")
+    p = _parent(parent, masks.shape[1], "expand_masks").to(masks.device)
+    if masks.shape[1] == 0:
+        return masks.new_zeros((masks.shape[0], p.shape[0]))
+    return masks[:, p.clamp(min=0)].masked_fill_((p < 0)[None, :], 0)
+
+
+def transfer(values, xyz_src, xyz_dst, max_dist, fill=0):
+    """values [n, C] (or [n]) of the points xyz_src carried to the points xyz_dst [N, 3]: every destination takes the
+    row of its nearest source point within max_dist (pointops.nearest_point; ties to the lower index) or `fill` without
+    one.  Returns (out [N, C] or [N], idx int32 [N])."""
+    from . import pointops
+
+    if not torch.is_tensor(values) or values.shape[0] != xyz_src.shape[0]:
+        raise ValueError(f"transfer: values: expected a tensor with one row per source point [{xyz_src.shape[0]}, ...]")
+    idx, _ = pointops.nearest_point(xyz_dst, xyz_src, max_dist)
+    return expand_rows(values, idx, fill), idx

@@ -1119,6 +1119,50 @@ int gf_render_resolve(const long long* keys, int V, int W, int H, int S, const u
                       unsigned char* image, int32_t* index, void* stream);
 
 /* ===================================================================================
+ * Scans of any density (csrc/resample.hip; the statements are postprocess.grid_subsample_host and
+ * postprocess.nearest_point_host): a voxel-grid subsample whose representatives are real points, and the nearest point
+ * of one set for every point of another.  Integer atomics and 64-bit minima only: no result depends on the order in
+ * which the points arrive, bit-identical from call to call.  Every launch goes on `stream`; nothing is read back.
+ * =================================================================================== */
+
+/* Limits, as functions: the points of one set (2^29), the cells per axis of the subsample (2^21) and the cells per
+ * axis between the corners of the nearest-point grid (2^30: the range its 27-cell walk is proven for). */
+int gf_resample_max_points(void);
+int gf_grid_subsample_max_cells(void);
+double gf_nearest_point_max_cells(void);
+
+/* gf_grid_subsample: xyz fp32 [N, 3]; cell > 0, finite; mode 0 = first, 1 = center; origin: DEVICE fp32 [3], or NULL
+ * for the per-axis minimum of xyz (found on the device).  Per point and axis, fp32, every operation rounded on its own:
+ * t = (x - origin) / cell (correctly rounded division), c = floor(t); the point is valid when t is finite and
+ * 0 <= c < gf_grid_subsample_max_cells().  Cells are numbered in order of their lowest point index.
+ *   cell_of int32 [N]: the number of every point's cell;   count int32 [N], first M written: the points of a cell;
+ *   rep int32 [N], first M written: mode 0: the cell's lowest point index; mode 1: the point of the cell minimising
+ *     (d2, index), d = x - (origin + (c + 0.5) * cell) (add, multiply, add), d2 = (dx dx + dy dy) + dz dz;
+ *   d_words int32 [2] (device): {M, 1 when some point is invalid -- the outputs then mean nothing};
+ *   scratch: gf_grid_subsample_scratch_bytes(N).
+ * N < 0 or above gf_resample_max_points(), a cell that is not positive and finite, another mode, or a NULL pointer
+ * (origin aside) with N > 0 are GF_ERR_INVALID_ARG with nothing launched; N == 0 succeeds with nothing launched (and
+ * nothing written). */
+size_t gf_grid_subsample_scratch_bytes(int N);
+int gf_grid_subsample(const float* xyz, int N, float cell, int mode, const float* origin, void* scratch, int32_t* rep,
+                      int32_t* cell_of, int32_t* count, int32_t* d_words, void* stream);
+
+/* gf_nearest_point: query fp32 [Q, 3], xyz fp32 [n, 3], max_dist > 0, finite; r2 = max_dist * max_dist (fp32).  Per
+ * query: among the points with d2 <= r2, d2 = (dx dx + dy dy) + dz dz of d = query - point (fp32), the one minimising
+ * (d2, index): idx int32 [Q], d2 fp32 [Q]; (-1, inf) without one.  A point with a non-finite coordinate is never a
+ * candidate; a query with one gets (-1, inf), and so does, without a walk, a query more than a cell outside the
+ * points' bounding box.  The search walks the 27 cells of a hash grid (cells of max_dist * 1.001, coordinates taken
+ * in fp64 from the points' minimum corner) around the query's own.
+ *   d_flag int32 [1] (device): 1 when the points' bounding box spans gf_nearest_point_max_cells() cells or more on an
+ *     axis -- beyond the range the walk is proven complete for: the caller must not use the result;
+ *   scratch: gf_nearest_point_scratch_bytes(n).
+ * Q < 0, n < 0 or above gf_resample_max_points(), a max_dist that is not positive and finite, or a NULL pointer (xyz
+ * may be NULL when n == 0) are GF_ERR_INVALID_ARG with nothing launched; Q == 0 succeeds with nothing launched. */
+size_t gf_nearest_point_scratch_bytes(int n);
+int gf_nearest_point(const float* query, int Q, const float* xyz, int n, float max_dist, void* scratch, int32_t* idx,
+                     float* d2, int32_t* d_flag, void* stream);
+
+/* ===================================================================================
  * Backbone voxel transformer of the two deepest U-Net levels, fused (inference)
  * (UBlock: model/geoformer/geoformer_modules.py:64-68,120-127; TransformerEncoder(d_model=128, N,
  *  heads=4, d_ff=64): model/transformer.py:62-188)

@@ -12,6 +12,7 @@ greedy NMS) and the scene labelling of batch_eval.label_batches, written with ge
     python tools/predict_scenes.py --out out --tile 4 --halo 0.5 floor3.npy               # a large scan as overlapping 4 m tiles, instances joined
     python tools/predict_scenes.py --out out --tile 4 --tile-stitch core --panoptic floor3.npy  # ... and the tiles' semantics stitched: PQ of the scan
     python tools/predict_scenes.py --out out --render turntable:4 scene0011_00_inst_nostuff.npy  # + out/render/<name>_instance_pred_<view>.png
+    python tools/predict_scenes.py --out out --density 0.02 laser_scan.npy                 # a dense scan on one point per 2 cm cell, labels on every point
 
 Per scene <out>/<name>.npz (ids, owner, instance table: export.load_labels) and, with --scannet, <out>/<name>.txt plus
 <out>/predicted_masks/ (exclusive masks; --full-masks writes the picked masks as they are).  Without --checkpoint the
@@ -41,6 +42,10 @@ holds the parameters and `stitch` (null without --tile).
 around it, --render-size WxH pixels, in the colours of --render-task (input, semantic_gt, semantic_pred, instance_gt,
 instance_pred; semantic_pred takes the classes of the --semantic pass, which it switches on):
 <out>/render/<name>_<task>_<view>.png, 8-bit RGB.
+--density CELL runs every scene on one representative point per occupied CELL-metre cell (batch_eval.Density,
+csrc/resample.hip; --density-mode center: the point nearest the cell's centre, first: the cell's first point) and puts
+every result back on the scene's own points; tiles, segments and the mask split then see the subsampled scene.  The
+JSON line's `density` holds the parameters (null without the flag).
 """
 import argparse
 import json
@@ -137,6 +142,11 @@ def build_parser():
     ap.add_argument("--tile-stitch", choices=("core", "mean"), default=None,
                     help="with --tile: stitch the tiles' semantic scores per scan, each point from its core tile or the "
                          "mean over the tiles that hold it (batch_eval's stitch=); needed for --tile --panoptic")
+    ap.add_argument("--density", type=float, default=None, metavar="CELL",
+                    help="run every scene on one point per occupied CELL-metre cell and put the results back on its own "
+                         "points (batch_eval.Density)")
+    ap.add_argument("--density-mode", choices=("first", "center"), default=None,
+                    help="with --density: the cell's representative (default center)")
     ap.add_argument("--render", type=parse_views, default=None, metavar="top|turntable:K",
                     help="draw every scene on the GPU from above, or from K views around it: <out>/render/*.png")
     ap.add_argument("--render-size", type=parse_size, default=(1024, 768), metavar="WxH")
@@ -213,6 +223,14 @@ def main():
     elif args.halo is not None or args.tile_max_points is not None or args.tile_stitch is not None:
         ap.error("--halo, --tile-max-points and --tile-stitch go with --tile")
 
+    density = None
+    if args.density is not None:
+        if not args.density > 0:
+            ap.error("--density: CELL > 0")
+        density = kw["density"] = batch_eval.Density(cell=args.density, mode=args.density_mode or "center")
+    elif args.density_mode is not None:
+        ap.error("--density-mode goes with --density")
+
     def run(keep_masks):
         np.random.seed(0)
         return list(batch_eval.label_batches(model, items, args.batch_size, keep_masks=keep_masks, **kw))
@@ -242,6 +260,8 @@ def main():
 
         ev = evaluation.SemanticEvaluator(n_classes=model.cfg.classes, train_fold=model.cfg.train_fold)
         skw = {"tiles": tiling, "stitch": args.tile_stitch} if args.tile_stitch is not None else {}
+        if density is not None:
+            skw["density"] = density
         for name, preds in batch_eval.semantic_batches(model, items, args.batch_size, evaluator=ev, **skw):
             if not args.no_write:
                 export.write_scannet_semantic(os.path.join(args.out, "semantic"), name, preds, model.cfg.train_fold)
@@ -279,7 +299,7 @@ def main():
                       "labelled_points": sum(int((lab.owner >= 0).sum()) for _, lab in results),
                       "segment_pooling": "segments" in kw, "geometric_segments": args.geometric_segments,
                       "mask_split": args.split_masks, "tiling": dict(tiling.params, stitch=args.tile_stitch) if tiling else None,
-                      "scenes_per_s": rates, "out": None if args.no_write else args.out}))
+                      "density": density.params if density else None, "scenes_per_s": rates, "out": None if args.no_write else args.out}))
 
 
 if __name__ == "__main__":
