@@ -158,7 +158,8 @@ __device__ __forceinline__ float gf_wave_sum(float s) {
 #define GF_FLAT_BSTART 40
 #define GF_FLAT_BCUR 72
 #define GF_FLAT_GOFF 128
-#define GF_FLAT_BINS 1024  // default number of bins: four SIMDs of 256 compute units
+#define GF_FLAT_BINS 1024  // default (and largest) number of bins: four SIMDs of 256 compute units
+int gf_conv_flat_bins();   // current setting (dev knob gf_dev_conv_flat_bins, spconv_conv.hip): builder, planner and kernel
 #define GF_FLAT_PAD 32     // records of -1 behind the last step (the conv kernel's loads run ahead)
 #define GF_LW_WPB 12       // waves per workgroup of the LDS-weight kernel (three per SIMD)
 __host__ __device__ static inline size_t gf_flat_ppos_at(int ngroups) { return GF_FLAT_GOFF + (size_t)ngroups + 1; }

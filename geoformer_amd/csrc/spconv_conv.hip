@@ -1124,7 +1124,8 @@ extern "C" int gf_dev_conv_kernel_events(void* start, void* stop) {
 extern "C" int gf_dev_conv_kernel_events_taken(void) { return t_kev_taken ? 1 : 0; }
 
 // Dev knobs (include/geoformer_hip_dev.h: gf_dev_conv_*): force a launch shape regardless of the level's size; -1 / 0:
-// not set.  Read by conv_plan only (and `chunks` by the rulebooks, gf_conv_chunks).
+// not set.  Read by conv_plan only (and `chunks` by the rulebooks, gf_conv_chunks; `flat_bins` by the flat table's
+// builder and by gf_conv_lw, gf_conv_flat_bins).
 struct ConvKnobs {
     int split = -1, wide = -1, pair = -1;      // shapes of k_conv_os, k_conv_pair
     int block = 0;                             // threads per workgroup of k_conv_os' one-wave-per-group shape (0: 256)
@@ -1133,6 +1134,7 @@ struct ConvKnobs {
     int flat = -1, flat_items = 0;             // flat-chain kernel: use / item bound of the size-based choice
     int lw = -1, lw_groups = 0;                // LDS-weight kernel: use / group bound of the size-based choice
     int chunks = GF_CONV_CHUNKS;               // equal-cost chunks the next step tables are built with
+    int flat_bins = GF_FLAT_BINS;              // bins of the flat step tables: what is built next AND what the kernel reads
 };
 static ConvKnobs g_knobs;
 static int knob_tri(int v) { return v < 0 ? -1 : (v != 0); }
@@ -1179,6 +1181,16 @@ extern "C" int gf_dev_conv_chunks(int n) {
     return GF_OK;
 }
 int gf_conv_chunks() { return g_knobs.chunks; }
+// bins of the flat step table, shared by its builder (gf_rules_flat_steps), the planner (descriptor limit, grid) and
+// gf_conv_lw: a table is only read correctly under the value it was built with
+extern "C" int gf_dev_conv_flat_bins(int nbins) {
+    if (nbins == 0) nbins = GF_FLAT_BINS;
+    GF_CHECK_ARG(nbins > 0 && nbins % 4 == 0 && nbins <= GF_FLAT_BINS, "gf_dev_conv_flat_bins: %d (0 or a multiple of 4, at most %d)",
+                 nbins, GF_FLAT_BINS);
+    g_knobs.flat_bins = nbins;
+    return GF_OK;
+}
+int gf_conv_flat_bins() { return g_knobs.flat_bins; }
 
 // What the planner sees of a (validated) call: sizes, the tables and operands given, 16-byte alignment of the pointers
 // (in_scale and in_shift together; an absent operand counts as aligned).  out_scale / out_shift are aligned whenever
@@ -1239,9 +1251,9 @@ static ConvPlan conv_plan(const ConvQuery& q) {
         const bool pays = npass == 1 && nch == 2 && ngroups >= (kn.lw_groups > 0 ? kn.lw_groups : 1500);
         // 24-bit row multiply; an absent row's offset 0xFFFFFF * row_bytes (mod 2^32) >= 2^30 - row_bytes must lie beyond
         // the buffer.  A wave keeps its groups' descriptors one per lane.
-        if (ncb <= 2 && q.M_in < (1 << 24) && in_bytes <= (1ull << 30) - 4096ull && ngroups <= 64 * 3 * GF_FLAT_BINS &&
+        if (ncb <= 2 && q.M_in < (1 << 24) && in_bytes <= (1ull << 30) - 4096ull && ngroups <= 64 * (GF_LW_WPB / 4) * kn.flat_bins &&
             (kn.lw == 1 || pays))
-            return ConvPlan{CONV_LW, {npass, n0, nch - n0 * (npass - 1), ncb, GF_LW_WPB, q.prologue}, GF_FLAT_BINS / 4,
+            return ConvPlan{CONV_LW, {npass, n0, nch - n0 * (npass - 1), ncb, GF_LW_WPB, q.prologue}, (unsigned)(kn.flat_bins / 4),
                             64 * GF_LW_WPB, (unsigned)(K * n0 * ncb * 1024)};
     }
     if (flat && (q.nbr || K == 1) && !q.out2)

@@ -367,7 +367,7 @@ int gf_conv_lw(const float* in, const float* Wp, const uint32_t* gmask, const in
         a.ncb_total = ncb;
         a.M_out = M_out;
         a.Cout = Cout;
-        a.nbins = GF_FLAT_BINS;  // (tables are built with the default bins: gf_rules_flat_steps(..., 0, ...))
+        a.nbins = gf_conv_flat_bins();  // (the builder's: gf_rules_flat_steps makes tables of no other bin count)
         a.ngroups = ngroups;
         a.rounds = (ngroups + a.nbins - 1) / a.nbins;
         gf_with<int, 1, 2>(n, [&](auto NCH) { gf_with<int, 1, 2>(ncb, [&](auto NCB) {

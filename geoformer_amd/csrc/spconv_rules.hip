@@ -476,16 +476,22 @@ __global__ void k_flat_fill(const int32_t* __restrict__ nbr, const uint32_t* __r
 
 extern "C" size_t gf_rules_flat_words(int K, int ld) {
     const int ngroups = ld / 16;
-    return gf_flat_steps_at(ngroups, GF_FLAT_BINS) + ((size_t)K * ngroups + GF_FLAT_PAD) * 16;
+    // room for every bin count: ceil(groups / NB) + 1 rounds of NB descriptors are at most groups + 2 NB - 1 of them (at
+    // 1024 bins between groups + 1024 and groups + 2047: sizing by gf_flat_steps_at(groups, 1024) was short for a table
+    // of, say, 1020 bins and 1021 groups)
+    return gf_flat_desc_at(ngroups) + ((size_t)ngroups + 2 * GF_FLAT_BINS) * 4 + ((size_t)K * ngroups + GF_FLAT_PAD) * 16;
 }
 
 extern "C" int gf_rules_flat_steps(const int32_t* nbr, const uint32_t* gmask, int K, int M, int ld, int nbins,
                                    int32_t* flat, void* stream) {
     GF_CHECK_ARG(nbr && gmask && flat, "gf_rules_flat_steps: null argument");
     GF_CHECK_ARG(K >= 1 && K <= 31 && M >= 0 && ld >= M && (ld % 16) == 0, "gf_rules_flat_steps: K=%d M=%d ld=%d", K, M, ld);
-    if (nbins <= 0) nbins = GF_FLAT_BINS;
-    GF_CHECK_ARG(nbins % 4 == 0 && nbins <= GF_FLAT_BINS, "gf_rules_flat_steps: %d bins (a multiple of 4, at most %d)", nbins,
-                 GF_FLAT_BINS);
+    // one bin count for this builder, the planner and the kernel (gf_conv_flat_bins: 1024 unless the dev knob says otherwise);
+    // a table of any other count would be misread by gf_conv_fwd_flat, so it is not built
+    const int bins = gf_conv_flat_bins();
+    GF_CHECK_ARG(nbins <= 0 || nbins == bins, "gf_rules_flat_steps: %d bins, but gf_conv_fwd_flat reads tables of %d (pass 0)",
+                 nbins, bins);
+    nbins = bins;
     const int ngroups = (M + 15) / 16;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_flat_scan, dim3(1), dim3(1024), 0, st, gmask, ngroups, nbins, K, flat);

@@ -118,7 +118,8 @@ def subm_rules(coords: torch.Tensor, index: LevelIndex) -> SubmRules:
 
 
 def flat_steps(nbr: torch.Tensor, gmask: torch.Tensor, K: int, M: int, ld: int, nbins: int = 0) -> torch.Tensor:
-    """Flat step table of a [K, ld] relation (include/geoformer_hip.h: gf_rules_flat_steps)."""
+    """Flat step table of a [K, ld] relation (include/geoformer_hip.h: gf_rules_flat_steps).  nbins: 0 = the library's
+    bin count (dev_conv_flat_bins); any other value than that count is rejected."""
     lib = _lib.load()
     flat = torch.empty(lib.gf_rules_flat_words(K, ld), dtype=torch.int32, device=nbr.device)
     check(lib.gf_rules_flat_steps(ptr(nbr), ptr(gmask), K, M, ld, nbins, ptr(flat), stream_ptr()), "gf_rules_flat_steps")
@@ -249,6 +250,12 @@ def dev_conv_g16p_wpb(wpb=0):
 def dev_conv_chunks(n=0):
     """Dev hook: number of equal-cost chunks the next submanifold rulebooks are built with (0 = default)."""
     check(_lib.load().gf_dev_conv_chunks(n), "gf_dev_conv_chunks")
+
+
+def dev_conv_flat_bins(nbins=0):
+    """Dev hook: bins of the flat step table, for the tables built next AND for the LDS-weight kernel that reads them
+    (0 = the default 1024).  A table must be used under the value it was built with."""
+    check(_lib.load().gf_dev_conv_flat_bins(nbins), "gf_dev_conv_flat_bins")
 
 
 def resblock_fwd(x: torch.Tensor, wp0, wp1, wpi, nbr, gmask, K: int, M: int, ld: int, Cin: int, Cout: int, s0, t0, s1,

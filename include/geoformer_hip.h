@@ -162,9 +162,10 @@ int gf_conv_pack_weights_t(const float* W, int K, int Cin, int Cout, int flip, f
  * spconv keeps this as its indice pairs, spconv/ops.py get_indice_pairs via geoformer_modules.py:52-129): one 64-byte
  * record of 16 input rows per (16-row group, PRESENT offset), group-major and offset-ascending, behind a header, the
  * per-group step offsets and a bin table: the groups sorted by their number of steps (descending) and dealt to `nbins`
- * bins (0 = the default 1024 = one per SIMD; gf_conv_fwd_flat expects the default) in snake order, one
- * {group, first step, steps, offset mask} descriptor per (round, bin).  gf_conv_fwd_flat's LDS-weight kernel walks a
- * bin's records linearly.  K <= 31.  flat: int32 [gf_rules_flat_words(K, ld)] out. */
+ * bins in snake order, one {group, first step, steps, offset mask} descriptor per (round, bin).  gf_conv_fwd_flat's
+ * LDS-weight kernel walks a bin's records linearly.  nbins: 0 = the library's bin count (1024 = one per SIMD), which is
+ * also what gf_conv_fwd_flat reads a table with; any other value than that count is an argument error (the signature
+ * is kept for the ABI: pass 0).  K <= 31.  flat: int32 [gf_rules_flat_words(K, ld)] out. */
 size_t gf_rules_flat_words(int K, int ld);
 int gf_rules_flat_steps(const int32_t* nbr, const uint32_t* gmask, int K, int M, int ld, int nbins, int32_t* flat,
                         void* stream);

@@ -41,6 +41,12 @@ int gf_dev_conv_knob_flat(int use, int max_items);
 /* The LDS-weight kernel over a flat step table (k_conv_lw, spconv_lw.hip; only where gf_conv_fwd_flat is given such a
  * table): use 0 / 1 (whenever the shape allows) or -1 (size-based: at least `min_groups` 16-row groups, 0 = default). */
 int gf_dev_conv_knob_lw(int use, int min_groups);
+/* Number of bins of the flat step table, ONE value for its builder (gf_rules_flat_steps), the planner (a wave of the
+ * LDS-weight kernel keeps at most 64 groups, so at most 64 * 3 * nbins groups take it; nbins / 4 workgroups) and the
+ * kernel: 0 = the default 1024, otherwise a multiple of 4 of at most 1024.  With a few bins a table of a few hundred
+ * groups gives every wave a stream of many groups (the regime tests).  A table must be USED under the value it was BUILT
+ * with: gf_conv_fwd_flat has no other way to know its layout.  Process-wide; tests reset with 0. */
+int gf_dev_conv_flat_bins(int nbins);
 
 /* The launch gf_conv_fwd_flat would make for these arguments, without making it (the pointers are only compared, never
  * dereferenced): desc[10] = family (0 none, 1 k_conv_lw, 2 k_conv_flat, 3 k_conv_g16p, 4 k_conv_g16, 5 k_conv_pair,

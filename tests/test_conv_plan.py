@@ -13,7 +13,7 @@ OK, INVALID = 0, -1
 NONE, LW, FLAT, G16P, G16, PAIR, OS = range(7)
 FAMILY = ["none", "lw", "flat", "g16p", "g16", "pair", "os"]
 DEFAULT_KNOBS = dict(split=-1, wide=-1, pair=-1, block=0, g16=-1, g16_ldsw=-1, g16_gpw=0, g16_pipe=-1, flat=-1,
-                     flat_items=0, lw=-1, lw_items=0, wpb=0, chunks=0)
+                     flat_items=0, lw=-1, lw_items=0, wpb=0, chunks=0, bins=0)
 
 
 def _tri(v):
@@ -21,7 +21,7 @@ def _tri(v):
 
 
 def _norm(kn):
-    """The knob setters' normalisation (gf_dev_conv_knobs*, gf_dev_conv_knob_flat / _lw, _g16p_wpb, _chunks)."""
+    """The knob setters' normalisation (gf_dev_conv_knobs*, gf_dev_conv_knob_flat / _lw, _g16p_wpb, _chunks, _flat_bins)."""
     k = dict(DEFAULT_KNOBS, **kn)
     for n in ("split", "wide", "pair", "g16", "g16_ldsw", "g16_pipe", "flat", "lw"):
         k[n] = _tri(k[n])
@@ -29,6 +29,7 @@ def _norm(kn):
     for n in ("g16_gpw", "flat_items", "lw_items"):
         k[n] = max(k[n], 0)
     k["chunks"] = k["chunks"] if k["chunks"] > 0 else 3072
+    k["bins"] = k["bins"] or 1024  # bins of the flat step table: a wave of k_conv_lw keeps at most 64 groups of its bin
     return k
 
 
@@ -78,14 +79,14 @@ def head_plan(q, kn):
             npass = (nch + 1) // 2
             shape = lambda n: n in (1, 2) and ncb in (1, 2)  # noqa: E731
             lw = shape((nch + npass - 1) // npass) and shape(nch // npass)
-            lw = lw and M_in < (1 << 24) and M_in * Cin * 4 <= (1 << 30) - 4096 and ngroups <= 64 * 3 * 1024
+            lw = lw and M_in < (1 << 24) and M_in * Cin * 4 <= (1 << 30) - 4096 and ngroups <= 64 * 3 * kn["bins"]
             lw = lw and (forced or (npass == 1 and nch == 2 and ngroups >= (kn["lw_items"] or 1500)))
         if lw and (forced or not (g16 and nch == 1)):
             rest, ns = nch, []  # input chunks per pass: ceil(rest / passes left)
             for p in range(npass):
                 ns.append((rest + (npass - p) - 1) // (npass - p))
                 rest -= ns[-1]
-            return OK, [LW, npass, ns[0], ns[-1], ncb, 12, int(sc), 1024 // 4, 64 * 12, 27 * ns[0] * ncb * 1024]
+            return OK, [LW, npass, ns[0], ns[-1], ncb, 12, int(sc), kn["bins"] // 4, 64 * 12, 27 * ns[0] * ncb * 1024]
     if flat and (q["nbr"] or K == 1) and not out2:
         maxb = 4 if K * nch <= 16 * 4 * 4 else 6
         return OK, [FLAT, maxb, 0, 0, 0, 0, 0, ngroups * ncb, 1024, 0]
@@ -129,6 +130,7 @@ def _set_knobs(lib, kn):
     assert lib.gf_dev_conv_knob_lw(k["lw"], k["lw_items"]) == 0
     assert lib.gf_dev_conv_g16p_wpb(k["wpb"]) == 0
     assert lib.gf_dev_conv_chunks(k["chunks"]) == 0
+    assert lib.gf_dev_conv_flat_bins(k["bins"]) == 0
 
 
 # the shapes test_gpu_fullsize.py::test_every_launch_shape_forced forces, the LDS-weight kernel's knob and the rest
@@ -138,11 +140,14 @@ FORCED = [dict(split=0, pair=1, g16=0), dict(split=0, pair=0, g16=0), dict(split
           dict(g16=1, g16_ldsw=0, g16_pipe=1), dict(g16=1, g16_ldsw=1, g16_pipe=1)]
 KNOB_SETS = ([{}] + [dict(k, flat=0) for k in FORCED] + [dict(flat=1), dict(flat=-1, flat_items=1000)]
              + [dict(lw=1), dict(lw=0), dict(lw_items=100), dict(lw_items=3000), dict(wpb=8), dict(wpb=16),
-                dict(chunks=2048), dict(chunks=4096), dict(block=300), dict(block=100, split=0, g16=0, pair=0)])
+                dict(chunks=2048), dict(chunks=4096), dict(block=300), dict(block=100, split=0, g16=0, pair=0),
+                dict(bins=4), dict(bins=4, lw=1), dict(bins=64), dict(bins=64, lw=1), dict(bins=64, lw_items=100)])
 CHANNELS = [6, 16, 19, 21, 32, 48, 64, 96, 112, 224]
 # 16-row groups on both sides of every size threshold: 6000 (split), 256 items (wide / flat), 2048 (two column blocks
-# per wave), 1500 (LDS-weight kernel), 128 / 129 (256 items at two column blocks), one group, none
-GROUPS = [0, 1, 100, 128, 129, 256, 257, 1499, 1500, 2047, 2048, 5999, 6000, 12_000, 64 * 3 * 1024, 64 * 3 * 1024 + 1]
+# per wave), 1500 (LDS-weight kernel), 128 / 129 (256 items at two column blocks), one group, none; the LDS-weight
+# kernel's capacity of 64 groups per wave at 4, 64 and 1024 bins
+GROUPS = [0, 1, 100, 128, 129, 256, 257, 1499, 1500, 2047, 2048, 5999, 6000, 12_000, 64 * 3 * 1024, 64 * 3 * 1024 + 1,
+          64 * 3 * 4, 64 * 3 * 4 + 1, 64 * 3 * 64, 64 * 3 * 64 + 1]
 BASE = 1 << 20  # fake device addresses: 16-byte aligned, +4 = misaligned
 ALIGN_KEYS = ["in", "sc", "out", "res", "out2", "osc"]
 
@@ -225,6 +230,11 @@ def test_plan_reaches_every_shape(lib):  # noqa: F811
              ({"g16": 0}, q(10_000, 16, 16, flat=False), PAIR), ({"g16": 0}, q(10_000, 16, 16, flat=False, sc=True), PAIR),
              ({}, q(10_000, 64, 64, flat=False), OS), ({}, q(3000, 64, 64, flat=False), OS), ({}, q(200, 19, 21), OS), ({}, q(100, 19, 21), OS),
              ({"block": 64, "split": 0, "g16": 0, "pair": 0}, q(100, 48, 224, flat=False), OS),
+             # the capacity edge of the LDS-weight kernel: 64 groups per wave, three waves per bin
+             ({}, q(64 * 3 * 1024, 32, 32), LW), ({}, q(64 * 3 * 1024 + 1, 32, 32), OS),
+             ({"bins": 4, "lw": 1}, q(768, 32, 32), LW), ({"bins": 4, "lw": 1}, q(769, 32, 32), OS),
+             ({"bins": 64}, q(12_288, 32, 32), LW), ({"bins": 64}, q(12_289, 32, 32), OS),
+             ({"bins": 64, "lw": 1}, q(12_288, 112, 16, sc=True), LW), ({"bins": 64, "lw": 1}, q(12_289, 112, 16, sc=True), PAIR),
              ({}, q(10_000, 16, 16, steps=False, out2=True, osc=True, flat=False), "error"),
              ({}, q(10_000, 64, 64, nbr=False, steps=False, flat=False), "error")]
     desc = (ctypes.c_int * 10)()

@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests.conv_lw_cases import flat_layout, flat_reference, snake_slots, sorted_order, wave_streams
 from tests.util import random_voxels
 
 pytestmark = pytest.mark.gpu
@@ -240,26 +241,13 @@ def test_wgrad_without_table_is_xt_g(hip, M, Cin, Cout):
     assert float((dW[0].double() - 2 * want).abs().max()) <= 2 * tol
 
 
-def _flat_reference(nbr, M, K=27):
-    """The flat step table's step records restated in numpy: per 16-row group the present offsets, ascending."""
-    ng = (M + 15) // 16
-    pad = np.full((K, ng * 16), -1, np.int32)
-    pad[:, :M] = nbr[:, :M]
-    recs, goff, masks = [], [0], []
-    for g in range(ng):
-        blk = pad[:, g * 16:(g + 1) * 16]
-        ks = [k for k in range(K) if (blk[k] >= 0).any()]
-        masks.append(sum(1 << k for k in ks))
-        recs += [blk[k] for k in ks]
-        goff.append(goff[-1] + len(ks))
-    return np.array(recs, np.int32).reshape(-1, 16), np.array(goff), np.array(masks, np.uint32)
-
-
 @pytest.mark.parametrize("M,shape,nbins", [(3000, (40, 36, 30), 0), (30000, (90, 80, 60), 0), (777, (20, 22, 18), 64), (40, (8, 8, 8), 0)])
 def test_flat_step_table(hip, oracle, M, shape, nbins):
     """gf_rules_flat_steps against the neighbour table it restates: step records and per-group offsets bit for bit;
-    the bin table: every group exactly once, sizes descending along the sorted positions, snake order, bins balanced."""
-    from geoformer_amd import sparse
+    the bin table: every group exactly once, sizes descending along the sorted positions, snake order, bins balanced,
+    each wave's stream of group sizes as tests/conv_lw_cases.py restates the dealing.  The bin count is the library's
+    one setting (gf_dev_conv_flat_bins): a table of another count is not built."""
+    from geoformer_amd import _lib, sparse
 
     rng = np.random.default_rng(M)
     coords = random_voxels(rng, M, shape, 1, surface=True)
@@ -267,8 +255,14 @@ def test_flat_step_table(hip, oracle, M, shape, nbins):
     nbr = oracle.rules_subm3(coords, shape)
     c = _dev(coords)
     rules = sparse.subm_rules(c, sparse.build_index(c, 1, shape))
-    flat = sparse.flat_steps(rules.nbr, rules.gmask, 27, M, rules.ld, nbins).cpu().numpy()
-    recs, goff, masks = _flat_reference(nbr, M)
+    try:
+        sparse.dev_conv_flat_bins(nbins)
+        flat = sparse.flat_steps(rules.nbr, rules.gmask, 27, M, rules.ld, nbins).cpu().numpy()
+        with pytest.raises(_lib.GeoFormerHipError):  # an explicit bin count that is not the current one
+            sparse.flat_steps(rules.nbr, rules.gmask, 27, M, rules.ld, 128)
+    finally:
+        sparse.dev_conv_flat_bins(0)
+    recs, goff, masks = flat_reference(nbr, M)
     ng = (M + 15) // 16
     S = int(goff[-1])
     nb = nbins if nbins else 1024
@@ -280,14 +274,14 @@ def test_flat_step_table(hip, oracle, M, shape, nbins):
     assert (flat[128: 128 + ng + 1] == goff).all()
     ppos = flat[128 + ng + 1: 128 + 2 * ng + 1]
     assert (np.sort(ppos) == np.arange(ng)).all()
-    d_at = (128 + 2 * ng + 1 + 63) // 64 * 64
-    desc = flat[d_at: d_at + (rounds + 1) * nb * 4].reshape(rounds + 1, nb, 4)
-    s_at = d_at + (rounds + 1) * nb * 4
-    got = flat[s_at: s_at + (S + 32) * 16].reshape(-1, 16)
+    d_at, s_at, end = flat_layout(ng, nb, S)
+    assert end <= flat.size
+    desc = flat[d_at: s_at].reshape(rounds + 1, nb, 4)
+    got = flat[s_at: end].reshape(-1, 16)
     assert (got[:S] == recs).all()
     assert (got[S:] == -1).all()
     # sorted positions: round j runs over the bins forwards (even) or backwards (odd)
-    order = np.concatenate([desc[j] if j % 2 == 0 else desc[j, ::-1] for j in range(rounds + 1)])
+    order = sorted_order(desc)
     filled = order[:, 0] >= 0
     assert filled[:ng].all() and not filled[ng:].any()
     gs = order[:ng, 0]
@@ -297,6 +291,14 @@ def test_flat_step_table(hip, oracle, M, shape, nbins):
     assert (np.diff(order[:ng, 2]) <= 0).all()
     load = np.where(desc[:, :, 0] >= 0, desc[:, :, 2], 0).sum(0)
     assert load.max() - load.min() <= 27
+    # what the kernel's wave t of bin b reads (rounds t, t + 3, ... of column b) is the restated stream of sizes
+    rnd, b = snake_slots(ng, nb)
+    assert (desc[rnd, b, 0] == gs).all()
+    streams = wave_streams(sizes, nb)
+    for bb in range(nb):
+        for t in range(3):
+            col = desc[t::3, bb]
+            assert col[col[:, 0] >= 0, 2].tolist() == streams[(bb, t)], (bb, t)
 
 
 @pytest.mark.parametrize("Cin,Cout", [(16, 16), (32, 16), (16, 32), (32, 32), (64, 32), (48, 32), (64, 16)])
