@@ -8,13 +8,14 @@
 //   k_ie_keys       one pass over the N gt ids: each point's key (-1 void, -2 padding up to a whole 1024-point chunk),
 //                   the presence mark of its key; zero-fills the outputs (capacity, G is not known yet)
 //   k_ie_slots      one workgroup: exclusive scan of the presence table -> compact slot per key in ascending id order
-//                   (np.unique's order), G, the id of every slot
+//                   (np.unique's order), G, the id of every slot (post_steps.h's gf_presence_to_slots)
 //   k_ie_hist       grid (point chunks of 1024, groups of IE_ROWS rows): each thread keeps 4 points' slots and
 //                   IE_ROWS x 4 mask bits in registers, a workgroup counts them in an LDS histogram [IE_ROWS, tile] and
 //                   flushes one integer atomic per nonzero (row, slot); slots beyond one LDS tile are handled by
 //                   further passes over the same registers (the masks are read once).  Row n is a virtual all-ones
 //                   row: its counts are the instances' point counts.
 #include "common.h"
+#include "post_steps.h"
 
 namespace {
 
@@ -49,8 +50,7 @@ __global__ __launch_bounds__(IE_THREADS) void k_ie_keys(const long long* __restr
         int key = -2;
         if (i < N) {
             const long long g = gt_ids[i];
-            long long q = g / 1000;  // floor division, as numpy's //
-            if (g % 1000 != 0 && g < 0) --q;
+            const long long q = gf_floor_div_1000(g);
             const int rank = ie_class_rank(q, class_ids, C);
             key = -1;
             if (rank >= 0) {
@@ -72,28 +72,8 @@ __global__ __launch_bounds__(IE_SCAN_THREADS) void k_ie_slots(int32_t* __restric
     __shared__ int32_t sorted_cls[IE_MAX_CLASSES];
     const int t = threadIdx.x;
     if (t < C) sorted_cls[ie_class_rank(class_ids[t], class_ids, C)] = class_ids[t];
-    const int per = (K + IE_SCAN_THREADS - 1) / IE_SCAN_THREADS;
-    const int b = min(K, t * per), e = min(K, b + per);
-    int s = 0;
-    for (int k = b; k < e; ++k) s += table[k] != 0;
-    sums[t] = s;
-    __syncthreads();
-    for (int off = 1; off < IE_SCAN_THREADS; off <<= 1) {  // inclusive Hillis-Steele scan
-        const int v = t >= off ? sums[t - off] : 0;
-        __syncthreads();
-        sums[t] += v;
-        __syncthreads();
-    }
-    int slot = sums[t] - s;
-    for (int k = b; k < e; ++k) {
-        if (table[k] != 0) {
-            if (slot < max_gt) gt_id[slot] = (long long)sorted_cls[k / 1000] * 1000 + k % 1000;
-            table[k] = slot++;
-        } else {
-            table[k] = -1;
-        }
-    }
-    if (t == IE_SCAN_THREADS - 1) *d_G = sums[t];
+    const int incl = gf_presence_to_slots<IE_SCAN_THREADS>(table, K, sorted_cls, sums, t, max_gt, gt_id);
+    if (t == IE_SCAN_THREADS - 1) *d_G = incl;
 }
 
 template <bool VEC>

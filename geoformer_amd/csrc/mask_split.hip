@@ -11,11 +11,10 @@
 //   k_ms_core     a member counts the entries of its own row whose bit is set in the pick's bit row (it stops at
 //                 min_samples); the ballot of the core lanes is the pick's core word.  comp doubles as the parent
 //                 array: i for a core point, -1 for every other point; count = 0 at core points.  members += popcount
-//   k_ms_hook     a core lane walks its row and unions with every core entry: oversegment.hip's lock-free union -- the
-//                 larger root goes under the smaller by atomicCAS, the finds halve their paths, parent[x] <= x always
-//   k_ms_flatten  comp[i] = root(i) for core points, in place (a word only ever moves to an ancestor, and a root's word
-//                 never changes, so concurrent walks still end at the root); count[root] += the number of the wave's
-//                 lanes with that root: ONE integer atomicAdd per distinct root of the wave
+//   k_ms_hook     a core lane walks its row and unions with every core entry: post_steps.h's lock-free min-index union
+//                 (gf_uf_union)
+//   k_ms_flatten  comp[i] = root(i) for core points, in place (gf_uf_root); count[root] += the number of the wave's
+//                 lanes with that root: ONE integer atomicAdd per distinct root of the wave (gf_wave_add_per_key)
 //   k_ms_border   a member that is not core takes the smallest root among the core entries of its own row (final since
 //                 k_ms_flatten): reads core words of comp, writes non-core words; count[root] += 1, aggregated as above
 //   k_ms_dissolve comp = -1 where count[comp] < min_points; a kept root adds itself to the pick's table (clusters,
@@ -27,6 +26,7 @@
 // picks: nothing of one pick is read by another.  An index outside [0, N) in a row is skipped, never followed, and only
 // columns 0 .. min(deg[i], k - 1) of a row are read.  Every r * N + i is formed in 64 bits.
 #include "common.h"
+#include "post_steps.h"
 
 namespace {
 
@@ -43,20 +43,6 @@ __device__ __forceinline__ bool ms_bit(const u64* __restrict__ row, int j) { ret
 __device__ __forceinline__ long long ms_word(long long W) {
     const long long w = (long long)blockIdx.x * MS_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     return w < W ? w : -1;
-}
-
-// count[root] += the number of lanes of the wave that are `on` with that root: one atomicAdd per distinct root (a
-// 3000-point cluster would otherwise send every one of its adds to one address).  Wave-uniform control flow.
-__device__ __forceinline__ void ms_count_roots(bool on, int root, int32_t* count) {
-    const int lane = threadIdx.x & 63;
-    u64 todo = __ballot(on);
-    while (todo) {
-        const int lead = __ffsll((long long)todo) - 1;
-        const int r0 = __shfl(root, lead, 64);
-        const u64 same = __ballot(on && root == r0);
-        if (lane == lead) atomicAdd(&count[r0], __popcll(same));
-        todo &= ~same;
-    }
 }
 
 __global__ __launch_bounds__(MS_THREADS) void k_ms_pack(const int32_t* __restrict__ masks, int n_rows, long long N,
@@ -124,17 +110,6 @@ __global__ __launch_bounds__(MS_THREADS) void k_ms_core(const int32_t* __restric
     }
 }
 
-// root of x while other threads hook roots, halving the path on the way (oversegment.hip's sc_find_live)
-__device__ __forceinline__ int ms_find_live(int32_t* parent, int x) {
-    for (;;) {
-        const int p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (p == x) return x;
-        const int gp = __hip_atomic_load(&parent[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (gp != p) __hip_atomic_store(&parent[x], gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        x = gp;
-    }
-}
-
 __global__ __launch_bounds__(MS_THREADS) void k_ms_hook(const int32_t* __restrict__ I, const int32_t* __restrict__ deg,
                                                         long long N, int k, long long W, const u64* __restrict__ core,
                                                         int32_t* comp) {
@@ -150,16 +125,7 @@ __global__ __launch_bounds__(MS_THREADS) void k_ms_hook(const int32_t* __restric
     for (int c = 0; c <= last; ++c) {
         const int j = row[c];
         if ((unsigned long long)(long long)j >= (unsigned long long)N || j == i || !ms_bit(crow, j)) continue;
-        int a = (int)i, b = j;
-        for (;;) {
-            a = ms_find_live(parent, a);
-            b = ms_find_live(parent, b);
-            if (a == b) break;
-            const int hi = max(a, b), lo = min(a, b);
-            if (atomicCAS(&parent[hi], hi, lo) == hi) break;
-            a = hi;  // hi was hooked by another thread meanwhile: go on from there
-            b = lo;
-        }
+        gf_uf_union<__HIP_MEMORY_SCOPE_AGENT>(parent, (int)i, j);
     }
 }
 
@@ -173,17 +139,8 @@ __global__ __launch_bounds__(MS_THREADS) void k_ms_flatten(long long N, long lon
     const bool on = (cw >> lane) & 1ull;
     int32_t* parent = comp + r * N;
     int root = -1;
-    if (on) {
-        const int i = (int)(w * 64 + lane);
-        root = i;
-        for (;;) {  // nothing is hooked any more: other lanes only move words to ancestors
-            const int p = __hip_atomic_load(&parent[root], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (p == root) break;
-            root = p;
-        }
-        if (root != i) __hip_atomic_store(&parent[i], root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    ms_count_roots(on, root, count + r * N);
+    if (on) root = gf_uf_root<__HIP_MEMORY_SCOPE_AGENT>(parent, (int)(w * 64 + lane));  // nothing is hooked any more
+    gf_wave_add_per_key(lane, on, root, count + r * N);
 }
 
 __global__ __launch_bounds__(MS_THREADS) void k_ms_border(const int32_t* __restrict__ I, const int32_t* __restrict__ deg,
@@ -208,7 +165,7 @@ __global__ __launch_bounds__(MS_THREADS) void k_ms_border(const int32_t* __restr
         }
         if (best != 0x7fffffff) ids[i] = best;
     }
-    ms_count_roots(best != 0x7fffffff, best, count + r * N);
+    gf_wave_add_per_key(lane, best != 0x7fffffff, best, count + r * N);
 }
 
 __global__ __launch_bounds__(MS_THREADS) void k_ms_dissolve(long long N, int min_points, long long W,

@@ -12,11 +12,8 @@
 //
 // gf_smooth_components, five launches, none of them repeated "until nothing changes":
 //   k_sc_init     parent[i] = i, count[i] = 0
-//   k_sc_hook     one thread per row entry: the edge test, then a lock-free union -- find both roots, hook the LARGER
-//                 root under the smaller with atomicCAS(parent[hi], hi, lo); a failed CAS means another thread hooked hi
-//                 first, and the loop finds the new roots.  The finds halve the paths they walk.  parent[x] <= x always
-//                 and parent[x] names a member of x's set, so no cycle can form, and the root of a finished set is its
-//                 smallest index.
+//   k_sc_hook     one thread per row entry: the edge test, then post_steps.h's lock-free min-index union
+//                 (gf_uf_union): the root of a finished set is its smallest index.
 //   k_sc_flatten  root[i] = find(i) for flat points (parent is read-only now), count[root] += 1 (integer atomicAdd) while
 //                 the count is below min_points -- all the dissolve needs to know
 //   k_sc_dissolve ids[i] = root[i] where count[root[i]] >= min_points, else -1; -1 for non-flat points
@@ -26,6 +23,7 @@
 // call whatever the order in which the unions land.  No floating-point atomics.  An index outside [0, n) in a row is
 // skipped, never followed, and only columns 0 .. min(deg[i], k - 1) of a row are read.
 #include "common.h"
+#include "post_steps.h"
 
 namespace {
 
@@ -143,19 +141,6 @@ __global__ __launch_bounds__(OS_THREADS) void k_sc_init(int n, int32_t* __restri
     count[i] = 0;
 }
 
-// root of x while other threads hook roots, halving the path on the way: every load is an atomic one, parent[y] <= y, so
-// the walk ends.  Only a NON-root's word is rewritten (to its grandparent: still below it, still in its set), and a
-// non-root never becomes a root again, so the atomicCAS on roots in k_sc_hook is not disturbed.
-__device__ __forceinline__ int sc_find_live(int32_t* parent, int x) {
-    for (;;) {
-        const int p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (p == x) return x;
-        const int gp = __hip_atomic_load(&parent[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (gp != p) __hip_atomic_store(&parent[x], gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        x = gp;
-    }
-}
-
 __global__ __launch_bounds__(OS_THREADS) void k_sc_hook(const float* __restrict__ xyz, const float4* __restrict__ nrm,
                                                         const int32_t* __restrict__ I,
                                                         const int32_t* __restrict__ deg, int n, int k,
@@ -171,16 +156,7 @@ __global__ __launch_bounds__(OS_THREADS) void k_sc_hook(const float* __restrict_
     const float4 ni = nrm[i], nj = nrm[j];
     if (fabsf(fmaf(ni.x, nj.x, fmaf(ni.y, nj.y, ni.z * nj.z))) < cos_thresh) return;
     if (sc_plane_dist(ni, xyz, i, j) > offset) return;
-    int a = i, b = j;
-    for (;;) {
-        a = sc_find_live(parent, a);
-        b = sc_find_live(parent, b);
-        if (a == b) break;
-        const int hi = max(a, b), lo = min(a, b);
-        if (atomicCAS(&parent[hi], hi, lo) == hi) break;
-        a = hi;  // hi was hooked by another thread meanwhile: go on from there
-        b = lo;
-    }
+    gf_uf_union<__HIP_MEMORY_SCOPE_AGENT>(parent, i, j);
 }
 
 __global__ __launch_bounds__(OS_THREADS) void k_sc_flatten(const float4* __restrict__ nrm, int n, float flatness,

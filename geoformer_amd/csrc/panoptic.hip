@@ -13,6 +13,7 @@
 //   k_pan_keys      one pass over the points (the only read of owner, sem, gt_ids): row and key of every point packed
 //                   in one word, the presence mark of the key in its scene's table, pan; zero-fills inter and gt_id
 //   k_pan_slots     one workgroup per scene: exclusive scan of the presence table -> slot per key, G_s, gt_id
+//                   (post_steps.h's gf_presence_to_slots)
 //   k_pan_count     a workgroup owns PAN_RUN consecutive points, cut at the scene boundaries the run contains (empty
 //                   scenes are stepped over).  Per piece, one (row, column) pair per point, counted in one of two ways:
 //                     R * (G_s + 1) <= lds_bins: an LDS table of that many words (LDS atomics), flushed as one global
@@ -25,6 +26,7 @@
 
 #include "common.h"
 #include "geoformer_hip_dev.h"
+#include "post_steps.h"
 
 namespace {
 
@@ -38,19 +40,6 @@ constexpr int PAN_SCAN_THREADS = 1024;
 constexpr int PAN_KEY_BITS = 17;                    // key + 1 <= 64 * 1000 < 2^17; the row sits above
 
 std::atomic<int> g_lds_bins{-1};  // dev knob: capacity of the LDS table in bins, -1 = PAN_LDS_BINS
-
-// the scene of point p: the last s with offsets[s] <= p (empty scenes before it share the value), inside [0, S - 1]
-__device__ __forceinline__ int pan_scene_of(const int32_t* __restrict__ offsets, int S, long long p) {
-    int lo = 0, hi = S;  // first index in [0, S] whose offset exceeds p
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (offsets[mid] > p)
-            hi = mid;
-        else
-            lo = mid + 1;
-    }
-    return max(lo - 1, 0);
-}
 
 __global__ __launch_bounds__(PAN_THREADS) void k_pan_keys(
     const int32_t* __restrict__ owner, const int32_t* __restrict__ ids, const int32_t* __restrict__ sem,
@@ -79,7 +68,7 @@ __global__ __launch_bounds__(PAN_THREADS) void k_pan_keys(
     const int R = P + n_stuff + 1;
     const long long stride = (long long)gridDim.x * PAN_RUN;
     for (long long run_lo = (long long)blockIdx.x * PAN_RUN; run_lo < N; run_lo += stride) {
-        const int s0 = pan_scene_of(offsets, S, run_lo);  // (uniform over the workgroup)
+        const int s0 = gf_scene_of(offsets, S, run_lo);  // (uniform over the workgroup)
 #pragma unroll
         for (int i = 0; i < PAN_PER; ++i) {
             const long long p = run_lo + i * PAN_THREADS + t;
@@ -104,8 +93,7 @@ __global__ __launch_bounds__(PAN_THREADS) void k_pan_keys(
             if (!gt_ids) continue;  // (uniform: labels only)
             // ground-truth key
             const long long g = gt_ids[p];
-            long long q = g / 1000;  // floor division, as numpy's //
-            if (g % 1000 != 0 && g < 0) --q;
+            const long long q = gf_floor_div_1000(g);
             int key = -1;
             for (int c = 0; c < C; ++c) {
                 if ((long long)s_cls[c] == q) {
@@ -137,28 +125,8 @@ __global__ __launch_bounds__(PAN_SCAN_THREADS) void k_pan_slots(int32_t* __restr
         for (int c = 0; c < C; ++c) rank += class_ids[c] < v;
         sorted_cls[rank] = v;
     }
-    const int per = (K + PAN_SCAN_THREADS - 1) / PAN_SCAN_THREADS;
-    const int b = min(K, t * per), e = min(K, b + per);
-    int s = 0;
-    for (int k = b; k < e; ++k) s += table[k] != 0;
-    sums[t] = s;
-    __syncthreads();
-    for (int off = 1; off < PAN_SCAN_THREADS; off <<= 1) {  // inclusive Hillis-Steele scan
-        const int v = t >= off ? sums[t - off] : 0;
-        __syncthreads();
-        sums[t] += v;
-        __syncthreads();
-    }
-    int slot = sums[t] - s;
-    for (int k = b; k < e; ++k) {
-        if (table[k] != 0) {
-            if (slot < max_gt) gid[slot] = (long long)sorted_cls[k / 1000] * 1000 + k % 1000;
-            table[k] = slot++;
-        } else {
-            table[k] = -1;
-        }
-    }
-    if (t == PAN_SCAN_THREADS - 1) d_G[blockIdx.x] = sums[t];
+    const int incl = gf_presence_to_slots<PAN_SCAN_THREADS>(table, K, sorted_cls, sums, t, max_gt, gid);
+    if (t == PAN_SCAN_THREADS - 1) d_G[blockIdx.x] = incl;
 }
 
 __global__ __launch_bounds__(PAN_THREADS) void k_pan_count(const int32_t* __restrict__ packed,
@@ -178,7 +146,7 @@ __global__ __launch_bounds__(PAN_THREADS) void k_pan_count(const int32_t* __rest
         pk[i] = p < N ? packed[p] : -1;
     }
     const int W = max_gt + 1;
-    int s = pan_scene_of(offsets, S, run_lo);
+    int s = gf_scene_of(offsets, S, run_lo);
     for (int lo = (int)run_lo; lo < run_hi && s < S; ++s) {
         const int hi = min(run_hi, offsets[s + 1]);
         if (hi <= lo) continue;  // an empty scene
@@ -218,6 +186,8 @@ __global__ __launch_bounds__(PAN_THREADS) void k_pan_count(const int32_t* __rest
 #pragma unroll
                 for (int i = 0; i < PAN_PER; ++i) {
                     // the lanes that hold the first open lane's pair leave together: one atomic per distinct pair
+                    // (post_steps.h's gf_wave_add_per_key with the pair decoded before the add; written out: the
+                    // shared loop over a functor makes the kernel 12 instructions longer)
                     unsigned long long open = __ballot(pair[i] >= 0);
                     while (open) {
                         const int leader = __ffsll((long long)open) - 1;

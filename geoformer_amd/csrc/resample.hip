@@ -3,8 +3,9 @@
 // postprocess.grid_subsample_host and postprocess.nearest_point_host; see include/geoformer_hip.h for the arguments.
 //
 // gf_grid_subsample (the first five steps are voxelize_idx.hip's, keyed by a cell of floats instead of integer voxels):
-//   k_rs_bounds  (default origin only) per-axis minimum of the points as order-preserving 32-bit keys: at most 512
-//                workgroups stride over the points, reduce in registers and LDS and issue one integer atomicMin per axis
+//   k_rs_bounds  (default origin only) per-axis minimum of the points as order-preserving 32-bit keys (post_steps.h's
+//                gf_float_key): at most 512 workgroups stride over the points, reduce in registers and LDS and issue one
+//                integer atomicMin per axis
 //   k_rs_org     one thread: the origin of the call -- the caller's three floats or the decoded minimum -- into scratch
 //   k_rs_insert  one thread per point: t = (p - origin) / cell (one subtraction, one correctly rounded division),
 //                c = floor t, the cell key cx | cy << 21 | cz << 42 claimed in an open-addressing table by 64-bit CAS;
@@ -25,6 +26,7 @@
 //                records with d2 <= r2.  A bucket may hold several cells and several of the 27 cells may share a bucket;
 //                a minimum does not care.  The order inside a bucket depends on arrival, the minimum does not.
 #include "common.h"
+#include "post_steps.h"
 
 namespace {
 
@@ -36,14 +38,6 @@ constexpr int RS_AXIS_BITS = 21;
 constexpr u64 RS_EMPTY = 0xffffffffffffffffull;
 constexpr double NP_MAX_CELLS = 1073741824.0;  // 2^30 cells per axis: the proven range of the 27-cell walk
 
-// floats <-> 32-bit keys that ascend with the float (-inf lowest, +inf highest among the non-NaN)
-__device__ __forceinline__ unsigned fkey(float f) {
-    const unsigned b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float fkey_inv(unsigned k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
 __device__ __forceinline__ bool finite3(float x, float y, float z) {
     return isfinite(x) && isfinite(y) && isfinite(z);
 }
@@ -75,7 +69,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_bounds(const float* __restric
 #pragma unroll
         for (int a = 0; a < 3; ++a)
             if (ok && p[a] == p[a]) {
-                const unsigned k = fkey(p[a]);
+                const unsigned k = gf_float_key(p[a]);
                 mn[a] = min(mn[a], k);
                 mx[a] = max(mx[a], k);
             }
@@ -163,7 +157,7 @@ __device__ __forceinline__ T rs_peek(const T* p) {
 }
 
 __global__ void k_rs_org(const float* __restrict__ origin, RsScratch s) {
-    if (threadIdx.x < 3) s.org[threadIdx.x] = origin ? origin[threadIdx.x] : fkey_inv(s.okey[threadIdx.x]);
+    if (threadIdx.x < 3) s.org[threadIdx.x] = origin ? origin[threadIdx.x] : gf_float_unkey(s.okey[threadIdx.x]);
 }
 
 __global__ __launch_bounds__(RS_THREADS) void k_rs_insert(const float* __restrict__ xyz, int N, float cell, int center,
@@ -310,8 +304,8 @@ __global__ void k_np_plan(NpScratch s, double cell, int32_t* __restrict__ flag) 
     P.inv_cell = 1.0 / cell;
     int beyond = 0;
     for (int a = 0; a < 3; ++a) {
-        P.lo[a] = P.any ? (double)fkey_inv(s.bkey[a]) : 0.0;
-        P.ext[a] = P.any ? ((double)fkey_inv(s.bkey[4 + a]) - P.lo[a]) * P.inv_cell : 0.0;
+        P.lo[a] = P.any ? (double)gf_float_unkey(s.bkey[a]) : 0.0;
+        P.ext[a] = P.any ? ((double)gf_float_unkey(s.bkey[4 + a]) - P.lo[a]) * P.inv_cell : 0.0;
         if (!(P.ext[a] < NP_MAX_CELLS)) beyond = 1;
     }
     *s.plan = P;

@@ -65,10 +65,11 @@ __global__ __launch_bounds__(SE_THREADS) void k_semantic_confusion(const float* 
     }
     if (!labels) return;
 
-    // the scene of the run's first point: the last s with offsets[s] <= run_lo (empty scenes before it share the value)
+    // the scene of the run's first point: post_steps.h's gf_scene_of(offsets, S, run_lo) (written out: the call makes
+    // the kernel four instructions longer)
     int s;
     {
-        int lo = 0, hi = S;  // first index in [0, S] whose offset exceeds run_lo
+        int lo = 0, hi = S;
         while (lo < hi) {
             const int mid = (lo + hi) >> 1;
             if (offsets[mid] > run_lo)

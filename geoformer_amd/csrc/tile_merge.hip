@@ -13,9 +13,9 @@
 //                  shared[a, t], shared[b, s], inter[a, b] and inter[b, a] for the set bits a, b, with the pairs (a, b)
 //                  dealt over the 64 lanes -- a wall of 10 000 shared points reaches a counter as 160 adds, not 10 000
 //   k_tm_merge     ONE workgroup of 1024 threads: the edges of the upper triangle of inter hook a min-index union-find in
-//                  LDS (oversegment.hip's lock-free union: the larger root goes under the smaller by atomicCAS, the
-//                  finds halve their paths); then comp, the ranks of the roots (global ids), the class of the root and
-//                  the maximum member score by an integer-ordered atomicMax in LDS
+//                  LDS (post_steps.h's lock-free union at workgroup scope, gf_uf_union); then comp, the ranks of the
+//                  roots (global ids), the class of the root and the maximum member score by an integer-ordered
+//                  atomicMax in LDS (gf_float_key)
 //   k_tm_assemble  one thread per point of the scan: for every tile of the point and every set bit, atomicOr on the
 //                  instance's output word; the lanes whose word was 0 before count, one atomicAdd per distinct instance
 //                  of the wave
@@ -23,6 +23,7 @@
 // outputs are bit-identical from call to call.  A tile id outside [0, T), a local index outside [0, n_s), a pick outside
 // [0, n_rows) or a row outside [0, P) is skipped, never an address.  Every row * N + point is formed in 64 bits.
 #include "common.h"
+#include "post_steps.h"
 
 namespace {
 
@@ -151,27 +152,6 @@ __global__ __launch_bounds__(TM_THREADS) void k_tm_overlaps(const long long* __r
     tm_pair(tab, T, multi, tl.z, tl.w, lc.z, lc.w, bits, P, inter, shared);
 }
 
-// root of x in the LDS parent array while other threads hook roots, halving the path on the way (oversegment.hip's
-// sc_find_live)
-__device__ __forceinline__ int tm_find_live(int* parent, int x) {
-    for (;;) {
-        const int p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (p == x) return x;
-        const int gp = __hip_atomic_load(&parent[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (gp != p) __hip_atomic_store(&parent[x], gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        x = gp;
-    }
-}
-
-// a float as an unsigned word whose integer order is the float order (no NaN among the scores)
-__device__ __forceinline__ uint32_t tm_key(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float tm_unkey(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
 __global__ __launch_bounds__(TM_MERGE_THREADS) void k_tm_merge(const int32_t* __restrict__ inter,
                                                                const int32_t* __restrict__ shared,
                                                                const long long* __restrict__ cls,
@@ -201,28 +181,13 @@ __global__ __launch_bounds__(TM_MERGE_THREADS) void k_tm_merge(const int32_t* __
         if (ta == tb || (unsigned)ta >= (unsigned)T || (unsigned)tb >= (unsigned)T || cls[a] != cls[b]) continue;
         const int small = min(shared[(long long)a * T + tb], shared[(long long)b * T + ta]);
         if (!((double)v >= iom * (double)small)) continue;
-        int x = a, y = b;
-        for (;;) {
-            x = tm_find_live(s_parent, x);
-            y = tm_find_live(s_parent, y);
-            if (x == y) break;
-            const int hi = max(x, y), lo = min(x, y);
-            if (atomicCAS(&s_parent[hi], hi, lo) == hi) break;
-            x = hi;  // hi was hooked by another thread meanwhile: go on from there
-            y = lo;
-        }
+        gf_uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(s_parent, a, b);
     }
     __syncthreads();
-    // flatten: nothing is hooked any more, a word only ever moves to an ancestor and a root's word never changes
+    // flatten: nothing is hooked any more; the key of a score keeps its order (no NaN among the scores)
     for (int i = tid; i < P; i += TM_MERGE_THREADS) {
-        int root = i;
-        for (;;) {
-            const int p = __hip_atomic_load(&s_parent[root], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            if (p == root) break;
-            root = p;
-        }
-        if (root != i) __hip_atomic_store(&s_parent[i], root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        atomicMax(&s_key[root], tm_key(scores[i]));
+        const int root = gf_uf_root<__HIP_MEMORY_SCOPE_WORKGROUP>(s_parent, i);
+        atomicMax(&s_key[root], gf_float_key(scores[i]));
     }
     __syncthreads();
     // global ids: the rank of every root among the roots; a thread owns TM_ROWS_PER_THREAD consecutive rows
@@ -230,6 +195,7 @@ __global__ __launch_bounds__(TM_MERGE_THREADS) void k_tm_merge(const int32_t* __
     int mine = 0;
 #pragma unroll
     for (int q = 0; q < TM_ROWS_PER_THREAD; ++q) mine += (i0 + q < P && s_parent[i0 + q] == i0 + q) ? 1 : 0;
+    // post_steps.h's gf_lds_incl_scan (written out: the call adds one scalar instruction to the scan's first step)
     s_scan[tid] = mine;
     __syncthreads();
     for (int d = 1; d < TM_MERGE_THREADS; d <<= 1) {
@@ -245,7 +211,7 @@ __global__ __launch_bounds__(TM_MERGE_THREADS) void k_tm_merge(const int32_t* __
         if (i < P && s_parent[i] == i) {
             s_gid[i] = next;
             inst_cls[next] = cls[i];
-            inst_scores[next] = tm_unkey(s_key[i]);
+            inst_scores[next] = gf_float_unkey(s_key[i]);
             ++next;
         }
     }
@@ -304,6 +270,7 @@ __global__ __launch_bounds__(TM_THREADS) void k_tm_assemble(const long long* __r
                 if (gid >= 0 && gid < G) fresh = atomicOr(&masks[(long long)gid * N + g], 1) == 0;
             }
             // count[gid] += the lanes with a fresh word of that instance: one atomicAdd per distinct instance
+            // (written out: gf_wave_add_per_key gives the same instructions here, but a few of them in another order)
             u64 todo = __ballot(fresh);
             while (todo) {
                 const int lead = __ffsll((long long)todo) - 1;

@@ -3,7 +3,9 @@
 #   tools/isa_diff.sh <parent-ref> [file.hip ...]      (default: every geoformer_amd/csrc/*.hip)
 # Compiles each source device-only to gfx950 assembly with the library's own flags (geoformer_amd/_build.py), once from
 # <parent-ref> (git archive into a temporary directory) and once from the working tree, drops the lines that hold the
-# per-compilation __hip_cuid_ symbol and compares.  The .amdhsa_* directives (registers, LDS, scratch) are part of the
+# per-compilation __hip_cuid_ symbol and the assembler comment lines (first non-blank character `;`) and compares.  The
+# compiler moves its `; implicit-def:` notes when a loop becomes an inlined call although no instruction moves; every
+# instruction, label and directive is still compared.  The .amdhsa_* directives (registers, LDS, scratch) are part of the
 # text, so occupancy is covered.  Prints a verdict per file, under a file that differs the kernels whose bodies differ
 # (needs c++filt); exit status 1 if any file differs or fails to compile.
 #   ISA_DIFF_KEEP=<dir>: keep the assembly there (<dir>/parent, <dir>/head) instead of a temporary directory
@@ -27,7 +29,7 @@ asm() {  # <tree> <name.hip> <out.s>
     [ -f "$1/geoformer_amd/csrc/$2" ] || return 1
     "$hipcc" --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-gpu-rdc -Wno-unused-result \
         "-I$1/include" "-I$1/geoformer_amd/csrc" --cuda-device-only -S "$1/geoformer_amd/csrc/$2" -o "$3.raw" 2> "$3.err" || return 1
-    grep -v __hip_cuid_ "$3.raw" > "$3"; rm -f "$3.raw"
+    grep -v -e __hip_cuid_ -e '^[[:space:]]*;' "$3.raw" > "$3"; rm -f "$3.raw"
 }
 export -f asm; export hipcc
 for n in $names; do
