@@ -258,7 +258,9 @@ __global__ CONV_WPE_ATTR __launch_bounds__(SW > 8 ? 1024 : 256, (SW <= 8 && NCBW
         __builtin_amdgcn_wave_barrier();
         const int nsteps = __popc(mask) * NCH;
         const int sstride = SPLIT ? NSW : 1;
-        const unsigned inv_nch = (65536u + (unsigned)NCH - 1u) / (unsigned)NCH;  // s / NCH for s < 4096, NCH <= 16
+        // s / NCH, exact for s < K * NCH with K <= 32 while NCH <= 50 (first miss: NCH = 51, s = 1325); conv_fwd_impl
+        // admits Cin <= CONV_MAX_CIN, NCH <= 32
+        const unsigned inv_nch = (65536u + (unsigned)NCH - 1u) / (unsigned)NCH;
         for (int s0 = SPLIT ? w : 0; s0 < nsteps; s0 += PF * sstride) {
             float4 a[PF];
             float4 b[PF][NCBW];
@@ -428,7 +430,8 @@ __device__ __forceinline__ void conv_flat_item(const FlatOp& A, int item, float4
     const __amdgpu_buffer_rsrc_t rs_in2 = gf_buffer_rsrc(two ? A.in2 : in, (int)(two ? A.in2_bytes : A.in_bytes));
     const __amdgpu_buffer_rsrc_t rs_w = gf_buffer_rsrc(A.Wp, K * NCH * NCB * 1024);
     const unsigned rowbytes = (unsigned)(two ? A.Cin1 : Cin) * 4u, rowbytes2 = (unsigned)(Cin - (two ? A.Cin1 : 0)) * 4u;
-    const unsigned inv_nch = (65536u + (unsigned)NCH - 1u) / (unsigned)NCH;  // s / NCH for s < 4096, NCH <= 16
+    // s / NCH, exact for s < K * NCH with K <= 32 while NCH <= 50 (as in k_conv_os; here NCH <= 16: conv_plan)
+    const unsigned inv_nch = (65536u + (unsigned)NCH - 1u) / (unsigned)NCH;
 
     // ---- everything whose address is known now ----
     float av_s = 0.f, av_t = 0.f;
@@ -1294,6 +1297,8 @@ static int conv_fwd_impl(const float* in, const float* Wp, const int32_t* nbr, c
                          float* out2, void* stream, int* desc = nullptr) {
     GF_CHECK_ARG(K >= 1 && K <= 32, "gf_conv_fwd: K=%d out of range [1,32]", K);
     GF_CHECK_ARG(Cin >= 1 && Cout >= 1, "gf_conv_fwd: Cin=%d Cout=%d", Cin, Cout);
+    // (NCH <= 32: what keeps the kernels' reciprocal step -> offset division exact, k_conv_os / conv_flat_item)
+    GF_CHECK_ARG(Cin <= CONV_MAX_CIN, "gf_conv_fwd: Cin=%d (at most %d)", Cin, CONV_MAX_CIN);
     GF_CHECK_ARG(sc == nullptr || Cin <= CONV_MAX_CIN - 16, "gf_conv_fwd: fused prologue supports Cin <= %d", CONV_MAX_CIN - 16);
     GF_CHECK_ARG(nbr != nullptr || steps != nullptr || K == 1, "gf_conv_fwd: no table requires K==1");
     GF_CHECK_ARG((sc == nullptr) == (sh == nullptr), "gf_conv_fwd: in_scale/in_shift must come together");

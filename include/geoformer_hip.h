@@ -173,6 +173,7 @@ int gf_rules_flat_steps(const int32_t* nbr, const uint32_t* gmask, int K, int M,
 /* Forward gather-GEMM (output-stationary): out[o,:] = sum_k act(in[nbr[k][o],:]) @ W[k] (+ residual[o,:])
  *   in fp32 [M_in,Cin]   Wp = packed W (gf_conv_pack_weights)   out fp32 [M_out,Cout]
  *   (M_in bounds the buffer descriptor the gathers go through)
+ *   1 <= K <= 32, Cin <= 512 (496 with in_scale / in_shift): wider inputs are rejected
  *   nbr may be NULL with K == 1 (identity map: plain GEMM, the k=1 "i_branch" conv)
  *   in_scale/in_shift  optional fp32 [Cin]: act(x) = max(x*scale + shift, 0) fused on the
  *                      gathered rows (eval-mode BatchNorm1d + ReLU, geoformer_modules.py:19-26)

@@ -132,7 +132,7 @@ class Table:
 
     def __init__(self, name, nbins, M_in, M_out, nbr, sizes):
         self.name, self.nbins, self.M_in, self.M_out = name, nbins, M_in, M_out
-        self.nbr, self.ld = nbr, nbr.shape[1]
+        self.nbr, self.ld, self.K = nbr, nbr.shape[1], nbr.shape[0]  # (K offsets: 27 here, 8 / 1 in conv_fwd_cases.py)
         self.ngroups = (M_out + 15) // 16
         self.gmask = np.zeros(self.ld // 16, np.uint32)
         self.gmask[: self.ngroups] = group_masks(nbr, M_out)
@@ -143,12 +143,19 @@ class Table:
         return wave_streams(self.sizes, self.nbins)
 
 
-def build_table(name, nbins, sizes, M_out=None, M_in=None, absent=0.3, shuffle=True):
-    """A [27, ld] table whose group g has sizes[g] present offsets (in table order after an optional shuffle of
+def build_table(name, nbins, sizes, M_out=None, M_in=None, absent=0.3, shuffle=True, K=K):
+    """A [K, ld] table whose group g has sizes[g] present offsets (in table order after an optional shuffle of
     `sizes`, so that the builder's sort has work to do).  A present offset's rows are random in [0, M_in) or, with
     probability `absent`, -1 -- but at least one of the group's rows below M_out has a neighbour (else the offset would
-    not be present)."""
+    not be present).  An entry of `sizes` may also be a tuple: exactly THESE offsets are the group's present ones."""
     rng = np.random.default_rng(seed_of("table", name))
+    given = {}
+    if any(isinstance(n, tuple) for n in sizes):  # prescribed offsets travel with their group through the shuffle
+        spec = list(sizes)
+        if shuffle:
+            spec = [spec[i] for i in rng.permutation(len(spec) - 1)] + [spec[-1]]
+        given = {g: sorted(n) for g, n in enumerate(spec) if isinstance(n, tuple)}
+        sizes, shuffle = [len(n) if isinstance(n, tuple) else n for n in spec], False
     sizes = np.array(sizes, np.int64)
     if shuffle:
         last = sizes[-1]  # (the last group may be partial: it keeps its place)
@@ -163,7 +170,7 @@ def build_table(name, nbins, sizes, M_out=None, M_in=None, absent=0.3, shuffle=T
     nbr = np.full((K, ld), -1, np.int32)
     for g in range(ng):
         valid = min(16, M_out - 16 * g)
-        for k in rng.choice(K, int(sizes[g]), replace=False):
+        for k in (given[g] if g in given else rng.choice(K, int(sizes[g]), replace=False)):
             rows = rng.integers(0, M_in, valid).astype(np.int32)
             gone = rng.random(valid) < absent
             gone[rng.integers(0, valid)] = False
@@ -262,10 +269,10 @@ def case_id(case):
 # operands and the reference
 # ---------------------------------------------------------------------------------------------------------------
 def operands(tbl, form, leg):
-    """x [M_in, Cin], W [27, Cin, Cout], in_scale / in_shift [Cin], residual [M_out, Cout], out_scale / out_shift
-    [Cout] as float32 (all of them, whether the form uses them or not)."""
+    """x [M_in, Cin], W [K, Cin, Cout] (K = the table's offsets), in_scale / in_shift [Cin], residual [M_out, Cout],
+    out_scale / out_shift [Cout] as float32 (all of them, whether the form uses them or not)."""
     rng = np.random.default_rng(seed_of("operands", tbl.name, form.key(), leg))
-    Cin, Cout = form.Cin, form.Cout
+    Cin, Cout, K = form.Cin, form.Cout, tbl.K
     if leg == "int":
         x = rng.integers(-X_LIM, X_LIM + 1, (tbl.M_in, Cin))
         W = rng.integers(-W_LIM, W_LIM + 1, (K, Cin, Cout))
@@ -281,7 +288,7 @@ def operands(tbl, form, leg):
     return tuple(np.ascontiguousarray(a, np.float32) for a in (x, W, sc, sh, res, osc, osh))
 
 
-def int_bound(form):
+def int_bound(form, K=K):
     """Largest magnitude any partial sum, sum (+ residual) or epilogue value of the integer leg can reach."""
     a = max(SC_VALUES) * X_LIM + SH_LIM if form.aff else X_LIM
     s = K * form.Cin * a * W_LIM + (RES_LIM if form.res != "none" else 0)

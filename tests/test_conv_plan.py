@@ -45,6 +45,8 @@ def head_plan(q, kn):
         return INVALID, None
     if not (1 <= K <= 32) or Cin < 1 or Cout < 1 or (sc and Cin > 512 - 16):
         return INVALID, None
+    if Cin > 512:  # CONV_MAX_CIN, with or without a prologue: what keeps the kernels' reciprocal step division exact
+        return INVALID, None
     if not (q["nbr"] or q["steps"] or K == 1):
         return INVALID, None
     if osc and not al["osc"]:
@@ -235,6 +237,10 @@ def test_plan_reaches_every_shape(lib):  # noqa: F811
              ({"bins": 4, "lw": 1}, q(768, 32, 32), LW), ({"bins": 4, "lw": 1}, q(769, 32, 32), OS),
              ({"bins": 64}, q(12_288, 32, 32), LW), ({"bins": 64}, q(12_289, 32, 32), OS),
              ({"bins": 64, "lw": 1}, q(12_288, 112, 16, sc=True), LW), ({"bins": 64, "lw": 1}, q(12_289, 112, 16, sc=True), PAIR),
+             # the widest input: 512 channels, 496 with a prologue
+             ({}, q(100, 512, 32, flat=False), OS), ({}, q(100, 513, 32, flat=False), "error"),
+             ({}, q(100, 816, 32, flat=False), "error"), ({}, q(10_000, 528, 16, flat=False), "error"),
+             ({}, q(100, 496, 32, flat=False, sc=True), OS), ({}, q(100, 512, 32, flat=False, sc=True), "error"),
              ({}, q(10_000, 16, 16, steps=False, out2=True, osc=True, flat=False), "error"),
              ({}, q(10_000, 64, 64, nbr=False, steps=False, flat=False), "error")]
     desc = (ctypes.c_int * 10)()

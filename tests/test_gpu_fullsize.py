@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import conv_fwd_cases as FC
 from tests.util import random_voxels
 
 pytestmark = pytest.mark.gpu
@@ -220,19 +221,24 @@ def test_every_launch_shape_forced(hip, oracle, Cin, Cout):
     finally:
         sparse.STEPS_MIN_ROWS = old_min
     # the step table against the neighbour table it restates: present offsets in ascending order, four per entry
+    # (the shared numpy builder of tests/conv_fwd_cases.py: every block the device builder writes, in every group)
     st = rules.steps.cpu().numpy()
     ng = rules.ld // 16
     blocks = st[: ng * 7 * 64].reshape(ng, 7, 16, 4)
+    want = FC.write_step_blocks(st.copy(), nbr, M, rules.ld)[: ng * 7 * 64].reshape(ng, 7, 16, 4)
+    assert (blocks == want).all()
     for g in rng.integers(0, ng, 40):
         ks = [k for k in range(27) if (nbr[k, g * 16:(g + 1) * 16] >= 0).any()]
         for s_, k in enumerate(ks):
-            assert (blocks[g, s_ // 4, :, s_ % 4] == nbr[k, g * 16:(g + 1) * 16]).all()
+            assert (want[g, s_ // 4, :, s_ % 4] == nbr[k, g * 16:(g + 1) * 16]).all()
         for s_ in range(len(ks), max(12, (len(ks) + 3) // 4 * 4)):
-            assert (blocks[g, s_ // 4, :, s_ % 4] == -1).all()
+            assert (want[g, s_ // 4, :, s_ % 4] == -1).all()
     tail = st[ng * 7 * 64:]
     nchunks = int(tail[0])
     bounds = tail[1: nchunks + 2]
     assert bounds[0] == 0 and bounds[-1] == (M + 15) // 16 and (np.diff(bounds) >= 0).all()
+    sizes = [sum(bool((nbr[k, g * 16:(g + 1) * 16] >= 0).any()) for k in range(27)) for g in range((M + 15) // 16)]
+    assert bounds.tolist() == FC.group_chunks(sizes, nchunks)
     x, w, s, t, r = _dev(feats), _dev(W), _dev(scale), _dev(shift), _dev(res)
     try:
         for knobs in KNOBS:
