@@ -101,7 +101,9 @@ extern "C" int gf_proposal_stats_batched(const long long* table, int S, int nq, 
 extern "C" int gf_proposal_select_batched(const int32_t* final_, const int32_t* cls_pred, const float* scores, int S,
                                           int nq, int32_t* sel, long long* cls_out, float* scores_out, int32_t* counts,
                                           void* stream) {
-    GF_CHECK_ARG(final_ && cls_pred && scores && sel && cls_out && scores_out && counts && S >= 0 && nq >= 0,
+    // nq == 0: empty arrays have no address; the launch only writes counts[b] = 0
+    GF_CHECK_ARG(counts && S >= 0 && nq >= 0 &&
+                     (nq == 0 || (final_ && cls_pred && scores && sel && cls_out && scores_out)),
                  "gf_proposal_select_batched: bad arguments");
     if (S == 0) return GF_OK;
     hipLaunchKernelGGL(k_bp_select, dim3(S), dim3(1024), 0, (hipStream_t)stream, final_, cls_pred, scores, nq, sel,

@@ -262,7 +262,8 @@ __global__ __launch_bounds__(1024) void k_proposal_select(const int32_t* __restr
 
 extern "C" int gf_proposal_select(const int32_t* final_, const int32_t* cls_pred, const float* scores, int nq,
                                   int32_t* sel, long long* cls_out, float* scores_out, int32_t* d_count, void* stream) {
-    GF_CHECK_ARG(final_ && cls_pred && scores && sel && cls_out && scores_out && d_count && nq >= 0,
+    // nq == 0: empty arrays have no address; the launch only writes *d_count = 0
+    GF_CHECK_ARG(d_count && nq >= 0 && (nq == 0 || (final_ && cls_pred && scores && sel && cls_out && scores_out)),
                  "gf_proposal_select: bad arguments");
     hipLaunchKernelGGL(k_proposal_select, dim3(1), dim3(1024), 0, (hipStream_t)stream, final_, cls_pred, scores, nq, sel,
                        cls_out, scores_out, d_count);

@@ -720,7 +720,8 @@ int gf_relpos_prepare(const float* geo, const int32_t* inds, int nq, int n, int 
                       void* stream);
 
 /* The accepted queries of gf_proposal_stats in ascending order with their classes / scores (geoformer.py:236-243),
- * compacted on the device: sel int32 [nq], cls_out int64 [nq], scores_out fp32 [nq] (capacity nq), *d_count = how many. */
+ * compacted on the device: sel int32 [nq], cls_out int64 [nq], scores_out fp32 [nq] (capacity nq), *d_count = how many.
+ * nq == 0: the arrays may be NULL, *d_count = 0. */
 int gf_proposal_select(const int32_t* final_, const int32_t* cls_pred, const float* scores, int nq, int32_t* sel,
                        long long* cls_out, float* scores_out, int32_t* d_count, void* stream);
 
@@ -747,7 +748,7 @@ int gf_proposal_stats_batched(const long long* table, int S, int nq, const float
                               long long sem_stride, int ncls, float logit_thresh, float score_thresh, int npoint_thresh,
                               int min_class, int* cls_pred, int* npoints, float* scores, int* final_mask, void* stream);
 /* gf_proposal_select per scene: row b of sel / cls_out / scores_out ([S, nq]) holds scene b's accepted queries in
- * ascending order, counts int32 [S] how many. */
+ * ascending order, counts int32 [S] how many.  nq == 0: the arrays may be NULL, every count is 0. */
 int gf_proposal_select_batched(const int32_t* final_, const int32_t* cls_pred, const float* scores, int S, int nq,
                                int32_t* sel, long long* cls_out, float* scores_out, int32_t* counts, void* stream);
 /* gf_proposal_scatter of every scene into ONE zero-filled int32 buffer: scene b's block [counts[b], num_points_b]

@@ -706,12 +706,14 @@ ORC_API void orc_proposal_stats(const float *mask_logits, const float *cls_logit
         float den = 0.f;
         for (int32_t k = 0; k < ncls; k++) den += expf(c[k] - mx);
         float cls_score = 1.0f / den;
-        int32_t n = 0; float sp = 0.f, ss = 0.f;
+        /* the two sums in double: a serial fp32 sum of N terms is off by up to N * 2^-24 relative (5e-5 on a constant
+         * row of 8193 points), far more than the kernels' tree sums */
+        int32_t n = 0; double sp = 0.0, ss = 0.0;
         for (int32_t p = 0; p < N; p++) {
             float pr = 1.0f / (1.0f + expf(-mask_logits[(size_t)q * N + p]));
             if (pr >= logit_thresh) { n++; sp += pr; ss += sem_prob[(size_t)p * ncls + arg]; }
         }
-        float d = (float)n + 1e-6f, mask_score = sp / d, sem_score = ss / d;
+        float d = (float)n + 1e-6f, mask_score = (float)(sp / d), sem_score = (float)(ss / d);
         cls_pred[q] = arg; npoints[q] = n;
         scores[q] = mask_score * sqrtf(cls_score) * sem_score;
         final_mask[q] = (arg >= min_class) && (n >= npoint_thresh) && (mask_score >= score_thresh);
@@ -723,12 +725,12 @@ ORC_API void orc_proposal_stats_fs(const float *mask_logits, const float *sim, i
                                    float score_thresh, int32_t npoint_thresh, float sim_thresh, int32_t *npoints,
                                    float *scores, int32_t *final_mask) {
     for (int32_t q = 0; q < nq; q++) {
-        int32_t n = 0; float sp = 0.f;
+        int32_t n = 0; double sp = 0.0;  /* in double, as in orc_proposal_stats */
         for (int32_t p = 0; p < N; p++) {
             float pr = 1.0f / (1.0f + expf(-mask_logits[(size_t)q * N + p]));
             if (pr >= logit_thresh) { n++; sp += pr; }
         }
-        float mask_score = sp / ((float)n + 1e-6f);
+        float mask_score = (float)(sp / ((float)n + 1e-6f));
         npoints[q] = n;
         scores[q] = mask_score * sqrtf(sim[q]);
         final_mask[q] = (sim[q] >= sim_thresh) && (n >= npoint_thresh) && (mask_score >= score_thresh);
