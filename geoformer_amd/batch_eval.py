@@ -8,6 +8,8 @@
     ap, avgs = evaluate(model, [(name, raw), ...], batch_size=4, semantic=ev)    # AP and mIoU from one pass
     res = evaluate_semantic(model, [(name, raw), ...], batch_size=4)             # backbone + semantic head only
     print(evaluation.format_semantic_results(res))
+    res = evaluate_boxes(model, [(name, raw), ...], batch_size=4, kind="oriented")   # box mAP@0.25 / mAP@0.5
+    print(evaluation.format_box_results(res))
     for name, labels in label_batches(model, [(name, raw), ...], batch_size=4):
         ...                                   # labels.ids / .owner [N], labels.table: one row per instance (host)
     for name, labels, pan in panoptic_batches(model, [(name, raw), ...], batch_size=4):
@@ -669,10 +671,11 @@ def evaluate_panoptic(model, scenes_with_gt, batch_size, classes=0, **kw):
 
 
 @torch.no_grad()
-def evaluate(model, scenes_with_gt, batch_size, classes=0, *, cvfold=None, **kw):
+def evaluate(model, scenes_with_gt, batch_size, classes=0, *, cvfold=None, boxes=None, **kw):
     """ScanNet AP / AP50 / AP25 of the model over (name, raw [N, 8]) scenes whose labels are the ground truth
     (evaluation.gt_ids_from_labels): (ap [C, n_overlaps], averages), as evaluation.InstanceEvaluator.evaluate.
-    Keywords go to predict_batches."""
+    boxes: an evaluation.BoxEvaluator that is given every scene of the same pass with the scene's own xyz (box AP from
+    the pass that gives AP); None: nothing is added to the loop.  Other keywords go to predict_batches."""
     cvfold = model.cfg.cvfold if cvfold is None else cvfold
     items = list(scenes_with_gt)
     raws = dict(items)
@@ -683,7 +686,36 @@ def evaluate(model, scenes_with_gt, batch_size, classes=0, *, cvfold=None, **kw)
             continue  # test.py: a scene without proposals is skipped
         r = torch.as_tensor(np.asarray(raws[name]), device=dev)
         gt = evaluation.gt_ids_from_labels(r[:, 6].long(), r[:, 7].long())
-        ev.add_scene(name, gt, evaluation.benchmark_label_ids(cls, cvfold), sc, masks, pick)
+        labels = evaluation.benchmark_label_ids(cls, cvfold)
+        ev.add_scene(name, gt, labels, sc, masks, pick)
+        if boxes is not None:
+            boxes.add_scene(name, gt, labels, sc, masks, pick, r[:, :3].to(torch.float32).contiguous())
+    return ev.evaluate()
+
+
+@torch.no_grad()
+def evaluate_boxes(model, scenes_with_gt, batch_size, classes=0, kind="aligned", *, cvfold=None, evaluator=None, **kw):
+    """Box AP (detection mAP@0.25 / mAP@0.5 over the 3D boxes of the picked masks) of the model over (name, raw [N, 8])
+    scenes whose columns 6 / 7 are the ground truth: evaluation.BoxEvaluator.evaluate's dict.  kind: "aligned" or
+    "oriented"; evaluator: a BoxEvaluator of the caller's (classes and kind are then its own); overlaps, angles and
+    min_points go to the BoxEvaluator, other keywords to predict_batches.  Per scene: the two native calls of
+    BoxEvaluator.add_scene on the forward's device and one small copy.  A scene without proposals is left out, as in
+    evaluate.  A tiled or subsampled scan (tiles=, density=) comes out of predict_batches over its own points and is
+    boxed on the raw scan's xyz."""
+    cvfold = model.cfg.cvfold if cvfold is None else cvfold
+    ev = evaluator
+    if ev is None:
+        ev = evaluation.BoxEvaluator(classes, kind, **{k: kw.pop(k) for k in ("overlaps", "angles", "min_points") if k in kw})
+    items = list(scenes_with_gt)
+    raws = dict(items)
+    dev = next(model.parameters()).device
+    for name, cls, sc, masks, pick in predict_batches(model, items, batch_size, cvfold=cvfold, **kw):
+        if not torch.is_tensor(cls):
+            continue
+        r = torch.as_tensor(np.asarray(raws[name]), device=dev)
+        gt = evaluation.gt_ids_from_labels(r[:, 6].long(), r[:, 7].long())
+        ev.add_scene(name, gt, evaluation.benchmark_label_ids(cls, cvfold), sc, masks, pick,
+                     r[:, :3].to(torch.float32).contiguous())
     return ev.evaluate()
 
 

@@ -11,6 +11,9 @@ dataset-level matching and AP integration run on the host once per evaluation.
     ev = InstanceEvaluator(classes=0)                 # cvfold 0 / 1, or "all" (the 18 benchmark classes)
     ev.add_scene(name, gt_ids, label_ids, scores, masks, pick)
     ap, avgs = ev.evaluate(); print(ev.format_results(avgs))
+    bx = BoxEvaluator(classes=0, kind="oriented")     # box AP: detection mAP@0.25 / mAP@0.5 over the instances' 3D boxes
+    bx.add_scene(name, gt_ids, label_ids, scores, masks, pick, xyz)
+    print(bx.format_results())
 """
 from __future__ import annotations
 
@@ -1005,3 +1008,188 @@ class PanopticEvaluator:
 
     def format_results(self, res=None):
         return format_panoptic_results(self.evaluate() if res is None else res)
+
+
+# ---- box AP: detection mAP over the instances' 3D boxes (csrc/boxes.hip) ------------------------------------------------
+BOX_KINDS = ("aligned", "oriented")
+BOX_OVERLAPS = (0.25, 0.5)
+
+
+class _BoxScene:
+    """What a scene leaves behind for the box AP: its instances (ids ascending, point counts) and its predictions in
+    pick order (nyu40 label, confidence, point count, IoU with every instance's box)."""
+
+    __slots__ = ("name", "gt_id", "gt_count", "label", "conf", "count", "iou")
+
+    def __init__(self, name, gt_id, gt_count, label, conf, count, iou):
+        self.name = name
+        self.gt_id = np.asarray(gt_id, dtype=np.int64)
+        self.gt_count = np.asarray(gt_count, dtype=np.int64)
+        self.label = np.asarray(label, dtype=np.int64)
+        self.conf = np.asarray(conf, dtype=np.float64)
+        self.count = np.asarray(count, dtype=np.int64)
+        self.iou = np.asarray(iou, dtype=np.float64).reshape(self.label.shape[0], self.gt_id.shape[0])
+
+    def tables(self):
+        return {k: getattr(self, k) for k in self.__slots__}
+
+
+def _box_ap(scenes, cid, threshold, min_points):
+    """(AP, recall) of class cid at one IoU threshold over the scenes, or (nan, nan) without an instance of the class.
+    Predictions in descending score order (stable: ties keep scene order, then pick rank); a prediction is a true
+    positive when its highest IoU among its own scene's boxes of the class (the lowest index among equals) is above the
+    threshold and that box is unclaimed; AP is the area under the monotone precision envelope (VOC 2010, all points)."""
+    conf, where, cand, n_gt = [], [], [], 0
+    for si, s in enumerate(scenes):
+        g = np.nonzero((s.gt_id // 1000 == cid) & (s.gt_count >= min_points))[0]
+        cand.append(g)
+        n_gt += g.shape[0]
+        for r in np.nonzero((s.label == cid) & (s.count >= min_points))[0]:
+            conf.append(s.conf[r])
+            where.append((si, r))
+    if n_gt == 0:
+        return float("nan"), float("nan")
+    order = np.argsort(-np.asarray(conf, dtype=np.float64), kind="stable")
+    claimed = [np.zeros(g.shape[0], dtype=bool) for g in cand]
+    tp = np.zeros(order.shape[0])
+    for k, j in enumerate(order):
+        si, r = where[j]
+        if cand[si].shape[0] == 0:
+            continue
+        row = scenes[si].iou[r, cand[si]]
+        b = int(np.argmax(row))  # the first of the highest
+        if row[b] > threshold and not claimed[si][b]:
+            claimed[si][b] = True
+            tp[k] = 1.0
+    ctp = np.cumsum(tp)
+    rec = ctp / n_gt
+    prec = ctp / np.arange(1, order.shape[0] + 1)
+    mrec = np.concatenate([[0.0], rec, [1.0]])
+    mpre = np.maximum.accumulate(np.concatenate([[0.0], prec, [0.0]])[::-1])[::-1]
+    i = np.nonzero(mrec[1:] != mrec[:-1])[0]
+    return float(np.sum((mrec[i + 1] - mrec[i]) * mpre[i + 1])), float(rec[-1]) if rec.shape[0] else 0.0
+
+
+def format_box_results(res):
+    """BoxEvaluator.evaluate's dict as a printable table: per class AP and recall at every threshold, then the means."""
+    ov = [f"{t:g}" for t in res["overlaps"]]
+    head = "".join(f"{'AP@' + o:>12}{'AR@' + o:>12}" for o in ov)
+    w = 15 + 1 + 24 * len(ov)
+    lines = ["#" * w, f"{'box ' + res['kind']:<15}:{head}", "#" * w]
+    for name, c in res["classes"].items():
+        lines.append(f"{name:<15}:" + "".join(f"{c['ap@' + o]:>12.3f}{c['recall@' + o]:>12.3f}" for o in ov))
+    lines.append("-" * w)
+    lines.append(f"{'mean':<15}:" + "".join(f"{res['mAP@' + o]:>12.3f}{res['mAR@' + o]:>12.3f}" for o in ov))
+    return "\n".join(lines)
+
+
+class BoxEvaluator:
+    """Box AP of instance predictions over a set of scenes: detection mAP over the 3D boxes of the predicted masks
+    against the boxes of the ground-truth instances (the ScanNet detection protocol of VoteNet: mAP@0.25 / mAP@0.5).
+
+    classes: as InstanceEvaluator.  kind: "aligned" (axis-aligned boxes) or "oriented" (upright boxes of least footprint
+    among `angles` headings, postprocess.instance_boxes).  overlaps: the IoU thresholds.  min_points: predictions and
+    instances with fewer points are dropped.  The protocol is _box_ap's."""
+
+    def __init__(self, classes=0, kind="aligned", overlaps=BOX_OVERLAPS, angles=90, min_points=1):
+        from . import postprocess
+
+        if kind not in BOX_KINDS:
+            raise ValueError(f"BoxEvaluator: kind must be one of {BOX_KINDS}, got {kind!r}")
+        postprocess.box_angle_table(angles)  # (checks the range)
+        self.class_ids, self.class_names = class_set(classes)
+        self.kind = kind
+        self.overlaps = tuple(float(o) for o in overlaps)
+        self.angles = int(angles) if kind == "oriented" else 1
+        self.min_points = int(min_points)
+        self.scenes = []
+        self._dev_classes = {}
+
+    def add_scene(self, name, gt_ids, label_ids, scores, masks, pick, xyz):
+        """One scene's predictions: masks [n_rows, N] (nonzero = member; [] without proposals), label_ids [n_rows] nyu40
+        ids, scores [n_rows], pick: the rows to evaluate, in order (None: all rows), gt_ids [N] val_gt ids
+        (gt_ids_from_labels), xyz [N, 3].  The ground-truth boxes are those of the ids >= 1000 whose class is in the
+        class set, in ascending id order.  Device tensors (xyz on the GPU): one gf_instance_boxes_batched call for both
+        sets of boxes, one gf_box_iou_batched call and one device-to-host copy of the IoU block with the counts; host
+        arrays: the numpy statements, with the same tables."""
+        if any(s.name == name for s in self.scenes):
+            raise ValueError(f"scene {name!r} was added already")
+        if _is_tensor(xyz) and xyz.is_cuda:
+            self.scenes.append(_BoxScene(name, *self._tables_device(gt_ids, label_ids, scores, masks, pick, xyz)))
+        else:
+            self.scenes.append(_BoxScene(name, *self._tables_host(gt_ids, label_ids, scores, masks, pick, xyz)))
+
+    def _tables_host(self, gt_ids, label_ids, scores, masks, pick, xyz):
+        from . import postprocess
+
+        h = postprocess._np
+        gt = np.asarray(h(gt_ids), dtype=np.int64).reshape(-1)
+        valid = (gt >= 1000) & np.isin(gt // 1000, self.class_ids)
+        gt_id, slot = np.unique(gt[valid], return_inverse=True)
+        group = np.full(gt.shape[0], -1, np.int32)
+        group[valid] = slot
+        n = len(masks)
+        pick = np.arange(n) if pick is None else np.asarray(h(pick), dtype=np.int64).reshape(-1)
+        k = 2 if self.kind == "oriented" else 1
+        pred = postprocess.instance_boxes_host(masks if n else [], pick, xyz, self.angles)
+        inst = postprocess.id_boxes_host(group, gt_id.shape[0], xyz, self.angles)
+        labels = np.asarray(h(label_ids), dtype=np.int64).reshape(-1)[pick]
+        conf = np.asarray(h(scores), dtype=np.float64).reshape(-1)[pick]
+        return gt_id, inst[0], labels, conf, pred[0], postprocess.box_iou_host(pred[k], inst[k])
+
+    def _tables_device(self, gt_ids, label_ids, scores, masks, pick, xyz):
+        import torch
+
+        from . import postprocess
+
+        dev = xyz.device
+        cls = self._dev_classes.get(dev)
+        if cls is None:
+            cls = self._dev_classes[dev] = torch.tensor(self.class_ids, dtype=torch.int64, device=dev)
+        gt = torch.as_tensor(gt_ids, device=dev).to(torch.int64).reshape(-1)
+        valid = (gt >= 1000) & torch.isin(torch.div(gt, 1000, rounding_mode="floor"), cls)
+        gt_id, slot = torch.unique(gt[valid], return_inverse=True)  # (ascending; its size is read back)
+        group = torch.full((gt.shape[0],), -1, dtype=torch.int32, device=dev)
+        group[valid] = slot.to(torch.int32)
+        G = int(gt_id.shape[0])
+        n = len(masks)
+        pick = torch.arange(n, device=dev) if pick is None else torch.as_tensor(pick, device=dev).to(torch.int64).reshape(-1)
+        P = int(pick.shape[0])
+        _, count, aligned, oriented = postprocess._boxes_packed([("rows", masks if n else [], pick, xyz),
+                                                                 ("ids", group, G, xyz)], self.angles)
+        rows = oriented if self.kind == "oriented" else aligned
+        iou = postprocess.box_iou_batched([rows[:P]], [rows[P:P + G]])[0]
+        f64 = lambda t: torch.as_tensor(t, device=dev).to(torch.float64).reshape(-1)  # noqa: E731
+        labels = f64(label_ids)[pick] if P else f64([])
+        conf = f64(scores)[pick] if P else f64([])
+        # the IoU block, the counts and what else the host keeps of the scene cross in one copy
+        h = torch.cat([iou.reshape(-1), count.to(torch.float64), gt_id.to(torch.float64), labels, conf]).cpu().numpy()
+        cut = np.cumsum([0, P * G, P, G, G, P, P])
+        part = [h[cut[i]:cut[i + 1]] for i in range(6)]
+        return part[3], part[2], part[4], part[5], part[1], part[0]
+
+    def scene_tables(self):
+        """Per scene, in the order added, the kept tables as a dict of numpy arrays (and the name)."""
+        return [s.tables() for s in self.scenes]
+
+    def evaluate(self):
+        """{"kind", "overlaps", "ap" [C, T], "recall" [C, T], "mAP@t" / "mAR@t" per threshold t (means over the classes
+        that have ground truth; nan without any), "classes": {name: {"ap@t", "recall@t"}}}; a class without ground
+        truth is nan and left out of the means."""
+        C, T = len(self.class_ids), len(self.overlaps)
+        ap, rec = np.full((C, T), np.nan), np.full((C, T), np.nan)
+        for ci, cid in enumerate(self.class_ids):
+            for ti, t in enumerate(self.overlaps):
+                ap[ci, ti], rec[ci, ti] = _box_ap(self.scenes, int(cid), t, self.min_points)
+        res = {"kind": self.kind, "overlaps": self.overlaps, "ap": ap, "recall": rec, "classes": {}}
+        has = ~np.isnan(ap[:, 0]) if T else np.zeros(C, dtype=bool)
+        for ti, t in enumerate(self.overlaps):
+            res[f"mAP@{t:g}"] = float(ap[has, ti].mean()) if has.any() else float("nan")
+            res[f"mAR@{t:g}"] = float(rec[has, ti].mean()) if has.any() else float("nan")
+        for ci, name in enumerate(self.class_names):
+            res["classes"][name] = {f"{k}@{t:g}": float(v[ci, ti]) for ti, t in enumerate(self.overlaps)
+                                    for k, v in (("ap", ap), ("recall", rec))}
+        return res
+
+    def format_results(self, res=None):
+        return format_box_results(self.evaluate() if res is None else res)

@@ -264,3 +264,28 @@ def save_scannet_segments(path, ids):
         raise ValueError(f"save_scannet_segments: expected an integer array [N], got {seg.dtype} {seg.shape}")
     with open(path, "w") as f:
         json.dump({"segIndices": [int(v) for v in seg]}, f)
+
+
+BOX_FORMAT = "%.9g"  # float32 extents and their float64 means survive the text to well below a micrometre
+
+
+def write_boxes(path, boxes, label_ids, scores):
+    """One text line per box of a postprocess.Boxes: ``cx cy cz du dv dz yaw label_id score`` -- the centre, the sizes
+    along the box's own axes (du along (cos yaw, sin yaw), dv across it, dz along z), the heading in radians about z,
+    the label id and the score (SCORE_FORMAT).  label_ids, scores: one per box.  Returns the path."""
+    h = lambda a: _host_array(a)  # noqa: E731
+    center, size, yaw = (np.asarray(h(a), dtype=np.float64) for a in (boxes.center, boxes.size, boxes.yaw))
+    center, size, yaw = center.reshape(-1, 3), size.reshape(-1, 3), yaw.reshape(-1)
+    labels = np.asarray(h(label_ids), dtype=np.int64).reshape(-1)
+    scores = np.asarray(h(scores), dtype=np.float64).reshape(-1)
+    if not (labels.shape[0] == scores.shape[0] == yaw.shape[0] == center.shape[0] == size.shape[0]):
+        raise ValueError(f"write_boxes: {center.shape[0]} boxes, {labels.shape[0]} labels, {scores.shape[0]} scores")
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(path, "w") as f:
+        for c, s, y, l, sc in zip(center, size, yaw, labels, scores):
+            nums = " ".join(BOX_FORMAT % v for v in (*c, *s, y))
+            f.write(f"{nums} {int(l)} {SCORE_FORMAT % sc}\n")
+    return path
+

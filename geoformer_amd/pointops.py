@@ -2102,3 +2102,49 @@ def nearest_point(query, xyz, max_dist, check=True, return_flag=False):
             raise ValueError(f"nearest_point: the points span {int(NEAREST_MAX_CELLS)} cells of max_dist or more on an "
                              f"axis, beyond the range the search is proven complete for")
     return (idx, d2, flag) if return_flag else (idx, d2)
+
+
+# ---- 3D boxes of instances and the IoU of boxes (csrc/boxes.hip) ---------------------------------------------------------
+def box_limits():
+    """(points per workgroup chunk, most angles, most groups of a scene) of gf_instance_boxes_batched, from the library."""
+    from .postprocess import BOX_MAX_ANGLES, BOX_MAX_GROUPS
+
+    lib = _lib.load()
+    lim = lib.gf_box_chunk(), lib.gf_box_max_angles(), lib.gf_box_max_groups()
+    assert lim[1:] == (BOX_MAX_ANGLES, BOX_MAX_GROUPS), lim
+    return lim
+
+
+def instance_boxes_batched(table, sizes, angles):
+    """gf_instance_boxes_batched on a device box scene table (postprocess.box_scene_table): (count int32 [rows], aligned
+    float64 [rows, GF_BOX_FLOATS], oriented float64 [rows, GF_BOX_FLOATS]).  angles: fp32 [A, 2] (cos, sin) on the
+    device.  Two memsets and two launches on the current stream, nothing read back."""
+    from .postprocess import BOX_FLOATS
+
+    _f32c(angles, "angles")
+    dev = table.device
+    rows, A = int(sizes["rows"]), angles.shape[0]
+    lib = _lib.load()
+    count = torch.empty(max(rows, 1), dtype=torch.int32, device=dev)
+    out = torch.empty((2, max(rows, 1), BOX_FLOATS), dtype=torch.float64, device=dev)
+    ws = torch.empty(lib.gf_instance_boxes_scratch_bytes(rows, A) // 8 + 1, dtype=torch.int64, device=dev)
+    check(lib.gf_instance_boxes_batched(ptr(table), table.shape[0], int(sizes["max_points"]), int(sizes["max_groups"]),
+                                        rows, ptr(angles), A, ptr(ws), ptr(count), ptr(out[0]), ptr(out[1]),
+                                        stream_ptr()), "gf_instance_boxes_batched")
+    return count[:rows], out[0, :rows], out[1, :rows]
+
+
+def box_iou_batched(table, sizes, a, b):
+    """gf_box_iou_batched on a device IoU table (postprocess.box_iou_table): float64 [sizes["out"]], every scene's
+    [P, G] block at its offset.  a, b: packed boxes float64 [., GF_BOX_FLOATS] on the device.  One launch."""
+    from .postprocess import BOX_FLOATS
+
+    for t, name, rows in ((a, "a", sizes["a"]), (b, "b", sizes["b"])):
+        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == (rows, BOX_FLOATS)):
+            raise RuntimeError(f"box_iou_batched: {name}: expected a contiguous float64 tensor [{rows}, {BOX_FLOATS}] on "
+                               f"the GPU")
+    n = int(sizes["out"])
+    out = torch.empty(max(n, 1), dtype=torch.float64, device=table.device)
+    check(_lib.load().gf_box_iou_batched(ptr(table), table.shape[0], int(sizes["max_pairs"]), ptr(a), ptr(b), ptr(out),
+                                         stream_ptr()), "gf_box_iou_batched")
+    return out[:n]

@@ -1228,3 +1228,381 @@ def transfer(values, xyz_src, xyz_dst, max_dist, fill=0):
         raise ValueError(f"transfer: values: expected a tensor with one row per source point [{xyz_src.shape[0]}, ...]")
     idx, _ = pointops.nearest_point(xyz_dst, xyz_src, max_dist)
     return expand_rows(values, idx, fill), idx
+
+
+# ---- 3D boxes of instances and the IoU of boxes (csrc/boxes.hip) ---------------------------------------------------------
+BOX_SCENE_FIELDS = _abi.const("GF_BOX_SCENE_FIELDS")
+BOX_FLOATS = _abi.const("GF_BOX_FLOATS")
+BOX_IOU_FIELDS = _abi.const("GF_BOX_IOU_FIELDS")
+BOX_FORMS = {"rows": _abi.const("GF_BOX_FORM_ROWS"), "ids": _abi.const("GF_BOX_FORM_IDS")}
+BOX_MAX_ANGLES = 192    # gf_box_max_angles(): asserted against the library in pointops.box_limits()
+BOX_MAX_GROUPS = 65535  # gf_box_max_groups()
+BOX_ANGLES = 90         # headings over [0, 90 degrees): one per degree
+_BOX_HOST_SLICE = 1 << 15  # members of a group taken at a time by the statement (bounds its [m, A] temporaries)
+
+
+class Boxes(NamedTuple):
+    """One upright box per group (numpy arrays, or tensors on the inputs' device).  size[:, 0] lies along (cos, sin),
+    size[:, 1] along (-sin, cos), size[:, 2] along z; an empty group is all zeros."""
+    center: object  # float64 [p, 3]
+    size: object  # float64 [p, 3]
+    cos: object  # float64 [p]: the fp32 table entry, widened
+    sin: object  # float64 [p]
+    yaw: object  # float64 [p]: radians about z, angle_index * (pi / 2) / angles
+    angle_index: object  # int32 [p]
+    count: object  # int32 [p]: points of the group
+    rows: object = None  # float64 [p, BOX_FLOATS]: the packed rows as the kernels write and read them
+
+
+def box_angle_table(angles=BOX_ANGLES):
+    """fp32 [A, 2] = (cos, sin) of A equal steps over [0, 90 degrees), computed in float64 and rounded once."""
+    A = int(angles)
+    if not 1 <= A <= BOX_MAX_ANGLES or A != angles:
+        raise ValueError(f"boxes: angles must be an integer in [1, {BOX_MAX_ANGLES}], got {angles!r}")
+    th = np.arange(A, dtype=np.float64) * (np.pi / 2 / A)
+    return np.stack([np.cos(th), np.sin(th)], axis=1).astype(np.float32)
+
+
+def _boxes_from_rows(rows, count, A):
+    idx = rows[:, 8]
+    i32 = idx.to(torch.int32) if torch.is_tensor(idx) else idx.astype(np.int32)
+    return Boxes(rows[:, 0:3], rows[:, 3:6], rows[:, 6], rows[:, 7], idx * (np.pi / 2 / A), i32, count, rows)
+
+
+def _box_rows_of(b):
+    """float64 [p, BOX_FLOATS] of a Boxes (or of packed rows given as they are)."""
+    if not isinstance(b, Boxes):
+        return b
+    if b.rows is not None:
+        return b.rows
+    if torch.is_tensor(b.center):
+        col = lambda v: v.to(torch.float64).reshape(-1, 1)  # noqa: E731
+        return torch.cat([b.center.to(torch.float64), b.size.to(torch.float64), col(b.cos), col(b.sin),
+                          col(b.angle_index), col(b.count)], dim=1).contiguous()
+    col = lambda v: np.asarray(v, dtype=np.float64).reshape(-1, 1)  # noqa: E731
+    return np.concatenate([np.asarray(b.center, np.float64).reshape(-1, 3), np.asarray(b.size, np.float64).reshape(-1, 3),
+                           col(b.cos), col(b.sin), col(b.angle_index), col(b.count)], axis=1)
+
+
+def _float_keys(a):
+    """fp32 -> uint32 whose integer order is the float order (gf_float_key: -0 below +0)."""
+    u = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+    return np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def _float_unkeys(k):
+    k = np.asarray(k, dtype=np.uint32)
+    return np.where(k & np.uint32(0x80000000), k & np.uint32(0x7FFFFFFF), ~k).astype(np.uint32).view(np.float32)
+
+
+def _box_row(ulo, uhi, vlo, vhi, zlo, zhi, c, s, index, count):
+    d = np.float64
+    ulo, uhi, vlo, vhi, zlo, zhi, c, s = (d(v) for v in (ulo, uhi, vlo, vhi, zlo, zhi, c, s))
+    lu, lv = (ulo + uhi) * d(0.5), (vlo + vhi) * d(0.5)
+    return [lu * c - lv * s, lu * s + lv * c, (zlo + zhi) * d(0.5), uhi - ulo, vhi - vlo, zhi - zlo, c, s, d(index),
+            d(count)]
+
+
+def _box_rows_host(members, xyz, table):
+    """(count int32 [p], aligned float64 [p, 10], oriented float64 [p, 10]) of the groups whose member indices are given:
+    the statement of gf_instance_boxes_batched.  numpy rounds every ufunc on its own, in the kernel's order."""
+    p, A = len(members), table.shape[0]
+    c, s = np.ascontiguousarray(table[:, 0]), np.ascontiguousarray(table[:, 1])
+    count = np.zeros(p, np.int32)
+    aligned, oriented = np.zeros((p, BOX_FLOATS)), np.zeros((p, BOX_FLOATS))
+    for r, idx in enumerate(members):
+        m = count[r] = idx.shape[0]
+        if m == 0:
+            continue
+        lo = np.full(2 * A + 3, 0xFFFFFFFF, np.uint32)  # keys of u [A], v [A], x, y, z
+        hi = np.zeros(2 * A + 3, np.uint32)
+        for b in range(0, m, _BOX_HOST_SLICE):
+            q = xyz[idx[b:b + _BOX_HOST_SLICE]]
+            x, y = q[:, 0:1], q[:, 1:2]
+            u = x * c[None, :] + y * s[None, :]  # fp32: two products and a sum, each rounded
+            v = y * c[None, :] - x * s[None, :]
+            k = _float_keys(np.concatenate([u, v, q], axis=1))
+            lo, hi = np.minimum(lo, k.min(0)), np.maximum(hi, k.max(0))
+        lo, hi = _float_unkeys(lo), _float_unkeys(hi)
+        area = (hi[:A] - lo[:A]) * (hi[A:2 * A] - lo[A:2 * A])  # fp32
+        a = int(np.argmin(area))  # the first of the least
+        z = (lo[2 * A + 2], hi[2 * A + 2])
+        aligned[r] = _box_row(lo[2 * A], hi[2 * A], lo[2 * A + 1], hi[2 * A + 1], *z, np.float32(1), np.float32(0), 0, m)
+        oriented[r] = _box_row(lo[a], hi[a], lo[A + a], hi[A + a], *z, c[a], s[a], a, m)
+    return count, aligned, oriented
+
+
+def _xyz_host(xyz):
+    return np.ascontiguousarray(_np(xyz), dtype=np.float32).reshape(-1, 3)
+
+
+def instance_boxes_host(masks, pick, xyz, angles=BOX_ANGLES):
+    """The statement of the rows form: (count, aligned rows, oriented rows) of the groups masks[pick[r]] != 0 over xyz
+    [N, 3].  A pick outside the masks is an empty group; masks may overlap."""
+    table = box_angle_table(angles)
+    xyz = _xyz_host(xyz)
+    pick = np.asarray(_np(pick), dtype=np.int64).reshape(-1)
+    masks = _np(masks)
+    masks = masks.reshape(-1, xyz.shape[0]) if masks.size else np.zeros((0, xyz.shape[0]), np.int32)
+    none = np.zeros(0, np.int64)
+    return _box_rows_host([np.nonzero(masks[r])[0] if 0 <= r < masks.shape[0] else none for r in pick], xyz, table)
+
+
+def id_boxes_host(group, n_groups, xyz, angles=BOX_ANGLES):
+    """The statement of the ids form: the groups {i : group[i] == r} for r in [0, n_groups)."""
+    table = box_angle_table(angles)
+    xyz = _xyz_host(xyz)
+    g = np.asarray(_np(group)).reshape(-1)
+    if g.shape[0] != xyz.shape[0]:
+        raise ValueError(f"id_boxes: group [{g.shape[0]}] against {xyz.shape[0]} points")
+    order = np.argsort(g, kind="stable")
+    cuts = np.searchsorted(g[order], np.arange(int(n_groups) + 1))
+    return _box_rows_host([order[cuts[r]:cuts[r + 1]] for r in range(int(n_groups))], xyz, table)
+
+
+def box_scene_table(forms, widths, ns, ps, group_ptrs, pick_ptrs, xyz_ptrs):
+    """(int64 [S, BOX_SCENE_FIELDS] box scene table, sizes) for scenes of ps[b] groups over widths[b] points; forms[b]:
+    "rows" (ns[b] masks, pick_ptrs[b]) or "ids".  sizes: the rows in total and the largest per-scene point / group
+    counts of the launches."""
+    N = np.asarray(widths, dtype=np.int64).reshape(-1)
+    n = np.asarray(ns, dtype=np.int64).reshape(-1)
+    p = np.asarray(ps, dtype=np.int64).reshape(-1)
+    if (n < 0).any() or (N < 0).any() or (p < 0).any():
+        raise ValueError("box_scene_table: negative size")
+    if (p > BOX_MAX_GROUPS).any():
+        raise ValueError(f"boxes: at most {BOX_MAX_GROUPS} groups per scene, got {int(p.max())}")
+    S = N.shape[0]
+    t = np.zeros((S, BOX_SCENE_FIELDS), dtype=np.int64)
+    t[:, 0] = [BOX_FORMS[f] for f in forms]
+    t[:, 1], t[:, 2], t[:, 3] = N, n, p
+    t[:, 4] = np.asarray(group_ptrs, dtype=np.int64)
+    t[:, 5] = np.asarray(pick_ptrs, dtype=np.int64)
+    t[:, 6] = np.asarray(xyz_ptrs, dtype=np.int64)
+    t[:, 7] = np.concatenate([[0], np.cumsum(p)[:-1]]) if S else []
+    sizes = {"rows": int(p.sum()), "max_points": int(N.max()) if S else 0, "max_groups": int(p.max()) if S else 0}
+    return t, sizes
+
+
+def box_iou_table(Ps, Gs):
+    """(int64 [S, BOX_IOU_FIELDS] IoU table, sizes) for scenes of Ps[b] boxes against Gs[b]: offsets of each scene's rows
+    in the packed arrays and of its [P, G] block."""
+    P = np.asarray(Ps, dtype=np.int64).reshape(-1)
+    G = np.asarray(Gs, dtype=np.int64).reshape(-1)
+    if P.shape != G.shape or (P < 0).any() or (G < 0).any():
+        raise ValueError("box_iou_table: one non-negative count per scene in both lists")
+    S = P.shape[0]
+    excl = lambda a: np.concatenate([[0], np.cumsum(a)[:-1]]) if S else []  # noqa: E731
+    t = np.zeros((S, BOX_IOU_FIELDS), dtype=np.int64)
+    t[:, 0], t[:, 1], t[:, 2], t[:, 3], t[:, 4] = P, G, excl(P), excl(G), excl(P * G)
+    sizes = {"a": int(P.sum()), "b": int(G.sum()), "out": int((P * G).sum()), "max_pairs": int((P * G).max()) if S else 0}
+    return t, sizes
+
+
+_box_tables_dev = {}
+
+
+def _box_angles_dev(A, dev):
+    t = _box_tables_dev.get((dev, A))
+    if t is None:
+        t = _box_tables_dev[dev, A] = torch.from_numpy(box_angle_table(A)).to(dev)
+    return t
+
+
+def _boxes_packed(specs, angles):
+    """One gf_instance_boxes_batched call over scenes of either form: specs = ("rows", masks, pick, xyz) or ("ids",
+    group, n_groups, xyz) per scene.  Returns (scene table (host), count int32 [rows], aligned, oriented float64
+    [rows, BOX_FLOATS]) on the device."""
+    from . import pointops
+
+    box_angle_table(angles)  # (checks the range)
+    dev = next((s[3].device for s in specs if torch.is_tensor(s[3])), None)
+    if dev is None or dev.type != "cuda":
+        raise RuntimeError("boxes: the kernels run on the GPU; instance_boxes / id_boxes have the numpy path")
+    keep, forms, Ns, ns, ps, gp, pp, xp = [], [], [], [], [], [], [], []
+    for form, g, pk, x in specs:
+        x = torch.as_tensor(x, device=dev).to(torch.float32).reshape(-1, 3).contiguous()
+        N = x.shape[0]
+        if form == "rows":
+            pk = torch.as_tensor(pk, device=dev).to(torch.int64).reshape(-1).contiguous()
+            if torch.is_tensor(g) and g.numel():
+                g = (g if g.dtype == torch.int32 else (g != 0).int()).to(dev).contiguous()
+                if g.dim() != 2 or g.shape[1] != N:
+                    raise ValueError(f"instance_boxes: masks {tuple(g.shape)} against {N} points")
+                n, gptr = g.shape[0], g.data_ptr()
+            else:
+                n, gptr = 0, 0  # no masks: every pick is an empty group
+            p, pptr = pk.shape[0], pk.data_ptr() if pk.shape[0] else 0
+        elif form == "ids":
+            g = torch.as_tensor(g, device=dev).to(torch.int32).reshape(-1).contiguous()
+            if g.shape[0] != N:
+                raise ValueError(f"id_boxes: group [{g.shape[0]}] against {N} points")
+            n, p, gptr, pptr = 0, int(pk), g.data_ptr() if N else 0, 0
+        else:
+            raise ValueError(f"boxes: form must be 'rows' or 'ids', got {form!r}")
+        keep += [g, pk, x]
+        forms.append(form), Ns.append(N), ns.append(n), ps.append(p), gp.append(gptr), pp.append(pptr)
+        xp.append(x.data_ptr() if N else 0)
+    table, sizes = box_scene_table(forms, Ns, ns, ps, gp, pp, xp)
+    out = pointops.instance_boxes_batched(pointops._table_dev(table, dev), sizes, _box_angles_dev(int(angles), dev))
+    del keep  # (alive until the launches were queued on the current stream)
+    return (table, *out)
+
+
+def _split_boxes(table, count, rows, A):
+    out = []
+    for t in table:
+        p, o = int(t[3]), int(t[7])
+        out.append(_boxes_from_rows(rows[o:o + p], count[o:o + p], A))
+    return out
+
+
+def _boxes_batched(specs, oriented, angles):
+    A = int(angles) if oriented else 1
+    box_angle_table(angles)
+    table, count, aligned, orient = _boxes_packed(specs, A)
+    return _split_boxes(table, count, orient if oriented else aligned, A)
+
+
+def instance_boxes_batched(masks, picks, xyzs, *, oriented=False, angles=BOX_ANGLES):
+    """instance_boxes of several scenes at once on the GPU: lists with one entry per scene ([] for the masks of a scene
+    without proposals).  One table upload and one gf_instance_boxes_batched call for the whole batch; returns one Boxes
+    per scene, on the device (views of the batch's buffers)."""
+    if not len(masks) == len(picks) == len(xyzs):
+        raise ValueError("instance_boxes_batched: one entry per scene in every list")
+    return _boxes_batched([("rows", m, p, x) for m, p, x in zip(masks, picks, xyzs)], oriented, angles)
+
+
+def id_boxes_batched(groups, n_groups, xyzs, *, oriented=False, angles=BOX_ANGLES):
+    """id_boxes of several scenes at once on the GPU; lists with one entry per scene."""
+    if not len(groups) == len(n_groups) == len(xyzs):
+        raise ValueError("id_boxes_batched: one entry per scene in every list")
+    return _boxes_batched([("ids", g, p, x) for g, p, x in zip(groups, n_groups, xyzs)], oriented, angles)
+
+
+def instance_boxes(masks, pick, xyz, *, oriented=False, angles=BOX_ANGLES):
+    """The 3D box of every picked mask of one scene: masks [n, N] (nonzero = member; they may overlap), pick [p] rows of
+    masks (one outside [0, n) is an empty group), xyz [N, 3].  oriented=False: the axis-aligned box.  oriented=True: the
+    upright box of least footprint among `angles` equal headings over [0, 90 degrees) (the lowest heading among equals).
+    CUDA tensors take the kernels (csrc/boxes.hip) and the Boxes stays on the device; numpy arrays / CPU tensors take the
+    statement instance_boxes_host, which the kernels match bit for bit."""
+    if torch.is_tensor(xyz) and xyz.is_cuda:
+        return instance_boxes_batched([masks], [pick], [xyz], oriented=oriented, angles=angles)[0]
+    box_angle_table(angles)
+    A = int(angles) if oriented else 1
+    count, aligned, orient = instance_boxes_host(masks, pick, xyz, A)
+    return _boxes_from_rows(orient if oriented else aligned, count, A)
+
+
+def id_boxes(group, n_groups, xyz, *, oriented=False, angles=BOX_ANGLES):
+    """The 3D box of every group of a per-point map: group int [N] with values in [-1, n_groups), -1 = no group (ground
+    truth instances, label maps' owner).  Otherwise as instance_boxes."""
+    if torch.is_tensor(xyz) and xyz.is_cuda:
+        return id_boxes_batched([group], [n_groups], [xyz], oriented=oriented, angles=angles)[0]
+    box_angle_table(angles)
+    A = int(angles) if oriented else 1
+    count, aligned, orient = id_boxes_host(group, n_groups, xyz, A)
+    return _boxes_from_rows(orient if oriented else aligned, count, A)
+
+
+def _overlap_1d(d, ha, hb):
+    o = np.minimum(ha, d + hb) - np.maximum(-ha, d - hb)
+    return np.where(o > 0.0, o, 0.0)
+
+
+def _clip_host(pu, pv, m, axis, sign, h):
+    """One pass of Sutherland-Hodgman over K polygons at once (pu, pv float64 [K, 8], m [K] vertices each) against
+    sign * w >= -h, w the first (axis 0) or second coordinate: box_clip of csrc/boxes.hip, operation for operation."""
+    K = pu.shape[0]
+    rows = np.arange(K)
+    k = -h if sign > 0 else h
+    qu, qv, out = np.zeros_like(pu), np.zeros_like(pv), np.zeros(K, np.int64)
+    pw, po = (pv, pu) if axis else (pu, pv)
+    for i in range(8):
+        act = i < m
+        j = np.maximum(m - 1, 0) if i == 0 else np.full(K, i - 1)
+        cw, co, lw, lo = pw[:, i], po[:, i], pw[rows, j], po[rows, j]
+        cin, lin = (cw >= k, lw >= k) if sign > 0 else (cw <= k, lw <= k)
+        with np.errstate(all="ignore"):
+            tt = (k - lw) / (cw - lw)
+            io = lo + tt * (co - lo)
+        put = act & (cin != lin) & (out < 8)
+        qu[rows[put], out[put]] = (io if axis else k)[put]
+        qv[rows[put], out[put]] = (k if axis else io)[put]
+        out[put] += 1
+        put = act & cin & (out < 8)
+        qu[rows[put], out[put]] = pu[put, i]
+        qv[rows[put], out[put]] = pv[put, i]
+        out[put] += 1
+    return qu, qv, out
+
+
+def box_iou_host(a, b):
+    """float64 [P, G]: the 3D IoU of every box of a (Boxes or rows [P, BOX_FLOATS]) with every box of b -- the statement
+    of gf_box_iou_batched (include/geoformer_hip.h gives the rules), numpy float64 ufuncs in the kernel's order."""
+    A = np.asarray(_np(_box_rows_of(a)), dtype=np.float64).reshape(-1, BOX_FLOATS)
+    B = np.asarray(_np(_box_rows_of(b)), dtype=np.float64).reshape(-1, BOX_FLOATS)
+    P, G = A.shape[0], B.shape[0]
+    if P == 0 or G == 0:
+        return np.zeros((P, G))
+    A, B = np.repeat(A, G, axis=0), np.tile(B, (P, 1))  # one row per pair
+    hau, hav, haz = A[:, 3] * 0.5, A[:, 4] * 0.5, A[:, 5] * 0.5
+    hbu, hbv, hbz = B[:, 3] * 0.5, B[:, 4] * 0.5, B[:, 5] * 0.5
+    volA, volB = (A[:, 3] * A[:, 4]) * A[:, 5], (B[:, 3] * B[:, 4]) * B[:, 5]
+    oz = _overlap_1d(B[:, 2] - A[:, 2], haz, hbz)
+    area = _overlap_1d(B[:, 0] - A[:, 0], hau, hbu) * _overlap_1d(B[:, 1] - A[:, 1], hav, hbv)
+    poly = np.nonzero((A[:, 7] != 0.0) | (B[:, 7] != 0.0))[0]
+    if poly.shape[0]:
+        a_, b_ = A[poly], B[poly]
+        ca, sa, cb, sb = a_[:, 6], a_[:, 7], b_[:, 6], b_[:, 7]
+        dx, dy = a_[:, 0] - b_[:, 0], a_[:, 1] - b_[:, 1]
+        cu, cv = dx * cb + dy * sb, dy * cb - dx * sb
+        cr, sr = ca * cb + sa * sb, sa * cb - ca * sb
+        ux, uy, vx, vy = hau[poly] * cr, hau[poly] * sr, hav[poly] * sr, hav[poly] * cr
+        K = poly.shape[0]
+        pu, pv = np.zeros((K, 8)), np.zeros((K, 8))
+        pu[:, 0], pv[:, 0] = (cu - ux) + vx, (cv - uy) - vy
+        pu[:, 1], pv[:, 1] = (cu + ux) + vx, (cv + uy) - vy
+        pu[:, 2], pv[:, 2] = (cu + ux) - vx, (cv + uy) + vy
+        pu[:, 3], pv[:, 3] = (cu - ux) - vx, (cv - uy) + vy
+        m = np.full(K, 4, np.int64)
+        for axis, sign, h in ((0, 1, hbu[poly]), (0, -1, hbu[poly]), (1, 1, hbv[poly]), (1, -1, hbv[poly])):
+            pu, pv, m = _clip_host(pu, pv, m, axis, sign, h)
+        rows, acc = np.arange(K), np.zeros(K)
+        for i in range(8):
+            j = np.where(i + 1 == m, 0, min(i + 1, 7))
+            term = pu[:, i] * pv[rows, j] - pu[rows, j] * pv[:, i]
+            acc = np.where(i < m, acc + term, acc)
+        area[poly] = np.where(m >= 3, np.abs(acc) * 0.5, 0.0)
+    inter = np.where((volA > 0.0) & (volB > 0.0), area * oz, 0.0)
+    den = (volA + volB) - inter
+    with np.errstate(all="ignore"):
+        return np.where(den > 0.0, inter / den, 0.0).reshape(P, G)
+
+
+def box_iou_batched(a_list, b_list):
+    """box_iou of several scenes in one launch on the GPU: a_list[b] (Boxes or rows) against b_list[b]; returns one
+    float64 [P_b, G_b] tensor per scene, views of one packed buffer."""
+    from . import pointops
+
+    if len(a_list) != len(b_list):
+        raise ValueError("box_iou_batched: one entry per scene in both lists")
+    ra, rb = [_box_rows_of(a) for a in a_list], [_box_rows_of(b) for b in b_list]
+    dev = next((r.device for r in ra + rb if torch.is_tensor(r)), None)
+    if dev is None or dev.type != "cuda":
+        raise RuntimeError("box_iou_batched: the kernel runs on the GPU; box_iou_host has the numpy path")
+    rows = lambda r: torch.as_tensor(r, device=dev).to(torch.float64).reshape(-1, BOX_FLOATS)  # noqa: E731
+    ra, rb = [rows(r) for r in ra], [rows(r) for r in rb]
+    table, sizes = box_iou_table([r.shape[0] for r in ra], [r.shape[0] for r in rb])
+    cat = lambda rs: (rs[0] if len(rs) == 1 else torch.cat(rs)).contiguous() if rs else torch.zeros((0, BOX_FLOATS), dtype=torch.float64, device=dev)  # noqa: E731
+    out = pointops.box_iou_batched(pointops._table_dev(table, dev), sizes, cat(ra), cat(rb))
+    return [out[int(t[4]):int(t[4]) + int(t[0]) * int(t[1])].view(int(t[0]), int(t[1])) for t in table]
+
+
+def box_iou(a, b):
+    """float64 [P, G]: the 3D IoU of every box of a with every box of b (Boxes, or packed rows [., BOX_FLOATS]): upright
+    boxes, exact rectangle clipping in float64.  CUDA tensors take gf_box_iou_batched and the result stays on the
+    device; numpy arrays take box_iou_host, which the kernel matches bit for bit."""
+    ra, rb = _box_rows_of(a), _box_rows_of(b)
+    if any(torch.is_tensor(r) and r.is_cuda for r in (ra, rb)):
+        return box_iou_batched([ra], [rb])[0]
+    return box_iou_host(ra, rb)

@@ -552,3 +552,42 @@ def colors_for(task, raw_scene=None, labels=None, semantic=None, palette=None, d
         return classes(sem), None, keep
     inst = t[:, 7].to(torch.int32).contiguous()
     return instance_colors(inst), inst, keep
+
+
+# ---- boxes as points: the existing splat draws them over a scene ------------------------------------------------------
+BOX_EDGES = ((0, 1), (1, 2), (2, 3), (3, 0), (4, 5), (5, 6), (6, 7), (7, 4), (0, 4), (1, 5), (2, 6), (3, 7))
+
+
+def box_corners(boxes):
+    """float64 [p, 8, 3]: the corners of every box of a postprocess.Boxes: the lower face counter-clockwise from the
+    (-u, -v) corner, then the upper face in the same order."""
+    h = lambda a: np.asarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a, dtype=np.float64)  # noqa: E731
+    c, s = h(boxes.cos).reshape(-1, 1), h(boxes.sin).reshape(-1, 1)
+    center, half = h(boxes.center).reshape(-1, 3), h(boxes.size).reshape(-1, 3) / 2
+    su = np.array([-1.0, 1.0, 1.0, -1.0, -1.0, 1.0, 1.0, -1.0])[None, :]
+    sv = np.array([-1.0, -1.0, 1.0, 1.0, -1.0, -1.0, 1.0, 1.0])[None, :]
+    sz = np.array([-1.0] * 4 + [1.0] * 4)[None, :]
+    u, v = su * half[:, 0:1], sv * half[:, 1:2]
+    return np.stack([center[:, 0:1] + u * c - v * s, center[:, 1:2] + u * s + v * c, center[:, 2:3] + sz * half[:, 2:3]],
+                    axis=2)
+
+
+def box_points(boxes, step=0.02, rgb=(255, 0, 0)):
+    """(xyz fp32 [M, 3], rgb uint8 [M, 3]): the 12 edges of every box as points `step` metres apart (both end points
+    included), box after box, edge after edge in BOX_EDGES' order.  rgb: one colour, or one per box [p, 3].  Concatenate
+    them with a scene's points and colours and render.render draws the boxes over the scene."""
+    if not step > 0:
+        raise ValueError(f"box_points: step must be positive, got {step!r}")
+    corners = box_corners(boxes)
+    p = corners.shape[0]
+    colours = np.broadcast_to(np.asarray(rgb, dtype=np.uint8).reshape(-1, 3), (p, 3)) if p else np.zeros((0, 3), np.uint8)
+    pts, cols = [np.zeros((0, 3), np.float32)], [np.zeros((0, 3), np.uint8)]
+    for b in range(p):
+        for i, j in BOX_EDGES:
+            a, e = corners[b, i], corners[b, j]
+            k = int(np.ceil(np.linalg.norm(e - a) / step)) + 1
+            t = np.linspace(0.0, 1.0, max(k, 2))[:, None]
+            seg = (a[None, :] * (1.0 - t) + e[None, :] * t).astype(np.float32)
+            pts.append(seg)
+            cols.append(np.broadcast_to(colours[b], seg.shape).copy())
+    return np.concatenate(pts), np.concatenate(cols)

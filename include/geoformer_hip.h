@@ -1398,6 +1398,61 @@ int gf_aug_test_query(const GfAugBatch* b, double scale, int full_scale_min, int
 int gf_aug_support_block(const GfAugBatch* b, long long* support_masks, int32_t* scene_sizes, double scale,
                          int full_scale_min, int max_scene_points, void* stream);
 
+/* ===================================================================================
+ * 3D boxes of instances and the IoU of boxes (csrc/boxes.hip; the statements are postprocess.instance_boxes_host and
+ * postprocess.box_iou_host).  A box is upright: oriented about z only, the heading convention of indoor detection.
+ * Only extents (integer maxima of order-preserving keys) and integer counts are reduced: every output is a function of
+ * the inputs, bit-identical from call to call and to the statement.  Coordinates are finite.  Every launch goes on
+ * `stream`; no host synchronisation, no read-back.
+ * =================================================================================== */
+
+/* A box, GF_BOX_FLOATS float64: {cx, cy, cz, du, dv, dz, c, s, angle index, count}: du lies along (c, s), dv along
+ * (-s, c), dz along z; an empty group is a row of zeros.
+ * Box scene table, int64 [S, GF_BOX_SCENE_FIELDS], one row per scene:
+ *   {form, N, n, p, groups, pick, xyz (fp32 [N, 3]), row_off (rows into count / aligned / oriented, p of them)}
+ *   GF_BOX_FORM_ROWS: groups = masks int32 [n, N], nonzero = member (masks may overlap; NULL when n == 0); pick int64
+ *     [p]: group r is row pick[r]; a pick outside [0, n) is an empty group, never an address.
+ *   GF_BOX_FORM_IDS: groups = int32 [N] with values in [-1, p), -1 = no group (any other value outside [0, p) names no
+ *     group either); n and pick are not read.
+ * Limits, as functions: the points of one workgroup's chunk, the most angles, the most groups of one scene. */
+enum { GF_BOX_SCENE_FIELDS = 8, GF_BOX_FLOATS = 10, GF_BOX_IOU_FIELDS = 5 };
+enum { GF_BOX_FORM_ROWS = 0, GF_BOX_FORM_IDS = 1 };
+int gf_box_chunk(void);
+int gf_box_max_angles(void);
+int gf_box_max_groups(void);
+
+/* gf_instance_boxes_batched (two memsets, two launches for any S, p and forms): per group its point count, its
+ * axis-aligned box and the box of least footprint among the A headings of `angles`.
+ *   max_points / max_groups: the largest N / p of the table; rows: the sum of p; angles fp32 [A, 2] = (c, s) pairs,
+ *   1 <= A <= gf_box_max_angles(); scratch: gf_instance_boxes_scratch_bytes(rows, A), preset by the call.
+ *   count int32 [rows]; aligned, oriented float64 [rows, GF_BOX_FLOATS].
+ * Aligned: the minima and maxima of the members' fp32 x, y, z; c = 1, s = 0, index 0.
+ * Oriented: per angle a the extents of u = fl(fl(x c) + fl(y s)) and v = fl(fl(y c) - fl(x s)) over the members, fp32,
+ *   every operation rounded on its own; area_a = fl(fl(umax - umin) fl(vmax - vmin)); the box is the angle of least
+ *   area, the lowest index among equals.
+ * Both: sizes max - min and the frame's centre (min + max) / 2 in float64 from the fp32 extents (exact); cx = lu c - lv s,
+ *   cy = lu s + lv c in float64, every operation rounded on its own.  Extents are ordered as their keys are: -0 below +0.
+ * Bad sizes, A outside its range or a NULL pointer with rows > 0 are GF_ERR_INVALID_ARG with nothing launched; S == 0
+ * or rows == 0 succeeds with nothing launched. */
+size_t gf_instance_boxes_scratch_bytes(long long rows, int A);
+int gf_instance_boxes_batched(const long long* table, int S, long long max_points, int max_groups, long long rows,
+                              const float* angles, int A, void* scratch, int32_t* count, double* aligned,
+                              double* oriented, void* stream);
+
+/* gf_box_iou_batched (one launch, one thread per pair): the 3D IoU of every (a, b) pair of every scene.
+ *   IoU table, int64 [S, GF_BOX_IOU_FIELDS]: {P, G, a_off (rows of a), b_off (rows of b), out_off (elements of out)};
+ *   a, b: packed boxes, float64 [., GF_BOX_FLOATS]; out: float64, scene block [P, G] row-major at out_off; max_pairs:
+ *   the largest P G of the table.
+ * float64, every + - * / rounded on its own, no sin / cos.  Per axis the overlap of two intervals with half sizes ha,
+ *   hb whose centres are d apart is max(0, min(ha, d + hb) - max(-ha, d - hb)).  Both boxes with s == 0 (their sides
+ *   along the axes): area = overlap in x times overlap in y.  Otherwise: a's rectangle is taken into b's frame
+ *   (counter-clockwise from the (-u, -v) corner) and cut by b's four sides in the order u >= -hu, u <= hu, v >= -hv,
+ *   v <= hv (Sutherland-Hodgman, at most 8 vertices), area = |shoelace sum in vertex order| / 2.
+ *   inter = area times the overlap in z, 0 when either box has no volume; IoU = inter / (volA + volB - inter), 0 where
+ *   that denominator is <= 0; vol = (du dv) dz. */
+int gf_box_iou_batched(const long long* table, int S, long long max_pairs, const double* a, const double* b, double* out,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

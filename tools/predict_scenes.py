@@ -13,6 +13,7 @@ greedy NMS) and the scene labelling of batch_eval.label_batches, written with ge
     python tools/predict_scenes.py --out out --tile 4 --tile-stitch core --panoptic floor3.npy  # ... and the tiles' semantics stitched: PQ of the scan
     python tools/predict_scenes.py --out out --render turntable:4 scene0011_00_inst_nostuff.npy  # + out/render/<name>_instance_pred_<view>.png
     python tools/predict_scenes.py --out out --density 0.02 laser_scan.npy                 # a dense scan on one point per 2 cm cell, labels on every point
+    python tools/predict_scenes.py --out out --boxes oriented scene0011_00_inst_nostuff.npy  # + out/boxes/<name>.txt, one 3D box per instance
 
 Per scene <out>/<name>.npz (ids, owner, instance table: export.load_labels) and, with --scannet, <out>/<name>.txt plus
 <out>/predicted_masks/ (exclusive masks; --full-masks writes the picked masks as they are).  Without --checkpoint the
@@ -46,6 +47,11 @@ instance_pred; semantic_pred takes the classes of the --semantic pass, which it 
 csrc/resample.hip; --density-mode center: the point nearest the cell's centre, first: the cell's first point) and puts
 every result back on the scene's own points; tiles, segments and the mask split then see the subsampled scene.  The
 JSON line's `density` holds the parameters (null without the flag).
+--boxes aligned|oriented writes <out>/boxes/<name>.txt: one line per kept instance of the label map that owns a point,
+``cx cy cz du dv dz yaw label_id score`` (export.write_boxes), the box of the points the instance owns
+(postprocess.id_boxes over the map's owner column on the GPU, csrc/boxes.hip): axis-aligned, or the upright box of least
+footprint among 90 headings.  The JSON line's `boxes` names the kind (null without the flag) and `boxes_written` the
+count.
 """
 import argparse
 import json
@@ -105,6 +111,25 @@ def write_renders(out_dir, results, raws, views, size, task, semantic=None, devi
     return paths
 
 
+def write_boxes(out_dir, results, raws, kind, device="cuda"):
+    """<out_dir>/boxes/<name>.txt of every (name, SceneLabels) of results: the box of the points every kept instance
+    owns, computed on the device; raws: name -> raw [N, 8].  Returns the number of boxes written."""
+    from geoformer_amd import export, postprocess
+
+    written = 0
+    for name, lab in results:
+        xyz = torch.as_tensor(np.asarray(raws[name])[:, :3].astype(np.float32), device=device)
+        p = int(lab.table.count.shape[0])
+        b = postprocess.id_boxes(torch.as_tensor(lab.owner, device=device), p, xyz, oriented=kind == "oriented")
+        rows = b.rows.cpu().numpy()
+        on = rows[:, 9] > 0  # (an instance that is not kept, or that lost every point to better ones, owns nothing)
+        b = postprocess._boxes_from_rows(rows[on], rows[on, 9].astype(np.int32), postprocess.BOX_ANGLES if kind == "oriented" else 1)
+        export.write_boxes(os.path.join(out_dir, "boxes", f"{name}.txt"), b, np.asarray(lab.table.label_id)[on],
+                           np.asarray(lab.table.score)[on])
+        written += int(on.sum())
+    return written
+
+
 def build_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("scenes", nargs="*", help="scene .npy files, [N, 8] = xyz, rgb, semantic label, instance label")
@@ -151,6 +176,8 @@ def build_parser():
                     help="draw every scene on the GPU from above, or from K views around it: <out>/render/*.png")
     ap.add_argument("--render-size", type=parse_size, default=(1024, 768), metavar="WxH")
     ap.add_argument("--render-task", choices=RENDER_TASKS, default="instance_pred", help="what the colours show")
+    ap.add_argument("--boxes", choices=("aligned", "oriented"), default=None,
+                    help="also write <out>/boxes/<name>.txt: one 3D box per kept instance (postprocess.id_boxes)")
     ap.add_argument("--no-write", action="store_true")
     ap.add_argument("--reps", type=int, default=3, help="timed passes per keep_masks setting")
     return ap
@@ -254,6 +281,9 @@ def main():
             export.save_labels(os.path.join(args.out, f"{name}.npz"), lab._replace(masks=None), pans.get(name))
             if args.scannet:
                 export.write_scannet_predictions(args.out, name, lab, lab.masks if args.full_masks else None)
+    boxes_written = 0
+    if args.boxes is not None and not args.no_write:
+        boxes_written = write_boxes(args.out, results, dict(items), args.boxes, dev)
     sem_preds = {}
     if args.semantic or getattr(model.cfg, "save_semantic", False) or (args.render and args.render_task == "semantic_pred"):
         from geoformer_amd import evaluation
@@ -299,7 +329,8 @@ def main():
                       "labelled_points": sum(int((lab.owner >= 0).sum()) for _, lab in results),
                       "segment_pooling": "segments" in kw, "geometric_segments": args.geometric_segments,
                       "mask_split": args.split_masks, "tiling": dict(tiling.params, stitch=args.tile_stitch) if tiling else None,
-                      "density": density.params if density else None, "scenes_per_s": rates, "out": None if args.no_write else args.out}))
+                      "density": density.params if density else None, "boxes": args.boxes,
+                      "boxes_written": boxes_written, "scenes_per_s": rates, "out": None if args.no_write else args.out}))
 
 
 if __name__ == "__main__":
