@@ -612,15 +612,16 @@ def _panoptic_of_batch(ev, count_gt, names, raws, table, packed, tap, dev):
 
     pts, ti, _ = packed
     sem = torch.cat([tap.preds.pop(n) for n in names]).contiguous()
-    off_h = torch.from_numpy(np.concatenate([[0], np.cumsum(table[:, 1])]).astype(np.int32))
-    P = int(table[:, 3].max()) if len(table) else 0
+    rows = postprocess.scene_rows(table, postprocess.LBL_ROW)
+    off_h = torch.from_numpy(np.concatenate([[0], np.cumsum(rows["N"])]).astype(np.int32))
+    P = int(rows["p"].max()) if len(rows) else 0
     if count_gt:
         gts = []
         for n in names:
             r = torch.as_tensor(np.asarray(raws[n])[:, 6:8], device=dev)
             gts.append(evaluation.gt_ids_from_labels(r[:, 0].long(), r[:, 1].long()))
         ti_h = ti.cpu().numpy()
-        label_ids = [ti_h[int(t[10]):int(t[10]) + int(t[3]), 2] for t in table]
+        label_ids = [ti_h[o:o + p, postprocess._LBL_I.label_id] for o, p in rows[["row_off", "p"]].tolist()]
         pan = ev.add_batch(pts[0], pts[1], sem, torch.cat(gts), off_h.to(dev), label_ids, names, offsets_host=off_h)
     else:
         cls, st, sos = ev.device_tables(dev)

@@ -13,9 +13,9 @@
 //   k_bp_greedy_ious   score order, one barrier per pick.
 #include "proposal_rows.h"
 
-#define BP_PROP_FIELDS GF_PROP_SCENE_FIELDS
-#define BP_NMS_FIELDS GF_NMS_SCENE_FIELDS
 #define BP_NMS_MAX_N GF_NMS_MAX_N
+static_assert(sizeof(GfPropScene) == 8 * GF_PROP_SCENE_FIELDS && sizeof(GfNmsScene) == 8 * GF_NMS_SCENE_FIELDS,
+              "the rows of include/geoformer_hip.h");
 
 __global__ __launch_bounds__(PR_THREADS) void k_bp_stats(const long long* __restrict__ table, int nq,
                                                          const float* __restrict__ cls_logits,
@@ -25,12 +25,12 @@ __global__ __launch_bounds__(PR_THREADS) void k_bp_stats(const long long* __rest
                                                          int* __restrict__ npoints, float* __restrict__ scores,
                                                          int* __restrict__ final_out) {
     const int q = blockIdx.x, b = blockIdx.y;
-    const long long* t = table + (size_t)b * BP_PROP_FIELDS;
-    const int N = (int)t[1];
-    const float* row = (const float*)t[0] + (size_t)q * N;
+    const GfPropScene* t = gf_row<GfPropScene>(table, b);
+    const int N = (int)t->N;
+    const float* row = (const float*)t->logits + (size_t)q * N;
     const size_t o = (size_t)b * nq + q;
-    pr_stats_row(row, cls_logits + o * ncls, sem_prob + t[2], (size_t)sem_stride, N, ncls, logit_thresh, score_thresh,
-                 npoint_thresh, min_class, cls_pred + o, npoints + o, scores + o, final_out + o);
+    pr_stats_row(row, cls_logits + o * ncls, sem_prob + t->fg_off, (size_t)sem_stride, N, ncls, logit_thresh,
+                 score_thresh, npoint_thresh, min_class, cls_pred + o, npoints + o, scores + o, final_out + o);
 }
 
 __global__ __launch_bounds__(1024) void k_bp_select(const int32_t* __restrict__ final_, const int32_t* __restrict__ cls_pred,
@@ -54,15 +54,15 @@ __global__ __launch_bounds__(256) void k_bp_scatter(const long long* __restrict_
         const int c = counts[b];
         if (r < row0 + c) break;
         row0 += c;
-        base += (size_t)c * (size_t)table[(size_t)b * BP_PROP_FIELDS + 4];
+        base += (size_t)c * (size_t)gf_row<GfPropScene>(table, b)->num_points;
     }
     if (b == S) return;
-    const long long* t = table + (size_t)b * BP_PROP_FIELDS;
-    const int N = (int)t[1];
-    const long long pt_off = t[3], num_points = t[4];
+    const GfPropScene* t = gf_row<GfPropScene>(table, b);
+    const int N = (int)t->N;
+    const long long pt_off = t->pt_off, num_points = t->num_points;
     const int i = r - row0;
-    const float* row = (const float*)t[0] + (size_t)sel[(size_t)b * nq + i] * N;
-    const long long* fg = fg_idxs + t[2];
+    const float* row = (const float*)t->logits + (size_t)sel[(size_t)b * nq + i] * N;
+    const long long* fg = fg_idxs + t->fg_off;
     int* out = packed + base + (size_t)i * num_points;
     const int stride = gridDim.x * 256;
     for (int p0 = blockIdx.x * 256 + threadIdx.x; p0 < N; p0 += 4 * stride) {
@@ -131,10 +131,10 @@ extern "C" int gf_proposal_scatter_batched(const long long* table, int S, int nq
 // ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_bp_pack_bits(const long long* __restrict__ table,
                                                       unsigned long long* __restrict__ bits) {
-    const long long* t = table + (size_t)blockIdx.y * BP_NMS_FIELDS;
-    const int32_t* masks = (const int32_t*)t[0];
-    const long long N = t[1], n = t[2], W2 = (N + 63) / 64;
-    unsigned long long* out = bits + t[3];
+    const GfNmsScene* t = gf_row<GfNmsScene>(table, blockIdx.y);
+    const int32_t* masks = (const int32_t*)t->masks;
+    const long long N = t->N, n = t->n, W2 = (N + 63) / 64;
+    unsigned long long* out = bits + t->bits_off;
     const int lane = threadIdx.x & 63;
     // one wave per (row, 64-point block), grid-stride over the scene's waves (wave-uniform trip count)
     for (long long w = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); w < n * W2; w += (long long)gridDim.x * 4) {
@@ -149,10 +149,10 @@ __global__ __launch_bounds__(256) void k_bp_pack_bits(const long long* __restric
 __global__ __launch_bounds__(256) void k_bp_intersections(const long long* __restrict__ table,
                                                           const unsigned long long* __restrict__ bits,
                                                           int32_t* __restrict__ inter) {
-    const long long* t = table + (size_t)blockIdx.y * BP_NMS_FIELDS;
-    const long long N = t[1], n = t[2], W2 = (N + 63) / 64;
-    const unsigned long long* sb = bits + t[3];
-    int32_t* out = inter + t[4];
+    const GfNmsScene* t = gf_row<GfNmsScene>(table, blockIdx.y);
+    const long long N = t->N, n = t->n, W2 = (N + 63) / 64;
+    const unsigned long long* sb = bits + t->bits_off;
+    int32_t* out = inter + t->inter_off;
     const int lane = threadIdx.x & 63;
     for (long long w = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); w < n * n; w += (long long)gridDim.x * 4) {
         const long long i = w / n, j = w - i * n;
@@ -211,16 +211,16 @@ __global__ __launch_bounds__(1024) void k_bp_matrix_nms(const long long* __restr
     __shared__ int s_ord[BP_NMS_MAX_N];
     __shared__ int s_keep[BP_NMS_MAX_N];
     __shared__ int s_w[16];
-    const long long* t = table + (size_t)blockIdx.x * BP_NMS_FIELDS;
-    const int n = (int)t[2];
+    const GfNmsScene* t = gf_row<GfNmsScene>(table, blockIdx.x);
+    const int n = (int)t->n;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (n <= 0 || n > BP_NMS_MAX_N) {  // (the host rejects n > BP_NMS_MAX_N before the launch)
         if (tid == 0) pick_counts[blockIdx.x] = 0;
         return;
     }
-    const float* scores = (const float*)t[5];
-    const long long* cats = (const long long*)t[6];
-    const int32_t* inter = inter_all + t[4];
+    const float* scores = (const float*)t->scores;
+    const long long* cats = (const long long*)t->cats;
+    const int32_t* inter = inter_all + t->inter_off;
     // 1. rank = #(higher score, or equal score and lower index): a permutation for non-NaN scores; slots a NaN leaves
     //    unwritten keep index 0 (in bounds)
     for (int a = tid; a < n; a += 1024) s_ord[a] = 0;
@@ -282,7 +282,7 @@ __global__ __launch_bounds__(1024) void k_bp_matrix_nms(const long long* __restr
     }
     __syncthreads();
     // 4. kept positions in order -> original indices
-    int32_t* out = picks + t[7];
+    int32_t* out = picks + t->pick_off;
     int run = 0;
     for (int base = 0; base < n; base += 1024) {
         const int a = base + tid;
@@ -407,13 +407,14 @@ __global__ __launch_bounds__(1024) void k_bp_greedy_nms(const long long* __restr
                                                         const int32_t* __restrict__ inter_all, float threshold,
                                                         int32_t* __restrict__ picks,
                                                         int32_t* __restrict__ pick_counts) {
-    const long long* t = table + (size_t)blockIdx.x * BP_NMS_FIELDS;
-    const int n = (int)t[2];
+    const GfNmsScene* t = gf_row<GfNmsScene>(table, blockIdx.x);
+    const int n = (int)t->n;
     if (n <= 0 || n > BP_NMS_MAX_N) {  // (the host rejects n > BP_NMS_MAX_N before the launch)
         if (threadIdx.x == 0) pick_counts[blockIdx.x] = 0;
         return;
     }
-    bp_greedy_walk<true>(inter_all + t[4], (const float*)t[5], n, threshold, picks + t[7], pick_counts + blockIdx.x);
+    bp_greedy_walk<true>(inter_all + t->inter_off, (const float*)t->scores, n, threshold, picks + t->pick_off,
+                         pick_counts + blockIdx.x);
 }
 
 __global__ __launch_bounds__(1024) void k_bp_greedy_ious(const float* __restrict__ ious,

@@ -20,37 +20,36 @@
 #include "common.h"
 #include "post_steps.h"
 
-#define BOX_FIELDS GF_BOX_SCENE_FIELDS
 #define BOX_FLOATS GF_BOX_FLOATS
+#define BOX_AT(member) (offsetof(GfBox, member) / sizeof(double))
 #define BOX_THREADS 256
 #define BOX_CHUNK 2048                    // points per workgroup: eight per thread
 #define BOX_PER_THREAD (BOX_CHUNK / BOX_THREADS)
 #define BOX_MAX_ANGLES 192                // A + 2 slots <= BOX_THREADS
 #define BOX_MAX_GROUPS 65535              // grid.y
-#define BOX_IOU_FIELDS GF_BOX_IOU_FIELDS
+static_assert(sizeof(GfBoxScene) == 8 * GF_BOX_SCENE_FIELDS && sizeof(GfBoxIouScene) == 8 * GF_BOX_IOU_FIELDS &&
+                  sizeof(GfBox) == 8 * GF_BOX_FLOATS, "the rows of include/geoformer_hip.h");
 
 extern "C" int gf_box_chunk(void) { return BOX_CHUNK; }
 extern "C" int gf_box_max_angles(void) { return BOX_MAX_ANGLES; }
 extern "C" int gf_box_max_groups(void) { return BOX_MAX_GROUPS; }
 
-// scene table row: {form (GF_BOX_FORM_ROWS / GF_BOX_FORM_IDS), N, n, p, groups (masks int32 [n, N] / group int32 [N]),
-// pick (int64 [p]; rows form only), xyz, row_off}
 __global__ __launch_bounds__(BOX_THREADS) void k_box_extents(const long long* __restrict__ table,
                                                              const float* __restrict__ ang, int A,
                                                              uint32_t* __restrict__ kmin, uint32_t* __restrict__ kmax,
                                                              int32_t* __restrict__ cnt) {
     __shared__ float s_x[BOX_CHUNK], s_y[BOX_CHUNK], s_z[BOX_CHUNK];
     __shared__ int s_n;
-    const long long* t = table + (size_t)blockIdx.z * BOX_FIELDS;
-    const long long N = t[1], n = t[2], p = t[3];
+    const GfBoxScene* t = gf_row<GfBoxScene>(table, blockIdx.z);
+    const long long N = t->N, n = t->n, p = t->p;
     const long long nch = (N + BOX_CHUNK - 1) / BOX_CHUNK;
     const long long r = blockIdx.y, c = blockIdx.x;
     if (r >= p || c >= nch) return;  // (uniform over the workgroup)
-    const bool rows = t[0] == GF_BOX_FORM_ROWS;
-    const int32_t* g = (const int32_t*)t[4];
+    const bool rows = t->form == GF_BOX_FORM_ROWS;
+    const int32_t* g = (const int32_t*)t->group;
     int want = (int)r;  // ids form: the members are the points whose group is r
     if (rows) {
-        const long long row = ((const long long*)t[5])[r];
+        const long long row = ((const long long*)t->pick)[r];
         if (row < 0 || row >= n) return;  // (a pick outside the masks is an empty group, never an address)
         g += row * N;
     }
@@ -64,7 +63,7 @@ __global__ __launch_bounds__(BOX_THREADS) void k_box_extents(const long long* __
         const long long pt = p0 + (long long)k * BOX_THREADS;
         v[k] = g[pt < N ? pt : N - 1];
     }
-    const float* xyz = (const float*)t[6];
+    const float* xyz = (const float*)t->xyz;
 #pragma unroll
     for (int k = 0; k < BOX_PER_THREAD; k++) {
         const long long pt = p0 + (long long)k * BOX_THREADS;
@@ -101,7 +100,7 @@ __global__ __launch_bounds__(BOX_THREADS) void k_box_extents(const long long* __
             lo0 = min(lo0, kz), hi0 = max(hi0, kz);
         }
     }
-    const long long row_out = t[7] + r;
+    const long long row_out = t->row_off + r;
     const long long k2 = (row_out * (A + 2) + a) * 2;
     atomicMin(&kmin[k2], lo0);
     atomicMax(&kmax[k2], hi0);
@@ -114,7 +113,7 @@ __global__ __launch_bounds__(BOX_THREADS) void k_box_extents(const long long* __
 }
 
 // lo, hi: the slot's two minima / maxima (u, v); zlo, zhi: the first word of the z slot's
-__device__ __forceinline__ void box_write_row(double* o, const uint32_t* lo, const uint32_t* hi, uint32_t kzlo,
+__device__ __forceinline__ void box_write_row(GfBox& o, const uint32_t* lo, const uint32_t* hi, uint32_t kzlo,
                                               uint32_t kzhi, float cs, float sn, int index, int count) {
     // sizes and frame-local centres in float64 from the fp32 extents: exact
     const double ulo = gf_float_unkey(lo[0]), uhi = gf_float_unkey(hi[0]);
@@ -122,16 +121,16 @@ __device__ __forceinline__ void box_write_row(double* o, const uint32_t* lo, con
     const double zlo = gf_float_unkey(kzlo), zhi = gf_float_unkey(kzhi);
     const double lu = __dmul_rn(__dadd_rn(ulo, uhi), 0.5), lv = __dmul_rn(__dadd_rn(vlo, vhi), 0.5);
     const double c = cs, s = sn;
-    o[0] = __dsub_rn(__dmul_rn(lu, c), __dmul_rn(lv, s));
-    o[1] = __dadd_rn(__dmul_rn(lu, s), __dmul_rn(lv, c));
-    o[2] = __dmul_rn(__dadd_rn(zlo, zhi), 0.5);
-    o[3] = __dsub_rn(uhi, ulo);
-    o[4] = __dsub_rn(vhi, vlo);
-    o[5] = __dsub_rn(zhi, zlo);
-    o[6] = c;
-    o[7] = s;
-    o[8] = (double)index;
-    o[9] = (double)count;
+    o.cx = __dsub_rn(__dmul_rn(lu, c), __dmul_rn(lv, s));
+    o.cy = __dadd_rn(__dmul_rn(lu, s), __dmul_rn(lv, c));
+    o.cz = __dmul_rn(__dadd_rn(zlo, zhi), 0.5);
+    o.du = __dsub_rn(uhi, ulo);
+    o.dv = __dsub_rn(vhi, vlo);
+    o.dz = __dsub_rn(zhi, zlo);
+    o.c = c;
+    o.s = s;
+    o.angle = (double)index;
+    o.count = (double)count;
 }
 
 // (area, index) <- the lesser of the lane's own and lane ^ D's: the lesser area, the lower index among equals; an index
@@ -179,8 +178,8 @@ __global__ __launch_bounds__(256) void k_box_rows(const float* __restrict__ ang,
         return;
     }
     const uint32_t kzlo = lo[2 * (A + 1)], kzhi = hi[2 * (A + 1)];
-    box_write_row(oa, lo + 2 * A, hi + 2 * A, kzlo, kzhi, 1.f, 0.f, 0, m);
-    box_write_row(oo, lo + 2 * at, hi + 2 * at, kzlo, kzhi, ang[2 * at], ang[2 * at + 1], at, m);
+    box_write_row(*(GfBox*)oa, lo + 2 * A, hi + 2 * A, kzlo, kzhi, 1.f, 0.f, 0, m);
+    box_write_row(*(GfBox*)oo, lo + 2 * at, hi + 2 * at, kzlo, kzhi, ang[2 * at], ang[2 * at + 1], at, m);
 }
 
 extern "C" size_t gf_instance_boxes_scratch_bytes(long long rows, int A) {
@@ -253,26 +252,29 @@ __device__ __forceinline__ int box_clip(const double* pu, const double* pv, int 
     return out;
 }
 
-// iou table row: {P, G, a_off (rows of a), b_off (rows of b), out_off (elements of out)}
 __global__ __launch_bounds__(256) void k_box_iou(const long long* __restrict__ table, const double* __restrict__ a,
                                                  const double* __restrict__ b, double* __restrict__ out) {
-    const long long* t = table + (size_t)blockIdx.y * BOX_IOU_FIELDS;
-    const long long P = t[0], G = t[1];
+    const GfBoxIouScene* t = gf_row<GfBoxIouScene>(table, blockIdx.y);
+    const long long P = t->P, G = t->G;
     const long long pair = (long long)blockIdx.x * 256 + threadIdx.x;
     if (pair >= P * G) return;
-    const double* A = a + (t[2] + pair / G) * BOX_FLOATS;
-    const double* B = b + (t[3] + pair % G) * BOX_FLOATS;
-    const double hau = __dmul_rn(A[3], 0.5), hav = __dmul_rn(A[4], 0.5), haz = __dmul_rn(A[5], 0.5);
-    const double hbu = __dmul_rn(B[3], 0.5), hbv = __dmul_rn(B[4], 0.5), hbz = __dmul_rn(B[5], 0.5);
-    const double volA = __dmul_rn(__dmul_rn(A[3], A[4]), A[5]), volB = __dmul_rn(__dmul_rn(B[3], B[4]), B[5]);
-    const double oz = box_overlap_1d(__dsub_rn(B[2], A[2]), haz, hbz);
+    // the rows stay float64 words at the struct's offsets: read through GfBox, the loads are scheduled differently
+    enum : int { CX = BOX_AT(cx), CY = BOX_AT(cy), CZ = BOX_AT(cz), DU = BOX_AT(du), DV = BOX_AT(dv), DZ = BOX_AT(dz),
+                 C = BOX_AT(c), S = BOX_AT(s) };
+    const double* A = a + (t->a_off + pair / G) * BOX_FLOATS;
+    const double* B = b + (t->b_off + pair % G) * BOX_FLOATS;
+    const double hau = __dmul_rn(A[DU], 0.5), hav = __dmul_rn(A[DV], 0.5), haz = __dmul_rn(A[DZ], 0.5);
+    const double hbu = __dmul_rn(B[DU], 0.5), hbv = __dmul_rn(B[DV], 0.5), hbz = __dmul_rn(B[DZ], 0.5);
+    const double volA = __dmul_rn(__dmul_rn(A[DU], A[DV]), A[DZ]), volB = __dmul_rn(__dmul_rn(B[DU], B[DV]), B[DZ]);
+    const double oz = box_overlap_1d(__dsub_rn(B[CZ], A[CZ]), haz, hbz);
     double area;
-    if (A[7] == 0.0 && B[7] == 0.0) {  // both along the axes: interval overlaps
-        area = __dmul_rn(box_overlap_1d(__dsub_rn(B[0], A[0]), hau, hbu), box_overlap_1d(__dsub_rn(B[1], A[1]), hav, hbv));
+    if (A[S] == 0.0 && B[S] == 0.0) {  // both along the axes: interval overlaps
+        area = __dmul_rn(box_overlap_1d(__dsub_rn(B[CX], A[CX]), hau, hbu),
+                         box_overlap_1d(__dsub_rn(B[CY], A[CY]), hav, hbv));
     } else {
         // a's rectangle in b's frame, counter-clockwise, cut by b's four sides
-        const double ca = A[6], sa = A[7], cb = B[6], sb = B[7];
-        const double dx = __dsub_rn(A[0], B[0]), dy = __dsub_rn(A[1], B[1]);
+        const double ca = A[C], sa = A[S], cb = B[C], sb = B[S];
+        const double dx = __dsub_rn(A[CX], B[CX]), dy = __dsub_rn(A[CY], B[CY]);
         const double cu = __dadd_rn(__dmul_rn(dx, cb), __dmul_rn(dy, sb));
         const double cv = __dsub_rn(__dmul_rn(dy, cb), __dmul_rn(dx, sb));
         const double cr = __dadd_rn(__dmul_rn(ca, cb), __dmul_rn(sa, sb));
@@ -298,7 +300,7 @@ __global__ __launch_bounds__(256) void k_box_iou(const long long* __restrict__ t
     double inter = __dmul_rn(area, oz);
     if (!(volA > 0.0) || !(volB > 0.0)) inter = 0.0;  // a box without volume overlaps nothing
     const double den = __dsub_rn(__dadd_rn(volA, volB), inter);
-    out[t[4] + pair] = den > 0.0 ? __ddiv_rn(inter, den) : 0.0;
+    out[t->out_off + pair] = den > 0.0 ? __ddiv_rn(inter, den) : 0.0;
 }
 
 extern "C" int gf_box_iou_batched(const long long* table, int S, long long max_pairs, const double* a, const double* b,

@@ -72,6 +72,13 @@ bool gf_rules_level_parallel();
 
 static inline int gf_div_up(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// Row i of a scene table (int64 [S, F]) as the struct geoformer_hip.h declares for it: every member one int64 word.
+template <class Row>
+__host__ __device__ __forceinline__ const Row* gf_row(const long long* table, long long i) {
+    static_assert(sizeof(Row) % sizeof(long long) == 0 && alignof(Row) == alignof(long long), "a row of int64 words");
+    return reinterpret_cast<const Row*>(table) + i;
+}
+
 // f(std::integral_constant<T, V>{}) for the V among Vs that equals v: a run-time launch parameter -> a template instance
 template <class T, T... Vs, class F>
 static inline void gf_with(T v, F&& f) {

@@ -1,7 +1,7 @@
 // Scene labelling from the picked masks: one label per point and one table row per picked instance
 // (util/visualize.py:219-227 paints the picked instances from the last to the first, skipping score < min_score, a later
 // paint wins: the owner of a point is the LOWEST rank r in pick with score >= min_score whose mask covers the point).
-// Every kernel reads a device scene table (int64 rows, GF_LBL_SCENE_FIELDS in include/geoformer_hip.h); S scenes take
+// Every kernel reads a device scene table (one GfLblScene of include/geoformer_hip.h per scene); S scenes take
 // three launches whatever S, n and p are:
 //   k_lm_pack    grid (chunks, ranks, S): one workgroup per (rank r, chunk of LM_CHUNK points) reads its piece of mask
 //                row pick[r] ONCE (the only pass over the int32 masks), writes the ballot-packed bits [p, ceil(N / 64)]
@@ -14,14 +14,16 @@
 // N alone, and both reductions run in a fixed order, so a scene's table is bit-identical alone or in any batch.
 #include "common.h"
 
-#define LM_FIELDS GF_LBL_SCENE_FIELDS
 #define LM_CHUNK GF_LBL_CHUNK          // points per workgroup: 4 waves x LM_WORDS words x 64 lanes
 #define LM_WORDS (LM_CHUNK / 256)      // 64-point words per wave
 #define LM_OWN_SPLIT GF_LBL_OWN_SPLIT  // k_lm_owner's workgroups per chunk: own_part holds that many records per partial
 #define LM_OWN_THREADS (LM_CHUNK / LM_OWN_SPLIT)  // 1024: 16 waves, one 64-point word each
+// k_lm_table writes the float row as fp32 words at the struct's offsets: through GfLblRowF the stores are scheduled
+// differently
+#define LM_ATF(member) ((int)(offsetof(GfLblRowF, member) / sizeof(float)))
 #define LM_PARTF 9                     // fp32 per partial: xyz sum, box min, box max
-#define LM_TABI GF_LBL_TABLE_INTS
-#define LM_TABF GF_LBL_TABLE_FLOATS
+static_assert(sizeof(GfLblScene) == 8 * GF_LBL_SCENE_FIELDS && sizeof(GfLblRowI) == 4 * GF_LBL_TABLE_INTS &&
+                  sizeof(GfLblRowF) == 4 * GF_LBL_TABLE_FLOATS, "the rows of include/geoformer_hip.h");
 
 __device__ __forceinline__ float lm_wave_min(float m) {
     m = fminf(m, gf_shfl_xor<32>(m));
@@ -33,21 +35,20 @@ __device__ __forceinline__ float lm_wave_min(float m) {
     return m;
 }
 
-// table row: {masks, N, n, p, pick, scores, label_ids, xyz, bits_off, part_off, row_off, pt_off}
 __global__ __launch_bounds__(256) void k_lm_pack(const long long* __restrict__ table, float min_score,
                                                  unsigned long long* __restrict__ bits, float* __restrict__ part_f,
                                                  int32_t* __restrict__ part_cnt) {
-    const long long* t = table + (size_t)blockIdx.z * LM_FIELDS;
-    const long long N = t[1], n = t[2], p = t[3];
+    const GfLblScene* t = gf_row<GfLblScene>(table, blockIdx.z);
+    const long long N = t->N, n = t->n, p = t->p;
     const long long nch = (N + LM_CHUNK - 1) / LM_CHUNK, W2 = (N + 63) / 64;
     const long long r = blockIdx.y, c = blockIdx.x;
     if (r >= p || c >= nch) return;
-    const long long row = ((const long long*)t[4])[r];
+    const long long row = ((const long long*)t->pick)[r];
     const bool valid = row >= 0 && row < n;  // (a pick outside the masks is an empty row, never an address)
-    const bool kept = valid && ((const float*)t[5])[row] >= min_score;  // the bits serve the owner: kept rows only
-    const int32_t* m = (const int32_t*)t[0] + (valid ? row : 0) * N;
-    const float* xyz = (const float*)t[7];
-    unsigned long long* out = bits + t[8] + r * W2;
+    const bool kept = valid && ((const float*)t->scores)[row] >= min_score;  // the bits serve the owner: kept rows only
+    const int32_t* m = (const int32_t*)t->masks + (valid ? row : 0) * N;
+    const float* xyz = (const float*)t->xyz;
+    unsigned long long* out = bits + t->bits_off + r * W2;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const long long w0 = c * (LM_CHUNK / 64) + (long long)wave * LM_WORDS;
     // the loads of the wave's 16 words first, all in flight together: unconditional, a point past the end reads the
@@ -99,7 +100,7 @@ __global__ __launch_bounds__(256) void k_lm_pack(const long long* __restrict__ t
         f[0] = sx, f[1] = sy, f[2] = sz, f[3] = lx, f[4] = ly, f[5] = lz, f[6] = hx, f[7] = hy, f[8] = hz;
     }
     __syncthreads();
-    const long long o = t[9] + r * nch + c;
+    const long long o = t->part_off + r * nch + c;
     if (threadIdx.x < LM_PARTF) {
         const int j = threadIdx.x;
         float a = s_f[0][j];
@@ -117,15 +118,15 @@ __global__ __launch_bounds__(LM_OWN_THREADS) void k_lm_owner(const long long* __
                                                              int32_t* __restrict__ ids, int32_t* __restrict__ own_part) {
     __shared__ int s_lab[GF_NMS_MAX_N];  // label id of rank r, -1 where the rank is not kept
     __shared__ int s_hist[GF_NMS_MAX_N];
-    const long long* t = table + (size_t)blockIdx.y * LM_FIELDS;
-    const long long N = t[1], n = t[2];
-    const int p = (int)t[3];
+    const GfLblScene* t = gf_row<GfLblScene>(table, blockIdx.y);
+    const long long N = t->N, n = t->n;
+    const int p = (int)t->p;
     const long long nob = (N + LM_OWN_THREADS - 1) / LM_OWN_THREADS, W2 = (N + 63) / 64;
     const long long c = blockIdx.x;
     if (c >= nob) return;
-    const long long* pick = (const long long*)t[4];
-    const float* scores = (const float*)t[5];
-    const long long* labels = (const long long*)t[6];
+    const long long* pick = (const long long*)t->pick;
+    const float* scores = (const float*)t->scores;
+    const long long* labels = (const long long*)t->label_ids;
     for (int r = threadIdx.x; r < p; r += LM_OWN_THREADS) {
         const long long row = pick[r];
         const bool kept = row >= 0 && row < n && scores[row] >= min_score;
@@ -139,7 +140,7 @@ __global__ __launch_bounds__(LM_OWN_THREADS) void k_lm_owner(const long long* __
     const int lane = threadIdx.x & 63;
     const long long w = c * (LM_OWN_THREADS / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (w < W2) {  // (wave-uniform)
-        const unsigned long long* sb = bits + t[8] + w;
+        const unsigned long long* sb = bits + t->bits_off + w;
         int own = -1;
         unsigned long long open = ~0ull;  // lanes without an owner yet
         for (int r0 = 0; r0 < p && open; r0 += 8) {
@@ -155,13 +156,13 @@ __global__ __launch_bounds__(LM_OWN_THREADS) void k_lm_owner(const long long* __
         }
         const long long pt = w * 64 + lane;
         if (pt < N) {
-            owner[t[11] + pt] = own;
-            ids[t[11] + pt] = own < 0 ? 0 : s_lab[own] * 1000 + own + 1;
+            owner[t->pt_off + pt] = own;
+            ids[t->pt_off + pt] = own < 0 ? 0 : s_lab[own] * 1000 + own + 1;
             if (own >= 0) atomicAdd(&s_hist[own], 1);  // (LDS, integers: exact in any order)
         }
     }
     __syncthreads();
-    int32_t* hp = own_part + t[9] * LM_OWN_SPLIT + c * p;
+    int32_t* hp = own_part + t->part_off * LM_OWN_SPLIT + c * p;
     for (int r = threadIdx.x; r < p; r += LM_OWN_THREADS) hp[r] = s_hist[r];
 }
 
@@ -170,8 +171,8 @@ __global__ __launch_bounds__(256) void k_lm_table(const long long* __restrict__ 
                                                   const int32_t* __restrict__ part_cnt,
                                                   const int32_t* __restrict__ own_part, float min_score,
                                                   int32_t* __restrict__ tab_i, float* __restrict__ tab_f) {
-    const long long* t = table + (size_t)blockIdx.y * LM_FIELDS;
-    const long long N = t[1], n = t[2], p = t[3];
+    const GfLblScene* t = gf_row<GfLblScene>(table, blockIdx.y);
+    const long long N = t->N, n = t->n, p = t->p;
     const long long nch = (N + LM_CHUNK - 1) / LM_CHUNK;
     const int lane = threadIdx.x & 63;
     const long long r = (long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -180,7 +181,7 @@ __global__ __launch_bounds__(256) void k_lm_table(const long long* __restrict__ 
     int cnt = 0, owned = 0;
     float s[3] = {0.f, 0.f, 0.f}, lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (long long c = lane; c < nch; c += 64) {
-        const long long o = t[9] + r * nch + c;
+        const long long o = t->part_off + r * nch + c;
         const float* f = part_f + o * LM_PARTF;
         cnt += part_cnt[o];
 #pragma unroll
@@ -191,29 +192,29 @@ __global__ __launch_bounds__(256) void k_lm_table(const long long* __restrict__ 
         }
     }
     const long long nob = (N + LM_OWN_THREADS - 1) / LM_OWN_THREADS;
-    for (long long c = lane; c < nob; c += 64) owned += own_part[t[9] * LM_OWN_SPLIT + c * p + r];
+    for (long long c = lane; c < nob; c += 64) owned += own_part[t->part_off * LM_OWN_SPLIT + c * p + r];
     cnt = gf_wave_sum_i(cnt), owned = gf_wave_sum_i(owned);
 #pragma unroll
     for (int j = 0; j < 3; j++) s[j] = gf_wave_sum(s[j]), lo[j] = lm_wave_min(lo[j]), hi[j] = gf_wave_max(hi[j]);
     if (lane != 0) return;
-    const long long row = ((const long long*)t[4])[r];
+    const long long row = ((const long long*)t->pick)[r];
     const bool valid = row >= 0 && row < n;
-    const float score = valid ? ((const float*)t[5])[row] : 0.f;
-    int32_t* ti = tab_i + (t[10] + r) * LM_TABI;
-    float* tf = tab_f + (t[10] + r) * LM_TABF;
-    ti[0] = cnt;
-    ti[1] = owned;
-    ti[2] = valid ? (int)((const long long*)t[6])[row] : 0;
-    ti[3] = (int)row;
-    ti[4] = valid && score >= min_score;
+    const float score = valid ? ((const float*)t->scores)[row] : 0.f;
+    GfLblRowI* ti = (GfLblRowI*)tab_i + (t->row_off + r);
+    float* tf = tab_f + (t->row_off + r) * GF_LBL_TABLE_FLOATS;
+    ti->count = cnt;
+    ti->owned = owned;
+    ti->label_id = valid ? (int)((const long long*)t->label_ids)[row] : 0;
+    ti->pick = (int)row;
+    ti->kept = valid && score >= min_score;
     const float inv = (float)cnt;
 #pragma unroll
     for (int j = 0; j < 3; j++) {
-        tf[j] = cnt ? s[j] / inv : 0.f;
-        tf[3 + j] = cnt ? lo[j] : 0.f;
-        tf[6 + j] = cnt ? hi[j] : 0.f;
+        tf[LM_ATF(centroid) + j] = cnt ? s[j] / inv : 0.f;
+        tf[LM_ATF(box_min) + j] = cnt ? lo[j] : 0.f;
+        tf[LM_ATF(box_max) + j] = cnt ? hi[j] : 0.f;
     }
-    tf[9] = score;
+    tf[LM_ATF(score)] = score;
 }
 
 extern "C" int gf_label_map_batched(const long long* table, int S, long long max_points, int max_picks, float min_score,

@@ -33,7 +33,8 @@ namespace {
 constexpr int MS_THREADS = 256;            // four waves: four 64-point words of one pick
 constexpr int MS_WAVES = MS_THREADS / 64;
 constexpr int MS_PACK_WORDS = 8;           // words per wave of k_ms_pack: 2048 points per workgroup
-constexpr int MS_TAB = GF_MSP_TABLE_INTS;  // {members, clusters kept, points in kept clusters, largest id, its size}
+constexpr int MS_TAB = GF_MSP_TABLE_INTS;
+static_assert(sizeof(GfMspRow) == 4 * GF_MSP_TABLE_INTS, "the row of include/geoformer_hip.h");
 
 typedef unsigned long long u64;
 
@@ -100,7 +101,7 @@ __global__ __launch_bounds__(MS_THREADS) void k_ms_core(const int32_t* __restric
             }
             is_core = need <= 0;
         }
-        if (lane == 0) atomicAdd(&tab[r * MS_TAB], __popcll(word));
+        if (lane == 0) atomicAdd(&((GfMspRow*)(tab + r * MS_TAB))->members, __popcll(word));  // (32-bit row index)
     }
     const u64 cw = __ballot(is_core);
     if (lane == 0) core[r * W + w] = cw;
@@ -203,8 +204,8 @@ __global__ __launch_bounds__(MS_THREADS) void k_ms_dissolve(long long N, int min
         key = o > key ? o : key;
     }
     if (lane == 0) {
-        atomicAdd(&tab[r * MS_TAB + 1], roots);
-        atomicAdd(&tab[r * MS_TAB + 2], points);
+        atomicAdd(&((GfMspRow*)tab)[r].clusters, roots);
+        atomicAdd(&((GfMspRow*)tab)[r].kept_points, points);
         atomicMax(&best[r], key);
     }
 }
@@ -213,8 +214,8 @@ __global__ __launch_bounds__(MS_THREADS) void k_ms_table(int p, const u64* __res
     const int r = blockIdx.x * MS_THREADS + threadIdx.x;
     if (r >= p) return;
     const u64 key = best[r];  // 0: no kept cluster (a cluster has at least one point)
-    tab[(long long)r * MS_TAB + 3] = key ? 0x7fffffff - (int)(key & 0xffffffffull) : -1;
-    tab[(long long)r * MS_TAB + 4] = (int)(key >> 32);
+    ((GfMspRow*)tab)[r].largest = key ? 0x7fffffff - (int)(key & 0xffffffffull) : -1;
+    ((GfMspRow*)tab)[r].largest_size = (int)(key >> 32);
 }
 
 // one workgroup per (row of masks, chunk of 1024 points): the first rank that picks the row decides it (every rank that
@@ -232,7 +233,7 @@ __global__ __launch_bounds__(MS_THREADS) void k_ms_keep_largest(const int32_t* _
         if (pick[r] == row) atomicMin(&s_rank, r);  // (LDS)
     __syncthreads();
     const int r = s_rank;
-    const int keep = r < p ? tab[(long long)r * MS_TAB + 3] : -1;
+    const int keep = r < p ? ((const GfMspRow*)tab)[r].largest : -1;
 #pragma unroll
     for (int q = 0; q < 4; q++) {
         const long long i = c * (4 * MS_THREADS) + q * MS_THREADS + threadIdx.x;

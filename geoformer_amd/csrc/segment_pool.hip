@@ -34,7 +34,6 @@ constexpr int SP_THREADS = 1024;         // one position per thread
 constexpr int SP_CHUNK = SP_THREADS;     // positions per workgroup
 constexpr int SP_WAVES = SP_THREADS / 64;
 constexpr int SP_QT = 16;                // queries per workgroup
-constexpr int SP_FIELDS = 4;             // {in, out, N_b, fg_off}
 constexpr int SP_IDX_THREADS = 256;
 
 struct SpScene {
@@ -45,12 +44,12 @@ struct SpScene {
 };
 
 __device__ __forceinline__ SpScene sp_scene(const long long* __restrict__ table, int s, long long n_fg) {
-    const long long* row = table + (size_t)s * SP_FIELDS;
+    const GfSegScene* row = gf_row<GfSegScene>(table, s);
     SpScene sc;
-    sc.in = (const float*)row[0];
-    sc.out = (float*)row[1];
-    sc.N = row[2];
-    sc.off = row[3];
+    sc.in = (const float*)row->in;
+    sc.out = (float*)row->out;
+    sc.N = row->N;
+    sc.off = row->off;
     sc.ok = sc.in != nullptr && sc.out != nullptr && (const float*)sc.out != sc.in && sc.N > 0 && sc.off >= 0 &&
             sc.off <= n_fg && sc.N <= n_fg - sc.off;
     return sc;
@@ -254,7 +253,7 @@ SpScratch sp_layout(int S, long long n_fg, int nq) {
 
 }  // namespace
 
-extern "C" int gf_segment_pool_scene_fields(void) { return SP_FIELDS; }
+extern "C" int gf_segment_pool_scene_fields(void) { return sizeof(GfSegScene) / sizeof(long long); }
 
 extern "C" int gf_segment_pool_chunk_points(void) { return SP_CHUNK; }
 
@@ -271,14 +270,14 @@ extern "C" int gf_segment_pool_batched(const long long* table, const long long* 
     if (table_host) {
         long long at = 0;
         for (int s = 0; s < S; ++s) {
-            const long long* row = table_host + (size_t)s * SP_FIELDS;
-            GF_CHECK_ARG(row[2] >= 0 && row[2] <= max_N && row[3] == at,
+            const GfSegScene* row = gf_row<GfSegScene>(table_host, s);
+            GF_CHECK_ARG(row->N >= 0 && row->N <= max_N && row->off == at,
                          "gf_segment_pool_batched: scene %d has N_b = %lld (max_N = %lld) at fg_off = %lld, expected %lld", s,
-                         row[2], max_N, row[3], at);
-            GF_CHECK_ARG(row[2] == 0 || (row[0] != 0 && row[1] != 0), "gf_segment_pool_batched: scene %d: NULL logits", s);
-            GF_CHECK_ARG(row[2] == 0 || row[0] != row[1],
+                         row->N, max_N, row->off, at);
+            GF_CHECK_ARG(row->N == 0 || (row->in != 0 && row->out != 0), "gf_segment_pool_batched: scene %d: NULL logits", s);
+            GF_CHECK_ARG(row->N == 0 || row->in != row->out,
                          "gf_segment_pool_batched: scene %d: out == in (the pooling is out of place)", s);
-            at += row[2];
+            at += row->N;
         }
         GF_CHECK_ARG(at == n_fg, "gf_segment_pool_batched: the scenes hold %lld foreground points, n_fg = %lld", at, n_fg);
     }

@@ -3,7 +3,7 @@
 //
 // The device never sees a coordinate: the plan arrives as two integer tables over the scan's N points, tile_of and
 // local_of int32 [N, 4] (the point's tiles in ascending order, -1 padded, and its index inside each), and the tiles as a
-// scene table of GF_TILE_SCENE_FIELDS int64 words each.  Rows are the picked masks of all tiles, tile-major.
+// scene table of one GfTileScene each.  Rows are the picked masks of all tiles, tile-major.
 //   k_tm_pack      one thread per (tile-local point, 32-pick word): the point's memberships in the tile's picks as a
 //                  bitset of ceil(p_s / 32) consecutive words, gathered from the dense int32 rows (coalesced over the
 //                  points of a row)
@@ -30,7 +30,7 @@ namespace {
 constexpr int TM_MAX_ROWS = 4096;  // P: the LDS tables of k_tm_merge
 constexpr int TM_MAX_PICKS = 256;  // p_s: a point's bitset is at most 8 words
 constexpr int TM_WORDS = TM_MAX_PICKS / 32;
-constexpr int TM_F = GF_TILE_SCENE_FIELDS;  // {masks, n_rows, n_s, pick, p_s, first row, first word}
+static_assert(sizeof(GfTileScene) == 8 * GF_TILE_SCENE_FIELDS, "the row of include/geoformer_hip.h");
 constexpr int TM_THREADS = 256;
 constexpr int TM_MERGE_THREADS = 1024;
 constexpr int TM_ROWS_PER_THREAD = TM_MAX_ROWS / TM_MERGE_THREADS;
@@ -38,20 +38,20 @@ constexpr int TM_ROWS_PER_THREAD = TM_MAX_ROWS / TM_MERGE_THREADS;
 typedef unsigned long long u64;
 
 __global__ __launch_bounds__(TM_THREADS) void k_tm_pack(const long long* __restrict__ tab, uint32_t* __restrict__ bits) {
-    const long long* row = tab + (long long)blockIdx.y * TM_F;
-    const long long n_rows = row[1], n_s = row[2], p_s = row[4];
+    const GfTileScene* row = gf_row<GfTileScene>(tab, blockIdx.y);
+    const long long n_rows = row->n_rows, n_s = row->n_s, p_s = row->p_s;
     const int w = blockIdx.z, wpp = (int)((p_s + 31) >> 5);
     const long long j = (long long)blockIdx.x * TM_THREADS + threadIdx.x;
     if (w >= wpp || j >= n_s) return;
-    const int32_t* masks = (const int32_t*)row[0];
-    const long long* pick = (const long long*)row[3];
+    const int32_t* masks = (const int32_t*)row->masks;
+    const long long* pick = (const long long*)row->pick;
     const int k0 = w * 32, kn = (int)min((long long)32, p_s - k0);
     uint32_t word = 0;
     for (int k = 0; k < kn; ++k) {
         const long long r = pick[k0 + k];  // (uniform over the workgroup)
         if ((u64)r < (u64)n_rows && masks[r * n_s + j] != 0) word |= 1u << k;
     }
-    bits[row[6] + j * wpp + w] = word;
+    bits[row->first_word + j * wpp + w] = word;
 }
 
 // One pair (s, t) of the tiles of this lane's point: see the head of the file.  Wave-uniform control flow.
@@ -65,15 +65,15 @@ __device__ __forceinline__ void tm_pair(const long long* __restrict__ tab, int T
     for (int w = 0; w < TM_WORDS; ++w) A[w] = B[w] = 0;
     int frs = 0, frt = 0;
     if (act) {
-        const long long *rs = tab + (long long)s * TM_F, *rt = tab + (long long)t * TM_F;
-        const long long ps = rs[4], pt = rt[4];
-        act = (u64)la < (u64)rs[2] && (u64)lb < (u64)rt[2] && ps <= TM_MAX_PICKS && pt <= TM_MAX_PICKS;
+        const GfTileScene *rs = gf_row<GfTileScene>(tab, s), *rt = gf_row<GfTileScene>(tab, t);
+        const long long ps = rs->p_s, pt = rt->p_s;
+        act = (u64)la < (u64)rs->n_s && (u64)lb < (u64)rt->n_s && ps <= TM_MAX_PICKS && pt <= TM_MAX_PICKS;
         if (act) {
-            frs = (int)rs[5];
-            frt = (int)rt[5];
+            frs = (int)rs->first_row;
+            frt = (int)rt->first_row;
             const int wa = (int)((ps + 31) >> 5), wb = (int)((pt + 31) >> 5);
-            const uint32_t* pa = bits + rs[6] + (long long)la * wa;
-            const uint32_t* pb = bits + rt[6] + (long long)lb * wb;
+            const uint32_t* pa = bits + rs->first_word + (long long)la * wa;
+            const uint32_t* pb = bits + rt->first_word + (long long)lb * wb;
             uint32_t any = 0;
 #pragma unroll
             for (int w = 0; w < TM_WORDS; ++w) {
@@ -246,12 +246,12 @@ __global__ __launch_bounds__(TM_THREADS) void k_tm_assemble(const long long* __r
         int wpp = 0, fr = 0;
         const uint32_t* pb = bits;
         if (act) {
-            const long long* row = tab + (long long)s * TM_F;
-            act = (u64)lc[c] < (u64)row[2] && row[4] <= TM_MAX_PICKS;
+            const GfTileScene* row = gf_row<GfTileScene>(tab, s);
+            act = (u64)lc[c] < (u64)row->n_s && row->p_s <= TM_MAX_PICKS;
             if (act) {
-                wpp = (int)((row[4] + 31) >> 5);
-                fr = (int)row[5];
-                pb = bits + row[6] + (long long)lc[c] * wpp;
+                wpp = (int)((row->p_s + 31) >> 5);
+                fr = (int)row->first_row;
+                pb = bits + row->first_word + (long long)lc[c] * wpp;
             }
         }
         // the lanes walk their set bits together, one bit per round: a round is over when no lane has a bit left
@@ -290,16 +290,16 @@ const char* tm_check_table(const long long* th, int T, int P, long long* max_n, 
     *max_n = 0;
     *max_words = 0;
     for (int s = 0; s < T; ++s) {
-        const long long* r = th + (long long)s * TM_F;
-        if (r[1] < 0 || r[2] < 0 || r[2] > 0x7fffffffLL || r[4] < 0) return "a negative n_rows, n_s or p_s";
-        if (r[4] > TM_MAX_PICKS) return "more than 256 picks in a tile";
-        if (r[4] > 0 && r[2] > 0 && (r[0] == 0 || r[3] == 0)) return "a NULL masks or pick pointer";
-        if (r[5] != row || r[6] != word) return "first row / first word do not follow the tile before";
-        const long long wpp = (r[4] + 31) >> 5;
-        row += r[4];
-        word += r[2] * wpp;
-        if (wpp > 0 && r[2] > *max_n) *max_n = r[2];
-        if (r[2] > 0 && wpp > *max_words) *max_words = (int)wpp;
+        const GfTileScene* r = gf_row<GfTileScene>(th, s);
+        if (r->n_rows < 0 || r->n_s < 0 || r->n_s > 0x7fffffffLL || r->p_s < 0) return "a negative n_rows, n_s or p_s";
+        if (r->p_s > TM_MAX_PICKS) return "more than 256 picks in a tile";
+        if (r->p_s > 0 && r->n_s > 0 && (r->masks == 0 || r->pick == 0)) return "a NULL masks or pick pointer";
+        if (r->first_row != row || r->first_word != word) return "first row / first word do not follow the tile before";
+        const long long wpp = (r->p_s + 31) >> 5;
+        row += r->p_s;
+        word += r->n_s * wpp;
+        if (wpp > 0 && r->n_s > *max_n) *max_n = r->n_s;
+        if (r->n_s > 0 && wpp > *max_words) *max_words = (int)wpp;
     }
     if (row != P) return "the picks of the tiles do not add up to P";
     *words = word;

@@ -3,7 +3,7 @@
 // arguments).
 //
 // As in tile_merge.hip the device sees integer tables only: tile_of / local_of int32 [N, 4], core_of int32 [N], and the
-// tiles as a table of GF_TILE_SCORE_FIELDS int64 words each, {scores pointer fp32 [n_s, C], n_s}.
+// tiles as a table of one GfTileScore each.
 //   k_ts_stitch  one workgroup of 256 threads per 256 consecutive points of the scan, in two steps:
 //                1. one thread per point: one 16-byte read each of its tile_of and local_of rows (and core_of in core
 //                   mode); every slot that counts is resolved to the address of its source row -- the tile id checked
@@ -21,7 +21,7 @@
 
 namespace {
 
-constexpr int TS_F = GF_TILE_SCORE_FIELDS;  // {scores, n_s}
+static_assert(sizeof(GfTileScore) == 8 * GF_TILE_SCORE_FIELDS, "the row of include/geoformer_hip.h");
 constexpr int TS_THREADS = 256;             // = the points of a workgroup
 constexpr int TS_SLOTS = 4;
 
@@ -30,9 +30,9 @@ typedef unsigned long long u64;
 // the address of point (s, l)'s row of C floats, or NULL when (s, l) names no row
 __device__ __forceinline__ const float* ts_row(const long long* __restrict__ tab, int T, int C, int s, int l) {
     if ((unsigned)s >= (unsigned)T) return nullptr;
-    const long long* row = tab + (long long)s * TS_F;
-    if ((u64)(long long)l >= (u64)row[1]) return nullptr;  // (a negative index is a huge one)
-    return (const float*)row[0] + (long long)l * C;
+    const GfTileScore* row = gf_row<GfTileScore>(tab, s);
+    if ((u64)(long long)l >= (u64)row->n_s) return nullptr;  // (a negative index is a huge one)
+    return (const float*)row->scores + (long long)l * C;
 }
 
 __global__ __launch_bounds__(TS_THREADS) void k_ts_stitch(const long long* __restrict__ tab, int T,
@@ -111,9 +111,9 @@ extern "C" int gf_tile_stitch_scores(const long long* table, const long long* ta
     GF_CHECK_ARG(N >= 0 && N <= 0x7fffffffLL * TS_THREADS, "gf_tile_stitch_scores: N = %lld points", N);
     GF_CHECK_ARG(table && table_host, "gf_tile_stitch_scores: NULL table or table_host");
     for (int s = 0; s < T; ++s) {
-        const long long* r = table_host + (long long)s * TS_F;
-        GF_CHECK_ARG(r[1] >= 0 && r[1] <= 0x7fffffffLL, "gf_tile_stitch_scores: tile %d: n_s = %lld", s, r[1]);
-        GF_CHECK_ARG(r[1] == 0 || r[0] != 0, "gf_tile_stitch_scores: tile %d: NULL scores with n_s = %lld", s, r[1]);
+        const GfTileScore* r = gf_row<GfTileScore>(table_host, s);
+        GF_CHECK_ARG(r->n_s >= 0 && r->n_s <= 0x7fffffffLL, "gf_tile_stitch_scores: tile %d: n_s = %lld", s, r->n_s);
+        GF_CHECK_ARG(r->n_s == 0 || r->scores != 0, "gf_tile_stitch_scores: tile %d: NULL scores with n_s = %lld", s, r->n_s);
     }
     if (N == 0) return GF_OK;
     GF_CHECK_ARG(tile_of && local_of && out && (mode != GF_TILE_STITCH_CORE || core_of),

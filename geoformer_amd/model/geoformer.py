@@ -1275,7 +1275,8 @@ class GeoFormer(nn.Module):
                                                                      min_class=4)
         sel, cls, sc, counts = pointops.proposal_select_batched(final, cls_pred, scores)
         pending = PendingBatchProposals(n_scenes, scene_ids, table_d, sel, cls, sc, counts, fg_idxs.contiguous(),
-                                        logit_thresh, npts, int(table[:, 1].max()), knn_flags)
+                                        logit_thresh, npts,
+                                        int(postprocess.scene_rows(table, postprocess.PROP_ROW)["N"].max()), knn_flags)
         pending.keep = logits  # (the scatter reads the logit rows through the table)
         return pending if defer else pending.get()
 

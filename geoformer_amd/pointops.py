@@ -1701,7 +1701,8 @@ def segment_pool_batched(logits_list, seg_fg, fg_offsets):
     lib = _lib.load()
     ws = torch.empty(lib.gf_segment_pool_scratch_bytes(S, n_fg, nq) // 4 + 1, dtype=torch.int32, device=dev)
     check(lib.gf_segment_pool_batched(ptr(table_d), table.ctypes.data, S, nq, ptr(keys_sorted), ptr(order), n_fg,
-                                      int(table[:, 2].max()), ptr(ws), stream_ptr()), "gf_segment_pool_batched")
+                                      int(postprocess.scene_rows(table, postprocess.SEG_ROW)["N"].max()), ptr(ws),
+                                      stream_ptr()), "gf_segment_pool_batched")
     return outs
 
 
@@ -1872,13 +1873,15 @@ def tile_check_caps(table_host):
     t = np.asarray(table_host)
     if t.ndim != 2 or t.shape[1] != TILE_SCENE_FIELDS or t.dtype != np.int64:
         raise RuntimeError(f"tile scene table: expected int64 [T, {TILE_SCENE_FIELDS}], got {t.dtype} {t.shape}")
-    most = int(t[:, 4].max()) if len(t) else 0
+    from . import postprocess
+
+    p_s = postprocess.scene_rows(t, postprocess.TILE_ROW)["p_s"]
+    most = int(p_s.max()) if len(t) else 0
     if most > TILE_MAX_PICKS:
-        raise RuntimeError(f"tile merge: {most} picks in tile {int(t[:, 4].argmax())} (at most {TILE_MAX_PICKS} per "
-                           f"tile)")
-    if int(t[:, 4].sum()) > TILE_MAX_ROWS:
-        raise RuntimeError(f"tile merge: {int(t[:, 4].sum())} picked rows over {len(t)} tiles (at most {TILE_MAX_ROWS})")
-    return int(t[:, 4].sum())
+        raise RuntimeError(f"tile merge: {most} picks in tile {int(p_s.argmax())} (at most {TILE_MAX_PICKS} per tile)")
+    if int(p_s.sum()) > TILE_MAX_ROWS:
+        raise RuntimeError(f"tile merge: {int(p_s.sum())} picked rows over {len(t)} tiles (at most {TILE_MAX_ROWS})")
+    return int(p_s.sum())
 
 
 def _tile_tables(table, table_host, tile_of, local_of, name):
@@ -1981,7 +1984,7 @@ def tile_stitch_limits():
 def tile_stitch_scores(table, table_host, tile_of, local_of, core_of, C, mode):
     """out fp32 [N, C]: the scan's per-point scores from its tiles' (gf_tile_stitch_scores, the statement is
     postprocess.stitch_tiles_host): one launch on the current stream, no memset, no atomics, nothing read back.  table /
-    table_host: int64 [T, GF_TILE_SCORE_FIELDS] = {scores pointer fp32 [n_s, C], n_s} on the device and on the host;
+    table_host: int64 [T, GF_TILE_SCORE_FIELDS] (postprocess.tile_score_table) on the device and on the host;
     tile_of, local_of int32 [N, 4] and core_of int32 [N] on the device: the plan's point tables; mode "core" or "mean".
     Shapes that disagree or C above the cap raise before anything is launched."""
     if mode not in TILE_STITCH_MODES:

@@ -15,6 +15,38 @@ NMS_SCENE_FIELDS = _abi.const("GF_NMS_SCENE_FIELDS")
 NMS_MAX_N = _abi.const("GF_NMS_MAX_N")
 
 
+# ---- a scene table's layout is its row struct in include/geoformer_hip.h: here a numpy record dtype, read by member name --
+PROP_ROW, NMS_ROW, LBL_ROW, SEG_ROW, TILE_ROW, TILE_SCORE_ROW, BOX_SCENE_ROW, BOX_IOU_ROW = (
+    np.dtype(_abi.struct("Gf" + name)) for name in ("PropScene", "NmsScene", "LblScene", "SegScene", "TileScene",
+                                                    "TileScore", "BoxScene", "BoxIouScene"))
+
+
+def scene_table(S, row):
+    """(table, rows): a zeroed int64 [S, F] scene table and its [S] record view (the same memory) for the row struct."""
+    rows = np.zeros(S, dtype=row)
+    return rows.view(np.int64).reshape(S, row.itemsize // 8), rows
+
+
+def scene_rows(table, row):
+    """The [S] record view of a host scene table int64 [S, F] (the same memory when the table is contiguous)."""
+    return np.ascontiguousarray(table, dtype=np.int64).view(row).reshape(-1)
+
+
+def _columns(name):
+    """The columns of an output row struct whose members share one scalar type, by member name: an index, or a slice
+    for an array member -- for numpy arrays and tensors [rows, columns] alike."""
+    cols = {}
+    for m, (dt, off, *_) in np.dtype(_abi.struct(name)).fields.items():
+        at, n = off // dt.base.itemsize, dt.itemsize // dt.base.itemsize
+        cols[m] = slice(at, at + n) if dt.shape else at
+    return type(name, (), cols)
+
+
+def _excl(a):
+    """Exclusive cumulative sum of a [S] array ([] when S == 0)."""
+    return np.concatenate([[0], np.cumsum(a)[:-1]]) if len(a) else []
+
+
 def matrix_non_max_suppression(proposals_pred, scores, categories, kernel="gaussian", sigma=2.0,
                                final_score_thresh=0.05):
     """Same signature and result as the reference: indices (into the inputs) of the proposals whose decayed score
@@ -81,12 +113,12 @@ def proposal_scene_table(logit_ptrs, fg_offsets, point_starts, point_counts):
     pc = np.asarray(point_counts, dtype=np.int64).reshape(-1)
     if fo.shape != (S + 1,) or ps.shape != (S,) or pc.shape != (S,):
         raise ValueError(f"proposal_scene_table: {S} scenes need S+1 foreground offsets and S point starts / counts")
-    t = np.zeros((S, PROP_SCENE_FIELDS), dtype=np.int64)
-    t[:, 0] = np.asarray(logit_ptrs, dtype=np.int64)
-    t[:, 1] = np.diff(fo)
-    t[:, 2] = fo[:-1]
-    t[:, 3] = ps
-    t[:, 4] = pc
+    t, r = scene_table(S, PROP_ROW)
+    r["logits"] = np.asarray(logit_ptrs, dtype=np.int64)
+    r["N"] = np.diff(fo)
+    r["fg_off"] = fo[:-1]
+    r["pt_off"] = ps
+    r["num_points"] = pc
     return t
 
 
@@ -102,15 +134,13 @@ def nms_scene_table(mask_ptrs, widths, ns, score_ptrs, cat_ptrs):
         raise ValueError(f"matrix NMS: at most {NMS_MAX_N} proposals per scene, got {int(n.max())}")
     words = n * ((N + 63) // 64)
     S = n.shape[0]
-    t = np.zeros((S, NMS_SCENE_FIELDS), dtype=np.int64)
-    t[:, 0] = np.asarray(mask_ptrs, dtype=np.int64)
-    t[:, 1] = np.where(n > 0, N, 0)
-    t[:, 2] = n
-    t[:, 3] = np.concatenate([[0], np.cumsum(words)[:-1]]) if S else []
-    t[:, 4] = np.concatenate([[0], np.cumsum(n * n)[:-1]]) if S else []
-    t[:, 5] = np.asarray(score_ptrs, dtype=np.int64)
-    t[:, 6] = np.asarray(cat_ptrs, dtype=np.int64)
-    t[:, 7] = np.concatenate([[0], np.cumsum(n)[:-1]]) if S else []
+    t, r = scene_table(S, NMS_ROW)
+    r["masks"] = np.asarray(mask_ptrs, dtype=np.int64)
+    r["N"] = np.where(n > 0, N, 0)
+    r["n"] = n
+    r["bits_off"], r["inter_off"], r["pick_off"] = _excl(words), _excl(n * n), _excl(n)
+    r["scores"] = np.asarray(score_ptrs, dtype=np.int64)
+    r["cats"] = np.asarray(cat_ptrs, dtype=np.int64)
     sizes = {"bits": int(words.sum()), "inter": int((n * n).sum()), "picks": int(n.sum()),
              "max_waves": int(words.max()) if S else 0, "max_pairs": int((n * n).max()) if S else 0}
     return t, sizes
@@ -151,7 +181,7 @@ def _nms_batch_table(who, masks, scores, categories=None):
 def _split_picks(table, picks, counts):
     counts_h = counts.cpu().tolist()  # the one read-back
     picks = picks.long()
-    return [picks[int(table[b, 7]):int(table[b, 7]) + counts_h[b]] for b in range(table.shape[0])]
+    return [picks[int(o):int(o) + counts_h[b]] for b, o in enumerate(scene_rows(table, NMS_ROW)["pick_off"])]
 
 
 def matrix_nms_batched(masks, scores, categories, kernel="gaussian", sigma=2.0, final_score_thresh=0.05):
@@ -265,8 +295,13 @@ class SceneLabels(NamedTuple):
         return SceneLabels(h(self.owner), h(self.ids), InstanceTable(*[h(c) for c in self.table]), h(self.masks))
 
 
+_LBL_I, _LBL_F = _columns("GfLblRowI"), _columns("GfLblRowF")
+
+
 def _table_from_packed(ti, tf):
-    return InstanceTable(ti[:, 0], ti[:, 1], ti[:, 2], ti[:, 3], ti[:, 4] != 0, tf[:, 9], tf[:, 0:3], tf[:, 3:6], tf[:, 6:9])
+    i, f = _LBL_I, _LBL_F
+    return InstanceTable(ti[:, i.count], ti[:, i.owned], ti[:, i.label_id], ti[:, i.pick], ti[:, i.kept] != 0,
+                         tf[:, f.score], tf[:, f.centroid], tf[:, f.box_min], tf[:, f.box_max])
 
 
 def _label_points_host(masks, scores, label_ids, pick, xyz, min_score):
@@ -321,15 +356,14 @@ def label_scene_table(mask_ptrs, widths, ns, ps, pick_ptrs, score_ptrs, label_pt
     S = N.shape[0]
     words = p * ((N + 63) // 64)
     parts = p * ((N + LBL_CHUNK - 1) // LBL_CHUNK)
-    excl = lambda a: np.concatenate([[0], np.cumsum(a)[:-1]]) if S else []  # noqa: E731
-    t = np.zeros((S, LBL_SCENE_FIELDS), dtype=np.int64)
-    t[:, 0] = np.asarray(mask_ptrs, dtype=np.int64)
-    t[:, 1], t[:, 2], t[:, 3] = N, n, p
-    t[:, 4] = np.asarray(pick_ptrs, dtype=np.int64)
-    t[:, 5] = np.asarray(score_ptrs, dtype=np.int64)
-    t[:, 6] = np.asarray(label_ptrs, dtype=np.int64)
-    t[:, 7] = np.asarray(xyz_ptrs, dtype=np.int64)
-    t[:, 8], t[:, 9], t[:, 10], t[:, 11] = excl(words), excl(parts), excl(p), excl(N)
+    t, r = scene_table(S, LBL_ROW)
+    r["masks"] = np.asarray(mask_ptrs, dtype=np.int64)
+    r["N"], r["n"], r["p"] = N, n, p
+    r["pick"] = np.asarray(pick_ptrs, dtype=np.int64)
+    r["scores"] = np.asarray(score_ptrs, dtype=np.int64)
+    r["label_ids"] = np.asarray(label_ptrs, dtype=np.int64)
+    r["xyz"] = np.asarray(xyz_ptrs, dtype=np.int64)
+    r["bits_off"], r["part_off"], r["row_off"], r["pt_off"] = _excl(words), _excl(parts), _excl(p), _excl(N)
     sizes = {"bits": int(words.sum()), "parts": int(parts.sum()), "rows": int(p.sum()), "points": int(N.sum()),
              "max_points": int(N.max()) if S else 0, "max_picks": int(p.max()) if S else 0}
     return t, sizes
@@ -371,8 +405,8 @@ def _label_batch_packed(masks, scores, label_ids, picks, xyzs, min_score):
 def _split_labels(table, pts, ti, tf):
     """One SceneLabels per row of the scene table: views of the packed buffers (device tensors or numpy arrays)."""
     out = []
-    for t in table:
-        N, p, r, o = int(t[1]), int(t[3]), int(t[10]), int(t[11])
+    for t in scene_rows(table, LBL_ROW):
+        N, p, r, o = int(t["N"]), int(t["p"]), int(t["row_off"]), int(t["pt_off"])
         out.append(SceneLabels(pts[0, o:o + N], pts[1, o:o + N], _table_from_packed(ti[r:r + p], tf[r:r + p])))
     return out
 
@@ -466,17 +500,15 @@ def segment_pool_host(logits, seg_fg):
 def segment_scene_table(in_ptrs, out_ptrs, fg_offsets):
     """int64 [S, fields] segment scene table of gf_segment_pool_batched: scene b's logits at in_ptrs[b], the pooled ones
     at out_ptrs[b] (both [nq, N_b]), its foreground rows fg_offsets[b]:fg_offsets[b+1] of the batch."""
-    from . import _lib
-
-    fo = np.asarray(fg_offsets, dtype=np.int64).reshape(-1)
+    fo =np.asarray(fg_offsets, dtype=np.int64).reshape(-1)
     S = len(in_ptrs)
     if fo.shape != (S + 1,) or len(out_ptrs) != S:
         raise ValueError(f"segment_scene_table: {S} scenes need S output pointers and S+1 foreground offsets")
-    t = np.zeros((S, _lib.load().gf_segment_pool_scene_fields()), dtype=np.int64)
-    t[:, 0] = np.asarray(in_ptrs, dtype=np.int64)
-    t[:, 1] = np.asarray(out_ptrs, dtype=np.int64)
-    t[:, 2] = np.diff(fo)
-    t[:, 3] = fo[:-1]
+    t, r = scene_table(S, SEG_ROW)
+    r["in"] = np.asarray(in_ptrs, dtype=np.int64)
+    r["out"] = np.asarray(out_ptrs, dtype=np.int64)
+    r["N"] = np.diff(fo)
+    r["off"] = fo[:-1]
     return t
 
 
@@ -648,6 +680,7 @@ def oversegment_host(xyz, I=None, deg=None, *, k=16, radius=0.07, normal_deg=15.
 
 # ---- picked masks split into connected clusters (csrc/mask_split.hip): the host statement -------------------------------
 MSP_TABLE_INTS = _abi.const("GF_MSP_TABLE_INTS")
+_MSP = _columns("GfMspRow")
 SPLIT_DEFAULTS = dict(radius=0.1, k=16, min_samples=1, min_points=50, mode="largest")
 SPLIT_MODES = ("largest", "split")
 
@@ -685,8 +718,8 @@ def mask_components_host(masks, pick, I, deg, min_samples=1, min_points=1):
       the largest cluster of a pick has the greatest size, ties go to the smaller id.
     With min_samples = 1 this is connected components of the graph restricted to the mask; with complete symmetric
     rows it is sklearn.cluster.DBSCAN(eps, min_samples) on the mask's points with the clusters named by their smallest
-    core index.  Returns (comp int32 [p, N]: the cluster id of every member point or -1, tab int32 [p, 5]: members,
-    clusters kept, points in kept clusters, id of the largest kept cluster or -1, its size)."""
+    core index.  Returns (comp int32 [p, N]: the cluster id of every member point or -1, tab int32 [p, MSP_TABLE_INTS]:
+    one GfMspRow of the header per rank)."""
     masks = np.asarray(_np(masks))
     pick = np.asarray(_np(pick)).astype(np.int64).reshape(-1)
     I, deg = np.asarray(_np(I)), np.asarray(_np(deg))
@@ -699,7 +732,7 @@ def mask_components_host(masks, pick, I, deg, min_samples=1, min_points=1):
     p = pick.shape[0]
     comp = np.full((p, N), -1, np.int32)
     tab = np.zeros((p, MSP_TABLE_INTS), np.int32)
-    tab[:, 3] = -1
+    tab[:, _MSP.largest] = -1
     if N == 0 or p == 0:
         return comp, tab
     src, col = np.nonzero(_valid_entries(I, deg, N))
@@ -715,7 +748,7 @@ def mask_components_host(masks, pick, I, deg, min_samples=1, min_points=1):
             continue
         done[row] = r
         M = masks[row] != 0
-        tab[r, 0] = M.sum()
+        tab[r, _MSP.members] = M.sum()
         inside = M[src] & M[dst]
         cnt = 1 + np.bincount(src[inside], minlength=N)
         core = M & (cnt >= min_samples)
@@ -731,10 +764,10 @@ def mask_components_host(masks, pick, I, deg, min_samples=1, min_points=1):
         ids[(ids >= 0) & (size[np.maximum(ids, 0)] < min_points)] = -1
         comp[r] = ids
         kept = np.unique(ids[ids >= 0])  # ascending: argmax takes the smaller id among equal sizes
-        tab[r, 1], tab[r, 2] = len(kept), (ids >= 0).sum()
+        tab[r, _MSP.clusters], tab[r, _MSP.kept_points] = len(kept), (ids >= 0).sum()
         if len(kept):
             big = kept[np.argmax(size[kept])]
-            tab[r, 3], tab[r, 4] = big, size[big]
+            tab[r, _MSP.largest], tab[r, _MSP.largest_size] = big, size[big]
     return comp, tab
 
 
@@ -745,7 +778,7 @@ def mask_keep_largest_host(masks, pick, comp, tab):
     out = masks.copy()
     for r, row in enumerate(np.asarray(_np(pick)).reshape(-1).tolist()):
         if 0 <= row < masks.shape[0]:
-            big = int(tab[r, 3])
+            big = int(tab[r, _MSP.largest])
             out[row] = np.where((comp[r] == big) & (big >= 0), masks[row], 0)
     return out
 
@@ -905,19 +938,18 @@ def merge_tiles_host(plan, per_tile, *, iom=0.5, min_shared=20, return_tables=Fa
 
 def tile_scene_table(plan, rows):
     """(table int64 [T, GF_TILE_SCENE_FIELDS], sizes) of gf_tile_pack_picks / gf_tile_overlaps / gf_tile_assemble from
-    _tile_rows' device tensors: {masks pointer, n_rows, n_s, pick pointer, p_s, first row, first word}; sizes: P rows,
-    uint32 words of the bitsets, row_tile int32 [P]."""
-    T = plan.T
-    table = np.zeros((T, TILE_SCENE_FIELDS), np.int64)
+    _tile_rows' device tensors, one GfTileScene of the header per tile; sizes: P rows, uint32 words of the bitsets,
+    row_tile int32 [P]."""
+    table, recs = scene_table(plan.T, TILE_ROW)
     row = word = 0
     row_tile = []
     for s, (masks, pick, _, _) in enumerate(rows):
         n_s = int(plan.offsets[s + 1] - plan.offsets[s])
         p_s = 0 if masks is None else int(pick.shape[0])
+        r = recs[s]
+        r["n_s"], r["first_row"], r["first_word"] = n_s, row, word
         if p_s:
-            table[s] = (masks.data_ptr(), masks.shape[0], n_s, pick.data_ptr(), p_s, row, word)
-        else:
-            table[s] = (0, 0, n_s, 0, 0, row, word)
+            r["masks"], r["n_rows"], r["pick"], r["p_s"] = masks.data_ptr(), masks.shape[0], pick.data_ptr(), p_s
         row += p_s
         word += n_s * ((p_s + 31) // 32)
         row_tile += [s] * p_s
@@ -1053,6 +1085,16 @@ def stitch_tiles_host(plan, per_tile_scores, mode):
     return out
 
 
+def tile_score_table(tiles):
+    """int64 [T, GF_TILE_SCORE_FIELDS] tile score table of gf_tile_stitch_scores, one GfTileScore of the header per
+    tile: the tile's scores tensor [n_s, C], or None for an empty tile (a row of zeros)."""
+    table, recs = scene_table(len(tiles), TILE_SCORE_ROW)
+    for r, x in zip(recs, tiles):
+        if x is not None:
+            r["scores"], r["n_s"] = x.data_ptr(), x.shape[0]
+    return table
+
+
 def stitch_tiles(plan, per_tile_scores, mode):
     """stitch_tiles_host on the tensors' device and the current stream (csrc/tile_stitch.hip, one launch of
     pointops.tile_stitch_scores for any number of tiles): fp32 [N, C], bit-identical to the host statement and from call
@@ -1066,13 +1108,10 @@ def stitch_tiles(plan, per_tile_scores, mode):
     from . import pointops
 
     C, tiles = _stitch_tiles_checked(plan, per_tile_scores, mode, "stitch_tiles")
-    table = np.zeros((plan.T, TILE_SCORE_FIELDS), np.int64)
     for s, x in enumerate(tiles):
-        if x is None:
-            continue
-        if not (torch.is_tensor(x) and x.device == dev and x.is_contiguous()):
+        if x is not None and not (torch.is_tensor(x) and x.device == dev and x.is_contiguous()):
             raise ValueError(f"stitch_tiles: tile {s}: expected a contiguous float32 tensor on {dev}")
-        table[s] = (x.data_ptr(), x.shape[0])
+    table = tile_score_table(tiles)
     if plan.N == 0:
         return torch.empty((0, C), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
@@ -1263,10 +1302,15 @@ def box_angle_table(angles=BOX_ANGLES):
     return np.stack([np.cos(th), np.sin(th)], axis=1).astype(np.float32)
 
 
+_BOX = _columns("GfBox")
+
+
 def _boxes_from_rows(rows, count, A):
-    idx = rows[:, 8]
+    b = _BOX
+    idx = rows[:, b.angle]
     i32 = idx.to(torch.int32) if torch.is_tensor(idx) else idx.astype(np.int32)
-    return Boxes(rows[:, 0:3], rows[:, 3:6], rows[:, 6], rows[:, 7], idx * (np.pi / 2 / A), i32, count, rows)
+    return Boxes(rows[:, b.cx:b.cz + 1], rows[:, b.du:b.dz + 1], rows[:, b.c], rows[:, b.s], idx * (np.pi / 2 / A), i32,
+                 count, rows)
 
 
 def _box_rows_of(b):
@@ -1276,12 +1320,16 @@ def _box_rows_of(b):
     if b.rows is not None:
         return b.rows
     if torch.is_tensor(b.center):
-        col = lambda v: v.to(torch.float64).reshape(-1, 1)  # noqa: E731
-        return torch.cat([b.center.to(torch.float64), b.size.to(torch.float64), col(b.cos), col(b.sin),
-                          col(b.angle_index), col(b.count)], dim=1).contiguous()
-    col = lambda v: np.asarray(v, dtype=np.float64).reshape(-1, 1)  # noqa: E731
-    return np.concatenate([np.asarray(b.center, np.float64).reshape(-1, 3), np.asarray(b.size, np.float64).reshape(-1, 3),
-                           col(b.cos), col(b.sin), col(b.angle_index), col(b.count)], axis=1)
+        rows = torch.empty((b.center.shape[0], BOX_FLOATS), dtype=torch.float64, device=b.center.device)
+        center, size = b.center, b.size
+    else:
+        center, size = np.asarray(b.center, np.float64).reshape(-1, 3), np.asarray(b.size, np.float64).reshape(-1, 3)
+        rows = np.empty((center.shape[0], BOX_FLOATS))
+    c = _BOX
+    rows[:, c.cx:c.cz + 1], rows[:, c.du:c.dz + 1] = center, size
+    for at, v in ((c.c, b.cos), (c.s, b.sin), (c.angle, b.angle_index), (c.count, b.count)):
+        rows[:, at] = v if torch.is_tensor(v) else np.asarray(v, dtype=np.float64).reshape(-1)
+    return rows
 
 
 def _float_keys(a):
@@ -1299,8 +1347,11 @@ def _box_row(ulo, uhi, vlo, vhi, zlo, zhi, c, s, index, count):
     d = np.float64
     ulo, uhi, vlo, vhi, zlo, zhi, c, s = (d(v) for v in (ulo, uhi, vlo, vhi, zlo, zhi, c, s))
     lu, lv = (ulo + uhi) * d(0.5), (vlo + vhi) * d(0.5)
-    return [lu * c - lv * s, lu * s + lv * c, (zlo + zhi) * d(0.5), uhi - ulo, vhi - vlo, zhi - zlo, c, s, d(index),
-            d(count)]
+    row, b = np.empty(BOX_FLOATS), _BOX
+    row[b.cx], row[b.cy], row[b.cz] = lu * c - lv * s, lu * s + lv * c, (zlo + zhi) * d(0.5)
+    row[b.du], row[b.dv], row[b.dz] = uhi - ulo, vhi - vlo, zhi - zlo
+    row[b.c], row[b.s], row[b.angle], row[b.count] = c, s, d(index), d(count)
+    return row
 
 
 def _box_rows_host(members, xyz, table):
@@ -1372,13 +1423,13 @@ def box_scene_table(forms, widths, ns, ps, group_ptrs, pick_ptrs, xyz_ptrs):
     if (p > BOX_MAX_GROUPS).any():
         raise ValueError(f"boxes: at most {BOX_MAX_GROUPS} groups per scene, got {int(p.max())}")
     S = N.shape[0]
-    t = np.zeros((S, BOX_SCENE_FIELDS), dtype=np.int64)
-    t[:, 0] = [BOX_FORMS[f] for f in forms]
-    t[:, 1], t[:, 2], t[:, 3] = N, n, p
-    t[:, 4] = np.asarray(group_ptrs, dtype=np.int64)
-    t[:, 5] = np.asarray(pick_ptrs, dtype=np.int64)
-    t[:, 6] = np.asarray(xyz_ptrs, dtype=np.int64)
-    t[:, 7] = np.concatenate([[0], np.cumsum(p)[:-1]]) if S else []
+    t, r = scene_table(S, BOX_SCENE_ROW)
+    r["form"] = [BOX_FORMS[f] for f in forms]
+    r["N"], r["n"], r["p"] = N, n, p
+    r["group"] = np.asarray(group_ptrs, dtype=np.int64)
+    r["pick"] = np.asarray(pick_ptrs, dtype=np.int64)
+    r["xyz"] = np.asarray(xyz_ptrs, dtype=np.int64)
+    r["row_off"] = _excl(p)
     sizes = {"rows": int(p.sum()), "max_points": int(N.max()) if S else 0, "max_groups": int(p.max()) if S else 0}
     return t, sizes
 
@@ -1391,9 +1442,8 @@ def box_iou_table(Ps, Gs):
     if P.shape != G.shape or (P < 0).any() or (G < 0).any():
         raise ValueError("box_iou_table: one non-negative count per scene in both lists")
     S = P.shape[0]
-    excl = lambda a: np.concatenate([[0], np.cumsum(a)[:-1]]) if S else []  # noqa: E731
-    t = np.zeros((S, BOX_IOU_FIELDS), dtype=np.int64)
-    t[:, 0], t[:, 1], t[:, 2], t[:, 3], t[:, 4] = P, G, excl(P), excl(G), excl(P * G)
+    t, r = scene_table(S, BOX_IOU_ROW)
+    r["P"], r["G"], r["a_off"], r["b_off"], r["out_off"] = P, G, _excl(P), _excl(G), _excl(P * G)
     sizes = {"a": int(P.sum()), "b": int(G.sum()), "out": int((P * G).sum()), "max_pairs": int((P * G).max()) if S else 0}
     return t, sizes
 
@@ -1450,8 +1500,8 @@ def _boxes_packed(specs, angles):
 
 def _split_boxes(table, count, rows, A):
     out = []
-    for t in table:
-        p, o = int(t[3]), int(t[7])
+    for t in scene_rows(table, BOX_SCENE_ROW):
+        p, o = int(t["p"]), int(t["row_off"])
         out.append(_boxes_from_rows(rows[o:o + p], count[o:o + p], A))
     return out
 
@@ -1541,20 +1591,20 @@ def box_iou_host(a, b):
     of gf_box_iou_batched (include/geoformer_hip.h gives the rules), numpy float64 ufuncs in the kernel's order."""
     A = np.asarray(_np(_box_rows_of(a)), dtype=np.float64).reshape(-1, BOX_FLOATS)
     B = np.asarray(_np(_box_rows_of(b)), dtype=np.float64).reshape(-1, BOX_FLOATS)
-    P, G = A.shape[0], B.shape[0]
+    P, G, k = A.shape[0], B.shape[0], _BOX
     if P == 0 or G == 0:
         return np.zeros((P, G))
     A, B = np.repeat(A, G, axis=0), np.tile(B, (P, 1))  # one row per pair
-    hau, hav, haz = A[:, 3] * 0.5, A[:, 4] * 0.5, A[:, 5] * 0.5
-    hbu, hbv, hbz = B[:, 3] * 0.5, B[:, 4] * 0.5, B[:, 5] * 0.5
-    volA, volB = (A[:, 3] * A[:, 4]) * A[:, 5], (B[:, 3] * B[:, 4]) * B[:, 5]
-    oz = _overlap_1d(B[:, 2] - A[:, 2], haz, hbz)
-    area = _overlap_1d(B[:, 0] - A[:, 0], hau, hbu) * _overlap_1d(B[:, 1] - A[:, 1], hav, hbv)
-    poly = np.nonzero((A[:, 7] != 0.0) | (B[:, 7] != 0.0))[0]
+    hau, hav, haz = A[:, k.du] * 0.5, A[:, k.dv] * 0.5, A[:, k.dz] * 0.5
+    hbu, hbv, hbz = B[:, k.du] * 0.5, B[:, k.dv] * 0.5, B[:, k.dz] * 0.5
+    volA, volB = (A[:, k.du] * A[:, k.dv]) * A[:, k.dz], (B[:, k.du] * B[:, k.dv]) * B[:, k.dz]
+    oz = _overlap_1d(B[:, k.cz] - A[:, k.cz], haz, hbz)
+    area = _overlap_1d(B[:, k.cx] - A[:, k.cx], hau, hbu) * _overlap_1d(B[:, k.cy] - A[:, k.cy], hav, hbv)
+    poly = np.nonzero((A[:, k.s] != 0.0) | (B[:, k.s] != 0.0))[0]
     if poly.shape[0]:
         a_, b_ = A[poly], B[poly]
-        ca, sa, cb, sb = a_[:, 6], a_[:, 7], b_[:, 6], b_[:, 7]
-        dx, dy = a_[:, 0] - b_[:, 0], a_[:, 1] - b_[:, 1]
+        ca, sa, cb, sb = a_[:, k.c], a_[:, k.s], b_[:, k.c], b_[:, k.s]
+        dx, dy = a_[:, k.cx] - b_[:, k.cx], a_[:, k.cy] - b_[:, k.cy]
         cu, cv = dx * cb + dy * sb, dy * cb - dx * sb
         cr, sr = ca * cb + sa * sb, sa * cb - ca * sb
         ux, uy, vx, vy = hau[poly] * cr, hau[poly] * sr, hav[poly] * sr, hav[poly] * cr
@@ -1595,7 +1645,7 @@ def box_iou_batched(a_list, b_list):
     table, sizes = box_iou_table([r.shape[0] for r in ra], [r.shape[0] for r in rb])
     cat = lambda rs: (rs[0] if len(rs) == 1 else torch.cat(rs)).contiguous() if rs else torch.zeros((0, BOX_FLOATS), dtype=torch.float64, device=dev)  # noqa: E731
     out = pointops.box_iou_batched(pointops._table_dev(table, dev), sizes, cat(ra), cat(rb))
-    return [out[int(t[4]):int(t[4]) + int(t[0]) * int(t[1])].view(int(t[0]), int(t[1])) for t in table]
+    return [out[o:o + P * G].view(P, G) for P, G, o in scene_rows(table, BOX_IOU_ROW)[["P", "G", "out_off"]].tolist()]
 
 
 def box_iou(a, b):

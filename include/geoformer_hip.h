@@ -736,11 +736,19 @@ int gf_mask_intersections(const int32_t* masks, int n, int N, void* scratch, int
  * (model/geoformer/geoformer.py:193-262) and matrix NMS (util/utils_3d.py:95-141) once per scene, in a fixed number of
  * launches.  Each call reads a device scene table of int64 rows.
  * =================================================================================== */
-/* Proposal scene table, int64 [S, GF_PROP_SCENE_FIELDS], one row per scene:
- *   {mask-logit pointer (fp32 [nq, N_b]), N_b (the scene's foreground points), fg_off (first column of the scene in
- *    sem_prob / first entry in fg_idxs), pt_off (first point of the scene in the batch), num_points (the scene's
- *    points), 0}. */
+/* Every scene table below is an int64 [S, GF_*_FIELDS] array whose row is the struct declared next to the constant:
+ * every member one int64 word (a pointer is its address), in column order.  Kernels, host checks and the Python side
+ * read a row through the struct's member names only. */
+/* Proposal scene table, int64 [S, GF_PROP_SCENE_FIELDS], one GfPropScene per scene. */
 #define GF_PROP_SCENE_FIELDS 6
+typedef struct {
+    long long logits;     /* mask-logit pointer (fp32 [nq, N_b]) */
+    long long N;          /* N_b, the scene's foreground points */
+    long long fg_off;     /* first column of the scene in sem_prob / first entry in fg_idxs */
+    long long pt_off;     /* first point of the scene in the batch */
+    long long num_points; /* the scene's points */
+    long long pad_;       /* 0 */
+} GfPropScene;
 /* gf_proposal_stats per (scene, query): the same formula and workgroup shape (bit-identical per query).
  *   cls_logits fp32 [S, nq, ncls], sem_prob fp32 CLASS-MAJOR [ncls, sem_stride] over the batch's foreground points;
  *   outputs int32 / fp32 [S, nq]. */
@@ -758,11 +766,17 @@ int gf_proposal_scatter_batched(const long long* table, int S, int nq, const int
                                 int total_rows, int max_N, const long long* fg_idxs, float logit_thresh, int* packed,
                                 void* stream);
 
-/* NMS scene table, int64 [S, GF_NMS_SCENE_FIELDS], one row per scene:
- *   {masks pointer (int32 [n_b, N_b], nonzero = member), N_b, n_b, bits_off (uint64 words into the bits scratch,
- *    n_b * ceil(N_b / 64) of them), inter_off (int32 elements into inter, n_b * n_b of them), scores pointer
- *    (fp32 [n_b]), categories pointer (int64 [n_b]), pick_off (int32 elements into picks, n_b of them)}. */
+/* NMS scene table, int64 [S, GF_NMS_SCENE_FIELDS], one GfNmsScene per scene. */
 #define GF_NMS_SCENE_FIELDS 8
+typedef struct {
+    long long masks;     /* masks pointer (int32 [n_b, N_b], nonzero = member) */
+    long long N, n;      /* N_b, n_b */
+    long long bits_off;  /* uint64 words into the bits scratch, n_b * ceil(N_b / 64) of them */
+    long long inter_off; /* int32 elements into inter, n_b * n_b of them */
+    long long scores;    /* scores pointer (fp32 [n_b]) */
+    long long cats;      /* categories pointer (int64 [n_b]) */
+    long long pick_off;  /* int32 elements into picks, n_b of them */
+} GfNmsScene;
 #define GF_NMS_MAX_N 1024
 /* gf_mask_intersections per scene: inter + inter_off is scene b's [n_b, n_b] block.  max_waves / max_pairs: the
  * largest n_b * ceil(N_b / 64) / n_b * n_b over the scenes. */
@@ -795,25 +809,41 @@ int gf_greedy_nms_ious(const float* ious, const float* scores, int n, float thre
  * skipped, a later paint wins): the owner of a point is the LOWEST rank r in pick whose score is >= min_score and whose
  * mask covers the point.  Three launches for any S, n, p; no read-back; no atomics in global memory (bit-identical
  * results from call to call, and for a scene alone or in a batch).
- * Label scene table, int64 [S, GF_LBL_SCENE_FIELDS], one row per scene:
- *   {masks pointer (int32 [n_b, N_b], nonzero = member), N_b, n_b, p_b (<= GF_NMS_MAX_N), pick pointer (int64 [p_b],
- *    rows of masks; a value outside [0, n_b) is an empty, not-kept row), scores pointer (fp32 [n_b]), label_ids pointer
- *    (int64 [n_b]), xyz pointer (fp32 [N_b, 3]), bits_off (uint64 words into bits, p_b * ceil(N_b / 64) of them),
- *    part_off (records into part_f / part_cnt / own_part, p_b * ceil(N_b / GF_LBL_CHUNK) of them), row_off (rows into
- *    tab_i / tab_f, p_b of them), pt_off (elements into owner / ids, N_b of them)}.
+ * Label scene table, int64 [S, GF_LBL_SCENE_FIELDS], one GfLblScene per scene.
  * Scratch: bits, part_f fp32 [records, 9], part_cnt int32 [records], own_part int32 [GF_LBL_OWN_SPLIT * records].
  * Outputs:
  *   owner int32: rank into pick or -1;  ids int32: label_ids[pick[owner]] * 1000 + owner + 1, 0 without an owner;
- *   tab_i int32 [rows, GF_LBL_TABLE_INTS]   = {count (points of the mask), owned (points with owner == r), label_id,
- *                                              pick[r], kept (score >= min_score)};
- *   tab_f fp32  [rows, GF_LBL_TABLE_FLOATS] = {centroid xyz, box_min xyz, box_max xyz (over the whole mask; zeros when
- *                                              count == 0), score}.
+ *   tab_i int32 [rows, GF_LBL_TABLE_INTS], one GfLblRowI per rank;  tab_f fp32 [rows, GF_LBL_TABLE_FLOATS], one GfLblRowF.
  * max_points / max_picks: the largest N_b / p_b over the scenes. */
 #define GF_LBL_SCENE_FIELDS 12
 #define GF_LBL_CHUNK 4096
 #define GF_LBL_OWN_SPLIT 4
 #define GF_LBL_TABLE_INTS 5
 #define GF_LBL_TABLE_FLOATS 10
+typedef struct {
+    long long masks;     /* masks pointer (int32 [n_b, N_b], nonzero = member) */
+    long long N, n;      /* N_b, n_b */
+    long long p;         /* p_b (<= GF_NMS_MAX_N) */
+    long long pick;      /* pick pointer (int64 [p_b], rows of masks; a value outside [0, n_b) is an empty, not-kept row) */
+    long long scores;    /* scores pointer (fp32 [n_b]) */
+    long long label_ids; /* label_ids pointer (int64 [n_b]) */
+    long long xyz;       /* xyz pointer (fp32 [N_b, 3]) */
+    long long bits_off;  /* uint64 words into bits, p_b * ceil(N_b / 64) of them */
+    long long part_off;  /* records into part_f / part_cnt / own_part, p_b * ceil(N_b / GF_LBL_CHUNK) of them */
+    long long row_off;   /* rows into tab_i / tab_f, p_b of them */
+    long long pt_off;    /* elements into owner / ids, N_b of them */
+} GfLblScene;
+typedef struct {
+    int count;    /* points of the mask */
+    int owned;    /* points with owner == r */
+    int label_id;
+    int pick;     /* pick[r] */
+    int kept;     /* score >= min_score */
+} GfLblRowI;
+typedef struct {
+    float centroid[3], box_min[3], box_max[3]; /* xyz each, over the whole mask; zeros when count == 0 */
+    float score;
+} GfLblRowF;
 int gf_label_map_batched(const long long* table, int S, long long max_points, int max_picks, float min_score,
                          void* bits, float* part_f, int32_t* part_cnt, int32_t* own_part, int32_t* owner, int32_t* ids,
                          int32_t* tab_i, float* tab_f, void* stream);
@@ -907,9 +937,7 @@ int gf_panoptic_overlaps(const int32_t* owner, const int32_t* ids, const int32_t
  * Mask logits pooled over a scene's over-segments (superpoints; ScanNet's *.segs.json, field segIndices) for the S
  * kept scenes of an eval forward (csrc/segment_pool.hip), between the mask head and gf_proposal_stats*:
  *     out[q, p] = mean of in[q, p'] over the foreground points p' of the scene in p's segment
- *   Segment scene table, int64 [S, gf_segment_pool_scene_fields()], one row per scene:
- *     {logits in (fp32 [nq, N_b]), logits out (fp32 [nq, N_b]), N_b (the scene's foreground points), fg_off (the
- *      scene's first foreground row in the batch; the rows of the scenes follow each other)}.
+ *   Segment scene table, int64 [S, gf_segment_pool_scene_fields()], one GfSegScene (below) per scene.
  *   table (device) and table_host (the same rows on the host, or NULL): given, table_host is checked before anything
  *   is launched -- out == in (the pooling is out of place), a NULL pointer with N_b > 0, N_b > max_N, rows that do not
  *   follow each other or do not add up to n_fg are GF_ERR_INVALID_ARG.  Not given, nothing is read back and a scene
@@ -930,7 +958,12 @@ int gf_panoptic_overlaps(const int32_t* owner, const int32_t* ids, const int32_t
  *   count -- bit-identical from call to call and for a scene alone or inside a batch; a segment of one row returns
  *   its logit bit for bit.
  *   scratch: gf_segment_pool_scratch_bytes(S, n_fg, nq). */
-int gf_segment_pool_scene_fields(void);
+typedef struct {
+    long long in, out; /* logits in / out pointers (fp32 [nq, N_b]) */
+    long long N;       /* N_b, the scene's foreground points */
+    long long off;     /* fg_off: the scene's first foreground row in the batch; the rows of the scenes follow each other */
+} GfSegScene;
+int gf_segment_pool_scene_fields(void); /* = sizeof(GfSegScene) / 8 */
 int gf_segment_pool_chunk_points(void);
 size_t gf_segment_pool_scratch_bytes(int S, long long n_fg, int nq);
 int gf_segment_pool_batched(const long long* table, const long long* table_host, int S, int nq,
@@ -980,8 +1013,8 @@ int gf_smooth_components(const float* xyz, const float* normals4, const int32_t*
  *   suffices); a cluster's id is its smallest core index.  A member that is not core (a BORDER point) takes the smallest
  *   cluster id among the core entries of its own row, -1 without one.  A cluster of fewer than min_points points (core
  *   and border) is dissolved to -1.
- *   comp int32 [p, N]: the cluster id of every member point or -1;  tab int32 [p, GF_MSP_TABLE_INTS]: {members, clusters
- *   kept, points in kept clusters, id of the largest kept cluster (ties: the smaller id) or -1, its size}.
+ *   comp int32 [p, N]: the cluster id of every member point or -1;  tab int32 [p, GF_MSP_TABLE_INTS]: one GfMspRow
+ *   per rank.
  *   Integer atomics only: comp and tab are a function of the inputs, bit-identical from call to call, and a pick's rows
  *   are the same alone or among other picks.  scratch: gf_mask_components_scratch_bytes(N, p), 8-byte aligned.
  * gf_mask_keep_largest (one launch): masks_out int32 [n_rows, N] (not overlapping masks) -- a picked row keeps its
@@ -991,6 +1024,13 @@ int gf_smooth_components(const float* xyz, const float* normals4, const int32_t*
  * GF_ERR_INVALID_ARG before anything is launched; N == 0 or p == 0 succeeds with nothing launched (masks_out is then
  * not written).  Every launch goes on `stream`; no host synchronisation, no read-back. */
 enum { GF_MSP_TABLE_INTS = 5 }; /* columns of tab */
+typedef struct {
+    int members;
+    int clusters;     /* clusters kept */
+    int kept_points;  /* points in kept clusters */
+    int largest;      /* id of the largest kept cluster (ties: the smaller id) or -1 */
+    int largest_size; /* its size */
+} GfMspRow;
 size_t gf_mask_components_scratch_bytes(int N, int p);
 int gf_mask_components(const int32_t* masks, int n_rows, int N, const long long* pick, int p, const int32_t* I,
                        const int32_t* deg, int k, int min_samples, int min_points, int32_t* comp, int32_t* tab,
@@ -1003,10 +1043,7 @@ int gf_mask_keep_largest(const int32_t* masks, int n_rows, int N, const long lon
  * is postprocess.merge_tiles_host, the tile plan scene.tile_plan).  The device receives integer tables only:
  *   tile_of, local_of int32 [N, 4], 16-byte aligned: the tiles of each of the scan's N points in ascending order, -1
  *   padded, and the point's index inside each of them.
- *   Tile scene table, int64 [T, GF_TILE_SCENE_FIELDS], one row per tile s (an empty tile has n_s = 0):
- *     {masks pointer (int32 [n_rows, n_s], nonzero = member), n_rows, n_s, pick pointer (int64 [p_s], rows of masks; a
- *      value outside [0, n_rows) is an empty row), p_s (<= gf_tile_merge_max_picks()), first row (the p_s of the tiles
- *      before), first word (uint32 words into bits: the n * ceil(p / 32) of the tiles before)}.
+ *   Tile scene table, int64 [T, GF_TILE_SCENE_FIELDS], one GfTileScene per tile s (an empty tile has n_s = 0).
  *   table (device) and table_host (the same rows on the host): table_host is checked before anything is launched -- a
  *   negative size, p_s over the cap, first row / first word that do not follow the tile before, picks that do not add
  *   up to P, P > gf_tile_merge_max_rows() or T > 65535 are GF_ERR_INVALID_ARG.
@@ -1031,6 +1068,14 @@ int gf_mask_keep_largest(const int32_t* masks, int n_rows, int N, const long lon
  * Every output is a function of the inputs: bit-identical from call to call.  Every launch goes on `stream`; no host
  * synchronisation, no read-back. */
 enum { GF_TILE_SCENE_FIELDS = 7 }; /* int64 words per row of the tile scene table */
+typedef struct {
+    long long masks;       /* masks pointer (int32 [n_rows, n_s], nonzero = member) */
+    long long n_rows, n_s;
+    long long pick;        /* pick pointer (int64 [p_s], rows of masks; a value outside [0, n_rows) is an empty row) */
+    long long p_s;         /* <= gf_tile_merge_max_picks() */
+    long long first_row;   /* the p_s of the tiles before */
+    long long first_word;  /* uint32 words into bits: the n * ceil(p / 32) of the tiles before */
+} GfTileScene;
 int gf_tile_merge_max_rows(void);
 int gf_tile_merge_max_picks(void);
 int gf_tile_pack_picks(const long long* table, const long long* table_host, int T, int P, uint32_t* bits, void* stream);
@@ -1046,8 +1091,7 @@ int gf_tile_assemble(const long long* table, const long long* table_host, int T,
 
 /* Per-point semantic scores of a scan stitched from the scores of its T tiles (csrc/tile_stitch.hip; the statement is
  * postprocess.stitch_tiles_host).  tile_of, local_of as above; core_of int32 [N]: the tile whose core holds the point.
- *   Tile score table, int64 [T, GF_TILE_SCORE_FIELDS], one row per tile s (an empty tile has n_s = 0):
- *     {scores pointer (fp32 [n_s, C], contiguous, the tile's points in the tile's own order), n_s}.
+ *   Tile score table, int64 [T, GF_TILE_SCORE_FIELDS], one GfTileScore per tile s (an empty tile has n_s = 0).
  *   table (device) and table_host (the same rows on the host): table_host is checked before the launch -- a negative
  *   n_s, a NULL pointer with n_s > 0, T outside 1..65535, C outside 1..gf_tile_stitch_max_classes(), a mode other than
  *   the two below or N < 0 are GF_ERR_INVALID_ARG; N == 0 succeeds with nothing launched.
@@ -1060,6 +1104,10 @@ int gf_tile_assemble(const long long* table, const long long* table_host, int T,
  *   A tile id outside [0, T) or a local index outside [0, n_s) contributes nothing and is never an address.  No
  *   atomics: bit-identical from call to call.  The launch goes on `stream`; no host synchronisation, no read-back. */
 enum { GF_TILE_SCORE_FIELDS = 2 }; /* int64 words per row of the tile score table */
+typedef struct {
+    long long scores; /* scores pointer (fp32 [n_s, C], contiguous, the tile's points in the tile's own order) */
+    long long n_s;
+} GfTileScore;
 enum { GF_TILE_STITCH_CORE = 0, GF_TILE_STITCH_MEAN = 1 };
 int gf_tile_stitch_max_classes(void); /* = gf_semantic_confusion_max_classes(): the scores only ever go there */
 int gf_tile_stitch_scores(const long long* table, const long long* table_host, int T, const int32_t* tile_of,
@@ -1406,17 +1454,35 @@ int gf_aug_support_block(const GfAugBatch* b, long long* support_masks, int32_t*
  * `stream`; no host synchronisation, no read-back.
  * =================================================================================== */
 
-/* A box, GF_BOX_FLOATS float64: {cx, cy, cz, du, dv, dz, c, s, angle index, count}: du lies along (c, s), dv along
- * (-s, c), dz along z; an empty group is a row of zeros.
- * Box scene table, int64 [S, GF_BOX_SCENE_FIELDS], one row per scene:
- *   {form, N, n, p, groups, pick, xyz (fp32 [N, 3]), row_off (rows into count / aligned / oriented, p of them)}
- *   GF_BOX_FORM_ROWS: groups = masks int32 [n, N], nonzero = member (masks may overlap; NULL when n == 0); pick int64
+/* A box is one GfBox, GF_BOX_FLOATS float64; an empty group is a row of zeros.
+ * Box scene table, int64 [S, GF_BOX_SCENE_FIELDS], one GfBoxScene per scene:
+ *   GF_BOX_FORM_ROWS: group = masks int32 [n, N], nonzero = member (masks may overlap; NULL when n == 0); pick int64
  *     [p]: group r is row pick[r]; a pick outside [0, n) is an empty group, never an address.
- *   GF_BOX_FORM_IDS: groups = int32 [N] with values in [-1, p), -1 = no group (any other value outside [0, p) names no
+ *   GF_BOX_FORM_IDS: group = int32 [N] with values in [-1, p), -1 = no group (any other value outside [0, p) names no
  *     group either); n and pick are not read.
  * Limits, as functions: the points of one workgroup's chunk, the most angles, the most groups of one scene. */
 enum { GF_BOX_SCENE_FIELDS = 8, GF_BOX_FLOATS = 10, GF_BOX_IOU_FIELDS = 5 };
 enum { GF_BOX_FORM_ROWS = 0, GF_BOX_FORM_IDS = 1 };
+typedef struct {
+    double cx, cy, cz; /* centre */
+    double du, dv, dz; /* sizes: du lies along (c, s), dv along (-s, c), dz along z */
+    double c, s;       /* heading */
+    double angle;      /* index of the heading in `angles` */
+    double count;      /* points of the group */
+} GfBox;
+typedef struct {
+    long long form;    /* GF_BOX_FORM_ROWS / GF_BOX_FORM_IDS */
+    long long N, n, p;
+    long long group;   /* groups pointer, by form */
+    long long pick;    /* pick pointer (int64 [p]) */
+    long long xyz;     /* xyz pointer (fp32 [N, 3]) */
+    long long row_off; /* rows into count / aligned / oriented, p of them */
+} GfBoxScene;
+typedef struct {
+    long long P, G;
+    long long a_off, b_off; /* rows of a / of b */
+    long long out_off;      /* elements of out */
+} GfBoxIouScene;
 int gf_box_chunk(void);
 int gf_box_max_angles(void);
 int gf_box_max_groups(void);
@@ -1440,7 +1506,7 @@ int gf_instance_boxes_batched(const long long* table, int S, long long max_point
                               double* oriented, void* stream);
 
 /* gf_box_iou_batched (one launch, one thread per pair): the 3D IoU of every (a, b) pair of every scene.
- *   IoU table, int64 [S, GF_BOX_IOU_FIELDS]: {P, G, a_off (rows of a), b_off (rows of b), out_off (elements of out)};
+ *   IoU table, int64 [S, GF_BOX_IOU_FIELDS], one GfBoxIouScene per scene;
  *   a, b: packed boxes, float64 [., GF_BOX_FLOATS]; out: float64, scene block [P, G] row-major at out_off; max_pairs:
  *   the largest P G of the table.
  * float64, every + - * / rounded on its own, no sin / cos.  Per axis the overlap of two intervals with half sizes ha,

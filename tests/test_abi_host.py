@@ -44,7 +44,7 @@ def test_struct_layouts_match_the_c_compiler(tmp_path):
     if cc is None:
         pytest.skip("no C compiler on this machine")
     names = re.findall(r"^\}\s*(Gf\w+)\s*;", _header(), re.M)  # every typedef struct of the header, by its own regex
-    assert len(names) == 7 and not re.search(r"typedef\s+struct", _header("geoformer_hip_dev.h"))
+    assert len(names) == 7 + 12 and not re.search(r"typedef\s+struct", _header("geoformer_hip_dev.h"))
     want, lines = {}, ['#include <stddef.h>', '#include <stdio.h>', '#include "geoformer_hip_dev.h"', "int main(void) {"]
     for s in names:
         cls = _abi.struct(s)
@@ -67,7 +67,11 @@ def test_struct_layouts_match_the_c_compiler(tmp_path):
     assert got == want, {k: (got[k], want[k]) for k in want if got[k] != want[k]}
     sizes = {s: got[s, ""] for s in names}
     assert sizes == {"GfTrainOp": 112, "GfTrainLevel": 88, "GfResBlockParams": 56, "GfUnetLevelParams": 288,
-                     "GfUnetParams": 2336, "GfFeederJob": 584, "GfAugBatch": 280}
+                     "GfUnetParams": 2336, "GfFeederJob": 584, "GfAugBatch": 280,
+                     # the rows of the scene tables (8 bytes per column) and of the kernels' output tables
+                     "GfPropScene": 48, "GfNmsScene": 64, "GfLblScene": 96, "GfLblRowI": 20, "GfLblRowF": 40,
+                     "GfSegScene": 32, "GfMspRow": 20, "GfTileScene": 56, "GfTileScore": 16, "GfBox": 80,
+                     "GfBoxScene": 64, "GfBoxIouScene": 40}
 
 
 # written by hand from the header text (not produced by the parser), compared by ctypes class identity

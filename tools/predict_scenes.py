@@ -122,8 +122,9 @@ def write_boxes(out_dir, results, raws, kind, device="cuda"):
         p = int(lab.table.count.shape[0])
         b = postprocess.id_boxes(torch.as_tensor(lab.owner, device=device), p, xyz, oriented=kind == "oriented")
         rows = b.rows.cpu().numpy()
-        on = rows[:, 9] > 0  # (an instance that is not kept, or that lost every point to better ones, owns nothing)
-        b = postprocess._boxes_from_rows(rows[on], rows[on, 9].astype(np.int32), postprocess.BOX_ANGLES if kind == "oriented" else 1)
+        count = rows[:, postprocess._BOX.count]
+        on = count > 0  # (an instance that is not kept, or that lost every point to better ones, owns nothing)
+        b = postprocess._boxes_from_rows(rows[on], count[on].astype(np.int32), postprocess.BOX_ANGLES if kind == "oriented" else 1)
         export.write_boxes(os.path.join(out_dir, "boxes", f"{name}.txt"), b, np.asarray(lab.table.label_id)[on],
                            np.asarray(lab.table.score)[on])
         written += int(on.sum())
