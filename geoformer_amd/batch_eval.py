@@ -23,6 +23,11 @@
                                               # the tiles' semantic scores stitched per scan: "core" or "mean"
     for name, cls, scores, masks, pick in predict_batches(model, [(name, raw), ...], batch_size=4, density=Density()):
         ...                                   # a dense scan runs on one point per 2 cm cell; masks still int32 [n, N]
+    for name, cls, scores, masks, pick in predict_batches(model, [(name, raw), ...], batch_size=4, views=Views(rotations=4)):
+        ...                                   # every scene under 4 rotations; masks int32 [G, N]: the views' instances
+                                              # paired by mutual best IoU, masks by per-point vote, scores the views' mean
+    ap, avgs = evaluate(model, [(name, raw), ...], batch_size=4, views=Views(rotations=8), semantic=ev)
+                                              # ... and mIoU from the mean of the views' semantic scores
 
 A batch of raw scenes ([N, 8] = xyz, rgb, semantic label, instance label, as prepare_data_inst.py stores them) is
 collated on the host (scene.collate_raw), uploaded and voxelised on the GPU one batch ahead (feeder.DeviceFeeder), and
@@ -223,16 +228,12 @@ class _TileSemantics:
         self.left = {n: int((np.diff(p.offsets) > 0).sum()) for n, p in plans.items()}
         self.kept = {}
 
-    def _hand_on(self, scores, labels, name):
-        off = torch.tensor([0, scores.shape[0]], dtype=torch.int32)
-        self.inner.add_batch(scores, labels, off.to(scores.device, non_blocking=True), [name], offsets_host=off)
-
     def add_batch(self, scores, labels, offsets, names, offsets_host=None):
         off = [int(o) for o in (offsets if offsets_host is None else offsets_host)]
         for i, name in enumerate(names):
             part = scores[off[i]:off[i + 1]]
             if not (isinstance(name, TileName) and name[0] in self.plans):
-                self._hand_on(part, labels[off[i]:off[i + 1]], name)
+                _hand_on(self.inner, part, labels[off[i]:off[i + 1]], name)
                 continue
             scan, s = name
             plan = self.plans[scan]
@@ -241,7 +242,7 @@ class _TileSemantics:
             if self.left[scan] == 0:
                 stitched = postprocess.stitch_tiles(plan, self.kept.pop(scan), self.stitch)
                 lab = torch.from_numpy(scene_dict(self.raws[scan])["label"]).to(scores.device, non_blocking=True)
-                self._hand_on(stitched, lab, scan)
+                _hand_on(self.inner, stitched, lab, scan)
 
 
 def _predict_tiled(model, raw_scenes, batch_size, tiling, stitch, kw):
@@ -281,6 +282,171 @@ def _predict_tiled(model, raw_scenes, batch_size, tiling, stitch, kw):
             per_tile = [got[scan].get(t, none) for t in range(plans[scan].T)]
             del got[scan]
             yield (scan, *tiling.merge(plans[scan], per_tile))
+
+
+class Views:
+    """``views=Views(rotations=4, flip=False, matrices=None, iou=0.5, min_views=None, vote=0.5)``: test-time
+    augmentation -- every scene is run under V views of the same points and the views' picked instances are joined by
+    postprocess.merge_views(iou, min_views, vote).  View k is the rotation about z by 360 * k / rotations degrees
+    (headings that are multiples of 90 degrees have exact 0 / +-1 entries); with flip every rotation is followed by its
+    x-mirrored twin (V = 2 * rotations); view 0 is always the identity.  matrices: explicit float64 [V, 3, 3] matrices
+    instead (rotations and flip are then unused): each orthogonal to 1e-9, the first the identity.  1 <= V <= 32.
+    min_views=None stands for (V + 1) // 2.  iou, vote and min_views are chosen by reasoning; no measurement stands
+    behind them."""
+
+    DEFAULTS = dict(rotations=4, flip=False, matrices=None, **postprocess.VIEW_DEFAULTS)
+
+    def __init__(self, **params):
+        unknown = sorted(set(params) - set(self.DEFAULTS))
+        if unknown:
+            raise TypeError(f"Views: unknown parameter(s) {', '.join(unknown)}; known: {', '.join(self.DEFAULTS)}")
+        self.params = p = dict(self.DEFAULTS, **params)
+        if p["matrices"] is not None:
+            m = np.array(p["matrices"], dtype=np.float64)
+            if m.ndim != 3 or m.shape[1:] != (3, 3) or not 1 <= m.shape[0] <= postprocess.VIEW_MAX_VIEWS:
+                raise ValueError(f"Views: matrices: expected [V, 3, 3] with 1 <= V <= {postprocess.VIEW_MAX_VIEWS}, "
+                                 f"got {m.shape}")
+            if not np.all(np.isfinite(m)) or np.abs(m @ m.transpose(0, 2, 1) - np.eye(3)).max() > 1e-9:
+                raise ValueError("Views: matrices: every matrix must be orthogonal (to 1e-9)")
+            if not np.array_equal(m[0], np.eye(3)):
+                raise ValueError("Views: matrices: the first matrix must be the identity")
+        else:
+            rot = p["rotations"]
+            if isinstance(rot, bool) or not isinstance(rot, (int, np.integer)) or rot < 1 \
+                    or rot * (2 if p["flip"] else 1) > postprocess.VIEW_MAX_VIEWS:
+                raise ValueError(f"Views: rotations: an integer >= 1 with at most {postprocess.VIEW_MAX_VIEWS} views "
+                                 f"in all, got {self!r}")
+            quarter = ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))
+            ms = []
+            for k in range(int(rot)):
+                if (4 * k) % rot == 0:
+                    c, s = quarter[(4 * k // rot) % 4]  # exact: cos(pi / 2) is not 0
+                else:
+                    c, s = np.cos(2 * np.pi * k / rot), np.sin(2 * np.pi * k / rot)
+                ms.append([[c, s, 0.0], [-s, c, 0.0], [0.0, 0.0, 1.0]])  # xyz @ m turns the points by the angle
+                if p["flip"]:
+                    ms.append([[-c + 0.0, s, 0.0], [s + 0.0, c, 0.0], [0.0, 0.0, 1.0]])  # ... then x -> -x
+            m = np.array(ms, dtype=np.float64)
+        self.matrices = m
+        self.V = int(m.shape[0])
+        if not (0.0 <= p["iou"] <= 1.0) or not (0.0 < p["vote"] <= 1.0):
+            raise ValueError(f"Views: 0 <= iou <= 1 and 0 < vote <= 1, got {self!r}")
+        mv = p["min_views"]
+        if mv is not None and (isinstance(mv, bool) or not isinstance(mv, (int, np.integer)) or not 1 <= mv <= self.V):
+            raise ValueError(f"Views: min_views: None or an integer in 1 .. V = {self.V}, got {mv!r}")
+
+    def __repr__(self):
+        return f"Views({', '.join(f'{k}={v!r}' for k, v in self.params.items())})"
+
+    @property
+    def min_views(self):
+        return (self.V + 1) // 2 if self.params["min_views"] is None else int(self.params["min_views"])
+
+    def of_scene(self, raw, k):
+        """View k of a raw [N, 8] scene: xyz @ matrices[k] in float64, columns 3..7, the points and their order
+        unchanged; view 0 is the scene itself."""
+        if k == 0:
+            return raw
+        r = np.array(raw.detach().cpu().numpy() if torch.is_tensor(raw) else raw)
+        r[:, :3] = (r[:, :3].astype(np.float64) @ self.matrices[k]).astype(r.dtype)
+        return r
+
+    def merge(self, N, per_view):
+        """(cls, scores, masks [G, N], pick) of a scene from its views' results (postprocess.merge_views); a scene
+        without a kept instance is a scene without proposals."""
+        cls, scores, masks, pick, _ = postprocess.merge_views(per_view, N, iou=self.params["iou"],
+                                                              min_views=self.min_views, vote=self.params["vote"])
+        if len(pick) == 0:
+            return [], [], [], torch.as_tensor(pick)
+        return cls, scores, masks, pick
+
+
+class ViewName(tuple):
+    """(scene name, view): the name of a view in view_items' expanded list."""
+    __slots__ = ()
+
+    def __new__(cls, name, view):
+        return super().__new__(cls, (name, int(view)))
+
+
+def view_items(items, views):
+    """The expanded items: every (name, raw) is replaced, in place, by its V views (ViewName(name, k),
+    views.of_scene(raw, k)) for k = 0 .. V-1."""
+    return [(ViewName(name, k), views.of_scene(raw, k)) for name, raw in items for k in range(views.V)]
+
+
+def _views(views):
+    if views is None or isinstance(views, Views):
+        return views
+    raise ValueError(f"views: None or a Views, got {views!r}")
+
+
+def _viewed_names(items, who):
+    """With semantic= the views' scores of a scene are kept by its name: two scenes of one name are a ValueError."""
+    names = [n for n, _ in items]
+    twice = sorted({str(n) for n in names if names.count(n) > 1})
+    if twice:
+        raise ValueError(f"{who}: views= with semantic=: the scene(s) {', '.join(twice)} share their name with another scene")
+
+
+class _ViewSemantics:
+    """Stands where predict_batches / semantic_batches take a SemanticEvaluator when scenes run under V views: a scene
+    that is no view is handed on to `inner` at once; the [N, C] scores of a scene's views are kept on the device (copies:
+    the next forward may write the same buffer) until the last view is in, then averaged (postprocess.mean_views, one
+    launch) and handed on once, under the scene's own name against view 0's labels.  A scene holds 4 * C * N * V bytes
+    until then.  Nothing is read back.  With tiles, _TileSemantics stands in front and this object is given every
+    view's stitched scan."""
+
+    def __init__(self, inner, V):
+        self.inner, self.V = inner, V
+        self.kept, self.labels = {}, {}
+
+    def add_batch(self, scores, labels, offsets, names, offsets_host=None):
+        off = [int(o) for o in (offsets if offsets_host is None else offsets_host)]
+        for i, name in enumerate(names):
+            part, lab = scores[off[i]:off[i + 1]], labels[off[i]:off[i + 1]]
+            if not isinstance(name, ViewName):
+                _hand_on(self.inner, part, lab, name)
+                continue
+            scan, k = name
+            got = self.kept.setdefault(scan, [None] * self.V)
+            got[k] = part.clone(memory_format=torch.contiguous_format)
+            if k == 0:
+                self.labels[scan] = lab.clone()
+            if all(x is not None for x in got):
+                del self.kept[scan]
+                _hand_on(self.inner, postprocess.mean_views(got), self.labels.pop(scan), scan)
+
+
+def _view_segments(segments, items, V):
+    """The segments= mapping of view_items' expanded list: the ids of a scene, given under the scene's name, serve every
+    one of its V views (the points and their order are the same in all of them).  A GeometricSegments (or None) passes
+    through: the ids are then computed per view."""
+    if segments is None or _geometric(segments) is not None:
+        return segments
+    out = dict(segments)
+    out.update({ViewName(n, k): segments[n] for n, _ in items if n in segments for k in range(V)})
+    return out
+
+
+def _predict_views(model, raw_scenes, batch_size, views, kw):
+    """The loop of predict_batches over view_items' expanded list (tiles= / stitch=, segments= and split= apply to every
+    view); a scene is yielded once, joined, under its own name when its last view has come out.  predict_batches has
+    checked the names (_viewed_names) before anything else ran."""
+    items = list(raw_scenes)
+    kw = dict(kw, segments=_view_segments(kw.get("segments"), items, views.V))
+    if kw.get("semantic") is not None:
+        kw["semantic"] = _ViewSemantics(kw["semantic"], views.V)
+    sizes = [(name, int(np.asarray(raw).shape[0]) if not torch.is_tensor(raw) else int(raw.shape[0])) for name, raw in items]
+    at, got = 0, []
+    for name, cls, sc, masks, pick in predict_batches(model, view_items(items, views), batch_size, **kw):
+        scan, N = sizes[at]
+        if not (isinstance(name, ViewName) and name == (scan, len(got))):
+            raise RuntimeError(f"predict_batches: views=: expected view {len(got)} of {scan!r}, got {name!r}")
+        got.append((cls, sc, masks, pick))
+        if len(got) == views.V:
+            yield (scan, *views.merge(N, got))
+            at, got = at + 1, []
 
 
 class Density:
@@ -394,14 +560,18 @@ def _density_segments(segments, maps):
 
 def _predict_dense(model, raw_scenes, batch_size, density, kw):
     """The loop of predict_batches over density_items' subsampled list: everything else (segments=, split=, tiles= /
-    stitch=) sees the subsampled scenes, and the masks of a subsampled scene are put back on its own points last."""
+    stitch=, views=) sees the subsampled scenes, and the masks of a subsampled scene are put back on its own points
+    last."""
     items = list(raw_scenes)
     dev = torch.device(kw["device"]) if kw.get("device") is not None else next(model.parameters()).device
     sub, maps = density_items(items, density, dev)
     kw = dict(kw, segments=_density_segments(kw.get("segments"), maps))
     if kw.get("semantic") is not None and maps:
         kw["semantic"] = _DensitySemantics(kw["semantic"], maps, {n: r for n, r in items if n in maps})
-    for name, cls, sc, masks, pick in predict_batches(model, sub, batch_size, **kw):
+    views = kw.pop("views", None)  # (checked by predict_batches, names included)
+    inner = predict_batches(model, sub, batch_size, **kw) if views is None else \
+        _predict_views(model, sub, batch_size, views, kw)
+    for name, cls, sc, masks, pick in inner:
         if name in maps and torch.is_tensor(masks):
             masks = postprocess.expand_masks(masks, maps[name].cell_of)
         yield name, cls, sc, masks, pick
@@ -453,7 +623,7 @@ def collate_batches(raw_scenes, batch_size, spatial_shape=None, scale=50, full_s
 def predict_batches(model, raw_scenes, batch_size, *, epoch=300, spatial_shape=None, nms_kernel="gaussian",
                     sigma=2.0, final_score_thresh=NMS_FINAL_SCORE, cvfold=None, reserve=True, device=None,
                     semantic=None, nms="matrix", nms_thresh=None, segments=None, split=None, tiles=None, stitch=None,
-                    density=None):
+                    density=None, views=None):
     """Yields (name, cls_final, scores_final, masks_final, pick) per scene, in input order.  raw_scenes: iterable of
     (name, raw [N, 8]).  The NMS categories are the benchmark label ids of the classes (evaluation.benchmark_label_ids
     with cvfold, default model.cfg.cvfold).  A scene without proposals yields ([], [], [], empty pick).  reserve: size
@@ -489,10 +659,32 @@ def predict_batches(model, raw_scenes, batch_size, *, epoch=300, spatial_shape=N
     points (every point takes its representative's column) and `semantic` is given its scores on all N points against
     its own labels.  A scene that keeps every point runs exactly as without density=; a subsampled scene whose name
     another scene carries is a ValueError; None: nothing is added to the loop.  What subsampling does to AP or mIoU has
-    not been measured."""
+    not been measured.
+    views: a Views -- test-time augmentation: every scene is replaced in the item list by its V views (view_items: the
+    same points in the same order, rotated about z and optionally mirrored; view 0 is the scene itself), the loop runs
+    over the expanded list (density= comes first, so the views are views of the subsampled scene; tiles= / stitch=,
+    segments= and split= apply to every view: a large view is tiled and comes out merged as [G_v, N], a segments=
+    mapping serves every view of a scene under the scene's name, "geometric" segments are computed per view), and when
+    a scene's last view has come out postprocess.merge_views joins the views' picked instances: rows pair one to one
+    by mutual best IoU, the mask is a per-point vote of the views, the score the views' mean with 0 for a view that
+    missed the instance.  The scene is yielded once, in input order, under its own name, with masks int32 [G, N] (0 / 1)
+    holding the G joined instances only and pick their score order (one read-back per scene); `semantic` is given the
+    scene once, its scores the views' mean (postprocess.mean_views) against view 0's labels, before the scene is
+    yielded, and two scenes of one name are then a ValueError.  Views(rotations=1) runs the join over the one view: it
+    yields the picked rows that hold a point, as 0 / 1 masks with their own scores, in pick order -- a filter and a
+    re-ordering.  None: nothing is added to the loop.  What the views do to AP or mIoU has not been measured."""
     _stitching(stitch, _tiling(tiles), "predict_batches")
+    if _views(views) is not None and semantic is not None:
+        raw_scenes = list(raw_scenes)
+        _viewed_names(raw_scenes, "predict_batches")
     if _density(density) is not None:
         yield from _predict_dense(model, raw_scenes, batch_size, density, dict(
+            epoch=epoch, spatial_shape=spatial_shape, nms_kernel=nms_kernel, sigma=sigma,
+            final_score_thresh=final_score_thresh, cvfold=cvfold, reserve=reserve, device=device, semantic=semantic,
+            nms=nms, nms_thresh=nms_thresh, segments=segments, split=split, tiles=tiles, stitch=stitch, views=views))
+        return
+    if views is not None:
+        yield from _predict_views(model, raw_scenes, batch_size, views, dict(
             epoch=epoch, spatial_shape=spatial_shape, nms_kernel=nms_kernel, sigma=sigma,
             final_score_thresh=final_score_thresh, cvfold=cvfold, reserve=reserve, device=device, semantic=semantic,
             nms=nms, nms_thresh=nms_thresh, segments=segments, split=split, tiles=tiles, stitch=stitch))
@@ -738,7 +930,7 @@ def _semantic_forwards(model, raw_scenes, batch_size, spatial_shape, reserve, de
 
 @torch.no_grad()
 def semantic_batches(model, raw_scenes, batch_size, *, spatial_shape=None, reserve=True, device=None, evaluator=None,
-                     tiles=None, stitch=None, density=None):
+                     tiles=None, stitch=None, density=None, views=None):
     """Yields (name, preds) per scene, in input order: preds int32 [N] on the device, a view of the batch's buffer -- the
     semantic head's class of every point (the first maximal score, the rule of the forward's foreground selection).
     Only the backbone and the semantic head run (forward_backbone with the fused voxel-row head; no arg-max by the
@@ -749,14 +941,20 @@ def semantic_batches(model, raw_scenes, batch_size, *, spatial_shape=None, reser
     scene is counted and yielded once, under its own name, with preds int32 [N] over the whole scan.  density: a Density
     -- every scene runs subsampled (density_items; tiles= then cuts the subsampled scene), its scores -- stitched, when
     tiled -- are put back on its own points through cell_of, and it is counted against its own labels and yielded with
-    preds int32 [N]."""
+    preds int32 [N].  views: a Views -- every scene (subsampled first, with density=) runs under its V views (view_items;
+    tiles= then cuts every view), the views' scores -- stitched, when tiled -- are kept on the device until the last view
+    is in, averaged (postprocess.mean_views) and counted once against view 0's labels; two scenes of one name are a
+    ValueError."""
     from . import pointops
 
     tiling = _tiling(tiles)
     _stitching(stitch, tiling, "semantic_batches")
     if tiling is not None and stitch is None:
         raise ValueError('semantic_batches: tiles= needs stitch="core" or "mean"')
-    if tiling is not None or _density(density) is not None:
+    if _views(views) is not None:
+        raw_scenes = list(raw_scenes)
+        _viewed_names(raw_scenes, "semantic_batches")
+    if tiling is not None or _density(density) is not None or views is not None:
         items = list(raw_scenes)
         sem = tap = _SemanticTap(evaluator)
         plans = {}
@@ -765,6 +963,9 @@ def semantic_batches(model, raw_scenes, batch_size, *, spatial_shape=None, reser
             raws = items
             items, maps = density_items(raws, density, dev)
             sem = _DensitySemantics(tap, maps, {n: r for n, r in raws if n in maps})
+        if views is not None:
+            items = view_items(items, views)
+            sem = _ViewSemantics(sem, views.V)
         expanded = items
         if tiling is not None:
             expanded, plans = tile_items(items, tiling)
@@ -774,6 +975,7 @@ def semantic_batches(model, raw_scenes, batch_size, *, spatial_shape=None, reser
             for name, _ in chunk:
                 # a scan is complete with its last tile, and is yielded in that tile's place
                 name = name[0] if isinstance(name, TileName) and name[0] in plans else name
+                name = name[0] if isinstance(name, ViewName) else name  # ... and a scene with its last view
                 if name in tap.preds:
                     yield name, tap.preds.pop(name)
         return

@@ -1121,6 +1121,265 @@ def stitch_tiles(plan, per_tile_scores, mode):
                                            torch.from_numpy(plan.core_of).to(dev, non_blocking=True), C, mode)
 
 
+# ---- instances and scores joined across the views of a scan (csrc/view_merge.hip): the host statement --------------------
+VIEW_DEFAULTS = dict(iou=0.5, min_views=None, vote=0.5)  # chosen by reasoning; no measurement stands behind them
+VIEW_MAX_VIEWS = 32  # gf_view_merge_max_views(): asserted against the library in view_merge.view_limits()
+
+
+def _view_args(V, iou, min_views, vote, who):
+    """min_views (the default (V + 1) // 2 filled in) after the checks of the three parameters (ValueError)."""
+    if not 1 <= V <= VIEW_MAX_VIEWS:
+        raise ValueError(f"{who}: {V} views (1 to {VIEW_MAX_VIEWS})")
+    if not float(iou) == float(iou):
+        raise ValueError(f"{who}: iou is NaN")
+    if not 0.0 < float(vote) <= 1.0:
+        raise ValueError(f"{who}: vote in (0, 1], got {vote!r}")
+    min_views = (V + 1) // 2 if min_views is None else int(min_views)
+    if not 1 <= min_views <= V:
+        raise ValueError(f"{who}: min_views in 1 .. V = {V}, got {min_views}")
+    return min_views
+
+
+def _view_rows(per_view, N, who):
+    """Per view (masks [n_rows, N], pick [p_v], cls, scores), or four Nones for a view without picks, shapes checked."""
+    out = []
+    for v, (cls, scores, masks, pick) in enumerate(per_view):
+        p_v = 0 if pick is None else int(len(pick))
+        if p_v == 0 or isinstance(masks, (list, tuple)):
+            if p_v:
+                raise ValueError(f"{who}: view {v} has {p_v} picks and no masks")
+            out.append((None, None, None, None))
+            continue
+        if masks.ndim != 2 or masks.shape[1] != N or masks.shape[0] < 1 or len(cls) != masks.shape[0] \
+                or len(scores) != masks.shape[0]:
+            raise ValueError(f"{who}: view {v}: masks {tuple(masks.shape)}, {len(cls)} classes and {len(scores)} "
+                             f"scores do not fit [n_rows >= 1, {N}]")
+        out.append((masks, pick, cls, scores))
+    return out
+
+
+def merge_views_host(per_view, N, *, iou=0.5, min_views=None, vote=0.5, return_tables=False):
+    """Instances of a scan that was run under V views -- the same N points in the same order, rotated or mirrored --
+    joined across the views: the statement csrc/view_merge.hip is tested against.  per_view: per view (cls, scores,
+    masks [n_v, N], pick) as predict_batches yields them; a view without proposals gives ([], [], [], empty pick).
+      Rows 0 .. P-1 are the picked rows, view-major and then by rank in pick; a pick outside the masks is an empty row.
+      B[a] = the points of row a (masks != 0), cnt[a] = |B[a]|, inter[a, b] = |B[a] & B[b]|, union = cnt[a] + cnt[b] -
+      inter.
+      best[a, v], for every view v other than a's: among the rows b of view v with cls[b] == cls[a] and inter[a, b] > 0
+      the one of the largest IoU, compared exactly (inter[a, b] * union[a, c] against inter[a, c] * union[a, b] in
+      int64), the smaller row on ties, -1 without one.
+      Rows a < b of different views join when best[a, view(b)] == b, best[b, view(a)] == a and
+      float64(inter[a, b]) >= iou * float64(union[a, b]) (one multiplication, one compare): one to one between two
+      views, so one sloppy mask cannot glue two neighbours of another view together through the threshold alone.
+      Instances are the connected components (comp[r]: the smallest row).  support = the number of distinct views among
+      the members; a component is kept when support >= min_views (default (V + 1) // 2) and its rows hold a point (an
+      empty row joins nothing and is dropped).  Global ids 0 .. G-1 follow the kept representatives in ascending order.
+      The class is the representative's (all members share it).  The score: m_v = the largest member score of view v,
+      float32(0) without a member; acc = m_0, then acc = acc + m_v in float32 for v = 1 .. V-1; score = acc /
+      float32(V), the IEEE division -- an instance that only some views found is marked down in proportion.
+      The mask: votes[p] = the views with a member row that holds p (two rows of one view count once); p belongs to the
+      instance when votes[p] > 0 and float64(votes[p]) >= vote * float64(support).  (With vote near 1 the mask of a
+      chain whose ends do not meet can be empty; the instance stays, with count 0.)
+    Returns (cls int64 [G], scores fp32 [G], masks int32 [G, N], pick int64 [G]: the stable argsort of -scores,
+    tables); tables is None, or with return_tables a dict of inter int32 [P, P], cnt int32 [P], best int32 [P, V],
+    comp int32 [P], members int32 [P] (row -> global id, -1 dropped), support int32 [G], count int32 [G] and row_view
+    int32 [P]."""
+    per_view = list(per_view)
+    V, N = len(per_view), int(N)
+    min_views = _view_args(V, iou, min_views, vote, "merge_views_host")
+    rows = _view_rows(per_view, N, "merge_views_host")
+    A, cls_all, sc_all, first = [], [], [], [0]
+    for masks, pick, cls, scores in rows:
+        if masks is None:
+            first.append(first[-1])
+            continue
+        pk = np.asarray(_np(pick)).astype(np.int64).reshape(-1)
+        m = np.asarray(_np(masks))
+        ok = (pk >= 0) & (pk < m.shape[0])
+        a = np.zeros((pk.size, N), bool)
+        a[ok] = m[pk[ok]] != 0
+        A.append(a)
+        safe = np.where(ok, pk, 0)  # (an empty row's class and score are never used: it is dropped)
+        cls_all.append(np.asarray(_np(cls)).astype(np.int64)[safe])
+        sc_all.append(np.asarray(_np(scores)).astype(np.float32)[safe])
+        first.append(first[-1] + pk.size)
+    P = first[-1]
+    B = np.concatenate(A) if A else np.zeros((0, N), bool)
+    cls_all = np.concatenate(cls_all) if cls_all else np.zeros(0, np.int64)
+    sc_all = np.concatenate(sc_all) if sc_all else np.zeros(0, np.float32)
+    row_view = np.repeat(np.arange(V, dtype=np.int32), np.diff(first))
+    inter = np.zeros((P, P), np.int64)
+    for s in range(0, N, 1 << 16):  # float32 products of 0 / 1 over at most 2^16 points: exact
+        blk = B[:, s:s + (1 << 16)].astype(np.float32)
+        inter += (blk @ blk.T).astype(np.int64)
+    cnt = B.sum(1, dtype=np.int64)
+    best = np.full((P, V), -1, np.int32)
+    for a in range(P):
+        for v in range(V):
+            if v == row_view[a]:
+                continue
+            b0 = first[v]
+            cand = b0 + np.nonzero((inter[a, b0:first[v + 1]] > 0) & (cls_all[b0:first[v + 1]] == cls_all[a]))[0]
+            bi, bu, bx = 0, 1, -1
+            for b in cand.tolist():
+                i = int(inter[a, b])
+                u = int(cnt[a] + cnt[b]) - i
+                if bx < 0 or i * bu > bi * u:  # ascending b: a tie keeps the smaller row
+                    bi, bu, bx = i, u, b
+            best[a, v] = bx
+    ea, eb = [], []
+    for a in range(P):
+        for v in range(V):
+            b = int(best[a, v])
+            if b > a and best[b, row_view[a]] == a:
+                union = cnt[a] + cnt[b] - inter[a, b]
+                if np.float64(inter[a, b]) >= np.float64(iou) * np.float64(union):
+                    ea.append(a)
+                    eb.append(b)
+    comp = _min_index_components(P, np.asarray(ea, np.int64), np.asarray(eb, np.int64)).astype(np.int64)
+    reps = np.unique(comp)
+    support_of = {int(r): len(set(row_view[comp == r].tolist())) for r in reps}
+    kept = [int(r) for r in reps if support_of[int(r)] >= min_views and cnt[r] > 0]
+    gid_of = {r: g for g, r in enumerate(kept)}
+    members = np.asarray([gid_of.get(int(c), -1) for c in comp], np.int32).reshape(P)
+    G = len(kept)
+    scores = np.zeros(G, np.float32)
+    masks = np.zeros((G, N), np.int32)
+    support = np.asarray([support_of[r] for r in kept], np.int32).reshape(G)
+    for g, r in enumerate(kept):
+        rows_g = np.nonzero(comp == r)[0]
+        votes = np.zeros(N, np.int64)
+        acc = None
+        for v in range(V):
+            rv = rows_g[row_view[rows_g] == v]
+            m = sc_all[rv].max() if rv.size else np.float32(0.0)
+            acc = np.float32(m) if acc is None else np.float32(acc + np.float32(m))
+            if rv.size:
+                votes += B[rv].any(0)
+        scores[g] = np.float32(acc / np.float32(V))
+        masks[g] = (votes > 0) & (votes.astype(np.float64) >= np.float64(vote) * np.float64(support[g]))
+    tables = None
+    if return_tables:
+        tables = dict(inter=inter.astype(np.int32), cnt=cnt.astype(np.int32), best=best, comp=comp.astype(np.int32),
+                      members=members, support=support, count=masks.sum(1, dtype=np.int32), row_view=row_view)
+    return (cls_all[kept].reshape(G), scores, masks, np.argsort(-scores, kind="stable").astype(np.int64), tables)
+
+
+def view_scene_table(rows, N):
+    """(table int64 [V, GF_TILE_SCENE_FIELDS], sizes) of gf_view_pack from _view_rows' device tensors, one GfTileScene
+    of the header per view (n_s = N, first_word unused); sizes: P rows, row_view int32 [P], view_first int32 [V + 1]."""
+    table, recs = scene_table(len(rows), TILE_ROW)
+    row, first = 0, [0]
+    for v, (masks, pick, _, _) in enumerate(rows):
+        p_v = 0 if masks is None else int(pick.shape[0])
+        r = recs[v]
+        r["n_s"], r["first_row"] = N, row
+        if p_v:
+            r["masks"], r["n_rows"], r["pick"], r["p_s"] = masks.data_ptr(), masks.shape[0], pick.data_ptr(), p_v
+        row += p_v
+        first.append(row)
+    first = np.asarray(first, np.int32)
+    return table, dict(rows=row, row_view=np.repeat(np.arange(len(rows), dtype=np.int32), np.diff(first)),
+                       view_first=first)
+
+
+def merge_views(per_view, N, *, iou=0.5, min_views=None, vote=0.5, return_tables=False):
+    """merge_views_host on the tensors' device and the current stream (csrc/view_merge.hip: view_merge.view_pack,
+    view_overlaps, view_best, view_merge, view_assemble -- five launches for any number of views and picks): (cls [G],
+    scores [G], masks int32 [G, N], pick, tables), every output bit-identical to the host statement and from call to
+    call.  One device-to-host read, of G, sizes the dense output (4 * G * N bytes).  More than view_merge.VIEW_MAX_VIEWS
+    views or VIEW_MAX_ROWS picked rows in all is an error before anything is launched.  Host arrays (no tensor on a GPU
+    among them) go to merge_views_host."""
+    per_view = list(per_view)
+    dev = next((x.device for view in per_view for x in view if torch.is_tensor(x) and x.is_cuda), None)
+    if dev is None:
+        out = merge_views_host(per_view, N, iou=iou, min_views=min_views, vote=vote, return_tables=return_tables)
+        if any(torch.is_tensor(x) for view in per_view for x in view):
+            out = tuple(torch.from_numpy(x) for x in out[:4]) + out[4:]
+        return out
+    from . import pointops, view_merge
+
+    V, N = len(per_view), int(N)
+    min_views = _view_args(V, iou, min_views, vote, "merge_views")
+    rows = []
+    for masks, pick, cls, scores in _view_rows(per_view, N, "merge_views"):
+        if masks is not None:
+            masks = (masks if masks.dtype == torch.int32 else (masks != 0).int()).to(dev).contiguous()
+            pick = torch.as_tensor(pick).to(dev, torch.int64).contiguous()
+            cls, scores = torch.as_tensor(cls).to(dev, torch.int64), torch.as_tensor(scores).to(dev, torch.float32)
+        rows.append((masks, pick, cls, scores))
+    table, sizes = view_scene_table(rows, N)
+    P = view_merge.view_check_caps(table, N)
+    with torch.cuda.device(dev):
+        with_picks = [r for r in rows if r[0] is not None]
+        safe = [torch.where((p >= 0) & (p < m.shape[0]), p, torch.zeros_like(p)) for m, p, _, _ in with_picks]
+        i64, f32 = dict(dtype=torch.int64, device=dev), dict(dtype=torch.float32, device=dev)
+        cls_all = torch.cat([c[p] for (_, _, c, _), p in zip(with_picks, safe)] + [torch.empty(0, **i64)]).contiguous()
+        sc_all = torch.cat([s[p] for (_, _, _, s), p in zip(with_picks, safe)] + [torch.empty(0, **f32)]).contiguous()
+        table_d = pointops._table_dev(table, dev)
+        row_view = torch.from_numpy(sizes["row_view"]).to(dev, non_blocking=True)
+        view_first = torch.from_numpy(sizes["view_first"]).to(dev, non_blocking=True)
+        bits, cnt = view_merge.view_pack(table_d, table, N)
+        inter = view_merge.view_overlaps(bits, N)
+        best = view_merge.view_best(inter, cnt, cls_all, row_view, view_first)
+        merged = view_merge.view_merge(inter, cnt, best, cls_all, sc_all, row_view, iou, min_views)
+        G = int(merged["G"].item())  # the one read-back: the dense output is sized by it
+        masks, count = view_merge.view_assemble(bits, merged, row_view, G, N, vote)
+    scores = merged["scores"][:G]
+    tables = None
+    if return_tables:
+        tables = dict(inter=inter, cnt=cnt, best=best, comp=merged["comp"], members=merged["members"],
+                      support=merged["support"][:G], count=count, row_view=row_view)
+    return merged["cls"][:G], scores, masks, torch.sort(-scores, stable=True)[1], tables
+
+
+def _mean_views_checked(per_view_scores, who):
+    """(N, C) of the views' scores after the checks: 1 .. 32 float32 arrays or tensors of one shape [N, C >= 1]."""
+    xs = list(per_view_scores)
+    if not 1 <= len(xs) <= VIEW_MAX_VIEWS:
+        raise ValueError(f"{who}: {len(xs)} views (1 to {VIEW_MAX_VIEWS})")
+    for v, x in enumerate(xs):
+        f32 = x.dtype == torch.float32 if torch.is_tensor(x) else getattr(x, "dtype", None) == np.float32
+        if not f32:
+            raise ValueError(f"{who}: view {v}: expected float32 scores, got {getattr(x, 'dtype', type(x).__name__)}")
+        if x.ndim != 2 or x.shape[1] < 1 or tuple(x.shape) != tuple(xs[0].shape):
+            raise ValueError(f"{who}: view {v}: expected scores {tuple(xs[0].shape)} = [N, C], got {tuple(x.shape)}")
+    return int(xs[0].shape[0]), int(xs[0].shape[1])
+
+
+def mean_views_host(per_view_scores):
+    """fp32 [N, C]: the mean of the V views' semantic scores (each float32 [N, C] over the scan's own points) -- the
+    statement gf_view_mean_scores is tested against, in exact float32: acc = s_0, then acc = acc + s_v for v = 1 .. V-1,
+    one rounded add per view, and acc / float32(V), the IEEE division."""
+    xs = list(per_view_scores)
+    _mean_views_checked(xs, "mean_views_host")
+    acc = np.array(_np(xs[0]), np.float32)
+    for x in xs[1:]:
+        acc = acc + np.asarray(_np(x), np.float32)
+    return acc / np.float32(len(xs))
+
+
+def mean_views(per_view_scores):
+    """mean_views_host on the tensors' device and the current stream (one launch of view_merge.view_mean_scores for any
+    number of views, no atomics, nothing read back): fp32 [N, C], bit-identical to the host statement and from call to
+    call.  The tensors must be float32 [N, C], contiguous and on one device (ValueError before anything is launched; C
+    above view_merge.TILE_STITCH_MAX_CLASSES is view_merge's RuntimeError).  Host arrays go to mean_views_host."""
+    xs = list(per_view_scores)
+    dev = next((x.device for x in xs if torch.is_tensor(x) and x.is_cuda), None)
+    if dev is None:
+        out = mean_views_host(xs)
+        return torch.from_numpy(out) if any(torch.is_tensor(x) for x in xs) else out
+    from . import pointops, view_merge
+
+    N, C = _mean_views_checked(xs, "mean_views")
+    for v, x in enumerate(xs):
+        if not (torch.is_tensor(x) and x.device == dev and x.is_contiguous()):
+            raise ValueError(f"mean_views: view {v}: expected a contiguous float32 tensor on {dev}")
+    table = tile_score_table(xs)
+    with torch.cuda.device(dev):
+        return view_merge.view_mean_scores(pointops._table_dev(table, dev), table, N, C)
+
+
 # ---- scans of any density: grid subsample, labels carried back (csrc/resample.hip) ---------------------------------------
 GRID_MODES = ("first", "center")
 GRID_AXIS_CELLS = 1 << 21  # gf_grid_subsample_max_cells(): asserted against the library in pointops.resample_limits()

@@ -1115,6 +1115,64 @@ int gf_tile_stitch_scores(const long long* table, const long long* table_host, i
                           void* stream);
 
 /* ===================================================================================
+ * Instances of a scan that was run under V views (rotations / mirrors of the same N points), joined across the views
+ * (csrc/view_merge.hip; the statement is postprocess.merge_views_host).  Every view holds all N points in the scan's
+ * own order, so there are no point tables:
+ *   View table, int64 [V, GF_TILE_SCENE_FIELDS], one GfTileScene per view v: masks, n_rows, n_s = N, pick, p_s,
+ *   first_row; first_word is unused (0).  table (device) and table_host (the same rows on the host): table_host is
+ *   checked before anything is launched -- a negative size, n_s != N, a NULL pointer with p_s > 0, a first row that does
+ *   not follow the view before or picks that do not add up to P are GF_ERR_INVALID_ARG, and so are, in every call,
+ *   P > gf_view_merge_max_rows(), V outside 1..gf_view_merge_max_views() and N outside [0, 2^31 - 1).
+ * Rows 0 .. P-1 are the picked masks of all views, view-major, then by rank in pick; row_view int32 [P] is the view of
+ * each row and view_first int32 [V + 1] the first row of each view (view_first[V] = P).  W = ceil(N / 32).
+ *
+ * gf_view_pack (one memset, one launch): bits uint32 [P, W], row-major bitsets -- bit p % 32 of word p / 32 of row a is
+ *   set when the row's mask holds point p; the unused bits of the last word are 0; a pick outside [0, n_rows) is an
+ *   empty row.  cnt int32 [P]: the points of each row (zeroed by the call; one integer add per wave).
+ * gf_view_overlaps (one launch): inter int32 [P, P], inter[a, b] = the points in both rows; symmetric, the diagonal is
+ *   cnt.  Every cell is defined by the call, whatever it held: stored by the one workgroup that owns it, or -- where
+ *   few row blocks would leave the chip idle and the words are split over workgroups as well -- zeroed by a memset of
+ *   the call and summed with integer atomic adds.
+ * gf_view_best (one launch): best int32 [P, V]: best[a, v] = the row b of view v != row_view[a] with cls[b] == cls[a] and
+ *   inter[a, b] > 0 of the largest IoU inter / (cnt[a] + cnt[b] - inter), compared exactly (cross-multiplied in int64),
+ *   the smaller row on ties; -1 without such a row and for v == row_view[a].
+ * gf_view_merge (one launch of ONE workgroup of 1024 threads): rows a < b are joined when best[a, row_view[b]] == b,
+ *   best[b, row_view[a]] == a and (double)inter[a, b] >= iou * (double)(cnt[a] + cnt[b] - inter[a, b]) (one double
+ *   multiplication and a compare).  comp int32 [P]: the smallest row of each row's connected component.  A component
+ *   is kept when it has members in at least min_views views and its smallest row holds a point; members int32 [P]: the
+ *   rank of the row's component among the kept ones (the global id) or -1; d_G int32 [1] = G.  First G valid of
+ *   [P]: inst_cls int64 (the smallest row's class), inst_support int32 (the number of views with a member) and
+ *   inst_scores fp32: m_v = the largest member score of view v or 0.0f, acc = m_0, acc = acc + m_v for v = 1 .. V-1
+ *   (fp32, one rounded add each), acc / (float)V correctly rounded.  inst_first int32 [P + 1] (first G + 1 valid) and
+ *   inst_rows int32 [P]: the member rows of instance g are inst_rows[inst_first[g] .. inst_first[g + 1]), ascending
+ *   (hence sorted by view).
+ * gf_view_assemble (one memset, one launch; every cell of masks is written): masks int32 [G, N] (0 / 1):
+ *   votes = the views with a member row that holds the point; 1 when votes > 0 and (double)votes >= vote *
+ *   (double)inst_support[g].  count int32 [G]: the points of each mask (zeroed by the call; one integer add per wave).
+ * gf_view_mean_scores (one launch, no atomics): out fp32 [N, C] = (((s_0 + s_1) + s_2) + ...) / (float)V in view
+ *   order, the correctly rounded division; score table int64 [V, GF_TILE_SCORE_FIELDS], one GfTileScore per view with
+ *   n_s = N; C in 1..gf_tile_stitch_max_classes().
+ * Integer atomics only; every output is a function of the inputs: bit-identical from call to call.  Every launch goes
+ * on `stream`; no host synchronisation, no read-back.
+ * =================================================================================== */
+int gf_view_merge_max_rows(void);
+int gf_view_merge_max_views(void);
+int gf_view_pack(const long long* table, const long long* table_host, int V, int P, long long N, uint32_t* bits,
+                 int32_t* cnt, void* stream);
+int gf_view_overlaps(const uint32_t* bits, int P, long long N, int32_t* inter, void* stream);
+int gf_view_best(const int32_t* inter, const int32_t* cnt, const long long* cls, const int32_t* row_view,
+                 const int32_t* view_first, int P, int V, int32_t* best, void* stream);
+int gf_view_merge(const int32_t* inter, const int32_t* cnt, const int32_t* best, const long long* cls,
+                  const float* scores, const int32_t* row_view, int P, int V, double iou, int min_views, int32_t* comp,
+                  int32_t* members, int32_t* d_G, long long* inst_cls, float* inst_scores, int32_t* inst_support,
+                  int32_t* inst_first, int32_t* inst_rows, void* stream);
+int gf_view_assemble(const uint32_t* bits, const int32_t* inst_first, const int32_t* inst_rows, const int32_t* row_view,
+                     const int32_t* inst_support, int P, int G, long long N, double vote, int32_t* masks, int32_t* count,
+                     void* stream);
+int gf_view_mean_scores(const long long* table, const long long* table_host, int V, long long N, int C, float* out,
+                        void* stream);
+
+/* ===================================================================================
  * Headless rendering of a scene's points to images (csrc/render.hip; stands where util/visualize.py opens a viewer;
  * the statement is render.splat_host / render.resolve_host): a z-buffered point splat with 64-bit atomicMin, then a
  * resolve pass.  A whole call is memset (the caller's), splat, resolve: three stream operations for any V.

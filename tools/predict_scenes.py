@@ -14,6 +14,7 @@ greedy NMS) and the scene labelling of batch_eval.label_batches, written with ge
     python tools/predict_scenes.py --out out --render turntable:4 scene0011_00_inst_nostuff.npy  # + out/render/<name>_instance_pred_<view>.png
     python tools/predict_scenes.py --out out --density 0.02 laser_scan.npy                 # a dense scan on one point per 2 cm cell, labels on every point
     python tools/predict_scenes.py --out out --boxes oriented scene0011_00_inst_nostuff.npy  # + out/boxes/<name>.txt, one 3D box per instance
+    python tools/predict_scenes.py --out out --views 4 scene0011_00_inst_nostuff.npy         # 4 rotated views per scene, instances joined by vote
 
 Per scene <out>/<name>.npz (ids, owner, instance table: export.load_labels) and, with --scannet, <out>/<name>.txt plus
 <out>/predicted_masks/ (exclusive masks; --full-masks writes the picked masks as they are).  Without --checkpoint the
@@ -52,6 +53,13 @@ JSON line's `density` holds the parameters (null without the flag).
 (postprocess.id_boxes over the map's owner column on the GPU, csrc/boxes.hip): axis-aligned, or the upright box of least
 footprint among 90 headings.  The JSON line's `boxes` names the kind (null without the flag) and `boxes_written` the
 count.
+--views K runs every scene under K views -- rotations about z by 360 / K degrees, with --view-flip each followed by its
+x-mirrored twin (2 K views) -- and joins the views' picked instances (batch_eval.Views, csrc/view_merge.hip): rows pair
+one to one by mutual best IoU of at least --view-iou (0.5), an instance needs members in --view-min views (default: half
+of them, rounded up), a point belongs to it when at least --view-vote (0.5) of its views say so, and its score is the
+views' mean, 0 for a view that missed it.  The --semantic pass then averages the views' scores.  Tiles, segments and the
+mask split apply to every view; --density comes first.  The three thresholds are chosen by reasoning, not measured.
+The JSON line's `views` holds the parameters (null without the flag).
 """
 import argparse
 import json
@@ -179,6 +187,16 @@ def build_parser():
     ap.add_argument("--render-task", choices=RENDER_TASKS, default="instance_pred", help="what the colours show")
     ap.add_argument("--boxes", choices=("aligned", "oriented"), default=None,
                     help="also write <out>/boxes/<name>.txt: one 3D box per kept instance (postprocess.id_boxes)")
+    ap.add_argument("--views", type=int, default=None, metavar="K",
+                    help="run every scene under K views rotated about z by 360 / K degrees and join the views' "
+                         "instances by mutual best IoU, a per-point vote and the mean score (batch_eval.Views)")
+    ap.add_argument("--view-flip", action="store_true", help="with --views: follow every rotation by its x-mirrored twin")
+    ap.add_argument("--view-iou", type=float, default=None, metavar="X",
+                    help="with --views: least IoU of two rows that join (default 0.5, not measured)")
+    ap.add_argument("--view-min", type=int, default=None, metavar="N",
+                    help="with --views: least number of views with a member (default: half the views, rounded up)")
+    ap.add_argument("--view-vote", type=float, default=None, metavar="X",
+                    help="with --views: least share of an instance's views that must hold a point (default 0.5, not measured)")
     ap.add_argument("--no-write", action="store_true")
     ap.add_argument("--reps", type=int, default=3, help="timed passes per keep_masks setting")
     return ap
@@ -259,6 +277,17 @@ def main():
     elif args.density_mode is not None:
         ap.error("--density-mode goes with --density")
 
+    views = None
+    if args.views is not None:
+        more = {k: v for k, v in (("iou", args.view_iou), ("min_views", args.view_min), ("vote", args.view_vote))
+                if v is not None}
+        try:
+            views = kw["views"] = batch_eval.Views(rotations=args.views, flip=args.view_flip, **more)
+        except ValueError as e:
+            ap.error(f"--views: {e}")
+    elif args.view_flip or args.view_iou is not None or args.view_min is not None or args.view_vote is not None:
+        ap.error("--view-flip, --view-iou, --view-min and --view-vote go with --views")
+
     def run(keep_masks):
         np.random.seed(0)
         return list(batch_eval.label_batches(model, items, args.batch_size, keep_masks=keep_masks, **kw))
@@ -293,6 +322,8 @@ def main():
         skw = {"tiles": tiling, "stitch": args.tile_stitch} if args.tile_stitch is not None else {}
         if density is not None:
             skw["density"] = density
+        if views is not None:
+            skw["views"] = views
         for name, preds in batch_eval.semantic_batches(model, items, args.batch_size, evaluator=ev, **skw):
             if not args.no_write:
                 export.write_scannet_semantic(os.path.join(args.out, "semantic"), name, preds, model.cfg.train_fold)
@@ -330,7 +361,8 @@ def main():
                       "labelled_points": sum(int((lab.owner >= 0).sum()) for _, lab in results),
                       "segment_pooling": "segments" in kw, "geometric_segments": args.geometric_segments,
                       "mask_split": args.split_masks, "tiling": dict(tiling.params, stitch=args.tile_stitch) if tiling else None,
-                      "density": density.params if density else None, "boxes": args.boxes,
+                      "density": density.params if density else None, "views": views.params if views else None,
+                      "boxes": args.boxes,
                       "boxes_written": boxes_written, "scenes_per_s": rates, "out": None if args.no_write else args.out}))
 
 
