@@ -1,0 +1,461 @@
+"""Scenes from posed depth frames: the step in front of every other entry point of the package when there is no
+reconstructed cloud yet, only a stream of depth images with intrinsics and camera-to-world poses (an RGB-D sensor, a
+phone, a headset).
+
+    fr = frames.make(depth, K, pose, color)            # depth uint16 [F, H, W] (millimetres) or float32
+    fused = frames.fuse(fr, cell=0.02, edge=0.05)      # one point per 2 cm cell: xyz, rgb, count, point_of
+    raw, shift = fused.raw_scene()                     # float64 [n, 8], what batch_eval.* takes
+    (name, labels), = batch_eval.label_batches(model, [("scan", raw)], 1)
+    ids = frames.gather(fused, labels.ids, fill=0)     # int32 [F, Hs, Ws]: the instance id of every depth pixel
+
+The hot path is csrc/frames.hip: gf_frames_backproject (pixel validity, the edge filter, the world point, an ordered
+compaction as count / scan / write), pointops.grid_subsample for the cells, and gf_frames_cell_means (fixed-point
+integer sums per cell, the mean, the cells seen often enough renumbered in order).  backproject_host, cell_means_host
+and fuse_host are the numpy statement -- the same operations in the same order -- and the kernels are tested bit for
+bit against them.  Conventions are render.py's: camera axes x right, y down, z forward, pixel i covers [i, i + 1), so
+its centre is i + 0.5; pose is camera to world, R = pose[:3, :3]^T, eye = pose[:3, 3].
+"""
+from __future__ import annotations
+
+from typing import NamedTuple
+
+import numpy as np
+import torch
+
+RECORD_FLOATS = 16        # gf_frames_record_floats(): {fx, fy, cx, cy, P[12]}; asserted against the library in limits()
+MAX_FRAMES = 1 << 16      # gf_frames_max_frames()
+MAX_SIDE = 1 << 13        # gf_frames_max_side()
+DEFAULT_CHUNK = 2048      # gf_frames_default_chunk(): elements one workgroup compacts
+MAX_CHUNK = 1 << 16
+MAX_POINTS = 1 << 29      # gf_resample_max_points()
+UNITS = 1048576.0         # fixed-point units per metre of the cell sums
+REACH = 16384.0           # metres from the origin the integer sums are proven for
+AGGREGATE = True          # runs of equal cells among adjacent lanes are added in the wave before the atomics
+IGNORE_LABEL = -100
+
+
+class Frames(NamedTuple):
+    """What make() checked: depth uint16 or float32 [F, H, W] and color uint8 [F, H, W, 3] or None as torch tensors (on
+    any device), table float32 [F, RECORD_FLOATS] on the host, the divisor that takes a depth value to metres."""
+    depth: torch.Tensor
+    color: object
+    table: np.ndarray
+    depth_shift: float
+
+
+class Fused(NamedTuple):
+    """xyz fp32 [n, 3], rgb uint8 [n, 3], count int32 [n] (the pixels that saw the point) and point_of int32 [F, Hs, Ws]:
+    the fused point of every sampled pixel, -1 for an invalid pixel or a dropped cell."""
+    xyz: torch.Tensor
+    rgb: torch.Tensor
+    count: torch.Tensor
+    point_of: torch.Tensor
+
+    def raw_scene(self, center=True):
+        """(raw float64 [n, 8], shift float64 [3]): the scene as data/scannetv2/prepare_data_inst.py stores one --
+        coordinates minus their float64 mean (the shift; zeros with center=False), colours / 127.5 - 1, both labels
+        -100 -- which every batch_eval entry point takes as it is.  raw[:, :3] + shift are the fused coordinates."""
+        xyz = self.xyz.detach().cpu().numpy().astype(np.float64)
+        shift = xyz.mean(0) if center and xyz.shape[0] else np.zeros(3)
+        raw = np.empty((xyz.shape[0], 8), np.float64)
+        raw[:, :3] = xyz - shift
+        raw[:, 3:6] = self.rgb.detach().cpu().numpy().astype(np.float64) / 127.5 - 1
+        raw[:, 6:] = IGNORE_LABEL
+        return raw, shift
+
+
+def _tensor(a, name):
+    if torch.is_tensor(a):
+        return a
+    if isinstance(a, np.ndarray):
+        return torch.from_numpy(np.ascontiguousarray(a))
+    raise ValueError(f"frames.make: {name}: expected a numpy array or a torch tensor, got {type(a).__name__}")
+
+
+def make(depth, K, pose, color=None, depth_shift=1000.0):
+    """Frames of depth [F, H, W] (uint16, or float32), K [4] or [F, 4] = (fx, fy, cx, cy) in pixels, pose [F, 4, 4]
+    camera to world, color uint8 [F, H, W, 3] aligned with the depth or None; a depth value d is d / depth_shift metres
+    (ScanNet: 1000; 1 for metres).  ValueError for wrong shapes or dtypes, a record that is not finite, fx or fy <= 0, or
+    a pose whose last row is not (0, 0, 0, 1).  Records are computed in float64 and rounded to float32 once."""
+    depth = _tensor(depth, "depth")
+    if depth.dim() != 3 or depth.dtype not in (torch.uint16, torch.float32) or 0 in depth.shape:
+        raise ValueError(f"frames.make: depth: expected uint16 or float32 [F, H, W], got {depth.dtype} {tuple(depth.shape)}")
+    F, H, W = depth.shape
+    if not (1 <= F <= MAX_FRAMES and H <= MAX_SIDE and W <= MAX_SIDE):
+        raise ValueError(f"frames.make: {F} frames of {W} x {H} pixels (1 to {MAX_FRAMES} frames, each side 1 to {MAX_SIDE})")
+    if color is not None:
+        color = _tensor(color, "color")
+        if color.dtype != torch.uint8 or tuple(color.shape) != (F, H, W, 3):
+            raise ValueError(f"frames.make: color: expected uint8 {(F, H, W, 3)}, got {color.dtype} {tuple(color.shape)}")
+        if color.device != depth.device:
+            raise ValueError(f"frames.make: color on {color.device}, depth on {depth.device}")
+        color = color.contiguous()
+    K = np.asarray(K.detach().cpu() if torch.is_tensor(K) else K)
+    pose = np.asarray(pose.detach().cpu() if torch.is_tensor(pose) else pose)
+    if K.dtype.kind not in "fiu" or K.shape not in ((4,), (F, 4)):
+        raise ValueError(f"frames.make: K: expected numbers [4] or [{F}, 4], got {K.dtype} {K.shape}")
+    if pose.dtype.kind not in "fiu" or pose.shape != (F, 4, 4):
+        raise ValueError(f"frames.make: pose: expected numbers [{F}, 4, 4], got {pose.dtype} {pose.shape}")
+    ds = np.float32(depth_shift)
+    if not (ds > 0 and np.isfinite(ds)):
+        raise ValueError(f"frames.make: depth_shift must be positive and finite in float32, got {depth_shift!r}")
+    t = np.empty((F, RECORD_FLOATS), np.float64)
+    t[:, :4] = np.broadcast_to(K.astype(np.float64), (F, 4))
+    t[:, 4:] = pose.astype(np.float64)[:, :3, :].reshape(F, 12)
+    if not np.isfinite(t).all() or not np.isfinite(pose.astype(np.float64)).all():
+        raise ValueError("frames.make: K or pose holds a value that is not finite")
+    if not (t[:, :2] > 0).all():
+        raise ValueError("frames.make: fx and fy must be positive")
+    if not (pose[:, 3, :] == np.array([0, 0, 0, 1])).all():
+        raise ValueError("frames.make: the last row of every pose must be (0, 0, 0, 1)")
+    with np.errstate(over="ignore"):
+        table = t.astype(np.float32)
+    if not np.isfinite(table).all() or not (table[:, :2] > 0).all():
+        raise ValueError("frames.make: a record is not finite (or fx, fy not positive) in float32")
+    return Frames(depth.contiguous(), color, table, float(ds))
+
+
+def camera(fr, f, size=None):
+    """The render.Camera of frame f, for images of size = (W, H) pixels (default: the frame's own size; another size
+    scales the intrinsics): predictions drawn with it are seen from the frame's own viewpoint.  ValueError unless
+    fx == fy (render's cameras have one focal length)."""
+    from . import render
+
+    F, H, W = fr.depth.shape
+    if not 0 <= int(f) < F:
+        raise ValueError(f"frames.camera: frame {f} of {F}")
+    fx, fy, cx, cy = (float(v) for v in fr.table[int(f), :4])
+    if fx != fy:
+        raise ValueError(f"frames.camera: frame {f}: fx = {fx} and fy = {fy} differ")
+    Wo, Ho = (W, H) if size is None else (int(s) for s in size)
+    sx, sy = Wo / W, Ho / H
+    if abs(sx - sy) > 1e-9 * max(sx, sy):
+        raise ValueError(f"frames.camera: size {Wo} x {Ho} does not keep the frame's aspect {W} x {H}")
+    P = fr.table[int(f), 4:].astype(np.float64).reshape(3, 4)
+    return render.Camera(tuple(P[:, 3]), tuple(P[:, :3].T.reshape(9)), "persp", fx * sx, cx * sx, cy * sy)
+
+
+# ---- the host statement -----------------------------------------------------------------------------------------------
+def _args(fr, stride, near, far, edge, who):
+    if not isinstance(fr, Frames):
+        raise ValueError(f"{who}: expected the Frames of frames.make")
+    stride = int(stride)
+    if stride < 1:
+        raise ValueError(f"{who}: stride = {stride} (>= 1)")
+    e = np.float32(0.0 if edge is None else edge)
+    if not (e >= 0 and np.isfinite(e)):
+        raise ValueError(f"{who}: edge must be None or >= 0 and finite in float32, got {edge!r}")
+    F, H, W = fr.depth.shape
+    Hs, Ws = -(-H // stride), -(-W // stride)
+    if F * Hs * Ws > MAX_POINTS:
+        raise ValueError(f"{who}: {F * Hs * Ws} sampled pixels (at most {MAX_POINTS})")
+    return stride, np.float32(near), np.float32(far), e, Hs, Ws
+
+
+def _chunk(chunk, who):
+    c = 0 if chunk is None else int(chunk)
+    if c and not (64 <= c <= MAX_CHUNK and c % 64 == 0):
+        raise ValueError(f"{who}: chunk = {chunk} (None, or a multiple of 64 from 64 to {MAX_CHUNK})")
+    return c
+
+
+def _shift2(a, dx, dy, fill):
+    """out[f, y, x] = a[f, y + dy, x + dx] inside the image, fill outside."""
+    from .render import _shifted
+
+    return _shifted(a, dx, dy, fill)
+
+
+def backproject_host(fr, stride=1, near=0.1, far=10.0, edge=None):
+    """The statement of gf_frames_backproject, float32 with every operation rounded on its own: (xyz fp32 [n, 3], rgb
+    uint8 [n, 3], pixel_of int32 [n], point_of int32 [F, Hs, Ws], flag).  The sampled pixel (i0, j0) is the pixel
+    (i0 stride, j0 stride); z = d / depth_shift; a pixel is valid when near <= z <= far and, with edge, none of its four
+    neighbours at one full-resolution pixel that is inside the image and itself in range has |zn - z| > edge z;
+    xc = (((i + 0.5) - cx) z) / fx, yc likewise; X = ((P0 xc + P1 yc) + P2 z) + P3.  Valid pixels in ascending order of
+    (f, j0, i0); flag: some coordinate is not finite."""
+    stride, near, far, edge, Hs, Ws = _args(fr, stride, near, far, edge, "backproject_host")
+    f32 = np.float32
+    d = fr.depth.detach().cpu().numpy()
+    F, H, W = d.shape
+    with np.errstate(all="ignore"):
+        z = d.astype(np.float32) / f32(fr.depth_shift)
+        assert z.dtype == np.float32
+        inr = (z >= near) & (z <= far)
+        ok = inr.copy()
+        if edge > 0:
+            lim = edge * z
+            for dx, dy in ((-1, 0), (1, 0), (0, -1), (0, 1)):
+                zn = _shift2(z, dx, dy, f32(0))
+                ok &= ~(_shift2(inr, dx, dy, False) & (np.abs(zn - z) > lim))
+        ok, z = ok[:, ::stride, ::stride], z[:, ::stride, ::stride]
+        t = fr.table
+        i = (np.arange(Ws, dtype=np.int64) * stride).astype(np.float32)[None, None, :]
+        j = (np.arange(Hs, dtype=np.int64) * stride).astype(np.float32)[None, :, None]
+        col = lambda k: t[:, k][:, None, None]  # noqa: E731
+        xc = (((i + f32(0.5)) - col(2)) * z) / col(0)
+        yc = (((j + f32(0.5)) - col(3)) * z) / col(1)
+        world = [((col(4 + 4 * a) * xc + col(5 + 4 * a) * yc) + col(6 + 4 * a) * z) + col(7 + 4 * a) for a in range(3)]
+        assert all(w.dtype == np.float32 for w in world)
+    sel = ok.reshape(-1)
+    pixel_of = np.nonzero(sel)[0].astype(np.int32)
+    xyz = np.stack([w.reshape(-1)[sel] for w in world], axis=1) if pixel_of.size else np.zeros((0, 3), np.float32)
+    if fr.color is not None:
+        rgb = fr.color.detach().cpu().numpy()[:, ::stride, ::stride].reshape(-1, 3)[sel]
+    else:
+        rgb = np.zeros((pixel_of.size, 3), np.uint8)
+    point_of = np.full(sel.shape, -1, np.int32)
+    point_of[sel] = np.arange(pixel_of.size, dtype=np.int32)
+    return (np.ascontiguousarray(xyz, np.float32), np.ascontiguousarray(rgb), pixel_of, point_of.reshape(F, Hs, Ws),
+            int(not np.isfinite(xyz).all()))
+
+
+def cell_means_host(xyz, rgb, cell_of, count, origin, min_obs=1):
+    """The statement of gf_frames_cell_means: (xyz_out fp32 [m, 3], rgb_out uint8 [m, 3], count_out int32 [m], new_id
+    int32 [M], flag).  Per point and axis, float64: q = (int64)floor((x - o) 1048576) -- units of 2^-20 m, the
+    multiplication exact; per cell the int64 sum of q, mean = (float)(o + (sum / count) 2^-20); colour per channel the
+    integer (sum + count // 2) // count.  Cells with count >= min_obs keep their order and are renumbered densely;
+    new_id is -1 for the others.  Integer sums: no result depends on the order of the points.  flag: a point with
+    !(0 <= x - o < 16384), beyond what the sums are proven for."""
+    h = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)  # noqa: E731
+    xyz, rgb, cell_of, count, origin = h(xyz), h(rgb), h(cell_of), h(count), h(origin)
+    n, M = xyz.shape[0], count.shape[0]
+    if not (xyz.dtype == np.float32 and xyz.shape == (n, 3) and rgb.dtype == np.uint8 and rgb.shape == (n, 3)
+            and cell_of.dtype == np.int32 and cell_of.shape == (n,) and count.dtype == np.int32 and count.ndim == 1
+            and origin.dtype == np.float32 and origin.shape == (3,)):
+        raise ValueError("cell_means_host: expected xyz float32 [n, 3], rgb uint8 [n, 3], cell_of int32 [n], count int32 [M] "
+                         "and origin float32 [3]")
+    if int(min_obs) < 1:
+        raise ValueError(f"cell_means_host: min_obs = {min_obs} (>= 1)")
+    if n and not (cell_of.min() >= 0 and cell_of.max() < M):
+        raise ValueError("cell_means_host: cell_of outside [0, M)")
+    if not (count >= 1).all():
+        raise ValueError("cell_means_host: every count must be at least 1")
+    o = origin.astype(np.float64)
+    with np.errstate(all="ignore"):
+        e = xyz.astype(np.float64) - o
+        good = ((e >= 0) & (e < REACH)).all(1)
+        q = np.floor(np.where(good[:, None], e, 0.0) * UNITS).astype(np.int64)
+    vals = np.concatenate([q, rgb.astype(np.int64)], axis=1)
+    order = np.argsort(cell_of[good], kind="stable")
+    csum = np.zeros((int(good.sum()) + 1, 6), np.int64)
+    np.cumsum(vals[good][order], axis=0, out=csum[1:])
+    start = np.searchsorted(cell_of[good][order], np.arange(M + 1))
+    sums = csum[start[1:]] - csum[start[:-1]]  # [M, 6]
+    keep = count >= int(min_obs)
+    new_id = np.where(keep, np.cumsum(keep) - 1, -1).astype(np.int32)
+    cnt = count[keep].astype(np.int64)
+    mean = (sums[keep, :3].astype(np.float64) / cnt[:, None].astype(np.float64)) * (1.0 / UNITS)
+    xyz_out = (o + mean).astype(np.float32)
+    rgb_out = ((sums[keep, 3:] + (cnt // 2)[:, None]) // cnt[:, None]).astype(np.uint8)
+    return xyz_out, rgb_out, count[keep].astype(np.int32), new_id, int(not good.all())
+
+
+def _origin_arg(origin, who):
+    if origin is None:
+        return None
+    o = origin.detach().cpu().numpy() if torch.is_tensor(origin) else np.asarray(origin)
+    o = o.astype(np.float32).reshape(-1)
+    if o.shape != (3,) or not np.isfinite(o).all():
+        raise ValueError(f"{who}: origin: three finite numbers")
+    return o
+
+
+def _fuse_args(cell, min_obs, who):
+    from . import postprocess
+
+    c = postprocess._grid_args(cell, "first", who)
+    if int(min_obs) < 1:
+        raise ValueError(f"{who}: min_obs = {min_obs} (>= 1)")
+    return c, int(min_obs)
+
+
+_NOT_FINITE = "a back-projected coordinate is not finite (depth, intrinsics and pose give a value beyond float32)"
+_BEYOND = f"a point lies {int(REACH)} m or more from the grid's origin"
+
+
+def fuse_host(fr, cell=0.02, stride=1, near=0.1, far=10.0, edge=None, min_obs=1, origin=None):
+    """The statement of fuse, on the host: backproject_host, postprocess.grid_subsample_host (mode "first"; origin: the
+    caller's, or the per-axis float32 minimum of the points), cell_means_host, and point_of composed through cell_of
+    and new_id.  Returns a Fused of CPU tensors."""
+    from . import postprocess
+
+    c, min_obs = _fuse_args(cell, min_obs, "fuse_host")
+    origin = _origin_arg(origin, "fuse_host")
+    xyz, rgb, _, point_of, flag = backproject_host(fr, stride, near, far, edge)
+    if flag:
+        raise ValueError(f"fuse_host: {_NOT_FINITE}")
+    if xyz.shape[0] == 0:
+        return _empty(point_of.shape, "cpu")
+    if origin is None:
+        origin = xyz.min(0)
+    _, cell_of, count = postprocess.grid_subsample_host(xyz, c, "first", origin)
+    xyz_out, rgb_out, count_out, new_id, flag = cell_means_host(xyz, rgb, cell_of, count, origin, min_obs)
+    if flag:
+        raise ValueError(f"fuse_host: {_BEYOND}")
+    fused_of = np.where(point_of >= 0, new_id[cell_of[np.maximum(point_of, 0)]], -1).astype(np.int32)
+    return Fused(*(torch.from_numpy(np.ascontiguousarray(a)) for a in (xyz_out, rgb_out, count_out, fused_of)))
+
+
+def _empty(shape, device):
+    return Fused(torch.zeros((0, 3), dtype=torch.float32, device=device), torch.zeros((0, 3), dtype=torch.uint8, device=device),
+                 torch.zeros(0, dtype=torch.int32, device=device), torch.full(tuple(shape), -1, dtype=torch.int32, device=device))
+
+
+# ---- device wrappers --------------------------------------------------------------------------------------------------
+def limits():
+    """(record floats, frames, side, default chunk, points) of the library, asserted against this module's constants."""
+    from . import _lib
+
+    lib = _lib.load()
+    got = (lib.gf_frames_record_floats(), lib.gf_frames_max_frames(), lib.gf_frames_max_side(), lib.gf_frames_default_chunk(),
+           lib.gf_resample_max_points())
+    if got != (RECORD_FLOATS, MAX_FRAMES, MAX_SIDE, DEFAULT_CHUNK, MAX_POINTS):
+        raise RuntimeError(f"frames: the library's limits {got} are not this module's")
+    return got
+
+
+def backproject(fr, stride=1, near=0.1, far=10.0, edge=None, chunk=None, return_origin=False):
+    """(xyz fp32 [n, 3], rgb uint8 [n, 3], pixel_of int32 [n], point_of int32 [F, Hs, Ws]) on fr.depth's device: the valid
+    pixels of the frames as world points, in ascending order of the sampled pixel (gf_frames_backproject on the current
+    stream: three launches, bit-identical to backproject_host and from call to call).  The two words {n, not finite}
+    are read back once (the only synchronisation); a coordinate that is not finite is a ValueError.  chunk: the pixels
+    one workgroup compacts (None: the default).  return_origin: also the per-axis minimum of xyz, float32 [3] on the
+    device (found by the kernel that writes the points; meaningless when n == 0) -- the default origin of fuse's grid.
+    Frames on the CPU run the statement."""
+    stride, near, far, e, Hs, Ws = _args(fr, stride, near, far, edge, "frames.backproject")
+    chunk = _chunk(chunk, "frames.backproject")
+    if not fr.depth.is_cuda:
+        xyz, rgb, pixel_of, point_of, flag = backproject_host(fr, stride, near, far, edge)
+        out = tuple(torch.from_numpy(a) for a in (xyz, rgb, pixel_of, point_of))
+        lo = torch.from_numpy(xyz.min(0) if xyz.shape[0] else np.zeros(3, np.float32))
+    else:
+        from . import _lib
+        from ._lib import check, ptr, stream_ptr
+
+        lib = _lib.load()
+        dev = fr.depth.device
+        F, H, W = fr.depth.shape
+        T = F * Hs * Ws
+        with torch.cuda.device(dev):
+            table = torch.from_numpy(fr.table).to(dev, non_blocking=True)
+            xyz = torch.empty((T, 3), dtype=torch.float32, device=dev)
+            rgb = torch.empty((T, 3), dtype=torch.uint8, device=dev)
+            pixel_of = torch.empty(T, dtype=torch.int32, device=dev)
+            point_of = torch.empty((F, Hs, Ws), dtype=torch.int32, device=dev)
+            words = torch.empty(2, dtype=torch.int32, device=dev)
+            lo = torch.empty(3, dtype=torch.float32, device=dev)
+            ws = torch.empty(lib.gf_frames_backproject_scratch_bytes(T, chunk) // 8 + 1, dtype=torch.int64, device=dev)
+            check(lib.gf_frames_backproject(ptr(fr.depth), int(fr.depth.dtype == torch.float32), fr.depth_shift, ptr(fr.color),
+                                            ptr(table), F, W, H, stride, float(near), float(far), float(e), chunk, ptr(ws),
+                                            ptr(xyz), ptr(rgb), ptr(pixel_of), ptr(point_of), ptr(lo), ptr(words), stream_ptr()),
+                  "gf_frames_backproject")
+            n, flag = words.tolist()
+        out = xyz[:n], rgb[:n], pixel_of[:n], point_of
+    if flag:
+        raise ValueError(f"frames.backproject: {_NOT_FINITE}")
+    return out + (lo,) if return_origin else out
+
+
+def cell_means(xyz, rgb, cell_of, count, origin, min_obs=1, chunk=None, aggregate=None):
+    """(xyz_out fp32 [m, 3], rgb_out uint8 [m, 3], count_out int32 [m], new_id int32 [M]) on xyz's device: one fused
+    point per cell with at least min_obs points, from the cell_of and count of pointops.grid_subsample(xyz, cell,
+    mode="first", origin=origin) (gf_frames_cell_means on the current stream: integer atomics only, bit-identical to
+    cell_means_host and from call to call).  origin: float32 [3] tensor on the same device.  The two words {m, beyond}
+    are read back once; a point 16384 m or more from the origin (or below it) is a ValueError.  aggregate: whether
+    adjacent lanes of one cell add up in the wave before the atomics (None: AGGREGATE; the result is the same).  CPU
+    tensors run the statement."""
+    if not (torch.is_tensor(xyz) and xyz.dtype == torch.float32 and xyz.dim() == 2 and xyz.shape[1] == 3 and xyz.is_contiguous()):
+        raise ValueError("frames.cell_means: xyz: expected a contiguous float32 tensor [n, 3]")
+    n, M, dev = xyz.shape[0], count.shape[0] if torch.is_tensor(count) else -1, xyz.device
+    for t, dt, shape, name in ((rgb, torch.uint8, (n, 3), "rgb"), (cell_of, torch.int32, (n,), "cell_of"),
+                               (count, torch.int32, (M,), "count"), (origin, torch.float32, (3,), "origin")):
+        if not (torch.is_tensor(t) and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev):
+            raise ValueError(f"frames.cell_means: {name}: expected a contiguous {dt} tensor {shape} on {dev}")
+    if int(min_obs) < 1:
+        raise ValueError(f"frames.cell_means: min_obs = {min_obs} (>= 1)")
+    chunk = _chunk(chunk, "frames.cell_means")
+    if n == 0 or M == 0:
+        if n or M:
+            raise ValueError(f"frames.cell_means: {n} points in {M} cells")
+        e = _empty((0,), dev)
+        return e.xyz, e.rgb, e.count, e.point_of
+    if not xyz.is_cuda:
+        *out, flag = cell_means_host(xyz, rgb, cell_of, count, origin, min_obs)
+        out = tuple(torch.from_numpy(a) for a in out)
+    else:
+        from . import _lib
+        from ._lib import check, ptr, stream_ptr
+
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            xyz_out = torch.empty((M, 3), dtype=torch.float32, device=dev)
+            rgb_out = torch.empty((M, 3), dtype=torch.uint8, device=dev)
+            out_i = torch.empty((2, M), dtype=torch.int32, device=dev)
+            words = torch.empty(2, dtype=torch.int32, device=dev)
+            ws = torch.empty(lib.gf_frames_cell_means_scratch_bytes(M, chunk) // 8 + 1, dtype=torch.int64, device=dev)
+            check(lib.gf_frames_cell_means(ptr(xyz), ptr(rgb), ptr(cell_of), ptr(count), n, M, ptr(origin), int(min_obs),
+                                           int(AGGREGATE if aggregate is None else aggregate), chunk, ptr(ws), ptr(xyz_out),
+                                           ptr(rgb_out), ptr(out_i[0]), ptr(out_i[1]), ptr(words), stream_ptr()),
+                  "gf_frames_cell_means")
+            m, flag = words.tolist()
+        out = xyz_out[:m], rgb_out[:m], out_i[0, :m], out_i[1]
+    if flag:
+        raise ValueError(f"frames.cell_means: {_BEYOND}")
+    return out
+
+
+def fuse(fr, cell=0.02, stride=1, near=0.1, far=10.0, edge=None, min_obs=1, origin=None, device="cuda"):
+    """Fused: the frames as one point per occupied cell of `cell` metres -- the mean position and colour of the pixels
+    that fell into it, the number of those pixels, and for every sampled pixel the point it went into.  stride: every
+    stride-th pixel of every stride-th row; near, far: the depth range in metres; edge: drop a pixel whose depth
+    differs from an in-range neighbour's by more than edge times its own (flying pixels at depth edges; None: off);
+    min_obs: cells seen by fewer pixels are dropped; origin: the grid's corner, three numbers no point lies below (None:
+    the per-axis minimum of the points).  Cells are numbered in order of their first pixel.  On the GPU: the frames are
+    moved to `device` when they are elsewhere, then gf_frames_backproject (which also finds the points' per-axis
+    minimum), pointops.grid_subsample, gf_frames_cell_means and gf_frames_compose on the current stream, with three small
+    read-backs ({n, flag}, {M, invalid}, {m, flag}) as the only synchronisations; bit-identical to fuse_host and from
+    call to call.  device "cpu" runs fuse_host."""
+    from . import pointops
+
+    c, min_obs = _fuse_args(cell, min_obs, "frames.fuse")
+    o = _origin_arg(origin, "frames.fuse")
+    _args(fr, stride, near, far, edge, "frames.fuse")
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        return fuse_host(fr, c, stride, near, far, edge, min_obs, o)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    if fr.depth.device != dev:
+        fr = fr._replace(depth=fr.depth.to(dev), color=None if fr.color is None else fr.color.to(dev))
+    from ._lib import check, ptr, stream_ptr
+    from . import _lib
+
+    with torch.cuda.device(dev):
+        xyz, rgb, _, point_of, lo = backproject(fr, stride, near, far, edge, return_origin=True)
+        if xyz.shape[0] == 0:
+            return _empty(point_of.shape, dev)
+        xyz, rgb = xyz.contiguous(), rgb.contiguous()  # (leading rows of the buffers: already contiguous)
+        org = lo if o is None else torch.from_numpy(o).to(dev)
+        try:
+            _, cell_of, count = pointops.grid_subsample(xyz, c, mode="first", origin=org)
+        except ValueError as e:
+            raise ValueError(f"frames.fuse: {e}") from None
+        xyz_out, rgb_out, count_out, new_id = cell_means(xyz, rgb, cell_of.contiguous(), count.contiguous(), org, min_obs)
+        check(_lib.load().gf_frames_compose(ptr(point_of), point_of.numel(), ptr(cell_of), ptr(new_id), stream_ptr()),
+              "gf_frames_compose")
+    return Fused(xyz_out, rgb_out, count_out, point_of)
+
+
+def gather(fused, values, fill=-1):
+    """Per-point values [n] or [n, C] (a tensor or an array: label ids, classes, panoptic ids, colours) as images
+    [F, Hs, Ws] or [F, Hs, Ws, C] on fused.point_of's device: every pixel takes the value of its fused point, `fill`
+    where it has none.  Exact: a pixel's point is the one it was fused into, nothing is projected or occluded."""
+    p = fused.point_of
+    v = torch.as_tensor(values).to(p.device)
+    n = fused.xyz.shape[0]
+    if v.dim() not in (1, 2) or v.shape[0] != n:
+        raise ValueError(f"frames.gather: values: expected [{n}] or [{n}, C], got {tuple(v.shape)}")
+    out = torch.full(tuple(p.shape) + tuple(v.shape[1:]), fill, dtype=v.dtype, device=p.device)
+    on = p >= 0
+    out[on] = v[p[on].long()]
+    return out

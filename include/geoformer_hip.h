@@ -1577,6 +1577,78 @@ int gf_instance_boxes_batched(const long long* table, int S, long long max_point
 int gf_box_iou_batched(const long long* table, int S, long long max_pairs, const double* a, const double* b, double* out,
                        void* stream);
 
+/* ===================================================================================
+ * Scenes from posed depth frames (csrc/frames.hip; the statements are frames.backproject_host and
+ * frames.cell_means_host): every depth pixel of a set of frames to a world point, and one fused point per grid cell
+ * as the mean of the points gf_grid_subsample put into it.  Ballots, integer scans and 64-bit integer atomic adds
+ * only: no result depends on the order in which pixels or points arrive, bit-identical from call to call.  No
+ * workgroup ever waits for another: a compaction is count, scan, write as three launches.  Every launch goes on
+ * `stream`; nothing is read back.
+ * =================================================================================== */
+
+/* Limits, as functions: the width of a frame record in floats (16), the frames of one call (65536), the side of a
+ * depth image in pixels (8192) and the default number of elements a workgroup compacts (2048). */
+int gf_frames_record_floats(void);
+int gf_frames_max_frames(void);
+int gf_frames_max_side(void);
+int gf_frames_default_chunk(void);
+
+/* gf_frames_backproject (two memsets, four launches): the valid pixels of F depth images as world points, compacted
+ * in ascending order of the sampled-pixel index t = (f Hs + j0) Ws + i0.
+ *   depth: kind 0: uint16 [F, H, W]; kind 1: fp32 [F, H, W];   depth_shift: fp32, positive and finite;
+ *   color: uint8 [F, H, W, 3] or NULL;
+ *   frames fp32 [F, 16]: {fx, fy, cx, cy, P[12]}, P rows 0..2 of the camera-to-world pose, row-major (camera axes: x
+ *     right, y down, z forward; pixel i covers [i, i + 1));
+ *   stride >= 1: the sampled pixel (i0, j0) is the pixel (i, j) = (i0 stride, j0 stride); Ws = ceil(W / stride), Hs
+ *     likewise; near, far: any floats; edge: >= 0 and finite, 0 = no edge filter;
+ *   chunk: the sampled pixels one workgroup compacts: a multiple of 64 in 64 .. 65536, or 0 for the default.  The block
+ *     counts are scanned by one workgroup, 256 at a time with a carry: more than 256 chunks is its second regime.
+ * Per sampled pixel, fp32, every operation rounded on its own, in this order:
+ *   z = (float)d / depth_shift (correctly rounded); invalid when !(z >= near) || !(z <= far);
+ *   with edge > 0: invalid when one of the pixels (i - 1, j), (i + 1, j), (i, j - 1), (i, j + 1) that lies inside the
+ *     image and is itself in [near, far] has |zn - z| > edge z (one subtraction, one multiplication, one compare);
+ *   xc = ((((float)i + 0.5) - cx) z) / fx, yc = ((((float)j + 0.5) - cy) z) / fy (correctly rounded divisions);
+ *   X = ((P0 xc + P1 yc) + P2 z) + P3, Y with P4..P7, Z with P8..P11.
+ * Outputs: xyz fp32 [T, 3], rgb uint8 [T, 3] (0 without color), pixel_of int32 [T]: the first n rows written;
+ *   point_of int32 [F, Hs, Ws]: the row of every valid pixel, -1 elsewhere (every cell written);
+ *   lo fp32 [3] (device) or NULL: the per-axis minimum of the written coordinates (by integer minima of ordered keys: -0
+ *     below +0; not used when n == 0) -- the default origin of the grid the points go into next;
+ *   d_words int32 [2] (device): {n, 1 when a written coordinate is not finite};
+ *   scratch: gf_frames_backproject_scratch_bytes(T, chunk), T = F Hs Ws.
+ * F outside 1 .. gf_frames_max_frames(), W or H outside 1 .. gf_frames_max_side(), T above
+ * gf_resample_max_points(), another kind, a bad depth_shift, stride, edge or chunk, or a NULL pointer (color aside)
+ * are GF_ERR_INVALID_ARG with nothing launched. */
+size_t gf_frames_backproject_scratch_bytes(long long T, int chunk);
+int gf_frames_backproject(const void* depth, int kind, float depth_shift, const unsigned char* color, const float* frames,
+                          int F, int W, int H, int stride, float near, float far, float edge, int chunk, void* scratch,
+                          float* xyz, unsigned char* rgb, int32_t* pixel_of, int32_t* point_of, float* lo,
+                          int32_t* d_words, void* stream);
+
+/* gf_frames_cell_means (two memsets, four launches): one fused point per cell that at least min_obs points fell into.
+ *   xyz fp32 [n, 3], rgb uint8 [n, 3]; cell_of int32 [n] in [0, M) and count int32 [M] >= 1 as gf_grid_subsample gave
+ *   them; origin: DEVICE fp32 [3], no coordinate above the points' (gf_grid_subsample's origin); min_obs >= 1;
+ *   chunk: the cells one workgroup compacts, as above.
+ * Per point and axis, float64: e = (double)x - (double)o, q = (int64)floor(e 1048576.0) (units of 2^-20 m; the
+ *   multiplication is exact); per cell sum_q by 64-bit integer atomic adds (adjacent lanes of a wave that hold the same
+ *   cell add their values first and issue one atomic when aggregate != 0: integer sums, so the same result), and
+ *   mean = (float)((double)o + ((double)sum_q / (double)count) (1.0 / 1048576.0)), every operation rounded on its own.
+ *   Colour per channel: (sum + count / 2) / count on 64-bit integer sums.
+ *   A point with !(0 <= e < 16384) raises the flag: within 2^14 m the 2^29 points of a call sum below 2^63.
+ * Kept cells (count >= min_obs) hold their order and are renumbered densely:
+ *   xyz_out fp32 [M, 3], rgb_out uint8 [M, 3], count_out int32 [M]: the first m rows written;
+ *   new_id int32 [M]: the row of a kept cell, -1 for a dropped one;
+ *   d_words int32 [2] (device): {m, flag};   scratch: gf_frames_cell_means_scratch_bytes(M, chunk).
+ * n or M outside 1 .. gf_resample_max_points(), min_obs < 1, a bad chunk or a NULL pointer are GF_ERR_INVALID_ARG with
+ * nothing launched. */
+size_t gf_frames_cell_means_scratch_bytes(int M, int chunk);
+int gf_frames_cell_means(const float* xyz, const unsigned char* rgb, const int32_t* cell_of, const int32_t* count, int n,
+                         int M, const float* origin, int min_obs, int aggregate, int chunk, void* scratch, float* xyz_out,
+                         unsigned char* rgb_out, int32_t* count_out, int32_t* new_id, int32_t* d_words, void* stream);
+
+/* gf_frames_compose (one launch): point_of int32 [T] of gf_frames_backproject, in place, to the fused point of every
+ * pixel: new_id[cell_of[p]] where p >= 0, -1 elsewhere.  T == 0 succeeds with nothing launched. */
+int gf_frames_compose(int32_t* point_of, long long T, const int32_t* cell_of, const int32_t* new_id, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,162 @@
+"""Posed depth frames of a synthetic room through csrc/frames.hip -- back-projection, the grid of cells, the cell means,
+the pixel-to-point map -- next to the numpy statement on the same input, for a kernel trace:
+
+    python tools/frames_trace.py                                   # 64 frames of 640 x 480, stride 1, 2 cm cells
+    rocprofv3 --kernel-trace --stats -d artifacts/frames -- python tools/frames_trace.py --no-host
+
+The depth images are ray casts of the inside of a 6 x 5 x 3 m room from cameras on a circle (uint16 millimetres, with
+colours).  Prints one JSON line: the time of every entry point from device events (median of --reps, buffers allocated
+ahead), the cell sums with and without the aggregation of equal cells among adjacent lanes, the whole frames.fuse (wall
+clock, the uploads of the frames not included), the numpy statement frames.fuse_host (wall clock) and whether the two
+agree bit for bit, and the share of the HBM peak the back-projection reaches on its algorithmic bytes (depth and colour
+read; points, colours and the two maps written).
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+HBM_PEAK = 8.0e12  # bytes per second, MI355X (specification)
+
+
+def room_frames(F, W, H, seed=0):
+    """(depth uint16 [F, H, W] in millimetres, color uint8 [F, H, W, 3], K [4], pose [F, 4, 4]): the inside of the box
+    [0, 6] x [0, 5] x [0, 3] m seen from F cameras on a circle of 1 m around its centre, each looking outwards and a
+    little down; the depth of a pixel is the camera-z of its ray's exit from the box."""
+    from geoformer_amd import render
+
+    lo, hi = np.zeros(3), np.array([6.0, 5.0, 3.0])
+    f = 0.9 * W
+    K = np.array([f, f, W / 2.0, H / 2.0])
+    i, j = np.meshgrid(np.arange(W) + 0.5, np.arange(H) + 0.5)
+    rays = np.stack([(i - K[2]) / f, (j - K[3]) / f, np.ones_like(i)], axis=-1)  # camera z = 1: t is the depth
+    depth = np.empty((F, H, W), np.uint16)
+    color = np.empty((F, H, W, 3), np.uint8)
+    pose = np.tile(np.eye(4), (F, 1, 1))
+    rng = np.random.default_rng(seed)
+    for k in range(F):
+        az = 2 * np.pi * k / F
+        eye = (lo + hi) / 2 + np.array([np.cos(az), np.sin(az), 0.2 * np.sin(3 * az)])
+        R = render.look_at(eye, eye + np.array([np.cos(az), np.sin(az), -0.25]))
+        pose[k, :3, :3], pose[k, :3, 3] = R.T, eye
+        d = rays @ R  # world directions
+        with np.errstate(divide="ignore"):
+            t = np.where(d > 0, (hi - eye) / d, np.where(d < 0, (lo - eye) / d, np.inf)).min(-1)
+        depth[k] = np.rint((t + rng.standard_normal(t.shape) * 0.002) * 1000).astype(np.uint16)
+        p = eye + d * t[..., None]
+        color[k] = (np.floor(p * 4).astype(np.int64) * np.array([37, 91, 53]) % 200 + 40).astype(np.uint8)
+    return depth, color, K, pose
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=64)
+    ap.add_argument("--size", default="640x480")
+    ap.add_argument("--stride", type=int, default=1)
+    ap.add_argument("--cell", type=float, default=0.02)
+    ap.add_argument("--edge", type=float, default=None)
+    ap.add_argument("--min-obs", type=int, default=1)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--no-host", action="store_true", help="skip the numpy statement (minutes at the default size)")
+    args = ap.parse_args()
+    W, H = (int(v) for v in args.size.lower().split("x"))
+
+    import geoformer_amd
+
+    geoformer_amd.configure_runtime()
+    from geoformer_amd import _lib, frames, pointops
+    from geoformer_amd._lib import check, ptr, stream_ptr
+
+    depth, color, K, pose = room_frames(args.frames, W, H)
+    fr = frames.make(depth, K, pose, color)
+    dfr = fr._replace(depth=fr.depth.cuda(), color=fr.color.cuda())
+    lib = _lib.load()
+    dev = torch.device("cuda")
+    F, s = args.frames, args.stride
+    Hs, Ws = -(-H // s), -(-W // s)
+    T = F * Hs * Ws
+    edge = 0.0 if args.edge is None else args.edge
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
+    table = torch.from_numpy(fr.table).cuda()
+    xyz, rgb = torch.empty((T, 3), dtype=torch.float32, device=dev), torch.empty((T, 3), dtype=torch.uint8, device=dev)
+    pixel_of, point_of, words = i32(T), i32(T), i32(2)
+    lo = torch.empty(3, dtype=torch.float32, device=dev)
+    ws = torch.empty(lib.gf_frames_backproject_scratch_bytes(T, 0) // 8 + 1, dtype=torch.int64, device=dev)
+
+    def backproject():
+        check(lib.gf_frames_backproject(ptr(dfr.depth), 0, fr.depth_shift, ptr(dfr.color), ptr(table), F, W, H, s, 0.1, 10.0,
+                                        edge, 0, ptr(ws), ptr(xyz), ptr(rgb), ptr(pixel_of), ptr(point_of), ptr(lo), ptr(words),
+                                        stream_ptr()), "gf_frames_backproject")
+
+    backproject()
+    n = int(words[0])
+    pts, cols = xyz[:n], rgb[:n]
+    org = lo.clone()
+    assert torch.equal(org, pts.amin(0))
+    _, cell_of, count = pointops.grid_subsample(pts, args.cell, mode="first", origin=org)
+    cell_of, count = cell_of.contiguous(), count.contiguous()
+    M = int(count.shape[0])
+    g_out, g_words = i32(3, n), i32(2)
+    g_ws = torch.empty(lib.gf_grid_subsample_scratch_bytes(n) // 8 + 1, dtype=torch.int64, device=dev)
+    m_xyz, m_rgb = torch.empty((M, 3), dtype=torch.float32, device=dev), torch.empty((M, 3), dtype=torch.uint8, device=dev)
+    m_out, m_words = i32(2, M), i32(2)
+    m_ws = torch.empty(lib.gf_frames_cell_means_scratch_bytes(M, 0) // 8 + 1, dtype=torch.int64, device=dev)
+    composed = i32(T)
+
+    def cells():
+        check(lib.gf_grid_subsample(ptr(pts), n, args.cell, 0, ptr(org), ptr(g_ws), ptr(g_out[0]), ptr(g_out[1]),
+                                    ptr(g_out[2]), ptr(g_words), stream_ptr()), "gf_grid_subsample")
+
+    def means(aggregate):
+        check(lib.gf_frames_cell_means(ptr(pts), ptr(cols), ptr(cell_of), ptr(count), n, M, ptr(org), args.min_obs, aggregate,
+                                       0, ptr(m_ws), ptr(m_xyz), ptr(m_rgb), ptr(m_out[0]), ptr(m_out[1]), ptr(m_words),
+                                       stream_ptr()), "gf_frames_cell_means")
+
+    def compose():
+        composed.copy_(point_of)
+        check(lib.gf_frames_compose(ptr(composed), T, ptr(cell_of), ptr(m_out[1]), stream_ptr()), "gf_frames_compose")
+
+    def timed(fn):
+        us = []
+        for i in range(args.reps + 2):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            if i >= 2:
+                us.append(a.elapsed_time(b) * 1e3)
+        return round(float(np.median(us)), 1)
+
+    stages = {"backproject_us": timed(backproject), "grid_subsample_us": timed(cells), "cell_means_aggregated_us": timed(lambda: means(1)),
+              "cell_means_plain_us": timed(lambda: means(0)), "compose_with_copy_us": timed(compose),
+              "copy_alone_us": timed(lambda: composed.copy_(point_of))}
+    m = int(m_words[0])
+    moved = T * (2 + 3 + 4) + n * (12 + 3 + 4)  # depth, colour, point_of; xyz, rgb, pixel_of
+    wall = []
+    for _ in range(5):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        fused = frames.fuse(dfr, args.cell, s, 0.1, 10.0, args.edge, args.min_obs)
+        torch.cuda.synchronize()
+        wall.append((time.perf_counter() - t) * 1e3)
+    out = {"frames": F, "size": [W, H], "stride": s, "cell": args.cell, "edge": args.edge, "min_obs": args.min_obs,
+           "sampled_pixels": T, "valid_pixels": n, "cells": M, "fused_points": m, **stages,
+           "backproject_bytes": moved, "backproject_share_of_hbm_peak": round(moved / (stages["backproject_us"] * 1e-6) / HBM_PEAK, 3),
+           "fuse_ms_wall": round(float(np.median(wall)), 2), "aggregate_default": frames.AGGREGATE}
+    if not args.no_host:
+        t = time.perf_counter()
+        want = frames.fuse_host(fr, args.cell, s, 0.1, 10.0, args.edge, args.min_obs)
+        out["fuse_host_numpy_ms"] = round((time.perf_counter() - t) * 1e3, 1)
+        out["equal_to_numpy"] = all(torch.equal(a.cpu(), b) for a, b in zip(fused, want))
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,112 @@
+"""Instance labels for posed depth frames: the frames are fused into one scene on the GPU (geoformer_amd.frames,
+csrc/frames.hip), the scene goes through batch_eval.label_batches, and the labels come back to every frame through the
+pixel-to-point map -- exactly, with no projection or occlusion guess.
+
+    python tools/predict_frames.py --frames scan.npz --out out
+    python tools/predict_frames.py --frames scan.npz --cell 0.03 --stride 2 --far 5 --edge 0.05 --min-obs 2 --out out
+
+scan.npz holds depth uint16 (millimetres; --depth-shift for another unit) or float32 [F, H, W], K [4] or [F, 4] =
+(fx, fy, cx, cy), pose [F, 4, 4] camera to world (camera axes x right, y down, z forward) and optionally color uint8
+[F, H, W, 3].  Written: <out>/<name>.ply (the fused points, export.write_ply), <out>/<name>.npz (export.save_labels) and
+per frame <out>/frames/<name>_<f>.npy (int32 [Hs, Ws]: the label id of every sampled pixel, 0 without an instance, -1
+where the pixel has no point) and <out>/frames/<name>_<f>.png in render.instance_colors (white: no point).  Without
+--checkpoint the benchmark's synthetic model runs.  Prints one JSON line.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--frames", required=True, metavar="FILE.npz", help="depth, K, pose and optionally color")
+    ap.add_argument("--out", default="predictions")
+    ap.add_argument("--cell", type=float, default=0.02, help="metres: one fused point per cell")
+    ap.add_argument("--stride", type=int, default=1, help="every stride-th pixel of every stride-th row")
+    ap.add_argument("--near", type=float, default=0.1)
+    ap.add_argument("--far", type=float, default=10.0)
+    ap.add_argument("--edge", type=float, default=None, help="drop pixels at relative depth jumps above this (off)")
+    ap.add_argument("--min-obs", type=int, default=1, help="drop cells seen by fewer pixels")
+    ap.add_argument("--depth-shift", type=float, default=None, help="depth units per metre (1000 for uint16, 1 for float32)")
+    ap.add_argument("--checkpoint", default=None, help="state dict (torch.save) of a GeoFormer of --config")
+    ap.add_argument("--config", default="test_geoformer_scannet.yaml")
+    return ap
+
+
+def frame_outputs(fused, labels):
+    """(ids int32 [F, Hs, Ws], -1 where a pixel has no point; image uint8 [F, Hs, Ws, 3]) of a Fused and its labels."""
+    from geoformer_amd import frames, render
+
+    dev = fused.point_of.device
+    ids = frames.gather(fused, torch.as_tensor(np.asarray(labels.ids), dtype=torch.int32), fill=-1)
+    owner = torch.as_tensor(np.asarray(labels.owner), dtype=torch.int32, device=dev)
+    image = frames.gather(fused, render.instance_colors(owner), fill=255)
+    return ids, image
+
+
+def main():
+    ap = build_parser()
+    args = ap.parse_args()
+
+    import geoformer_amd
+
+    geoformer_amd.configure_runtime()
+    import bench
+    from geoformer_amd import batch_eval, export, frames, scene
+    from geoformer_amd.model import GeoFormer, load_config
+
+    name = os.path.splitext(os.path.basename(args.frames))[0]
+    with np.load(args.frames) as z:
+        missing = [k for k in ("depth", "K", "pose") if k not in z.files]
+        if missing:
+            ap.error(f"{args.frames}: no {', '.join(missing)}")
+        depth, K, pose = z["depth"], z["K"], z["pose"]
+        color = z["color"] if "color" in z.files else None
+    shift = args.depth_shift if args.depth_shift is not None else (1000.0 if depth.dtype == np.uint16 else 1.0)
+    try:
+        fr = frames.make(depth, K, pose, color, shift)
+        t = time.perf_counter()
+        fused = frames.fuse(fr, args.cell, args.stride, args.near, args.far, args.edge, args.min_obs)
+        torch.cuda.synchronize()
+        fuse_s = time.perf_counter() - t
+    except ValueError as e:
+        ap.error(str(e))
+    n = int(fused.xyz.shape[0])
+    if n == 0:
+        ap.error("no pixel of the frames is valid: check --near, --far and the depth unit")
+    raw, _ = fused.raw_scene()
+    dev = torch.device("cuda")
+    if args.checkpoint:
+        model = GeoFormer(load_config(args.config))
+        sd = torch.load(args.checkpoint, map_location="cpu")
+        model.load_state_dict(sd.get("state_dict", sd) if isinstance(sd, dict) else sd)
+        model.to(dev)
+        model.eval()
+    else:
+        probe = scene.make_batch([batch_eval.scene_dict(raw)])
+        model = bench.build_model(dev, probe_batch=bench.to_device(probe, dev), cfg_name=args.config)
+    np.random.seed(0)
+    (_, labels), = batch_eval.label_batches(model, [(name, raw)], 1)
+    os.makedirs(os.path.join(args.out, "frames"), exist_ok=True)
+    export.write_ply(os.path.join(args.out, f"{name}.ply"), fused.xyz, fused.rgb)
+    export.save_labels(os.path.join(args.out, f"{name}.npz"), labels)
+    ids, image = frame_outputs(fused, labels)
+    ids, image = ids.cpu().numpy(), image.cpu().numpy()
+    for f in range(ids.shape[0]):
+        np.save(os.path.join(args.out, "frames", f"{name}_{f:04d}.npy"), ids[f])
+        export.write_png(os.path.join(args.out, "frames", f"{name}_{f:04d}.png"), image[f])
+    print(json.dumps({"frames": int(ids.shape[0]), "sampled_pixels": int(ids.size), "pixels_with_a_point": int((ids >= 0).sum()),
+                      "fused_points": n, "fuse_ms": round(fuse_s * 1e3, 2), "picked": int(len(labels.table.kept)),
+                      "kept": int(np.sum(labels.table.kept)), "labelled_points": int((np.asarray(labels.owner) >= 0).sum()),
+                      "out": args.out}))
+
+
+if __name__ == "__main__":
+    main()
