@@ -7,6 +7,8 @@ phone, a headset).
     raw, shift = fused.raw_scene()                     # float64 [n, 8], what batch_eval.* takes
     (name, labels), = batch_eval.label_batches(model, [("scan", raw)], 1)
     ids = frames.gather(fused, labels.ids, fill=0)     # int32 [F, Hs, Ws]: the instance id of every depth pixel
+    sem, inst = frames.lift_scene(fused, label_images, instance_images, ignore=0)   # pixel labels onto the points, by vote
+    raw, shift = fused.raw_scene(semantic=sem, instance=inst)                       # ... a scene with its ground truth
 
 The hot path is csrc/frames.hip: gf_frames_backproject (pixel validity, the edge filter, the world point, an ordered
 compaction as count / scan / write), pointops.grid_subsample for the cells, and gf_frames_cell_means (fixed-point
@@ -32,6 +34,9 @@ UNITS = 1048576.0         # fixed-point units per metre of the cell sums
 REACH = 16384.0           # metres from the origin the integer sums are proven for
 AGGREGATE = True          # runs of equal cells among adjacent lanes are added in the wave before the atomics
 IGNORE_LABEL = -100
+VOTE_MAX_PROBES = 128     # gf_frames_vote_max_probes(): the probes of a thread in a table of fewer than 2 T slots
+VOTE_MIN_SLOTS, VOTE_MAX_SLOTS = 64, 1 << 30
+VOTE_AGGREGATE = True     # runs of equal (group, value) pairs among adjacent lanes add once
 
 
 class Frames(NamedTuple):
@@ -51,17 +56,41 @@ class Fused(NamedTuple):
     count: torch.Tensor
     point_of: torch.Tensor
 
-    def raw_scene(self, center=True):
+    def raw_scene(self, center=True, semantic=None, instance=None):
         """(raw float64 [n, 8], shift float64 [3]): the scene as data/scannetv2/prepare_data_inst.py stores one --
         coordinates minus their float64 mean (the shift; zeros with center=False), colours / 127.5 - 1, both labels
-        -100 -- which every batch_eval entry point takes as it is.  raw[:, :3] + shift are the fused coordinates."""
+        -100 -- which every batch_eval entry point takes as it is.  raw[:, :3] + shift are the fused coordinates.
+        semantic, instance: per-point labels [n] (lift_scene's) for columns 6 and 7, which then hold a ground truth."""
         xyz = self.xyz.detach().cpu().numpy().astype(np.float64)
         shift = xyz.mean(0) if center and xyz.shape[0] else np.zeros(3)
         raw = np.empty((xyz.shape[0], 8), np.float64)
         raw[:, :3] = xyz - shift
         raw[:, 3:6] = self.rgb.detach().cpu().numpy().astype(np.float64) / 127.5 - 1
         raw[:, 6:] = IGNORE_LABEL
+        for col, lab, name in ((6, semantic, "semantic"), (7, instance, "instance")):
+            if lab is not None:
+                lab = lab.detach().cpu().numpy() if torch.is_tensor(lab) else np.asarray(lab)
+                if lab.shape != (xyz.shape[0],) or lab.dtype.kind not in "iu":
+                    raise ValueError(f"raw_scene: {name}: expected integers [{xyz.shape[0]}], got {lab.dtype} {lab.shape}")
+                raw[:, col] = lab
         return raw, shift
+
+
+class Lifted(NamedTuple):
+    """What a vote leaves per group (per fused point): label int32 [n] (the value most of the group's votes hold, the
+    smallest of them on a tie, `fill` without a vote), votes int32 [n] (the votes for it) and total int32 [n] (the
+    group's votes), as torch tensors on one device."""
+    label: torch.Tensor
+    votes: torch.Tensor
+    total: torch.Tensor
+
+    def where(self, min_votes=1, min_share=None, fill=IGNORE_LABEL):
+        """label, with `fill` where votes < min_votes or (with min_share) votes.double() < min_share * total.double():
+        one float64 multiplication and one comparison per point, the same result on every device."""
+        bad = self.votes < int(min_votes)
+        if min_share is not None:
+            bad = bad | (self.votes.double() < float(min_share) * self.total.double())
+        return torch.where(bad, torch.full_like(self.label, int(fill)), self.label)
 
 
 def _tensor(a, name):
@@ -459,3 +488,188 @@ def gather(fused, values, fill=-1):
     on = p >= 0
     out[on] = v[p[on].long()]
     return out
+
+
+# ---- labels of the pixels onto the fused points: a vote ---------------------------------------------------------------
+_VALUE_KINDS = {torch.uint8: 0, torch.uint16: 1, torch.int32: 2}
+
+
+def vote_slots(T, n):
+    """(default, proven) table sizes of a vote of T elements into n groups: the smallest power of two at or above
+    2 min(T, 8 n) -- a few MB that stay in cache for the usual one or two labels per point -- and at or above 2 T, which
+    no input overflows; both at least 64 (gf_frames_vote_default_slots)."""
+    def pow2(v):
+        p = VOTE_MIN_SLOTS
+        while p < v:
+            p <<= 1
+        return p
+
+    return pow2(2 * min(int(T), 8 * int(n))), pow2(2 * int(T))
+
+
+def _vote_args(group, value, n, ignore, fill, who):
+    def h(a):  # (a read-only or strided array is copied: a tensor wants writable, contiguous memory)
+        return a if torch.is_tensor(a) else torch.from_numpy(a if a.flags.writeable and a.flags.c_contiguous else np.array(a, order="C"))
+
+    if not (torch.is_tensor(group) or isinstance(group, np.ndarray)) or not (torch.is_tensor(value) or isinstance(value, np.ndarray)):
+        raise ValueError(f"{who}: group and value: numpy arrays or torch tensors")
+    group, value = h(group), h(value)
+    if group.dtype != torch.int32:
+        raise ValueError(f"{who}: group: expected int32, got {group.dtype}")
+    if value.dtype not in _VALUE_KINDS:
+        raise ValueError(f"{who}: value: expected uint8, uint16 or int32, got {value.dtype}")
+    n = int(n)
+    if not 0 <= n <= MAX_POINTS:
+        raise ValueError(f"{who}: n = {n} groups (0 to {MAX_POINTS})")
+    if group.numel() > MAX_POINTS:
+        raise ValueError(f"{who}: {group.numel()} elements (at most {MAX_POINTS})")
+    if ignore is not None and int(ignore) != ignore:
+        raise ValueError(f"{who}: ignore must be None or an integer, got {ignore!r}")
+    if not -2 ** 31 <= int(fill) < 2 ** 31:
+        raise ValueError(f"{who}: fill = {fill} is no int32")
+    return group, value, n, None if ignore is None else int(ignore), int(fill)
+
+
+def vote_host(group, value, n, ignore=None, fill=IGNORE_LABEL):
+    """(Lifted of CPU tensors, pairs): the statement of gf_frames_vote.  group int32 and value uint8, uint16 or int32
+    of one shape, flattened to T elements.  Element t votes when 0 <= group[t] < n, value[t] >= 0 and value[t] != ignore
+    (an int or None; ScanNet's label-filt and instance-filt images use 0 for "unannotated": lift them with ignore=0).
+    group[t] >= n is a ValueError; group[t] < 0 is no vote (point_of's -1).  Per group g: total[g] = its votes; among
+    its distinct values the one with the largest count wins, ties go to the smallest value; label[g] = the winner, or
+    fill without a vote; votes[g] = the winner's count, or 0.  pairs: the distinct (group, value) pairs among the
+    votes.  Integer counts and integer comparisons only: no result depends on the order of the elements."""
+    group, value, n, ignore, fill = _vote_args(group, value, n, ignore, fill, "vote_host")
+    if tuple(group.shape) != tuple(value.shape):
+        raise ValueError(f"vote_host: group {tuple(group.shape)} and value {tuple(value.shape)} differ in shape")
+    g = group.detach().cpu().numpy().reshape(-1).astype(np.int64)
+    v = value.detach().cpu().numpy().reshape(-1).astype(np.int64)
+    if (g >= n).any():
+        raise ValueError(f"vote_host: a group is {int(g.max())}, outside the {n} groups")
+    on = (g >= 0) & (v >= 0)
+    if ignore is not None:
+        on &= v != ignore
+    pair, cnt = np.unique((g[on] << 32) | v[on], return_counts=True)
+    pg, pv = pair >> 32, pair & 0xffffffff
+    total = np.zeros(n, np.int64)
+    np.add.at(total, pg, cnt)
+    best = np.zeros(n, np.int64)  # count << 32 | (0xffffffff - value): the largest count, then the smallest value
+    np.maximum.at(best, pg, (cnt.astype(np.int64) << 32) | (0xffffffff - pv))
+    label = np.where(best > 0, 0xffffffff - (best & 0xffffffff), fill)
+    out = Lifted(*(torch.from_numpy(a.astype(np.int32)) for a in (label, best >> 32, total)))
+    return out, int(pair.size)
+
+
+def _vote_device(group, value, F, H, W, stride, n, ignore, fill, slots, aggregate, who):
+    """gf_frames_vote on group's device: group [F, Hs, Ws] (as its numel says), value [F, H, W], both contiguous."""
+    from . import _lib
+    from ._lib import check, ptr, stream_ptr
+
+    lib = _lib.load()
+    dev, T = group.device, group.numel()
+    default, proven = vote_slots(T, n)
+    if slots is not None:
+        s = int(slots)
+        if not (VOTE_MIN_SLOTS <= s <= VOTE_MAX_SLOTS and s & (s - 1) == 0):
+            raise ValueError(f"{who}: slots = {slots} (None, or a power of two from {VOTE_MIN_SLOTS} to {VOTE_MAX_SLOTS})")
+    with torch.cuda.device(dev):
+        out = torch.empty((3, n), dtype=torch.int32, device=dev)
+        if T == 0 or n == 0:
+            if n == 0 and T and bool((group >= 0).any()):
+                raise ValueError(f"{who}: a group is outside the 0 groups")
+            out[0] = fill
+            out[1:] = 0
+            return Lifted(out[0], out[1], out[2]), 0
+        has = ignore is not None and -2 ** 31 <= ignore < 2 ** 31  # (no value is another int)
+        words = torch.empty(3, dtype=torch.int32, device=dev)
+        for s in ((default, proven) if slots is None else (int(slots),)):
+            ws = torch.empty(lib.gf_frames_vote_scratch_bytes(s, n) // 8 + 1, dtype=torch.int64, device=dev)
+            check(lib.gf_frames_vote(ptr(group), ptr(value), _VALUE_KINDS[value.dtype], F, W, H, stride, n,
+                                     ignore if has else 0, int(has), fill, s,
+                                     int(VOTE_AGGREGATE if aggregate is None else aggregate), ptr(ws), ptr(out[0]),
+                                     ptr(out[1]), ptr(out[2]), ptr(words), stream_ptr()), "gf_frames_vote")
+            pairs, overflow, beyond = words.tolist()
+            if beyond:
+                raise ValueError(f"{who}: a group is outside the {n} groups")
+            if not overflow:
+                return Lifted(out[0], out[1], out[2]), pairs
+            if slots is not None:
+                raise ValueError(f"{who}: the table of slots = {s} overflowed; {proven} slots are always enough for "
+                                 f"{T} elements")
+        raise RuntimeError(f"{who}: a table of {proven} >= 2 T slots overflowed")  # (proven impossible)
+
+
+def vote(group, value, n, ignore=None, fill=IGNORE_LABEL, slots=None, aggregate=None):
+    """(Lifted, pairs) on group's device: vote_host's rule by gf_frames_vote on the current stream (four memsets, three
+    launches; integer atomics on a hash table of the distinct pairs: bit-identical to vote_host and from call to
+    call).  The three words {pairs, overflow, group out of range} are read back once per run, the only synchronisation;
+    a group >= n is a ValueError.  slots: the table's entries, a power of two; with fewer than 2 T of them the table may
+    overflow, which is a ValueError that names the size that is always enough.  None: the default size of vote_slots
+    and, when that overflows, ONE more run at the proven size.  aggregate: whether adjacent lanes of one pair add once
+    (None: VOTE_AGGREGATE; the result is the same).  CPU tensors run the statement."""
+    group, value, n, ignore, fill = _vote_args(group, value, n, ignore, fill, "frames.vote")
+    if tuple(group.shape) != tuple(value.shape):
+        raise ValueError(f"frames.vote: group {tuple(group.shape)} and value {tuple(value.shape)} differ in shape")
+    if not group.is_cuda:
+        return vote_host(group, value, n, ignore, fill)
+    if value.device != group.device:
+        raise ValueError(f"frames.vote: value on {value.device}, group on {group.device}")
+    return _vote_device(group.contiguous(), value.contiguous(), 1, 1, group.numel(), 1, n, ignore, fill, slots, aggregate,
+                        "frames.vote")
+
+
+def _lift(fused, images, ignore, fill, stride, slots, aggregate, host, who):
+    if not isinstance(fused, Fused):
+        raise ValueError(f"{who}: expected the Fused of frames.fuse")
+    p = fused.point_of
+    n = int(fused.xyz.shape[0])
+    _, images, n, ignore, fill = _vote_args(p, images, n, ignore, fill, who)
+    if p.dim() != 3:
+        raise ValueError(f"{who}: point_of: expected [F, Hs, Ws], got {tuple(p.shape)}")
+    F, Hs, Ws = p.shape
+    s = 1 if stride is None else int(stride)
+    if s < 1:
+        raise ValueError(f"{who}: stride = {stride} (>= 1)")
+    if images.dim() != 3 or images.shape[0] != F or (-(-images.shape[1] // s), -(-images.shape[2] // s)) != (Hs, Ws):
+        raise ValueError(f"{who}: images {tuple(images.shape)} at stride {s} do not sample to point_of's {tuple(p.shape)}")
+    if host or not p.is_cuda:
+        return vote_host(p.detach().cpu(), images.detach().cpu().numpy()[:, ::s, ::s], n, ignore, fill)[0]
+    H, W = int(images.shape[1]), int(images.shape[2])
+    return _vote_device(p.contiguous(), images.to(p.device).contiguous(), F, H, W, s, n, ignore, fill, slots, aggregate, who)[0]
+
+
+def lift(fused, images, ignore=None, fill=IGNORE_LABEL, stride=None, slots=None, aggregate=None):
+    """Lifted on fused.point_of's device: per fused point the label most of its pixels carry -- vote() with group =
+    fused.point_of.  images: uint8, uint16 or int32, of point_of's shape [F, Hs, Ws]; with stride=s the full-resolution
+    images [F, H, W] as the sensor wrote them (Hs = ceil(H / s), as fuse samples), read at the sampled pixels by the
+    kernel: no conversion and no slicing pass.  ignore: a value that does not vote (0 for ScanNet's label-filt and
+    instance-filt).  Exact: a pixel votes for the point it was fused into, nothing is projected or occluded."""
+    return _lift(fused, images, ignore, fill, stride, slots, aggregate, False, "frames.lift")
+
+
+def _lift_scene(fused, semantic, instance, ignore, stride, min_votes, min_share, host, who):
+    sem = _lift(fused, semantic, ignore, IGNORE_LABEL, stride, None, None, host, who).label
+    ins = _lift(fused, instance, ignore, IGNORE_LABEL, stride, None, None, host, who).where(min_votes, min_share)
+    on = ins >= 0
+    ids = torch.unique(ins[on])  # ascending
+    new = torch.where(on, torch.searchsorted(ids, ins.clamp(min=0)).to(torch.int32), torch.full_like(ins, IGNORE_LABEL))
+    if ids.numel() == 0:
+        return sem, new
+    # points -> instances: the same vote, with the new instance id as the group and the points' lifted classes as values
+    cls = (vote_host if host else vote)(new, sem, int(ids.numel()))[0].label
+    return torch.where(on, cls[new.clamp(min=0).long()], sem), new
+
+
+def lift_scene(fused, semantic, instance, ignore=None, stride=None, min_votes=1, min_share=None):
+    """(semantic int32 [n], instance int32 [n]) on point_of's device: dataset-style labels of the fused points from the
+    frames' semantic and instance images (lift's shapes; instance ids consistent across the frames).  Both images are
+    lifted; a point whose instance label fails Lifted.where(min_votes, min_share) has instance -100; the surviving ids
+    are renumbered 0 .. I-1 in ascending order of the original id; an instance's class is the vote of its points' lifted
+    classes (the same kernel, points -> instances) and is written to all its points, so that
+    evaluation.gt_ids_from_labels' "label of the first point" is the instance's label whichever point comes first; a
+    point without an instance keeps its own lifted class (-100 without a vote)."""
+    return _lift_scene(fused, semantic, instance, ignore, stride, min_votes, min_share, False, "frames.lift_scene")
+
+
+def lift_scene_host(fused, semantic, instance, ignore=None, stride=None, min_votes=1, min_share=None):
+    """The statement of lift_scene on the host (vote_host throughout): CPU tensors."""
+    return _lift_scene(fused, semantic, instance, ignore, stride, min_votes, min_share, True, "lift_scene_host")

@@ -1649,6 +1649,38 @@ int gf_frames_cell_means(const float* xyz, const unsigned char* rgb, const int32
  * pixel: new_id[cell_of[p]] where p >= 0, -1 elsewhere.  T == 0 succeeds with nothing launched. */
 int gf_frames_compose(int32_t* point_of, long long T, const int32_t* cell_of, const int32_t* new_id, void* stream);
 
+/* gf_frames_vote (csrc/frames_vote.hip; the statement is frames.vote_host; four memsets, three launches): per group the
+ * value most of its elements hold -- per-pixel labels lifted onto the fused points through point_of.
+ *   group int32 [F, Hs, Ws]: the group of every sampled element; Hs = ceil(H / stride), Ws likewise;
+ *   value: kind 0: uint8, kind 1: uint16, kind 2: int32; [F, H, W], read at (j0 stride, i0 stride) for the sampled
+ *     element (f, j0, i0): with stride 1 the shape of group, otherwise the full-resolution image as the sensor wrote it.
+ *     F = H = 1, W = T, stride = 1 is the plain one-dimensional form;
+ *   n: the number of groups; ignore, has_ignore: a value that does not vote (when has_ignore != 0); fill: the label of a
+ *     group without a vote.
+ * Element t votes when 0 <= group[t] < n, value[t] >= 0 and value[t] is not the ignored value.  group[t] >= n sets
+ * d_words[2] (and does not vote); group[t] < 0 is no vote.  Per group g: total[g] = its votes; among its distinct values
+ * the one with the largest count wins, ties go to the smallest value; label[g] = the winner or fill, votes[g] = the
+ * winner's count or 0.  Integer counts and one integer maximum of count << 32 | (0xffffffff - value): no result depends
+ * on the order of the elements, bit-identical from call to call, with and without `aggregate` (adjacent lanes of a wave
+ * that hold the same pair add once, with the length of their run).
+ *   slots: the entries (8-byte key group << 32 | value, 4-byte count) of the open-addressing table of the distinct
+ *     pairs: a power of two from 64 to 2^30.  With slots >= 2 T the table is never more than half full and probing is
+ *     unbounded; with fewer a thread gives up after gf_frames_vote_max_probes() (128) probes and sets d_words[1].
+ *     gf_frames_vote_default_slots(T, n): the smallest power of two >= 2 min(T, 8 n), at least 64 (0 for T or n outside
+ *     0 .. gf_resample_max_points()).
+ *   Outputs label, votes, total int32 [n]; d_words int32 [3] (device): {distinct pairs, overflow, group out of range}.
+ *     With overflow clear every vote was counted and the outputs are exact; with it set they are unspecified.
+ *   scratch: gf_frames_vote_scratch_bytes(slots, n) (0 for a bad slots or n).
+ * T = F Hs Ws or n above gf_resample_max_points(), a negative F, W, H or n, stride < 1, another kind, a bad slots or a
+ * NULL pointer are GF_ERR_INVALID_ARG with nothing launched; T == 0 or n == 0 succeeds with nothing launched (and
+ * nothing written).  Everything goes on `stream`; nothing is read back. */
+int gf_frames_vote_max_probes(void);
+int gf_frames_vote_default_slots(long long T, int n);
+size_t gf_frames_vote_scratch_bytes(int slots, int n);
+int gf_frames_vote(const int32_t* group, const void* value, int kind, int F, int W, int H, int stride, int n, int ignore,
+                   int has_ignore, int fill, int slots, int aggregate, void* scratch, int32_t* label, int32_t* votes,
+                   int32_t* total, int32_t* d_words, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,11 @@ colours).  Prints one JSON line: the time of every entry point from device event
 ahead), the cell sums with and without the aggregation of equal cells among adjacent lanes, the whole frames.fuse (wall
 clock, the uploads of the frames not included), the numpy statement frames.fuse_host (wall clock) and whether the two
 agree bit for bit, and the share of the HBM peak the back-projection reaches on its algorithmic bytes (depth and colour
-read; points, colours and the two maps written).
+read; points, colours and the two maps written).  Under "vote": gf_frames_vote (csrc/frames_vote.hip) lifting a label
+image -- the 1 m block every pixel's own point lies in -- onto the fused points, as uint8, uint16 and int32, at the
+default and at the proven table size, with and without the aggregation of equal pairs among adjacent lanes; the numpy
+statement frames.vote_host on the same input and whether the two agree; the share of the HBM peak on point_of's 4 bytes
+plus the label's 1, 2 or 4 per pixel.
 """
 import argparse
 import json
@@ -155,6 +159,40 @@ def main():
         want = frames.fuse_host(fr, args.cell, s, 0.1, 10.0, args.edge, args.min_obs)
         out["fuse_host_numpy_ms"] = round((time.perf_counter() - t) * 1e3, 1)
         out["equal_to_numpy"] = all(torch.equal(a.cpu(), b) for a, b in zip(fused, want))
+
+    # ---- the vote (csrc/frames_vote.hip): a label image lifted onto the fused points ------------------------------------
+    # the label of a pixel is the 1 m block its OWN back-projected point lies in (1 .. 90; 0 without a point), so the
+    # pixels of a fused point next to a block's face disagree, as the pixels at a segment's border do
+    group = fused.point_of.reshape(-1).contiguous()
+    own = pts[point_of.clamp(min=0).long()].floor().clamp(min=0).to(torch.int32)
+    block = torch.where(point_of >= 0, 1 + own[:, 0].clamp(max=5) + 6 * own[:, 1].clamp(max=4) + 30 * own[:, 2].clamp(max=2),
+                        torch.zeros_like(point_of))
+    del own
+    default, proven = frames.vote_slots(T, m)
+    v_out, v_words = i32(3, m), i32(3)
+    v_ws = torch.empty(lib.gf_frames_vote_scratch_bytes(proven, m) // 8 + 1, dtype=torch.int64, device=dev)
+    vote = {"vote_groups": m, "vote_slots_default": default, "vote_slots_proven": proven,
+            "vote_aggregate_default": frames.VOTE_AGGREGATE}
+    for name, dt, kind in (("u8", torch.uint8, 0), ("u16", torch.uint16, 1), ("i32", torch.int32, 2)):
+        image = block.to(dt).contiguous()
+
+        def run(slots, aggregate):
+            check(lib.gf_frames_vote(ptr(group), ptr(image), kind, 1, T, 1, 1, m, 0, 1, -100, slots, aggregate, ptr(v_ws),
+                                     ptr(v_out[0]), ptr(v_out[1]), ptr(v_out[2]), ptr(v_words), stream_ptr()), "gf_frames_vote")
+
+        us = {"default_aggregated": timed(lambda: run(default, 1)), "default_plain": timed(lambda: run(default, 0)),
+              "proven_aggregated": timed(lambda: run(proven, 1)), "proven_plain": timed(lambda: run(proven, 0))}
+        run(default, 1)
+        pairs, overflow, beyond = v_words.tolist()
+        nbytes = T * (4 + image.element_size())
+        vote[name] = {**{f"vote_{k}_us": v for k, v in us.items()}, "pairs": pairs, "overflow": overflow, "bytes": nbytes,
+                      "share_of_hbm_peak": round(nbytes / (us["default_aggregated"] * 1e-6) / HBM_PEAK, 3)}
+        if not args.no_host and name == "u8":
+            t = time.perf_counter()
+            want, want_pairs = frames.vote_host(group.cpu(), image.cpu(), m, 0)
+            vote["vote_host_numpy_ms"] = round((time.perf_counter() - t) * 1e3, 1)
+            vote["vote_equal_to_numpy"] = bool(all(torch.equal(a.cpu(), b) for a, b in zip(v_out, want)) and pairs == want_pairs)
+    out["vote"] = vote
     print(json.dumps(out))
 
 

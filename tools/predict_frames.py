@@ -11,6 +11,15 @@ scan.npz holds depth uint16 (millimetres; --depth-shift for another unit) or flo
 per frame <out>/frames/<name>_<f>.npy (int32 [Hs, Ws]: the label id of every sampled pixel, 0 without an instance, -1
 where the pixel has no point) and <out>/frames/<name>_<f>.png in render.instance_colors (white: no point).  Without
 --checkpoint the benchmark's synthetic model runs.  Prints one JSON line.
+
+    python tools/predict_frames.py --frames scan.npz --labels --label-ignore 0 --out out
+
+With --labels, scan.npz also holds label and instance, uint8, uint16 or int32 [F, H, W]: per pixel the class in the
+coding the scene is to carry (the scores below expect the dataset's 0..19) and an instance id that is consistent across
+the frames; --label-ignore is the value of unannotated pixels, which do not vote (0 in ScanNet's label-filt and
+instance-filt images as shipped; whatever the remapping to 0..19 left for them otherwise).  They are lifted onto the fused points by vote (frames.lift_scene, csrc/frames_vote.hip), the scene
+is written with its labels as <out>/<name>_scene.npy (float64 [n, 8], what batch_eval.* and augment.train_merge take),
+and it is scored: batch_eval.evaluate (AP) and evaluation.SemanticEvaluator (mIoU), under "lifted" in the JSON line.
 """
 import argparse
 import json
@@ -37,7 +46,36 @@ def build_parser():
     ap.add_argument("--depth-shift", type=float, default=None, help="depth units per metre (1000 for uint16, 1 for float32)")
     ap.add_argument("--checkpoint", default=None, help="state dict (torch.save) of a GeoFormer of --config")
     ap.add_argument("--config", default="test_geoformer_scannet.yaml")
+    ap.add_argument("--labels", action="store_true",
+                    help="lift the npz's per-pixel `label` and `instance` images onto the fused points and score the scene")
+    ap.add_argument("--label-ignore", type=int, default=None, metavar="V",
+                    help='the value of "unannotated" pixels, which do not vote (0 for ScanNet\'s label-filt / instance-filt)')
+    ap.add_argument("--min-votes", type=int, default=1, help="pixels an instance label needs on a point")
+    ap.add_argument("--min-share", type=float, default=None, help="share of a point's votes its instance label needs")
     return ap
+
+
+def lifted_labels(fused, label, instance, ignore, stride, min_votes=1, min_share=None):
+    """(semantic, instance) int32 [n] of frames.lift_scene for images of the depth's shape (read at the stride)."""
+    from geoformer_amd import frames
+
+    if tuple(fused.point_of.shape) == tuple(label.shape):
+        stride = None
+    return frames.lift_scene(fused, label, instance, ignore=ignore, stride=stride, min_votes=min_votes, min_share=min_share)
+
+
+def score(model, name, raw, config_classes=0):
+    """{"ap", "ap50", "ap25", "miou", "labelled_points"} of one labelled scene: batch_eval.evaluate and a
+    SemanticEvaluator over batch_eval.evaluate_semantic."""
+    from geoformer_amd import batch_eval, evaluation
+
+    np.random.seed(0)
+    _, avgs = batch_eval.evaluate(model, [(name, raw)], 1, classes=config_classes)
+    ev = evaluation.SemanticEvaluator(n_classes=model.cfg.classes, train_fold=model.cfg.train_fold)
+    res = batch_eval.evaluate_semantic(model, [(name, raw)], 1, evaluator=ev)
+    num = lambda v: None if np.isnan(v) else float(v)  # noqa: E731
+    return {"ap": num(avgs["all_ap"]), "ap50": num(avgs["all_ap_50%"]), "ap25": num(avgs["all_ap_25%"]),
+            "miou": num(res["miou"]), "labelled_points": int(res["points"])}
 
 
 def frame_outputs(fused, labels):
@@ -69,6 +107,12 @@ def main():
             ap.error(f"{args.frames}: no {', '.join(missing)}")
         depth, K, pose = z["depth"], z["K"], z["pose"]
         color = z["color"] if "color" in z.files else None
+        label = instance = None
+        if args.labels:
+            missing = [k for k in ("label", "instance") if k not in z.files]
+            if missing:
+                ap.error(f"{args.frames}: --labels, but no {', '.join(missing)}")
+            label, instance = z["label"], z["instance"]
     shift = args.depth_shift if args.depth_shift is not None else (1000.0 if depth.dtype == np.uint16 else 1.0)
     try:
         fr = frames.make(depth, K, pose, color, shift)
@@ -81,7 +125,16 @@ def main():
     n = int(fused.xyz.shape[0])
     if n == 0:
         ap.error("no pixel of the frames is valid: check --near, --far and the depth unit")
-    raw, _ = fused.raw_scene()
+    sem = ins = None
+    if label is not None:
+        try:
+            t = time.perf_counter()
+            sem, ins = lifted_labels(fused, label, instance, args.label_ignore, args.stride, args.min_votes, args.min_share)
+            torch.cuda.synchronize()
+            lift_s = time.perf_counter() - t
+        except ValueError as e:
+            ap.error(str(e))
+    raw, _ = fused.raw_scene(semantic=sem, instance=ins)
     dev = torch.device("cuda")
     if args.checkpoint:
         model = GeoFormer(load_config(args.config))
@@ -102,10 +155,16 @@ def main():
     for f in range(ids.shape[0]):
         np.save(os.path.join(args.out, "frames", f"{name}_{f:04d}.npy"), ids[f])
         export.write_png(os.path.join(args.out, "frames", f"{name}_{f:04d}.png"), image[f])
-    print(json.dumps({"frames": int(ids.shape[0]), "sampled_pixels": int(ids.size), "pixels_with_a_point": int((ids >= 0).sum()),
-                      "fused_points": n, "fuse_ms": round(fuse_s * 1e3, 2), "picked": int(len(labels.table.kept)),
-                      "kept": int(np.sum(labels.table.kept)), "labelled_points": int((np.asarray(labels.owner) >= 0).sum()),
-                      "out": args.out}))
+    out = {"frames": int(ids.shape[0]), "sampled_pixels": int(ids.size), "pixels_with_a_point": int((ids >= 0).sum()),
+           "fused_points": n, "fuse_ms": round(fuse_s * 1e3, 2), "picked": int(len(labels.table.kept)),
+           "kept": int(np.sum(labels.table.kept)), "labelled_points": int((np.asarray(labels.owner) >= 0).sum()),
+           "out": args.out}
+    if sem is not None:
+        np.save(os.path.join(args.out, f"{name}_scene.npy"), raw)  # the fused scene with its lifted labels, [n, 8]
+        out["lifted"] = {"lift_ms": round(lift_s * 1e3, 2), "points_with_a_class": int((sem >= 0).sum()),
+                         "points_with_an_instance": int((ins >= 0).sum()), "instances": max(int(ins.max()), -1) + 1,
+                         **score(model, name, raw)}
+    print(json.dumps(out))
 
 
 if __name__ == "__main__":
