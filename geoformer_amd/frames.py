@@ -16,6 +16,12 @@ integer sums per cell, the mean, the cells seen often enough renumbered in order
 and fuse_host are the numpy statement -- the same operations in the same order -- and the kernels are tested bit for
 bit against them.  Conventions are render.py's: camera axes x right, y down, z forward, pixel i covers [i, i + 1), so
 its centre is i + 0.5; pose is camera to world, R = pose[:3, :3]^T, eye = pose[:3, 3].
+
+While the sensor is still moving (csrc/frames_stream.hip): a map that persists between calls.
+
+    fuser = frames.Fuser(cell=0.02, edge=0.05)         # the grid and the integer sums of fuse, kept between calls
+    cells = [fuser.add(chunk) for chunk in chunks]     # int32 [F, Hs, Ws] per chunk; a cell keeps its number
+    fused = fuser.snapshot(1, torch.cat(cells))        # what fuse(concat(chunks), origin=fuser.origin) returns, as bits
 """
 from __future__ import annotations
 
@@ -37,6 +43,12 @@ IGNORE_LABEL = -100
 VOTE_MAX_PROBES = 128     # gf_frames_vote_max_probes(): the probes of a thread in a table of fewer than 2 T slots
 VOTE_MIN_SLOTS, VOTE_MAX_SLOTS = 64, 1 << 30
 VOTE_AGGREGATE = True     # runs of equal (group, value) pairs among adjacent lanes add once
+STREAM_REACH = 4096.0     # gf_frames_map_reach(): metres from the origin a Fuser's integer sums are proven for
+STREAM_MAX_PIXELS = 2 ** 31 - 1   # gf_frames_map_max_pixels(): the valid pixels a Fuser takes in all
+STREAM_MAX_PROBES = 128   # gf_frames_map_max_probes(): the probes of a thread in a table of fewer than 2 (M + n) slots
+STREAM_MIN_SLOTS, STREAM_MAX_SLOTS = 64, 1 << 31
+STREAM_AGGREGATE = True   # runs of equal cells among adjacent lanes are added in the wave before the atomics
+STREAM_MARGIN = 64.0      # metres below the first chunk's minimum a Fuser puts its origin when none is given
 
 
 class Frames(NamedTuple):
@@ -673,3 +685,484 @@ def lift_scene(fused, semantic, instance, ignore=None, stride=None, min_votes=1,
 def lift_scene_host(fused, semantic, instance, ignore=None, stride=None, min_votes=1, min_share=None):
     """The statement of lift_scene on the host (vote_host throughout): CPU tensors."""
     return _lift_scene(fused, semantic, instance, ignore, stride, min_votes, min_share, True, "lift_scene_host")
+
+
+# ---- a map that persists between calls: frames fused chunk by chunk ---------------------------------------------------
+_BELOW = ("point(s) outside the grid (not finite in cells, below the origin, or 2097152 cells or more from it): give "
+          "origin= three numbers no point of the stream will lie below, or a larger margin=")
+_STREAM_BEYOND = f"a point lies {int(STREAM_REACH)} m or more from the map's origin (or below it): see origin= and margin="
+
+
+_CELLS_RANGE = "cells holds a value below -1, or one outside the map's"
+
+
+def concat(parts):
+    """The Frames of several Frames, one after the other along the frame axis.  ValueError unless all have the same
+    depth dtype, image size, depth_shift and device, and colour in all or in none."""
+    parts = list(parts)
+    if not parts or not all(isinstance(p, Frames) for p in parts):
+        raise ValueError("frames.concat: expected a non-empty list of the Frames of frames.make")
+    a = parts[0]
+    for k, p in enumerate(parts[1:], 1):
+        for what, x, y in (("depth dtype", a.depth.dtype, p.depth.dtype), ("image size", a.depth.shape[1:], p.depth.shape[1:]),
+                           ("depth_shift", a.depth_shift, p.depth_shift), ("device", a.depth.device, p.depth.device),
+                           ("colour", a.color is None, p.color is None)):
+            if x != y:
+                raise ValueError(f"frames.concat: part {k} differs from part 0 in {what}")
+    F = sum(p.depth.shape[0] for p in parts)
+    if F > MAX_FRAMES:
+        raise ValueError(f"frames.concat: {F} frames (at most {MAX_FRAMES})")
+    color = None if a.color is None else torch.cat([p.color for p in parts]).contiguous()
+    return Frames(torch.cat([p.depth for p in parts]).contiguous(), color,
+                  np.ascontiguousarray(np.concatenate([p.table for p in parts])), a.depth_shift)
+
+
+def stream_slots(M, n):
+    """(default, proven) table sizes of a map of M cells before a call of n points: the smallest power of two at or
+    above max(4 M, n / 8) (gf_frames_map_default_slots) and at or above 2 (M + n), which no input overflows; both at
+    least 64."""
+    def pow2(v):
+        p = STREAM_MIN_SLOTS
+        while p < v:
+            p <<= 1
+        return p
+
+    return pow2(max(4 * int(M), int(n) // 8)), pow2(2 * (int(M) + int(n)))
+
+
+def stream_limits():
+    """(probes, reach, pixels) of the library's map, asserted against this module's constants."""
+    from . import _lib
+
+    lib = _lib.load()
+    got = (lib.gf_frames_map_max_probes(), lib.gf_frames_map_reach(), lib.gf_frames_map_max_pixels())
+    if got != (STREAM_MAX_PROBES, STREAM_REACH, STREAM_MAX_PIXELS) or lib.gf_frames_default_chunk() != DEFAULT_CHUNK:
+        raise RuntimeError(f"frames: the library's map limits {got} are not this module's")
+    return got
+
+
+def _stream_args(cell, stride, edge, origin, margin, who):
+    c, _ = _fuse_args(cell, 1, who)
+    if int(stride) < 1:
+        raise ValueError(f"{who}: stride = {stride} (>= 1)")
+    e = np.float32(0.0 if edge is None else edge)
+    if not (e >= 0 and np.isfinite(e)):
+        raise ValueError(f"{who}: edge must be None or >= 0 and finite in float32, got {edge!r}")
+    m = np.float32(margin)
+    if not (m >= 0 and np.isfinite(m)):
+        raise ValueError(f"{who}: margin must be >= 0 and finite in float32, got {margin!r}")
+    return c, int(stride), _origin_arg(origin, who), m
+
+
+def _stream_sig(fr, sig, who):
+    """What every chunk of a stream must share with the first: image size, depth dtype, depth_shift, colour or none."""
+    if not isinstance(fr, Frames):
+        raise ValueError(f"{who}: expected the Frames of frames.make")
+    mine = (tuple(fr.depth.shape[1:]), fr.depth.dtype, fr.depth_shift, fr.color is not None)
+    if sig is not None and mine != sig:
+        raise ValueError(f"{who}: this chunk (size, dtype, depth_shift, colour) = {mine} differs from the stream's {sig}: "
+                         "a chunk may differ from the one before in the number of frames only")
+    return mine
+
+
+def _stream_budget(pixels, n, who):
+    if pixels + n > STREAM_MAX_PIXELS:
+        raise ValueError(f"{who}: {pixels} valid pixels so far and {n} more: a map takes at most {STREAM_MAX_PIXELS}")
+
+
+def _stream_points(xyz, rgb, who):
+    h = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)  # noqa: E731
+    xyz = h(xyz)
+    if xyz.dtype != np.float32 or xyz.ndim != 2 or xyz.shape[1] != 3:
+        raise ValueError(f"{who}: xyz: expected float32 [n, 3], got {xyz.dtype} {xyz.shape}")
+    rgb = np.zeros((xyz.shape[0], 3), np.uint8) if rgb is None else h(rgb)
+    if rgb.dtype != np.uint8 or rgb.shape != xyz.shape:
+        raise ValueError(f"{who}: rgb: expected uint8 {xyz.shape} or None, got {rgb.dtype} {rgb.shape}")
+    if xyz.shape[0] > MAX_POINTS:
+        raise ValueError(f"{who}: {xyz.shape[0]} points (at most {MAX_POINTS})")
+    if not np.isfinite(xyz).all():
+        raise ValueError(f"{who}: a coordinate is not finite")
+    return np.ascontiguousarray(xyz), np.ascontiguousarray(rgb)
+
+
+def _cells_arg(cells, M, device, who):
+    if cells is None:
+        return None
+    c = cells if torch.is_tensor(cells) else torch.from_numpy(np.ascontiguousarray(cells))
+    if c.dtype != torch.int32:
+        raise ValueError(f"{who}: cells: expected int32 (what add returned, or several of them concatenated), got {c.dtype}")
+    c = c.to(device).contiguous()
+    if not c.is_cuda and c.numel() and not (int(c.min()) >= -1 and int(c.max()) < M):  # (on the device: the lookup's flag)
+        raise ValueError(f"{who}: {_CELLS_RANGE} {M} cells")
+    return c
+
+
+class FuserHost:
+    """The statement of Fuser, in numpy: a map (cell, origin, stride, near, far, edge) that frames are added to a chunk
+    at a time.  Per cell, in order of first occurrence: count and six int64 sums (three coordinates in units of 2^-20 m,
+    three colour channels).
+
+    add(fr) -> cells int32 [F, Hs, Ws]: backproject_host's rule; every valid pixel's point into its cell by
+    grid_subsample_host's rule (t = (x - origin) / cell in float32, c = floor t, valid when t is finite and
+    0 <= c < 2^21 per axis); a cell never seen before takes the next numbers, in ascending order of the chunk's sampled
+    pixel index of its first pixel; q = (int64)floor(((double)x - (double)o) 2^20) and the colour bytes are added to the
+    cell's sums and 1 to its count.  cells: the cell number of every sampled pixel, -1 for an invalid one; numbers never
+    change afterwards.  ValueError -- and the map exactly as it was -- for a chunk that differs from the stream's in
+    size, dtype, depth_shift or colour, a coordinate that is not finite, a point outside the grid, a point with
+    !(0 <= x - o < 4096), or more than 2^31 - 1 valid pixels in all.
+
+    snapshot(min_obs=1, cells=None) -> Fused: cell_means_host's second half on the stored sums: mean =
+    (float)((double)o + ((double)sum_q / (double)count) 2^-20), colour (sum + count // 2) // count, cells with
+    count >= min_obs kept in order and renumbered densely; point_of = new_id[cells] (-1 stays -1) for the cells given
+    (one add's, or several concatenated along the frame axis), an empty [0, 0, 0] without.  Changes nothing.
+
+    For chunks c1..ck, snapshot(min_obs, cat(cells_1..cells_k)) equals fuse_host(concat(c1..ck), ..., min_obs,
+    origin=map.origin) in every field, bit for bit.  origin=None: fixed at the first add with a valid pixel, at that
+    chunk's per-axis float32 minimum minus margin (one float32 subtraction per axis)."""
+
+    def __init__(self, cell=0.02, stride=1, near=0.1, far=10.0, edge=None, origin=None, margin=STREAM_MARGIN):
+        self._who = "frames." + type(self).__name__
+        self._cell, self._stride, self._origin, self._margin = _stream_args(cell, stride, edge, origin, margin, self._who)
+        self._near, self._far, self._edge = near, far, edge
+        self._sig = None
+        self._keys = np.zeros(0, np.int64)
+        self._count = np.zeros(0, np.int64)
+        self._sums = np.zeros((0, 6), np.int64)
+        self._pixels = 0
+
+    origin = property(lambda self: None if self._origin is None else self._origin.copy(),
+                      doc="float32 [3], or None before the first add with a valid pixel")
+    cells = property(lambda self: int(self._keys.shape[0]), doc="the cells of the map")
+    pixels = property(lambda self: self._pixels, doc="the valid pixels added so far")
+
+    def state(self):
+        """(keys int64 [M], count int64 [M], sums int64 [M, 6]) in cell order, copies."""
+        return self._keys.copy(), self._count.copy(), self._sums.copy()
+
+    def _insert(self, xyz, rgb, who):
+        """cell_of int64 [n] of n >= 1 finite points; every check is made before anything changes."""
+        n, M = xyz.shape[0], self._keys.shape[0]
+        _stream_budget(self._pixels, n, who)
+        origin = self._origin if self._origin is not None else (xyz.min(0) - self._margin).astype(np.float32)
+        with np.errstate(all="ignore"):
+            t = (xyz - origin) / self._cell
+            c = np.floor(t)
+            bad = ~(np.isfinite(t) & (c >= 0) & (c < (1 << 21))).all(1)
+        if bad.any():
+            raise ValueError(f"{who}: {int(bad.sum())} {_BELOW}")
+        e = xyz.astype(np.float64) - origin.astype(np.float64)
+        if not ((e >= 0) & (e < STREAM_REACH)).all():
+            raise ValueError(f"{who}: {_STREAM_BEYOND}")
+        ci = c.astype(np.int64)
+        key = ci[:, 0] | ci[:, 1] << 21 | ci[:, 2] << 42
+        uniq, first, inv = np.unique(key, return_index=True, return_inverse=True)
+        inv = inv.reshape(-1)
+        uid = np.empty(uniq.shape[0], np.int64)
+        known = np.zeros(uniq.shape[0], bool)
+        if M:
+            order = np.argsort(self._keys, kind="stable")
+            at = np.minimum(np.searchsorted(self._keys[order], uniq), M - 1)
+            known = self._keys[order][at] == uniq
+            uid[known] = order[at[known]]
+        new = np.nonzero(~known)[0]
+        new = new[np.argsort(first[new], kind="stable")]  # ascending first point: the order of first occurrence
+        uid[new] = M + np.arange(new.shape[0])
+        vals = np.concatenate([np.floor(e * UNITS).astype(np.int64), rgb.astype(np.int64), np.ones((n, 1), np.int64)], axis=1)
+        by = np.argsort(inv, kind="stable")
+        csum = np.zeros((n + 1, 7), np.int64)
+        np.cumsum(vals[by], axis=0, out=csum[1:])
+        start = np.searchsorted(inv[by], np.arange(uniq.shape[0] + 1))
+        per = csum[start[1:]] - csum[start[:-1]]
+        # nothing above changed the map
+        self._origin = origin
+        self._keys = np.concatenate([self._keys, uniq[new]])
+        self._count = np.concatenate([self._count, np.zeros(new.shape[0], np.int64)])
+        self._sums = np.concatenate([self._sums, np.zeros((new.shape[0], 6), np.int64)])
+        self._sums[uid] += per[:, :6]  # (uid holds every cell once)
+        self._count[uid] += per[:, 6]
+        self._pixels += n
+        return uid[inv]
+
+    def add(self, fr):
+        who = self._who + ".add"
+        sig = _stream_sig(fr, self._sig, who)
+        _args(fr, self._stride, self._near, self._far, self._edge, who)
+        xyz, rgb, _, point_of, flag = backproject_host(fr, self._stride, self._near, self._far, self._edge)
+        if flag:
+            raise ValueError(f"{who}: {_NOT_FINITE}")
+        cells = point_of
+        if xyz.shape[0]:
+            cell_of = self._insert(xyz, rgb, who).astype(np.int32)
+            cells = np.where(point_of >= 0, cell_of[np.maximum(point_of, 0)], -1).astype(np.int32)
+        self._sig = sig
+        return torch.from_numpy(np.ascontiguousarray(cells))
+
+    def add_points(self, xyz, rgb=None):
+        """cells int32 [n]: n world points (float32 [n, 3], finite; rgb uint8 [n, 3] or None for black) added as add adds
+        a chunk's valid pixels, in their order -- for points that come from somewhere else than a depth image."""
+        who = self._who + ".add_points"
+        xyz, rgb = _stream_points(xyz, rgb, who)
+        if xyz.shape[0] == 0:
+            return torch.zeros(0, dtype=torch.int32)
+        return torch.from_numpy(self._insert(xyz, rgb, who).astype(np.int32))
+
+    def snapshot(self, min_obs=1, cells=None):
+        who = self._who + ".snapshot"
+        if int(min_obs) < 1:
+            raise ValueError(f"{who}: min_obs = {min_obs} (>= 1)")
+        M = self._keys.shape[0]
+        cells = _cells_arg(cells, M, "cpu", who)
+        if M == 0:
+            return _empty((0, 0, 0) if cells is None else cells.shape, "cpu")
+        o = self._origin.astype(np.float64)
+        keep = self._count >= int(min_obs)
+        new_id = np.where(keep, np.cumsum(keep) - 1, -1).astype(np.int32)
+        cnt = self._count[keep]
+        mean = (self._sums[keep, :3].astype(np.float64) / cnt[:, None].astype(np.float64)) * (1.0 / UNITS)
+        xyz_out = (o + mean).astype(np.float32)
+        rgb_out = ((self._sums[keep, 3:] + (cnt // 2)[:, None]) // cnt[:, None]).astype(np.uint8)
+        if cells is None:
+            point_of = np.zeros((0, 0, 0), np.int32)
+        else:
+            c = cells.numpy()
+            point_of = np.where(c >= 0, new_id[np.maximum(c, 0)], -1).astype(np.int32)
+        return Fused(*(torch.from_numpy(np.ascontiguousarray(a)) for a in (xyz_out, rgb_out, cnt.astype(np.int32), point_of)))
+
+
+class Fuser:
+    """FuserHost's map on the GPU (csrc/frames_stream.hip): the same add, add_points, snapshot, origin, cells
+    and pixels, bit-identical to the statement after every call and from run to run.  The state is torch tensors owned
+    here: an open-addressing table (key, id, first) of `slots` entries, count int32 [capacity] and sums int64
+    [capacity, 6].  Frames are moved to `device` per add, as fuse does; a chunk may differ from the one before in the
+    number of frames only.
+
+    add: gf_frames_backproject, gf_frames_map_insert (claim, rank, number), gf_frames_map_accumulate and
+    gf_frames_map_lookup on the current stream; the words {n, not finite} of the back-projection and {M', invalid,
+    overflow, beyond} of the insert are read back, the only synchronisations.  After a failed insert the table is
+    rehashed (which drops what the insert claimed) before the ValueError is raised: the map is exactly as it was.
+    snapshot: gf_frames_map_means, gf_frames_map_lookup; the words {m, accumulate's flag, a cell out of range} are read
+    back once, the only synchronisation (the lookup checks every cell against the map's M as it reads it: a value
+    below -1 or >= M is a ValueError).
+
+    slots: the table's entries, a power of two.  None: the table starts at stream_slots' default and is doubled by
+    gf_frames_map_rehash until slots >= 4 M' after an add; when an insert overflows it, the table is rehashed ONCE to
+    the proven size >= 2 (M + n) and the insert run ONCE more.  A given `slots` is kept: overflowing it is a ValueError
+    that names the proven size.  capacity: the initial rows of count and sums (they grow to at least double, zero
+    filled, the used rows copied).  chunk: the elements one workgroup compacts (None: the default).  aggregate: whether
+    adjacent lanes of one cell add up in the wave before the atomics (None: STREAM_AGGREGATE; the result is the same).
+    rehashes, retries, row_growths count what their names say.  device "cpu": FuserHost."""
+
+    def __init__(self, cell=0.02, stride=1, near=0.1, far=10.0, edge=None, origin=None, margin=STREAM_MARGIN, device="cuda",
+                 slots=None, capacity=None, chunk=None, aggregate=None):
+        self._who = who = "frames.Fuser"
+        dev = torch.device(device)
+        self._host = None
+        self.rehashes = self.retries = self.row_growths = 0
+        if dev.type != "cuda":
+            self._host = FuserHost(cell, stride, near, far, edge, origin, margin)
+            return
+        self._cell, self._stride, self._origin, self._margin = _stream_args(cell, stride, edge, origin, margin, who)
+        self._near, self._far, self._edge = near, far, edge
+        self._chunk = _chunk(chunk, who)
+        self._aggregate = int(STREAM_AGGREGATE if aggregate is None else aggregate)
+        if slots is not None:
+            s = int(slots)
+            if not (STREAM_MIN_SLOTS <= s <= STREAM_MAX_SLOTS and s & (s - 1) == 0):
+                raise ValueError(f"{who}: slots = {slots} (None, or a power of two from {STREAM_MIN_SLOTS} to {STREAM_MAX_SLOTS})")
+        self._slots_arg = None if slots is None else int(slots)
+        cap = 1024 if capacity is None else int(capacity)
+        if cap < 1:
+            raise ValueError(f"{who}: capacity = {capacity} (>= 1)")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        stream_limits()
+        self._dev = dev
+        self._sig = None
+        self._M = self._pixels = 0
+        self._org = None  # the origin on the device, float32 [3]
+        self._keys = self._ids = self._first = None
+        with torch.cuda.device(dev):
+            self._count = torch.zeros(cap, dtype=torch.int32, device=dev)
+            self._sums = torch.zeros((cap, 6), dtype=torch.int64, device=dev)
+            # {m of the last snapshot, accumulate's flag (only ever set), the last snapshot's "a cell out of range"}
+            self._words = torch.zeros(3, dtype=torch.int32, device=dev)
+
+    @property
+    def origin(self):
+        """float32 [3], or None before the first add with a valid pixel."""
+        if self._host is not None:
+            return self._host.origin
+        if self._origin is None and self._org is not None:
+            self._origin = self._org.cpu().numpy()
+        return None if self._origin is None else self._origin.copy()
+
+    cells = property(lambda self: self._host.cells if self._host is not None else self._M, doc="the cells of the map")
+    pixels = property(lambda self: self._host.pixels if self._host is not None else self._pixels,
+                      doc="the valid pixels added so far")
+    slots = property(lambda self: None if self._host is not None or self._keys is None else int(self._keys.shape[0]),
+                     doc="the table's entries (None before the first add with a valid pixel)")
+    capacity = property(lambda self: None if self._host is not None else int(self._count.shape[0]),
+                        doc="the rows of count and sums")
+
+    def state(self):
+        """FuserHost.state() of this map: (keys int64 [M], count int64 [M], sums int64 [M, 6]) in cell order, read from
+        the table's numbered slots."""
+        if self._host is not None:
+            return self._host.state()
+        M = self._M
+        keys = np.zeros(M, np.int64)
+        if M:
+            ids = self._ids.cpu().numpy()
+            on = ids >= 0
+            if int(on.sum()) != M or not (np.sort(ids[on]) == np.arange(M)).all():
+                raise RuntimeError(f"{self._who}: the table's numbered slots are not the map's {M} cells")
+            keys[ids[on]] = self._keys.cpu().numpy()[on]
+        return keys, self._count[:M].cpu().numpy().astype(np.int64), self._sums[:M].cpu().numpy()
+
+    def _rehash(self, new_slots):
+        """The table moved into a cleared one of new_slots entries (numbered slots only; ids untouched)."""
+        from . import _lib
+        from ._lib import check, ptr, stream_ptr
+
+        dev, old = self._dev, self._keys
+        keys = torch.empty(new_slots, dtype=torch.int64, device=dev)
+        ids = torch.empty((2, new_slots), dtype=torch.int32, device=dev)
+        check(_lib.load().gf_frames_map_rehash(ptr(old), ptr(self._ids), 0 if old is None else old.shape[0], self._M, ptr(keys),
+                                               ptr(ids[0]), ptr(ids[1]), new_slots, stream_ptr()), "gf_frames_map_rehash")
+        self._keys, self._ids, self._first = keys, ids[0], ids[1]
+        self.rehashes += old is not None
+
+    def _insert(self, xyz, rgb, lo, who):
+        """cell_of int32 [n] (device) of n >= 1 points on the device; the map changes only when every check has passed."""
+        from . import _lib
+        from ._lib import check, ptr, stream_ptr
+
+        lib = _lib.load()
+        dev, n, M = self._dev, xyz.shape[0], self._M
+        _stream_budget(self._pixels, n, who)
+        if self._org is not None:
+            org = self._org
+        elif self._origin is not None:
+            org = torch.from_numpy(self._origin).to(dev)
+        else:
+            org = torch.sub(lo, torch.full((3,), float(self._margin), dtype=torch.float32, device=dev))
+        default, proven = stream_slots(M, n)
+        if self._keys is None:
+            self._rehash(default if self._slots_arg is None else self._slots_arg)
+        elif self._slots_arg is None and self._keys.shape[0] < default:
+            self._rehash(default)
+        cell_of = torch.empty(n, dtype=torch.int32, device=dev)
+        words = torch.empty(4, dtype=torch.int32, device=dev)
+        ws = torch.empty(lib.gf_frames_map_insert_scratch_bytes(n, self._chunk) // 8 + 1, dtype=torch.int64, device=dev)
+        for attempt in (0, 1):
+            slots = self._keys.shape[0]
+            check(lib.gf_frames_map_insert(ptr(xyz), n, float(self._cell), ptr(org), ptr(self._keys), ptr(self._ids),
+                                           ptr(self._first), slots, M, self._chunk, ptr(ws), ptr(cell_of), ptr(words),
+                                           stream_ptr()), "gf_frames_map_insert")
+            M2, invalid, overflow, beyond = words.tolist()
+            if not (invalid or overflow or beyond):
+                break
+            if invalid or beyond or self._slots_arg is not None or attempt or proven > STREAM_MAX_SLOTS:
+                self._rehash(slots)  # drops what the failed insert claimed (M <= slots: every cell holds a slot)
+                if invalid:
+                    raise ValueError(f"{who}: {_BELOW}")
+                if beyond:
+                    raise ValueError(f"{who}: {_STREAM_BEYOND}")
+                if attempt:
+                    raise RuntimeError(f"{who}: a table of {slots} >= 2 (M + n) slots overflowed")  # (proven impossible)
+                raise ValueError(f"{who}: the table of slots = {slots} overflowed; {proven} slots are always enough for "
+                                 f"{M} cells and {n} more points")
+            self._rehash(proven)
+            self.retries += 1
+        cap = self._count.shape[0]
+        if M2 > cap:
+            cap = max(2 * cap, M2)
+            count = torch.zeros(cap, dtype=torch.int32, device=dev)
+            sums = torch.zeros((cap, 6), dtype=torch.int64, device=dev)
+            count[:M] = self._count[:M]
+            sums[:M] = self._sums[:M]
+            self._count, self._sums = count, sums
+            self.row_growths += 1
+        check(lib.gf_frames_map_accumulate(ptr(xyz), ptr(rgb), ptr(cell_of), n, M2, ptr(org), self._aggregate, ptr(self._count),
+                                           ptr(self._sums), ptr(self._words[1:2]), stream_ptr()), "gf_frames_map_accumulate")
+        self._org, self._M, self._pixels = org, M2, self._pixels + n
+        if self._slots_arg is None:
+            slots = self._keys.shape[0]
+            while slots < 4 * M2 and slots < STREAM_MAX_SLOTS:
+                slots <<= 1
+            if slots != self._keys.shape[0]:
+                self._rehash(slots)
+        return cell_of
+
+    def add(self, fr):
+        if self._host is not None:
+            return self._host.add(fr)
+        from . import _lib
+        from ._lib import check, ptr, stream_ptr
+
+        who = self._who + ".add"
+        sig = _stream_sig(fr, self._sig, who)
+        _args(fr, self._stride, self._near, self._far, self._edge, who)
+        dev = self._dev
+        if fr.depth.device != dev:
+            fr = fr._replace(depth=fr.depth.to(dev), color=None if fr.color is None else fr.color.to(dev))
+        with torch.cuda.device(dev):
+            xyz, rgb, _, point_of, lo = backproject(fr, self._stride, self._near, self._far, self._edge, self._chunk or None,
+                                                    return_origin=True)
+            if xyz.shape[0]:
+                cell_of = self._insert(xyz.contiguous(), rgb.contiguous(), lo, who)
+                check(_lib.load().gf_frames_map_lookup(ptr(point_of), point_of.numel(), ptr(cell_of), cell_of.shape[0],
+                                                       ptr(point_of), None, stream_ptr()), "gf_frames_map_lookup")
+        self._sig = sig
+        return point_of
+
+    def add_points(self, xyz, rgb=None):
+        """FuserHost.add_points on the device: cells int32 [n]."""
+        if self._host is not None:
+            return self._host.add_points(xyz, rgb)
+        who = self._who + ".add_points"
+        xyz, rgb = _stream_points(xyz, rgb, who)
+        dev = self._dev
+        if xyz.shape[0] == 0:
+            return torch.zeros(0, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            # (a tensor wants writable memory)
+            up = lambda a: torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)  # noqa: E731
+            x = up(xyz)
+            return self._insert(x, up(rgb), x.min(0).values, who)
+
+    def snapshot(self, min_obs=1, cells=None):
+        if self._host is not None:
+            return self._host.snapshot(min_obs, cells)
+        from . import _lib
+        from ._lib import check, ptr, stream_ptr
+
+        who = self._who + ".snapshot"
+        if int(min_obs) < 1:
+            raise ValueError(f"{who}: min_obs = {min_obs} (>= 1)")
+        lib = _lib.load()
+        dev, M = self._dev, self._M
+        with torch.cuda.device(dev):
+            cells = _cells_arg(cells, M, dev, who)
+            if M == 0:
+                return _empty((0, 0, 0) if cells is None else cells.shape, dev)
+            xyz_out = torch.empty((M, 3), dtype=torch.float32, device=dev)
+            rgb_out = torch.empty((M, 3), dtype=torch.uint8, device=dev)
+            out_i = torch.empty((2, M), dtype=torch.int32, device=dev)
+            ws = torch.empty(lib.gf_frames_map_means_scratch_bytes(M, self._chunk) // 8 + 1, dtype=torch.int64, device=dev)
+            check(lib.gf_frames_map_means(ptr(self._count), ptr(self._sums), M, ptr(self._org), int(min_obs), self._chunk, ptr(ws),
+                                          ptr(xyz_out), ptr(rgb_out), ptr(out_i[0]), ptr(out_i[1]), ptr(self._words),
+                                          stream_ptr()), "gf_frames_map_means")
+            if cells is None:
+                point_of = torch.zeros((0, 0, 0), dtype=torch.int32, device=dev)
+            else:
+                point_of = torch.empty_like(cells)
+                self._words[2:].zero_()
+                check(lib.gf_frames_map_lookup(ptr(cells), cells.numel(), ptr(out_i[1]), M, ptr(point_of), ptr(self._words[2:]),
+                                               stream_ptr()), "gf_frames_map_lookup")
+            m, late, outside = self._words.tolist()
+        if cells is not None and outside:
+            raise ValueError(f"{who}: {_CELLS_RANGE} {M} cells")
+        if late:  # (the insert's claim pass makes the same comparison first: proven impossible)
+            raise RuntimeError(f"{who}: an accumulate met a point beyond the map's reach")
+        return Fused(xyz_out[:m], rgb_out[:m], out_i[0, :m], point_of)

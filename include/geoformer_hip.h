@@ -1681,6 +1681,95 @@ int gf_frames_vote(const int32_t* group, const void* value, int kind, int F, int
                    int has_ignore, int fill, int slots, int aggregate, void* scratch, int32_t* label, int32_t* votes,
                    int32_t* total, int32_t* d_words, void* stream);
 
+/* ===================================================================================
+ * A map that persists between calls (csrc/frames_stream.hip; the statement is frames.FuserHost): the cells and the
+ * integer sums of gf_grid_subsample + gf_frames_cell_means, fed one chunk of frames at a time.  A cell keeps the number
+ * it got when it was first seen.  The caller owns every piece of state and passes pointers:
+ *   keys uint64 [slots], ids int32 [slots], first int32 [slots]: an open-addressing table, slots a power of two from 64
+ *     to 2^31.  keys: cx | cy << 21 | cz << 42, all ones = empty; ids: the cell's number, -1 = claimed in the current call
+ *     and not numbered yet; first: the lowest point index of the current call that claimed the slot, INT_MAX before;
+ *   count int32 [cap], sums int64 [cap, 6] (three coordinate sums in units of 2^-20 m, three colour sums), zero beyond
+ *     the cells in use.
+ * Integer atomics and minima only; no thread waits for another thread or workgroup; every launch goes on `stream`;
+ * nothing is read back.  Every argument is checked before the first launch (GF_ERR_INVALID_ARG, nothing launched).
+ * =================================================================================== */
+
+/* Limits, as functions: the probes of a thread in a table of fewer than 2 (M + n) slots (128); the metres from the
+ * origin the sums are proven for (4096: q < 2^32, so that the 2^31 - 1 pixels a map takes at most sum below 2^63 and
+ * every count fits an int32); that number of pixels; the default table of a map of M cells before a call of T points:
+ * the smallest power of two >= max(4 M, T / 8), at least 64 (0 for M or T outside 0 .. 2^31 - 1). */
+int gf_frames_map_max_probes(void);
+double gf_frames_map_reach(void);
+long long gf_frames_map_max_pixels(void);
+long long gf_frames_map_default_slots(long long M, long long T);
+
+/* gf_frames_map_rehash (two launches): clears the table of new_slots entries (keys all ones, ids -1, first INT_MAX),
+ * then moves every slot of the old table with id >= 0 into it: key and id copied, ids untouched by construction.  A
+ * claim without a number (the debris of a failed gf_frames_map_insert) is dropped.  `cells`: the numbered cells of the
+ * old table; new_slots >= cells is required: the keys are distinct, so every one finds a free slot and the probing ends
+ * (a caller that grows the table keeps two slots per cell and more; a same-size rehash that only cleans may find the
+ * table fuller).  old_slots == 0 (old pointers unused) only clears: a new map.  The tables must not overlap. */
+int gf_frames_map_rehash(const unsigned long long* old_keys, const int32_t* old_ids, long long old_slots, int cells,
+                         unsigned long long* new_keys, int32_t* new_ids, int32_t* new_first, long long new_slots,
+                         void* stream);
+
+/* gf_frames_map_insert (one memset, five launches): the cells of n points (the compact xyz fp32 [n, 3] of one
+ * gf_frames_backproject call), numbered into a map that holds M cells.
+ *   claim   per point, fp32: t = (x - origin) / cell (correctly rounded division), c = floor t, valid when t is finite
+ *           and 0 <= c < 2^21 per axis (gf_grid_subsample's rule; an invalid point sets d_words[1]); float64:
+ *           !(0 <= (double)x - (double)o < gf_frames_map_reach()) sets d_words[3].  The key is found or claimed (the slot
+ *           is read first, the 64-bit CAS issued on an empty slot only); a slot with id < 0 takes an integer atomicMin of
+ *           the point index on `first` (read first).  With slots >= 2 (M + n) probing is unbounded; with fewer a thread
+ *           gives up after gf_frames_map_max_probes() probes and sets d_words[2].
+ *   rank    exclusive scan in point order of "my slot has id < 0 and first == my index", as count / top / emit over
+ *           workgroups of `chunk` points (a multiple of 64 in 64 .. 65536, 0 = gf_frames_default_chunk()); top writes
+ *           d_words[0] = M + the new cells.
+ *   number  emit: a new cell's first point writes id = M + rank; then one more launch: cell_of[i] = ids[slot of i].
+ *           Both return without writing when d_words[1], [2] or [3] is set (a wave-uniform branch on a word read).
+ * origin: DEVICE fp32 [3].  cell_of int32 [n]; d_words int32 [4] (device): {M', invalid point, table overflow, beyond
+ * reach}.  With a flag set, the table holds claims without a number and must be cleaned by gf_frames_map_rehash; no id,
+ * count or sum has changed.  scratch: gf_frames_map_insert_scratch_bytes(n, chunk) (0 for a bad n or chunk).
+ * n outside 0 .. gf_resample_max_points(), M < 0, M + n > 2^31 - 1, a bad cell, slots or chunk, or a NULL pointer are
+ * GF_ERR_INVALID_ARG; n == 0 succeeds with nothing launched. */
+size_t gf_frames_map_insert_scratch_bytes(int n, int chunk);
+int gf_frames_map_insert(const float* xyz, int n, float cell, const float* origin, unsigned long long* keys, int32_t* ids,
+                         int32_t* first, long long slots, int M, int chunk, void* scratch, int32_t* cell_of,
+                         int32_t* d_words, void* stream);
+
+/* gf_frames_map_accumulate (one launch): per point, q = (int64)floor(((double)x - (double)o) 1048576.0) per axis and the
+ * colour bytes added to sums[cell_of[i]] by 64-bit integer atomic adds, and 1 to count[cell_of[i]] by a 32-bit one.
+ * With aggregate != 0 adjacent lanes of one cell add within the wave first (runs numbered by their head lanes from one
+ * ballot; a run's count is its length; a wave whose lanes are all alone skips the exchange): the same result.
+ *   cell_of int32 [n] in [0, M), as gf_frames_map_insert wrote it; M: the cells of the map after that insert, <= the rows
+ *   of count and sums.  A point beyond reach (the insert's float64 comparison, which owns the check: a caller who
+ *   honours its word never gets here with one) or a cell outside [0, M) adds nothing and sets *d_flag (device int32;
+ *   only ever set, never cleared here).
+ * n outside 0 .. gf_resample_max_points(), M < 1 with n > 0, or a NULL pointer are GF_ERR_INVALID_ARG; n == 0 succeeds
+ * with nothing launched. */
+int gf_frames_map_accumulate(const float* xyz, const unsigned char* rgb, const int32_t* cell_of, int n, int M,
+                             const float* origin, int aggregate, int32_t* count, long long* sums, int32_t* d_flag,
+                             void* stream);
+
+/* gf_frames_map_means (three launches): gf_frames_cell_means without its summing pass, on the stored count int32 [M]
+ * and sums int64 [M, 6]: mean = (float)((double)o + ((double)sum_q / (double)count) (1.0 / 1048576.0)), colour
+ * (sum + count / 2) / count; cells with count >= min_obs keep their order and are renumbered densely.
+ *   xyz_out fp32 [M, 3], rgb_out uint8 [M, 3], count_out int32 [M]: the first m rows written; new_id int32 [M]: the row
+ *   of a kept cell, -1 for a dropped one; d_m int32 [1] (device): m.  Nothing of the map is written.
+ *   scratch: gf_frames_map_means_scratch_bytes(M, chunk) (0 for a bad M or chunk).
+ * M outside 1 .. 2^31 - 1 - 65536, min_obs < 1, a bad chunk or a NULL pointer are GF_ERR_INVALID_ARG. */
+size_t gf_frames_map_means_scratch_bytes(int M, int chunk);
+int gf_frames_map_means(const int32_t* count, const long long* sums, int M, const float* origin, int min_obs, int chunk,
+                        void* scratch, float* xyz_out, unsigned char* rgb_out, int32_t* count_out, int32_t* new_id,
+                        int32_t* d_m, void* stream);
+
+/* gf_frames_map_lookup (one launch): out[t] = table[index[t]] where 0 <= index[t] < len, -1 elsewhere, for T elements
+ * (out may be index): a pixel's row to its cell (table = cell_of) and a pixel's cell to its fused point (table =
+ * new_id).  An index below -1 or at or above len reads nothing and sets *d_flag (device int32, or NULL; only ever set,
+ * never cleared here).  T < 0, len < 0 or a NULL index, table or out are GF_ERR_INVALID_ARG; T == 0 succeeds with
+ * nothing launched. */
+int gf_frames_map_lookup(const int32_t* index, long long T, const int32_t* table, int len, int32_t* out, int32_t* d_flag,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

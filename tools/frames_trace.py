@@ -14,6 +14,11 @@ image -- the 1 m block every pixel's own point lies in -- onto the fused points,
 default and at the proven table size, with and without the aggregation of equal pairs among adjacent lanes; the numpy
 statement frames.vote_host on the same input and whether the two agree; the share of the HBM peak on point_of's 4 bytes
 plus the label's 1, 2 or 4 per pixel.
+
+    python tools/frames_trace.py --no-host --stream 8               # ... and the same frames 8 at a time
+
+Under "stream" (with --stream K): frames.Fuser (csrc/frames_stream.hip) fed K frames per add, next to the one-shot
+frames.fuse on the same input in the same process; see stream_leg.
 """
 import argparse
 import json
@@ -68,6 +73,8 @@ def main():
     ap.add_argument("--min-obs", type=int, default=1)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--no-host", action="store_true", help="skip the numpy statement (minutes at the default size)")
+    ap.add_argument("--stream", type=int, default=0, metavar="K",
+                    help="also run the frames K at a time through frames.Fuser (K divides --frames); see stream_leg")
     args = ap.parse_args()
     W, H = (int(v) for v in args.size.lower().split("x"))
 
@@ -193,7 +200,132 @@ def main():
             vote["vote_host_numpy_ms"] = round((time.perf_counter() - t) * 1e3, 1)
             vote["vote_equal_to_numpy"] = bool(all(torch.equal(a.cpu(), b) for a, b in zip(v_out, want)) and pairs == want_pairs)
     out["vote"] = vote
+    if args.stream:
+        out["stream"] = stream_leg(args, fr, dfr, timed)
     print(json.dumps(out))
+
+
+def stream_leg(args, fr, dfr, timed):
+    """frames.Fuser (csrc/frames_stream.hip) on the same frames, --stream K at a time: per configuration (aggregation on
+    and off; the compact table that grows by doubling and a table of the proven size from the start) the device time of
+    every add and of the snapshot from events, and the wall clock of the whole stream next to one-shot frames.fuse in the
+    same process; the entry points on their own on the last chunk (an insert that meets known cells only, which numbers
+    nothing); peak device memory of a stream fed from host memory against the one-shot call; FuserHost on the host."""
+    from geoformer_amd import _lib, frames
+    from geoformer_amd._lib import check, ptr, stream_ptr
+
+    lib = _lib.load()
+    F, K, s = args.frames, args.stream, args.stride
+    if K < 1 or F % K:
+        raise SystemExit(f"--stream {K}: a divisor of --frames {F}")
+    kw = dict(cell=args.cell, stride=s, near=0.1, far=10.0, edge=args.edge)
+    cut = lambda f, a, b: f._replace(depth=f.depth[a:b], color=f.color[a:b], table=f.table[a:b])  # noqa: E731
+    parts = [cut(dfr, a, a + K) for a in range(0, F, K)]
+    origin = None
+
+    def stream(fu, source=parts):
+        cells = [fu.add(p) for p in source]
+        return fu.snapshot(args.min_obs, torch.cat(cells))
+
+    # the origin every configuration shares (the first chunk's minimum minus the margin), and the cells at the end
+    probe = frames.Fuser(**kw)
+    snap = stream(probe)
+    origin, M = probe.origin, probe.cells
+    one = frames.fuse(dfr, args.cell, s, 0.1, 10.0, args.edge, args.min_obs, origin=origin)
+    res = {"chunk_frames": K, "adds": F // K, "cells": M, "valid_pixels": probe.pixels, "origin": [float(v) for v in origin],
+           "equal_to_one_shot_fuse": all(torch.equal(a, b) for a, b in zip(snap, one)),
+           "default_table_slots_at_the_end": probe.slots, "rehashes": probe.rehashes, "retries": probe.retries,
+           "row_growths": probe.row_growths, "aggregate_default": frames.STREAM_AGGREGATE}
+    H, W = dfr.depth.shape[1:]
+    proven = frames.stream_slots(M, K * -(-H // s) * -(-W // s))[1]  # at least 2 (M + n) at every add
+    res["proven_table_slots"] = proven
+    for table, slots in (("compact", None), ("proven", proven)):
+        for agg in (1, 0):
+            adds, snaps, walls = [], [], []
+            for rep in range(args.reps + 1):
+                fu = frames.Fuser(**kw, origin=origin, slots=slots, capacity=None if slots is None else M, aggregate=agg)
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(parts) + 2)]
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                cells = []
+                for k, p in enumerate(parts):
+                    ev[k].record()
+                    cells.append(fu.add(p))
+                ev[len(parts)].record()
+                fu.snapshot(args.min_obs, torch.cat(cells))
+                ev[len(parts) + 1].record()
+                torch.cuda.synchronize()
+                if rep:  # (the first run warms the allocator up)
+                    walls.append((time.perf_counter() - t) * 1e3)
+                    adds.append([ev[k].elapsed_time(ev[k + 1]) * 1e3 for k in range(len(parts))])
+                    snaps.append(ev[len(parts)].elapsed_time(ev[len(parts) + 1]) * 1e3)
+            per_add = np.median(np.array(adds), axis=0)
+            res[f"{table}_{'aggregated' if agg else 'plain'}"] = {
+                "first_add_us": round(float(per_add[0]), 1),
+                "later_add_us_median": round(float(np.median(per_add[1:])), 1) if len(per_add) > 1 else None,
+                "adds_us_sum": round(float(per_add.sum()), 1), "snapshot_us": round(float(np.median(snaps)), 1),
+                "stream_ms_wall": round(float(np.median(walls)), 2), "slots_at_the_end": fu.slots, "rehashes": fu.rehashes}
+    wall = []
+    for _ in range(5):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        frames.fuse(dfr, args.cell, s, 0.1, 10.0, args.edge, args.min_obs, origin=origin)
+        torch.cuda.synchronize()
+        wall.append((time.perf_counter() - t) * 1e3)
+    res["one_shot_fuse_ms_wall"] = round(float(np.median(wall)), 2)
+
+    # the entry points on their own, on the last chunk and the final map: every cell is known, so the insert numbers
+    # nothing and may be repeated; the accumulate adds into a copy of the rows
+    last = parts[-1]
+    pts, cols, _, _, _ = frames.backproject(last, s, 0.1, 10.0, args.edge, return_origin=True)
+    pts, cols = pts.contiguous(), cols.contiguous()
+    n = int(pts.shape[0])
+    res["last_chunk"] = {"valid_pixels": n, "backproject_us": timed(lambda: frames.backproject(last, s, 0.1, 10.0, args.edge))}
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=pts.device)  # noqa: E731
+    cell_of, words = i32(n), i32(4)
+    ws = torch.empty(lib.gf_frames_map_insert_scratch_bytes(n, 0) // 8 + 1, dtype=torch.int64, device=pts.device)
+    count, sums = probe._count.clone(), probe._sums.clone()
+    org = torch.from_numpy(origin).to(pts.device)
+    for name, fu in (("compact", probe), ("proven", fu)):  # (fu: the last configuration above, a table of the proven size)
+        def insert():
+            check(lib.gf_frames_map_insert(ptr(pts), n, args.cell, ptr(org), ptr(fu._keys), ptr(fu._ids), ptr(fu._first), fu.slots,
+                                           fu.cells, 0, ptr(ws), ptr(cell_of), ptr(words), stream_ptr()), "gf_frames_map_insert")
+
+        res["last_chunk"][f"insert_known_cells_{name}_us"] = timed(insert)
+        assert words.tolist() == [M, 0, 0, 0]
+    for agg in (1, 0):
+        def accumulate():
+            check(lib.gf_frames_map_accumulate(ptr(pts), ptr(cols), ptr(cell_of), n, M, ptr(org), agg, ptr(count), ptr(sums),
+                                               ptr(words), stream_ptr()), "gf_frames_map_accumulate")
+
+        res["last_chunk"][f"accumulate_{'aggregated' if agg else 'plain'}_us"] = timed(accumulate)
+    res["last_chunk"]["rehash_to_the_same_size_us"] = timed(lambda: probe._rehash(probe.slots))
+    res["snapshot_means_only_us"] = timed(lambda: probe.snapshot(args.min_obs))
+    del pts, cols, cell_of, ws, count, sums, one, snap, fu, probe, last, parts
+
+    # peak device memory: the frames in host memory, uploaded a chunk at a time, against the one-shot call on all of them
+    def peak(fn):
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        fn()
+        torch.cuda.synchronize()
+        return round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1)
+
+    host_parts = [cut(fr, a, a + K) for a in range(0, F, K)]
+    res["peak_MiB_stream_from_host"] = peak(lambda: stream(frames.Fuser(**kw, origin=origin), host_parts))
+    res["peak_MiB_one_shot_from_host"] = peak(lambda: frames.fuse(fr, args.cell, s, 0.1, 10.0, args.edge, args.min_obs,
+                                                                  origin=origin))
+    res["resident_frames_MiB"] = round((dfr.depth.numel() * dfr.depth.element_size() + dfr.color.numel()) / 2 ** 20, 1)
+    if not args.no_host:
+        t = time.perf_counter()
+        fz = frames.FuserHost(**kw, origin=origin)
+        want = fz.snapshot(args.min_obs, torch.cat([fz.add(p) for p in host_parts]))
+        res["fuser_host_numpy_ms"] = round((time.perf_counter() - t) * 1e3, 1)
+        got = stream(frames.Fuser(**kw, origin=origin), host_parts)
+        res["equal_to_numpy"] = all(torch.equal(a.cpu(), b) for a, b in zip(got, want))
+    return res
 
 
 if __name__ == "__main__":

@@ -12,6 +12,12 @@ per frame <out>/frames/<name>_<f>.npy (int32 [Hs, Ws]: the label id of every sam
 where the pixel has no point) and <out>/frames/<name>_<f>.png in render.instance_colors (white: no point).  Without
 --checkpoint the benchmark's synthetic model runs.  Prints one JSON line.
 
+    python tools/predict_frames.py --frames scan.npz --chunk-frames 8 --out out
+
+With --chunk-frames K the frames go through a frames.Fuser (csrc/frames_stream.hip) K at a time, so that only one
+chunk's images are on the device at a time; the grid's origin is then the first chunk's minimum minus 64 m, not the
+minimum of all points, which moves the cell borders and nothing else.  Without the flag nothing changes.
+
     python tools/predict_frames.py --frames scan.npz --labels --label-ignore 0 --out out
 
 With --labels, scan.npz also holds label and instance, uint8, uint16 or int32 [F, H, W]: per pixel the class in the
@@ -44,6 +50,8 @@ def build_parser():
     ap.add_argument("--edge", type=float, default=None, help="drop pixels at relative depth jumps above this (off)")
     ap.add_argument("--min-obs", type=int, default=1, help="drop cells seen by fewer pixels")
     ap.add_argument("--depth-shift", type=float, default=None, help="depth units per metre (1000 for uint16, 1 for float32)")
+    ap.add_argument("--chunk-frames", type=int, default=0, metavar="K",
+                    help="fuse the frames K at a time through a frames.Fuser: one chunk on the device at a time")
     ap.add_argument("--checkpoint", default=None, help="state dict (torch.save) of a GeoFormer of --config")
     ap.add_argument("--config", default="test_geoformer_scannet.yaml")
     ap.add_argument("--labels", action="store_true",
@@ -62,6 +70,27 @@ def lifted_labels(fused, label, instance, ignore, stride, min_votes=1, min_share
     if tuple(fused.point_of.shape) == tuple(label.shape):
         stride = None
     return frames.lift_scene(fused, label, instance, ignore=ignore, stride=stride, min_votes=min_votes, min_share=min_share)
+
+
+def fuse_in_chunks(depth, K, pose, color, shift, args):
+    """(Fused, {"chunk_frames", "adds", "cells", "table_slots", "rehashes"}): the frames through a frames.Fuser,
+    --chunk-frames at a time.  Only one chunk's depth and colour are on the device at a time: the arrays stay in host
+    memory (as np.load gave them) and are sliced per add.  The Fused is the one frames.fuse would return for all frames
+    with origin=the Fuser's, so everything after it is the same."""
+    from geoformer_amd import frames
+
+    F, step = int(depth.shape[0]), int(args.chunk_frames)
+    if step < 1:
+        raise ValueError(f"--chunk-frames {step} (>= 1)")
+    K = np.asarray(K)
+    fu = frames.Fuser(args.cell, args.stride, args.near, args.far, args.edge)
+    cells = []
+    for a in range(0, F, step):
+        b = min(F, a + step)
+        part = frames.make(depth[a:b], K if K.ndim == 1 else K[a:b], pose[a:b], None if color is None else color[a:b], shift)
+        cells.append(fu.add(part))
+    fused = fu.snapshot(args.min_obs, torch.cat(cells))
+    return fused, {"chunk_frames": step, "adds": len(cells), "cells": fu.cells, "table_slots": fu.slots, "rehashes": fu.rehashes}
 
 
 def score(model, name, raw, config_classes=0):
@@ -115,9 +144,13 @@ def main():
             label, instance = z["label"], z["instance"]
     shift = args.depth_shift if args.depth_shift is not None else (1000.0 if depth.dtype == np.uint16 else 1.0)
     try:
-        fr = frames.make(depth, K, pose, color, shift)
-        t = time.perf_counter()
-        fused = frames.fuse(fr, args.cell, args.stride, args.near, args.far, args.edge, args.min_obs)
+        if args.chunk_frames:
+            t = time.perf_counter()
+            fused, stream = fuse_in_chunks(depth, K, pose, color, shift, args)
+        else:
+            fr = frames.make(depth, K, pose, color, shift)
+            t = time.perf_counter()
+            fused = frames.fuse(fr, args.cell, args.stride, args.near, args.far, args.edge, args.min_obs)
         torch.cuda.synchronize()
         fuse_s = time.perf_counter() - t
     except ValueError as e:
@@ -159,6 +192,8 @@ def main():
            "fused_points": n, "fuse_ms": round(fuse_s * 1e3, 2), "picked": int(len(labels.table.kept)),
            "kept": int(np.sum(labels.table.kept)), "labelled_points": int((np.asarray(labels.owner) >= 0).sum()),
            "out": args.out}
+    if args.chunk_frames:
+        out["stream"] = stream  # (fuse_ms then includes the upload of every chunk)
     if sem is not None:
         np.save(os.path.join(args.out, f"{name}_scene.npy"), raw)  # the fused scene with its lifted labels, [n, 8]
         out["lifted"] = {"lift_ms": round(lift_s * 1e3, 2), "points_with_a_class": int((sem >= 0).sum()),
