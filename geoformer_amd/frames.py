@@ -22,6 +22,13 @@ While the sensor is still moving (csrc/frames_stream.hip): a map th
     fuser = frames.Fuser(cell=0.02, edge=0.05)         # the grid and the integer sums of fuse, kept between calls
     cells = [fuser.add(chunk) for chunk in chunks]     # int32 [F, Hs, Ws] per chunk; a cell keeps its number
     fused = fuser.snapshot(1, torch.cat(cells))        # what fuse(concat(chunks), origin=fuser.origin) returns, as bits
+
+... and its labels with it (csrc/frames_vote_stream.hip): the votes persist as the cells do, nothing is kept.
+
+    sem_v, ins_v = frames.Voter(ignore=0), frames.Voter(ignore=0)
+    for chunk, labels, instances in stream:
+        cells = fuser.add(chunk); sem_v.add(cells, labels); ins_v.add(cells, instances)
+    sem, inst = frames.lift_scene_stream(fuser, sem_v, ins_v)   # lift_scene over every frame so far, as bits
 """
 from __future__ import annotations
 
@@ -49,6 +56,11 @@ STREAM_MAX_PROBES = 128   # gf_frames_map_max_probes(): the probes of a thread i
 STREAM_MIN_SLOTS, STREAM_MAX_SLOTS = 64, 1 << 31
 STREAM_AGGREGATE = True   # runs of equal cells among adjacent lanes are added in the wave before the atomics
 STREAM_MARGIN = 64.0      # metres below the first chunk's minimum a Fuser puts its origin when none is given
+VOTER_MAX_PROBES = 128    # gf_frames_votes_max_probes(): the probes of a thread in a table of fewer than 2 (P + T) slots
+VOTER_MAX_ELEMENTS = 2 ** 31 - 1  # gf_frames_votes_max_elements(): the elements a Voter takes in all, counted as offered
+VOTER_MIN_SLOTS, VOTER_MAX_SLOTS = 64, 1 << 31   # (a slot is recorded as a non-negative int32)
+VOTER_MAX_GROUPS = 2 ** 31 - 1    # the n of a snapshot
+VOTER_AGGREGATE = True    # runs of equal (group, value) pairs among adjacent lanes record one add
 
 
 class Frames(NamedTuple):
@@ -658,9 +670,18 @@ def lift(fused, images, ignore=None, fill=IGNORE_LABEL, stride=None, slots=None,
     return _lift(fused, images, ignore, fill, stride, slots, aggregate, False, "frames.lift")
 
 
-def _lift_scene(fused, semantic, instance, ignore, stride, min_votes, min_share, host, who):
-    sem = _lift(fused, semantic, ignore, IGNORE_LABEL, stride, None, None, host, who).label
-    ins = _lift(fused, instance, ignore, IGNORE_LABEL, stride, None, None, host, who).where(min_votes, min_share)
+def scene_labels(sem, ins, min_votes=1, min_share=None, host=False):
+    """(semantic int32 [n], instance int32 [n]) from the Lifted of the semantic and of the instance images over the same
+    n points (lift's, or a Voter's snapshot): the tail of lift_scene.  A point whose instance label fails
+    ins.where(min_votes, min_share) has instance -100; the surviving ids are renumbered 0 .. I-1 in ascending order of
+    the original id; an instance's class is the vote of its points' lifted classes (points -> instances, the same
+    kernel; vote_host with host=True) and is written to all its points; a point without an instance keeps its own."""
+    if not (isinstance(sem, Lifted) and isinstance(ins, Lifted)):
+        raise ValueError("frames.scene_labels: expected two Lifted")
+    if sem.label.shape != ins.label.shape or sem.label.device != ins.label.device:
+        raise ValueError(f"frames.scene_labels: the semantic labels {tuple(sem.label.shape)} on {sem.label.device} and the "
+                         f"instance labels {tuple(ins.label.shape)} on {ins.label.device} differ in shape or device")
+    sem, ins = sem.label, ins.where(min_votes, min_share)
     on = ins >= 0
     ids = torch.unique(ins[on])  # ascending
     new = torch.where(on, torch.searchsorted(ids, ins.clamp(min=0)).to(torch.int32), torch.full_like(ins, IGNORE_LABEL))
@@ -669,6 +690,12 @@ def _lift_scene(fused, semantic, instance, ignore, stride, min_votes, min_share,
     # points -> instances: the same vote, with the new instance id as the group and the points' lifted classes as values
     cls = (vote_host if host else vote)(new, sem, int(ids.numel()))[0].label
     return torch.where(on, cls[new.clamp(min=0).long()], sem), new
+
+
+def _lift_scene(fused, semantic, instance, ignore, stride, min_votes, min_share, host, who):
+    sem = _lift(fused, semantic, ignore, IGNORE_LABEL, stride, None, None, host, who)
+    ins = _lift(fused, instance, ignore, IGNORE_LABEL, stride, None, None, host, who)
+    return scene_labels(sem, ins, min_votes, min_share, host)
 
 
 def lift_scene(fused, semantic, instance, ignore=None, stride=None, min_votes=1, min_share=None):
@@ -928,6 +955,12 @@ class FuserHost:
             point_of = np.where(c >= 0, new_id[np.maximum(c, 0)], -1).astype(np.int32)
         return Fused(*(torch.from_numpy(np.ascontiguousarray(a)) for a in (xyz_out, rgb_out, cnt.astype(np.int32), point_of)))
 
+    def kept(self, min_obs=1):
+        """int32 [m]: the cell number of every point of snapshot(min_obs), ascending -- the cells with count >= min_obs."""
+        if int(min_obs) < 1:
+            raise ValueError(f"{self._who}.kept: min_obs = {min_obs} (>= 1)")
+        return torch.from_numpy(np.nonzero(self._count >= int(min_obs))[0].astype(np.int32))
+
 
 class Fuser:
     """FuserHost's map on the GPU (csrc/frames_stream.hip): the same add, add_points, snapshot, origin, cells
@@ -1166,3 +1199,342 @@ class Fuser:
         if late:  # (the insert's claim pass makes the same comparison first: proven impossible)
             raise RuntimeError(f"{who}: an accumulate met a point beyond the map's reach")
         return Fused(xyz_out[:m], rgb_out[:m], out_i[0, :m], point_of)
+
+    def kept(self, min_obs=1):
+        """FuserHost.kept on the device: int32 [m], a torch reduction over the M counts (nothing of the map is read back
+        but m, the length of the result)."""
+        if self._host is not None:
+            return self._host.kept(min_obs)
+        if int(min_obs) < 1:
+            raise ValueError(f"{self._who}.kept: min_obs = {min_obs} (>= 1)")
+        with torch.cuda.device(self._dev):
+            return torch.nonzero(self._count[:self._M] >= int(min_obs)).reshape(-1).to(torch.int32)
+
+
+# ---- votes that persist between calls: labels lifted chunk by chunk ---------------------------------------------------
+def voter_slots(P, T):
+    """(default, proven) table sizes of a voter of P stored pairs before an add of T elements: the smallest power of two
+    at or above max(4 P, T / 8) (gf_frames_votes_default_slots; at most VOTER_MAX_SLOTS) and at or above 2 (P + T), which
+    no input overflows; both at least 64."""
+    def pow2(v):
+        p = VOTER_MIN_SLOTS
+        while p < v:
+            p <<= 1
+        return p
+
+    return min(pow2(max(4 * int(P), int(T) // 8)), VOTER_MAX_SLOTS), pow2(2 * (int(P) + int(T)))
+
+
+def voter_limits():
+    """(probes, elements) of the library's persistent vote, asserted against this module's constants."""
+    from . import _lib
+
+    lib = _lib.load()
+    got = (lib.gf_frames_votes_max_probes(), lib.gf_frames_votes_max_elements())
+    if got != (VOTER_MAX_PROBES, VOTER_MAX_ELEMENTS) or lib.gf_resample_max_points() != MAX_POINTS:
+        raise RuntimeError(f"frames: the library's voter limits {got} are not this module's")
+    return got
+
+
+def _voter_add_args(group, value, stride, elements, who):
+    """(group, value, F, H, W, stride, T) of an add: tensors as given (any device), every check of shape, dtype and the
+    element budget made."""
+    def h(a):  # (a read-only or strided array is copied: a tensor wants writable, contiguous memory)
+        return a if torch.is_tensor(a) else torch.from_numpy(a if a.flags.writeable and a.flags.c_contiguous else np.array(a, order="C"))
+
+    if not (torch.is_tensor(group) or isinstance(group, np.ndarray)) or not (torch.is_tensor(value) or isinstance(value, np.ndarray)):
+        raise ValueError(f"{who}: group and value: numpy arrays or torch tensors")
+    group, value = h(group), h(value)
+    if group.dtype != torch.int32:
+        raise ValueError(f"{who}: group: expected int32, got {group.dtype}")
+    if value.dtype not in _VALUE_KINDS:
+        raise ValueError(f"{who}: value: expected uint8, uint16 or int32, got {value.dtype}")
+    s = 1 if stride is None else int(stride)
+    if s < 1:
+        raise ValueError(f"{who}: stride = {stride} (>= 1)")
+    if s == 1:
+        if tuple(group.shape) != tuple(value.shape):
+            raise ValueError(f"{who}: group {tuple(group.shape)} and value {tuple(value.shape)} differ in shape")
+        F, H, W = 1, 1, group.numel()
+    else:
+        if group.dim() != 3 or value.dim() != 3 or value.shape[0] != group.shape[0] or \
+                (-(-value.shape[1] // s), -(-value.shape[2] // s)) != tuple(group.shape[1:]):
+            raise ValueError(f"{who}: value {tuple(value.shape)} at stride {s} does not sample to group's {tuple(group.shape)}")
+        F, H, W = (int(d) for d in value.shape)
+    T = group.numel()
+    if T > MAX_POINTS:
+        raise ValueError(f"{who}: {T} elements in one add (at most {MAX_POINTS})")
+    if elements + T > VOTER_MAX_ELEMENTS:
+        raise ValueError(f"{who}: {elements} elements so far and {T} more: a voter takes at most {VOTER_MAX_ELEMENTS}")
+    return group, value, F, H, W, s, T
+
+
+def _voter_init_args(ignore, who):
+    if ignore is not None and int(ignore) != ignore:
+        raise ValueError(f"{who}: ignore must be None or an integer, got {ignore!r}")
+    return None if ignore is None else int(ignore)
+
+
+def _voter_snapshot_args(n, fill, rows, who):
+    n = int(n)
+    if not 0 <= n <= VOTER_MAX_GROUPS:
+        raise ValueError(f"{who}: n = {n} groups (0 to {VOTER_MAX_GROUPS})")
+    if not -2 ** 31 <= int(fill) < 2 ** 31:
+        raise ValueError(f"{who}: fill = {fill} is no int32")
+    if rows is not None:
+        rows = rows if torch.is_tensor(rows) else torch.from_numpy(np.ascontiguousarray(rows))
+        if rows.dtype != torch.int32 or rows.dim() != 1:
+            raise ValueError(f"{who}: rows: expected int32 [m], got {rows.dtype} {tuple(rows.shape)}")
+    return n, int(fill), rows
+
+
+_ROWS_RANGE = "rows holds a value outside the"
+
+
+class VoterHost:
+    """The statement of Voter, in numpy: the multiset of (group, value) pairs seen so far with an integer count each, for
+    one `ignore` (an int or None, as in vote_host) fixed at construction.
+
+    add(group, value, stride=None): lift's shapes -- group int32 [F, Hs, Ws] (what Fuser.add returns) with value uint8,
+    uint16 or int32 [F, H, W] read at the pixels (j0 stride, i0 stride) -- or, without a stride, group and value of one
+    equal shape.  Element t votes when group[t] >= 0, value[t] >= 0 and value[t] != ignore: vote_host's test without the
+    upper bound on the group.  The value dtype may differ from one add to the next.  At most MAX_POINTS elements per add
+    and VOTER_MAX_ELEMENTS in all, counted as offered; a failed add leaves the voter exactly as it was.
+
+    snapshot(n, fill=IGNORE_LABEL, rows=None) -> (Lifted of CPU tensors, pairs): vote_host's second half on the stored
+    counts, per group 0 <= g < n: total = the group's votes; the value with the largest count wins, ties go to the
+    smallest value; a group without a vote gets fill and 0 votes.  pairs: the distinct stored pairs.  A stored pair with
+    group >= n is a ValueError.  rows: int32 [m] with values in [0, n) (anything else is a ValueError): the groups
+    reported, in that order.  Changes nothing.
+
+    For adds (g1, v1) .. (gk, vk), snapshot(n, fill) equals vote_host(cat(g_i).ravel(), cat(sampled v_i).ravel(), n,
+    ignore, fill) in every field and in pairs, as bits."""
+
+    def __init__(self, ignore=None):
+        self._who = "frames." + type(self).__name__
+        self._ignore = _voter_init_args(ignore, self._who)
+        self._keys = np.zeros(0, np.int64)
+        self._count = np.zeros(0, np.int64)
+        self._elements = 0
+
+    pairs = property(lambda self: int(self._keys.shape[0]), doc="the distinct (group, value) pairs stored")
+    elements = property(lambda self: self._elements, doc="the elements offered so far, voting or not")
+
+    def state(self):
+        """(keys int64 [P] ascending, count int64 [P]) with key = group << 32 | value, copies."""
+        return self._keys.copy(), self._count.copy()
+
+    def add(self, group, value, stride=None):
+        who = self._who + ".add"
+        group, value, F, H, W, s, T = _voter_add_args(group, value, stride, self._elements, who)
+        g = group.detach().cpu().numpy().reshape(-1).astype(np.int64)
+        v = value.detach().cpu().numpy()
+        v = (v[:, ::s, ::s] if s != 1 else v).reshape(-1).astype(np.int64)
+        on = (g >= 0) & (v >= 0)
+        if self._ignore is not None:
+            on &= v != self._ignore
+        keys, inv = np.unique(np.concatenate([self._keys, (g[on] << 32) | v[on]]), return_inverse=True)
+        count = np.zeros(keys.shape[0], np.int64)
+        np.add.at(count, inv.reshape(-1), np.concatenate([self._count, np.ones(int(on.sum()), np.int64)]))
+        self._keys, self._count, self._elements = keys, count, self._elements + T
+
+    def snapshot(self, n, fill=IGNORE_LABEL, rows=None):
+        who = self._who + ".snapshot"
+        n, fill, rows = _voter_snapshot_args(n, fill, rows, who)
+        pg, pv = self._keys >> 32, self._keys & 0xffffffff
+        if pg.size and int(pg.max()) >= n:
+            raise ValueError(f"{who}: a stored group is {int(pg.max())}, outside the {n} groups")
+        total = np.zeros(n, np.int64)
+        np.add.at(total, pg, self._count)
+        best = np.zeros(n, np.int64)  # count << 32 | (0xffffffff - value): the largest count, then the smallest value
+        np.maximum.at(best, pg, (self._count << 32) | (0xffffffff - pv))
+        label = np.where(best > 0, 0xffffffff - (best & 0xffffffff), fill)
+        out = [a.astype(np.int32) for a in (label, best >> 32, total)]
+        if rows is not None:
+            r = rows.detach().cpu().numpy()
+            if r.size and not (int(r.min()) >= 0 and int(r.max()) < n):
+                raise ValueError(f"{who}: {_ROWS_RANGE} {n} groups")
+            out = [a[r] for a in out]
+        return Lifted(*(torch.from_numpy(np.ascontiguousarray(a)) for a in out)), self.pairs
+
+
+class Voter:
+    """VoterHost's votes on the GPU (csrc/frames_vote_stream.hip): the same add, snapshot, state, pairs and
+    elements, bit-identical to the statement after every call and from run to run.  The state is two torch tensors owned
+    here: an open-addressing table of `slots` entries, keys (group << 32 | value, all ones = empty) and counts.  group
+    and value are moved to `device` per add when they are on the host; a tensor on another GPU is a ValueError.
+
+    add: gf_frames_votes_add on the current stream (claim, then commit); the two words {new pairs, overflow} are read
+    back once, the only synchronisation.  An add that overflows its table has changed no count; the table is rehashed
+    (which drops the keys it claimed) before anything else happens, so a failed add leaves no trace.
+    snapshot: gf_frames_votes_pick and, with rows=, three gathers; {pairs, group out of range, rows out of range} are
+    read back once.
+
+    slots: the table's entries, a power of two.  None: the table starts at voter_slots' default and is doubled by
+    gf_frames_votes_rehash until slots >= 4 P' after an add; when an add overflows it, the table is rehashed ONCE to the
+    proven size >= 2 (P + T) and the add run ONCE more.  A given `slots` is kept: overflowing it is a ValueError that
+    names the proven size, raised after the cleaning rehash; so is a proven size above VOTER_MAX_SLOTS.  aggregate:
+    whether adjacent lanes of one pair record one add (None: VOTER_AGGREGATE; the result is the same).  rehashes and
+    retries count what their names say.  device "cpu": VoterHost."""
+
+    def __init__(self, ignore=None, device="cuda", slots=None, aggregate=None):
+        self._who = who = "frames.Voter"
+        dev = torch.device(device)
+        self._host = None
+        self.rehashes = self.retries = 0
+        if dev.type != "cuda":
+            self._host = VoterHost(ignore)
+            return
+        self._ignore = _voter_init_args(ignore, who)
+        self._aggregate = int(VOTER_AGGREGATE if aggregate is None else aggregate)
+        if slots is not None:
+            s = int(slots)
+            if not (VOTER_MIN_SLOTS <= s <= VOTER_MAX_SLOTS and s & (s - 1) == 0):
+                raise ValueError(f"{who}: slots = {slots} (None, or a power of two from {VOTER_MIN_SLOTS} to {VOTER_MAX_SLOTS})")
+        self._slots_arg = None if slots is None else int(slots)
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        voter_limits()
+        self._dev = dev
+        self._keys = self._cnt = None  # int64 / int32 [slots]: the bits of the library's uint64 / uint32
+        self._pairs = self._elements = 0
+
+    pairs = property(lambda self: self._host.pairs if self._host is not None else self._pairs,
+                     doc="the distinct (group, value) pairs stored")
+    elements = property(lambda self: self._host.elements if self._host is not None else self._elements,
+                        doc="the elements offered so far, voting or not")
+    slots = property(lambda self: None if self._host is not None or self._keys is None else int(self._keys.shape[0]),
+                     doc="the table's entries (None before the first add with an element)")
+
+    def state(self):
+        """VoterHost.state() of these votes: (keys int64 [P] ascending, count int64 [P]), read from the table's slots
+        that hold a count."""
+        if self._host is not None:
+            return self._host.state()
+        if self._keys is None:
+            return np.zeros(0, np.int64), np.zeros(0, np.int64)
+        keys, cnt = self._keys.cpu().numpy(), self._cnt.cpu().numpy().astype(np.int64)
+        on = (keys != -1) & (cnt > 0)
+        if int(on.sum()) != self._pairs:
+            raise RuntimeError(f"{self._who}: the table holds {int(on.sum())} counted pairs, not the voter's {self._pairs}")
+        order = np.argsort(keys[on], kind="stable")
+        return keys[on][order], cnt[on][order]
+
+    def _rehash(self, new_slots):
+        """The table moved into a cleared one of new_slots entries (slots with a count only)."""
+        from . import _lib
+        from ._lib import check, ptr, stream_ptr
+
+        dev, old = self._dev, self._keys
+        keys = torch.empty(new_slots, dtype=torch.int64, device=dev)
+        cnt = torch.empty(new_slots, dtype=torch.int32, device=dev)
+        check(_lib.load().gf_frames_votes_rehash(ptr(old), ptr(self._cnt), 0 if old is None else old.shape[0], self._pairs,
+                                                 ptr(keys), ptr(cnt), new_slots, stream_ptr()), "gf_frames_votes_rehash")
+        self._keys, self._cnt = keys, cnt
+        self.rehashes += old is not None
+
+    def add(self, group, value, stride=None):
+        if self._host is not None:
+            return self._host.add(group, value, stride)
+        from . import _lib
+        from ._lib import check, ptr, stream_ptr
+
+        who = self._who + ".add"
+        group, value, F, H, W, s, T = _voter_add_args(group, value, stride, self._elements, who)
+        dev, P = self._dev, self._pairs
+        for t, name in ((group, "group"), (value, "value")):
+            if t.is_cuda and t.device != dev:
+                raise ValueError(f"{who}: {name} on {t.device}, the voter on {dev}")
+        if T == 0:
+            return
+        lib = _lib.load()
+        default, proven = voter_slots(P, T)
+        has = self._ignore is not None and -2 ** 31 <= self._ignore < 2 ** 31  # (no value is another int)
+        with torch.cuda.device(dev):
+            group, value = group.to(dev).contiguous(), value.to(dev).contiguous()
+            if self._keys is None:
+                self._rehash(default if self._slots_arg is None else self._slots_arg)
+            elif self._slots_arg is None and self._keys.shape[0] < default:
+                self._rehash(default)
+            words = torch.empty(2, dtype=torch.int32, device=dev)
+            ws = torch.empty(lib.gf_frames_votes_add_scratch_bytes(T) // 8 + 1, dtype=torch.int64, device=dev)
+            for attempt in (0, 1):
+                slots = self._keys.shape[0]
+                check(lib.gf_frames_votes_add(ptr(group), ptr(value), _VALUE_KINDS[value.dtype], F, W, H, s,
+                                              self._ignore if has else 0, int(has), ptr(self._keys), ptr(self._cnt), slots, P,
+                                              self._aggregate, ptr(ws), ptr(words), stream_ptr()), "gf_frames_votes_add")
+                new, overflow = words.tolist()
+                if not overflow:
+                    break
+                if self._slots_arg is not None or attempt or proven > VOTER_MAX_SLOTS:
+                    self._rehash(slots)  # drops what the failed add claimed (P <= slots: every pair holds a slot)
+                    if attempt:
+                        raise RuntimeError(f"{who}: a table of {slots} >= 2 (P + T) slots overflowed")  # (proven impossible)
+                    raise ValueError(f"{who}: the table of slots = {slots} overflowed; {proven} slots are always enough for "
+                                     f"{P} pairs and {T} more elements" +
+                                     (f", above the largest table of {VOTER_MAX_SLOTS}" if proven > VOTER_MAX_SLOTS else ""))
+                self._rehash(proven)
+                self.retries += 1
+            self._pairs, self._elements = P + new, self._elements + T
+            if self._slots_arg is None:
+                slots = self._keys.shape[0]
+                while slots < 4 * self._pairs and slots < VOTER_MAX_SLOTS:
+                    slots <<= 1
+                if slots != self._keys.shape[0]:
+                    self._rehash(slots)
+
+    def snapshot(self, n, fill=IGNORE_LABEL, rows=None):
+        if self._host is not None:
+            return self._host.snapshot(n, fill, rows)
+        from . import _lib
+        from ._lib import check, ptr, stream_ptr
+
+        who = self._who + ".snapshot"
+        n, fill, rows = _voter_snapshot_args(n, fill, rows, who)
+        lib = _lib.load()
+        dev = self._dev
+        if rows is not None and rows.is_cuda and rows.device != dev:
+            raise ValueError(f"{who}: rows on {rows.device}, the voter on {dev}")
+        if rows is not None and not rows.is_cuda and rows.numel() and not (int(rows.min()) >= 0 and int(rows.max()) < n):
+            raise ValueError(f"{who}: {_ROWS_RANGE} {n} groups")
+        with torch.cuda.device(dev):
+            out = torch.empty((3, n), dtype=torch.int32, device=dev)
+            if n == 0 or self._keys is None:
+                if self._pairs:
+                    raise ValueError(f"{who}: a stored group is outside the {n} groups")
+                out[0] = fill
+                out[1:] = 0
+                words = torch.zeros(2, dtype=torch.int32, device=dev)
+            else:
+                words = torch.empty(2, dtype=torch.int32, device=dev)
+                ws = torch.empty(lib.gf_frames_votes_pick_scratch_bytes(n) // 8 + 1, dtype=torch.int64, device=dev)
+                check(lib.gf_frames_votes_pick(ptr(self._keys), ptr(self._cnt), self._keys.shape[0], n, fill, ptr(ws),
+                                               ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(words), stream_ptr()),
+                      "gf_frames_votes_pick")
+            if rows is not None:
+                rows = rows.to(dev)
+                bad = ((rows < 0) | (rows >= n)).any().to(torch.int32).reshape(1)
+                out = out[:, rows.clamp(0, max(n - 1, 0)).long()] if n else out[:, :0]
+                pairs, beyond, outside = torch.cat([words, bad]).tolist()  # the one read-back
+            else:
+                (pairs, beyond), outside = words.tolist(), 0
+        if beyond:
+            raise ValueError(f"{who}: a stored group is outside the {n} groups")
+        if outside:
+            raise ValueError(f"{who}: {_ROWS_RANGE} {n} groups")
+        if pairs != self._pairs:
+            raise RuntimeError(f"{who}: the table holds {pairs} counted pairs, not the voter's {self._pairs}")
+        return Lifted(out[0], out[1], out[2]), pairs
+
+
+def lift_scene_stream(fuser, sem_voter, ins_voter, min_obs=1, min_votes=1, min_share=None):
+    """(semantic int32 [m], instance int32 [m]) of the points of fuser.snapshot(min_obs): scene_labels of the two voters'
+    snapshots over fuser.kept(min_obs).  sem_voter and ins_voter were fed every chunk's cells (what fuser.add returned)
+    with its label and its instance images.  Equal, as bits, to lift_scene(fuser.snapshot(min_obs, all cells), all label
+    images, all instance images, ...) -- with nothing kept but the map and the two tables."""
+    if not isinstance(fuser, (Fuser, FuserHost)) or not all(isinstance(v, (Voter, VoterHost)) for v in (sem_voter, ins_voter)):
+        raise ValueError("frames.lift_scene_stream: expected a Fuser and two Voters (or their host statements)")
+    rows, n = fuser.kept(min_obs), fuser.cells
+    sem = sem_voter.snapshot(n, IGNORE_LABEL, rows)[0]
+    ins = ins_voter.snapshot(n, IGNORE_LABEL, rows)[0]
+    return scene_labels(sem, ins, min_votes, min_share, host=not sem.label.is_cuda)

@@ -1770,6 +1770,73 @@ int gf_frames_map_means(const int32_t* count, const long long* sums, int M, cons
 int gf_frames_map_lookup(const int32_t* index, long long T, const int32_t* table, int len, int32_t* out, int32_t* d_flag,
                          void* stream);
 
+/* ===================================================================================
+ * Votes that persist between calls (csrc/frames_vote_stream.hip; the statement is frames.VoterHost): gf_frames_vote's
+ * table of the distinct (group, value) pairs, kept by the caller and fed one chunk of elements at a time.  The caller
+ * owns the state and passes pointers:
+ *   keys uint64 [slots]: group << 32 | value, all ones = empty; cnt uint32 [slots]: the pair's votes.  slots: a power
+ *     of two from 64 to 2^31 (a slot is recorded as a non-negative int32).  A claimed key with cnt == 0 is the debris of
+ *     a failed add: absent for every reader, dropped by the rehash.
+ * Integer atomics and one integer maximum only; no thread waits for another thread or workgroup; every launch goes on
+ * `stream`; nothing is read back.  Every argument is checked before the first launch (GF_ERR_INVALID_ARG, nothing
+ * launched).
+ * =================================================================================== */
+
+/* Limits, as functions: the probes of a thread in a table of fewer than 2 (P + T) slots (128); the elements a table
+ * takes in all, counted as offered (2^31 - 1: every count and total fits an int32); the default table of P stored pairs
+ * before a call of T elements: the smallest power of two >= max(4 P, T / 8), at least 64 (0 for P or T outside
+ * 0 .. 2^31 - 1); the scratch of an add of T elements (8 bytes per element; 0 for T outside 0 .. 2^29) and of a pick
+ * over n groups (12 bytes per group; 0 for n outside 0 .. 2^31 - 1). */
+int gf_frames_votes_max_probes(void);
+long long gf_frames_votes_max_elements(void);
+long long gf_frames_votes_default_slots(long long P, long long T);
+size_t gf_frames_votes_add_scratch_bytes(long long T);
+size_t gf_frames_votes_pick_scratch_bytes(long long n);
+
+/* gf_frames_votes_add (one memset, two launches) = gf_frames_votes_claim, then gf_frames_votes_commit.  group, value,
+ * kind, F, W, H, stride, ignore, has_ignore: gf_frames_vote's, read in the same way; element t votes when
+ * group[t] >= 0, value[t] >= 0 and value[t] is not the ignored value (no upper bound on the group here: the pick has it).
+ *   claim   the two words zeroed; one thread per sampled element builds the key; with aggregate != 0 only the head lane
+ *           of a run of equal keys among adjacent lanes goes on, with the run's length.  The key is found or claimed
+ *           (the slot read first, the 64-bit CAS issued on an empty slot only); the head's slot and its add go to
+ *           scratch; no count changes.  d_words[0]: the keys claimed (the new pairs), one atomic per workgroup.  With
+ *           slots >= 2 (pairs + T) probing is unbounded; with fewer a thread gives up after gf_frames_votes_max_probes()
+ *           probes and sets d_words[1].
+ *   commit  returns without writing when d_words[1] is set (a uniform branch on a word read); otherwise every recorded
+ *           head adds its run length to cnt[slot].
+ * pairs: the occupied slots of the table before the call (the stored pairs: the caller cleans debris by a rehash).
+ * d_words int32 [2] (device): {new pairs, overflow}.  With overflow set no count has changed and the table holds
+ * debris.  scratch: gf_frames_votes_add_scratch_bytes(T), the same buffer for claim and commit.
+ * T = F Hs Ws above gf_resample_max_points(), a negative F, W or H, stride < 1, another kind, a bad slots, pairs outside
+ * 0 .. slots, pairs + T above gf_frames_votes_max_elements() or a NULL pointer are GF_ERR_INVALID_ARG; T == 0 succeeds
+ * with nothing launched (and nothing written). */
+int gf_frames_votes_claim(const int32_t* group, const void* value, int kind, int F, int W, int H, int stride, int ignore,
+                          int has_ignore, unsigned long long* keys, long long slots, long long pairs, int aggregate,
+                          void* scratch, int32_t* d_words, void* stream);
+int gf_frames_votes_commit(const void* scratch, long long T, uint32_t* cnt, long long slots, const int32_t* d_words,
+                           void* stream);
+int gf_frames_votes_add(const int32_t* group, const void* value, int kind, int F, int W, int H, int stride, int ignore,
+                        int has_ignore, unsigned long long* keys, uint32_t* cnt, long long slots, long long pairs,
+                        int aggregate, void* scratch, int32_t* d_words, void* stream);
+
+/* gf_frames_votes_rehash (two launches): clears the table of new_slots entries (keys all ones, cnt 0), then moves every
+ * slot of the old table with cnt > 0 into it, key and count copied; debris is dropped.  `pairs`: the stored pairs of
+ * the old table; new_slots >= pairs is required: the keys are distinct, so every one finds a free slot and the probing
+ * ends (a caller that grows the table keeps two slots per pair and more; a same-size rehash that only cleans may find
+ * the table fuller).  old_slots == 0 (old pointers unused) only clears: a new table.  The tables must not overlap. */
+int gf_frames_votes_rehash(const unsigned long long* old_keys, const uint32_t* old_cnt, long long old_slots, long long pairs,
+                           unsigned long long* new_keys, uint32_t* new_cnt, long long new_slots, void* stream);
+
+/* gf_frames_votes_pick (one memset, two launches): gf_frames_vote's second half over the stored table, per group
+ * 0 <= g < n: total[g] = its votes; the value with the largest count wins, ties go to the smallest value (one 64-bit
+ * integer maximum of count << 32 | (0xffffffff - value)); label[g] = the winner or fill, votes[g] = its count or 0.
+ * Slots with cnt == 0 are skipped; a stored group >= n sets d_words[1] and writes nothing.  At most 1024 workgroups
+ * stride over the table.  Outputs label, votes, total int32 [n]; d_words int32 [2] (device): {stored pairs, group out of
+ * range}.  scratch: gf_frames_votes_pick_scratch_bytes(n).  Nothing of the table is written.  A bad slots, n outside
+ * 0 .. 2^31 - 1 or a NULL pointer are GF_ERR_INVALID_ARG; n == 0 succeeds with nothing launched (and nothing written). */
+int gf_frames_votes_pick(const unsigned long long* keys, const uint32_t* cnt, long long slots, long long n, int fill,
+                         void* scratch, int32_t* label, int32_t* votes, int32_t* total, int32_t* d_words, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,8 @@ plus the label's 1, 2 or 4 per pixel.
 
     python tools/frames_trace.py --no-host --stream 8               # ... and the same frames 8 at a time
 
+Under "stream_vote" (with --stream K): frames.Voter (csrc/frames_vote_stream.hip) fed the label image K frames per add
+beside the Fuser, next to one gf_frames_vote over everything; see voter_leg.
 Under "stream" (with --stream K): frames.Fuser (csrc/frames_stream.hip) fed K frames per add, next to the one-shot
 frames.fuse on the same input in the same process; see stream_leg.
 """
@@ -75,6 +77,7 @@ def main():
     ap.add_argument("--no-host", action="store_true", help="skip the numpy statement (minutes at the default size)")
     ap.add_argument("--stream", type=int, default=0, metavar="K",
                     help="also run the frames K at a time through frames.Fuser (K divides --frames); see stream_leg")
+    ap.add_argument("--stream-no-host", action="store_true", help="with --stream: skip frames.VoterHost on the host")
     args = ap.parse_args()
     W, H = (int(v) for v in args.size.lower().split("x"))
 
@@ -202,6 +205,9 @@ def main():
     out["vote"] = vote
     if args.stream:
         out["stream"] = stream_leg(args, fr, dfr, timed)
+        labels = block.to(torch.uint8).reshape(F, Hs, Ws).contiguous()
+        del block, group
+        out["stream_vote"] = voter_leg(args, fr, dfr, labels, timed)
     print(json.dumps(out))
 
 
@@ -325,6 +331,146 @@ def stream_leg(args, fr, dfr, timed):
         res["fuser_host_numpy_ms"] = round((time.perf_counter() - t) * 1e3, 1)
         got = stream(frames.Fuser(**kw, origin=origin), host_parts)
         res["equal_to_numpy"] = all(torch.equal(a.cpu(), b) for a, b in zip(got, want))
+    return res
+
+
+def voter_leg(args, fr, dfr, labels, timed):
+    """frames.Voter (csrc/frames_vote_stream.hip) beside a frames.Fuser on the same frames, --stream K at a time, fed the
+    synthetic label image (uint8 [F, Hs, Ws] on the device): per configuration (aggregation on and off; the compact table
+    that grows by doubling and a table of the proven size from the start) the device time of every add and of the
+    snapshot from events and the wall clock of all adds plus one snapshot, next to one frames.vote (gf_frames_vote) over
+    everything in the same process; the claim / commit split of one add and a same-size rehash on the final table; the
+    peak device memory of a streamed fuse-and-lift fed from host memory against the path that keeps every cell and image
+    until the end; VoterHost on the host."""
+    from geoformer_amd import _lib, frames
+    from geoformer_amd._lib import check, ptr, stream_ptr
+
+    lib = _lib.load()
+    F, K, s = args.frames, args.stream, args.stride
+    kw = dict(cell=args.cell, stride=s, near=0.1, far=10.0, edge=args.edge)
+    cut = lambda f, a, b: f._replace(depth=f.depth[a:b], color=f.color[a:b], table=f.table[a:b])  # noqa: E731
+    spans = [(a, a + K) for a in range(0, F, K)]
+    fu = frames.Fuser(**kw)
+    cells = [fu.add(cut(dfr, a, b)) for a, b in spans]
+    origin, M = fu.origin, fu.cells
+    values = [labels[a:b].contiguous() for a, b in spans]
+    per_add = int(values[0].numel())
+
+    probe = frames.Voter(0)
+    for c, v in zip(cells, values):
+        probe.add(c, v)
+    got, pairs = probe.snapshot(M)
+    whole_g, whole_v = torch.cat(cells).reshape(-1), labels.reshape(-1)
+    one, one_pairs = frames.vote(whole_g, whole_v, M, 0)
+    proven = frames.voter_slots(pairs, per_add)[1]  # at least 2 (P + T) at every add
+    res = {"chunk_frames": K, "adds": len(spans), "groups": M, "elements_per_add": per_add, "pairs": pairs,
+           "equal_to_one_vote": bool(all(torch.equal(a, b) for a, b in zip(got, one)) and pairs == one_pairs),
+           "default_table_slots_at_the_end": probe.slots, "rehashes": probe.rehashes, "retries": probe.retries,
+           "proven_table_slots": proven, "aggregate_default": frames.VOTER_AGGREGATE}
+    for table, slots in (("compact", None), ("proven", proven)):
+        for agg in (1, 0):
+            adds, snaps, walls = [], [], []
+            for rep in range(args.reps + 1):
+                vt = frames.Voter(0, slots=slots, aggregate=agg)
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(spans) + 2)]
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                for k, (c, v) in enumerate(zip(cells, values)):
+                    ev[k].record()
+                    vt.add(c, v)
+                ev[len(spans)].record()
+                vt.snapshot(M)
+                ev[len(spans) + 1].record()
+                torch.cuda.synchronize()
+                if rep:  # (the first run warms the allocator up)
+                    walls.append((time.perf_counter() - t) * 1e3)
+                    adds.append([ev[k].elapsed_time(ev[k + 1]) * 1e3 for k in range(len(spans))])
+                    snaps.append(ev[len(spans)].elapsed_time(ev[len(spans) + 1]) * 1e3)
+            per = np.median(np.array(adds), axis=0)
+            res[f"{table}_{'aggregated' if agg else 'plain'}"] = {
+                "first_add_us": round(float(per[0]), 1),
+                "later_add_us_median": round(float(np.median(per[1:])), 1) if len(per) > 1 else None,
+                "adds_us_sum": round(float(per.sum()), 1), "snapshot_us": round(float(np.median(snaps)), 1),
+                "stream_ms_wall": round(float(np.median(walls)), 2), "slots_at_the_end": vt.slots, "rehashes": vt.rehashes,
+                "retries": vt.retries}
+    wall = []
+    for _ in range(5):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        frames.vote(whole_g, whole_v, M, 0)
+        torch.cuda.synchronize()
+        wall.append((time.perf_counter() - t) * 1e3)
+    res["one_vote_ms_wall"] = round(float(np.median(wall)), 2)
+    res["one_vote_us"] = timed(lambda: frames.vote(whole_g, whole_v, M, 0))
+
+    # one add in its two launches, on the last chunk and the final table: every key is known, so the claim claims nothing
+    # and may be repeated; the commit adds into a copy of the counts
+    g, v = cells[-1].contiguous(), values[-1]
+    Fk, Hs, Ws = g.shape
+    words = torch.empty(2, dtype=torch.int32, device=g.device)
+    ws = torch.empty(lib.gf_frames_votes_add_scratch_bytes(per_add) // 8 + 1, dtype=torch.int64, device=g.device)
+    cnt = probe._cnt.clone()
+    for agg in (1, 0):
+        def claim():
+            check(lib.gf_frames_votes_claim(ptr(g), ptr(v), 0, 1, per_add, 1, 1, 0, 1, ptr(probe._keys), probe.slots, pairs, agg,
+                                            ptr(ws), ptr(words), stream_ptr()), "gf_frames_votes_claim")
+
+        def commit():
+            check(lib.gf_frames_votes_commit(ptr(ws), per_add, ptr(cnt), probe.slots, ptr(words), stream_ptr()),
+                  "gf_frames_votes_commit")
+
+        name = "aggregated" if agg else "plain"
+        res[f"claim_known_pairs_{name}_us"] = timed(claim)
+        assert words.tolist() == [0, 0]
+        res[f"commit_{name}_us"] = timed(commit)
+    res["snapshot_us"] = timed(lambda: probe.snapshot(M))
+    res["rehash_to_the_same_size_us"] = timed(lambda: probe._rehash(probe.slots))
+    del g, v, ws, cnt, cells, values, whole_g, whole_v, got, one, probe, fu, vt
+
+    # peak device memory, the frames and the label images coming from host memory: everything streamed (nothing kept but
+    # the map and the two tables) against the path that keeps every chunk's cells and both images until the end
+    def peak(fn):
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        fn()
+        torch.cuda.synchronize()
+        return round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1)
+
+    host_labels = labels.cpu().numpy()
+    del labels
+
+    def streamed():
+        fz, sv, iv = frames.Fuser(**kw, origin=origin), frames.Voter(0), frames.Voter(0)
+        for a, b in spans:
+            c = fz.add(cut(fr, a, b))
+            sv.add(c, host_labels[a:b])
+            iv.add(c, host_labels[a:b])
+        return frames.lift_scene_stream(fz, sv, iv, args.min_obs)
+
+    def kept():
+        fz = frames.Fuser(**kw, origin=origin)
+        fused = fz.snapshot(args.min_obs, torch.cat([fz.add(cut(fr, a, b)) for a, b in spans]))
+        return frames.lift_scene(fused, host_labels, host_labels, ignore=0)
+
+    res["peak_MiB_streamed_fuse_and_lift"] = peak(streamed)
+    res["peak_MiB_keep_everything"] = peak(kept)
+    a, b = streamed(), kept()
+    res["streamed_equal_to_keep_everything"] = all(torch.equal(x, y) for x, y in zip(a, b))
+    if not (args.no_host or args.stream_no_host):
+        t = time.perf_counter()
+        vh = frames.VoterHost(0)
+        fz = frames.FuserHost(**kw, origin=origin)
+        for a, b in spans:
+            vh.add(fz.add(cut(fr, a, b)), host_labels[a:b])
+        want, want_pairs = vh.snapshot(fz.cells)
+        res["fuser_and_voter_host_numpy_ms"] = round((time.perf_counter() - t) * 1e3, 1)
+        vt, fz2 = frames.Voter(0), frames.Fuser(**kw, origin=origin)
+        for a, b in spans:
+            vt.add(fz2.add(cut(fr, a, b)), host_labels[a:b])
+        got, got_pairs = vt.snapshot(fz2.cells)
+        res["equal_to_numpy"] = bool(all(torch.equal(x.cpu(), y) for x, y in zip(got, want)) and got_pairs == want_pairs)
     return res
 
 

@@ -26,6 +26,9 @@ the frames; --label-ignore is the value of unannotated pixels, which do not vote
 instance-filt images as shipped; whatever the remapping to 0..19 left for them otherwise).  They are lifted onto the fused points by vote (frames.lift_scene, csrc/frames_vote.hip), the scene
 is written with its labels as <out>/<name>_scene.npy (float64 [n, 8], what batch_eval.* and augment.train_merge take),
 and it is scored: batch_eval.evaluate (AP) and evaluation.SemanticEvaluator (mIoU), under "lifted" in the JSON line.
+With --chunk-frames K and --labels together, the label and instance images go through two frames.Voter
+(csrc/frames_vote_stream.hip) K frames at a time beside the Fuser and the labelled scene comes from
+frames.lift_scene_stream: the same bytes, with one chunk of images on the device at a time ("voter" in the JSON line).
 """
 import argparse
 import json
@@ -72,11 +75,13 @@ def lifted_labels(fused, label, instance, ignore, stride, min_votes=1, min_share
     return frames.lift_scene(fused, label, instance, ignore=ignore, stride=stride, min_votes=min_votes, min_share=min_share)
 
 
-def fuse_in_chunks(depth, K, pose, color, shift, args):
-    """(Fused, {"chunk_frames", "adds", "cells", "table_slots", "rehashes"}): the frames through a frames.Fuser,
+def fuse_in_chunks(depth, K, pose, color, shift, args, label=None, instance=None):
+    """(Fused, {"chunk_frames", "adds", "cells", "table_slots", "rehashes"}, voters): the frames through a frames.Fuser,
     --chunk-frames at a time.  Only one chunk's depth and colour are on the device at a time: the arrays stay in host
     memory (as np.load gave them) and are sliced per add.  The Fused is the one frames.fuse would return for all frames
-    with origin=the Fuser's, so everything after it is the same."""
+    with origin=the Fuser's, so everything after it is the same.  With label and instance images, each chunk's go
+    through two frames.Voter (csrc/frames_vote_stream.hip) beside the Fuser, one chunk of images on the device at a
+    time; voters = (the Fuser, the semantic Voter, the instance Voter), what frames.lift_scene_stream takes (else None)."""
     from geoformer_amd import frames
 
     F, step = int(depth.shape[0]), int(args.chunk_frames)
@@ -84,13 +89,21 @@ def fuse_in_chunks(depth, K, pose, color, shift, args):
         raise ValueError(f"--chunk-frames {step} (>= 1)")
     K = np.asarray(K)
     fu = frames.Fuser(args.cell, args.stride, args.near, args.far, args.edge)
+    voters = None
+    if label is not None:
+        voters = (fu, frames.Voter(args.label_ignore), frames.Voter(args.label_ignore))
     cells = []
     for a in range(0, F, step):
         b = min(F, a + step)
         part = frames.make(depth[a:b], K if K.ndim == 1 else K[a:b], pose[a:b], None if color is None else color[a:b], shift)
         cells.append(fu.add(part))
+        if voters is not None:
+            stride = None if tuple(cells[-1].shape) == tuple(label[a:b].shape) else args.stride
+            voters[1].add(cells[-1], label[a:b], stride)
+            voters[2].add(cells[-1], instance[a:b], stride)
     fused = fu.snapshot(args.min_obs, torch.cat(cells))
-    return fused, {"chunk_frames": step, "adds": len(cells), "cells": fu.cells, "table_slots": fu.slots, "rehashes": fu.rehashes}
+    return (fused, {"chunk_frames": step, "adds": len(cells), "cells": fu.cells, "table_slots": fu.slots, "rehashes": fu.rehashes},
+            voters)
 
 
 def score(model, name, raw, config_classes=0):
@@ -146,7 +159,7 @@ def main():
     try:
         if args.chunk_frames:
             t = time.perf_counter()
-            fused, stream = fuse_in_chunks(depth, K, pose, color, shift, args)
+            fused, stream, voters = fuse_in_chunks(depth, K, pose, color, shift, args, label, instance)
         else:
             fr = frames.make(depth, K, pose, color, shift)
             t = time.perf_counter()
@@ -162,7 +175,10 @@ def main():
     if label is not None:
         try:
             t = time.perf_counter()
-            sem, ins = lifted_labels(fused, label, instance, args.label_ignore, args.stride, args.min_votes, args.min_share)
+            if args.chunk_frames:  # the votes are in: only the snapshot and the scene's tail are left
+                sem, ins = frames.lift_scene_stream(*voters, args.min_obs, args.min_votes, args.min_share)
+            else:
+                sem, ins = lifted_labels(fused, label, instance, args.label_ignore, args.stride, args.min_votes, args.min_share)
             torch.cuda.synchronize()
             lift_s = time.perf_counter() - t
         except ValueError as e:
@@ -199,6 +215,9 @@ def main():
         out["lifted"] = {"lift_ms": round(lift_s * 1e3, 2), "points_with_a_class": int((sem >= 0).sum()),
                          "points_with_an_instance": int((ins >= 0).sum()), "instances": max(int(ins.max()), -1) + 1,
                          **score(model, name, raw)}
+        if args.chunk_frames:
+            out["voter"] = {"pairs": [v.pairs for v in voters[1:]], "table_slots": [v.slots for v in voters[1:]],
+                            "rehashes": sum(v.rehashes for v in voters[1:]), "retries": sum(v.retries for v in voters[1:])}
     print(json.dumps(out))
 
 
