@@ -29,6 +29,12 @@ While the sensor is still moving (csrc/frames_stream.hip): a map th
     for chunk, labels, instances in stream:
         cells = fuser.add(chunk); sem_v.add(cells, labels); ins_v.add(cells, instances)
     sem, inst = frames.lift_scene_stream(fuser, sem_v, ins_v)   # lift_scene over every frame so far, as bits
+
+... and the model's instances keep their ids from one snapshot to the next (csrc/frames_track.hip).
+
+    tracker = frames.Tracker(iou=0.3, max_misses=2)
+    tracked = frames.track_scene(tracker, fuser, labels)        # labels: label_batches on fuser.snapshot()'s scene
+    ids = frames.gather(fused, tracked.ids)                     # the persistent id of every depth pixel
 """
 from __future__ import annotations
 
@@ -61,6 +67,13 @@ VOTER_MAX_ELEMENTS = 2 ** 31 - 1  # gf_frames_votes_max_elements(): the elements
 VOTER_MIN_SLOTS, VOTER_MAX_SLOTS = 64, 1 << 31   # (a slot is recorded as a non-negative int32)
 VOTER_MAX_GROUPS = 2 ** 31 - 1    # the n of a snapshot
 VOTER_AGGREGATE = True    # runs of equal (group, value) pairs among adjacent lanes record one add
+TRACK_MAX_ROWS = 4096     # gf_frames_track_max_rows(): the rows (instances) of one Tracker update
+TRACK_MAX_PROBES = 128    # gf_frames_track_max_probes(): the probes of a thread in a pair table of fewer than 2 m slots
+TRACK_MAX_TRACKS = 1 << 30   # gf_frames_track_max_tracks(): the ids a Tracker hands out in all
+TRACK_MIN_SLOTS, TRACK_MAX_SLOTS = 64, 1 << 30
+TRACK_AGGREGATE = True    # runs of equal (row, track) pairs among adjacent lanes add once
+_TRACK_WORDS = 16         # gf_frames_track_words()
+_TRACK_MIN_MAP, _TRACK_MIN_TABLE = 1024, 64   # the first capacities of a Tracker's map and table, doubled as needed
 
 
 class Frames(NamedTuple):
@@ -1538,3 +1551,451 @@ def lift_scene_stream(fuser, sem_voter, ins_voter, min_obs=1, min_votes=1, min_s
     sem = sem_voter.snapshot(n, IGNORE_LABEL, rows)[0]
     ins = ins_voter.snapshot(n, IGNORE_LABEL, rows)[0]
     return scene_labels(sem, ins, min_votes, min_share, host=not sem.label.is_cuda)
+
+
+# ---- instance ids that persist between model runs on successive snapshots ----------------------------------------------
+class TrackTable(NamedTuple):
+    """One entry per track, ids 0 .. T - 1 (never reused): cls int32 and score fp32 of the best-scored sighting (the
+    later one on a tie), born / seen int32 (the update index of the first and the last match), hits int32 (matches),
+    misses int32 (consecutive updates that saw its cells and did not match it), size int32 (cells of the map that are
+    this track's; 0 once retired) and alive bool."""
+    cls: object
+    score: object
+    born: object
+    seen: object
+    hits: object
+    misses: object
+    size: object
+    alive: object
+
+
+class Tracked(NamedTuple):
+    """What an update returns: ids int32 [m] (the map at `cells` after the update, -1 for no track or a retired one),
+    track int32 [p] (the row's track id, -1 for a row without one), matched bool [p] (the row continued a track), new
+    and retired int32 [.] (the ids of the tracks born and retired by this update, ascending)."""
+    ids: object
+    track: object
+    matched: object
+    new: object
+    retired: object
+
+
+def tracker_slots(p, live, m):
+    """(default, proven) pair-table sizes of an update of p rows and m points against `live` alive tracks: the smallest
+    power of two at or above 8 (p + live) (gf_frames_track_default_slots) and at or above 2 m, which no input overflows;
+    both at least 64.  An update starts at the smaller of the two."""
+    def pow2(v):
+        s = TRACK_MIN_SLOTS
+        while s < v and s < TRACK_MAX_SLOTS:
+            s <<= 1
+        return s
+
+    return pow2(8 * (int(p) + int(live))), pow2(2 * int(m))
+
+
+def tracker_limits():
+    """(rows, probes, tracks) of the library's tracker, asserted against this module's constants."""
+    from . import _lib
+
+    lib = _lib.load()
+    got = (lib.gf_frames_track_max_rows(), lib.gf_frames_track_max_probes(), lib.gf_frames_track_max_tracks())
+    if got != (TRACK_MAX_ROWS, TRACK_MAX_PROBES, TRACK_MAX_TRACKS) or lib.gf_resample_max_points() != MAX_POINTS or \
+            lib.gf_frames_track_columns() != len(TrackTable._fields) or lib.gf_frames_track_words() != _TRACK_WORDS:
+        raise RuntimeError(f"frames: the library's tracker limits {got} are not this module's")
+    return got
+
+
+def _tracker_init_args(iou, max_misses, min_points, same_class, who):
+    iou = float(iou)
+    if not 0.0 <= iou <= 1.0:
+        raise ValueError(f"{who}: iou = {iou} (0 to 1)")
+    if int(max_misses) != max_misses or int(max_misses) < 0 or int(max_misses) >= 2 ** 31 - 1:
+        raise ValueError(f"{who}: max_misses = {max_misses!r} (an integer >= 0)")
+    if int(min_points) != min_points or not 1 <= int(min_points) < 2 ** 31:
+        raise ValueError(f"{who}: min_points = {min_points!r} (an integer >= 1)")
+    return iou, int(max_misses), int(min_points), bool(same_class)
+
+
+_CELLS_ASCEND = "cells must be non-negative and strictly ascending (what Fuser.kept returns)"
+_OWNER_RANGE = "owner holds a value outside -1 .."
+
+
+def _tracker_update_args(cells, owner, cls, score, keep, T, who):
+    """(cells, owner, cls, score, keep) of an update as torch tensors (any device) of int32 [m], int32 [m], int32 [p],
+    fp32 [p], bool [p]: every check of shape and dtype made, and of the values of whatever is on the host."""
+    def h(a, name):
+        if torch.is_tensor(a):
+            return a.detach()
+        if isinstance(a, np.ndarray):
+            return torch.from_numpy(a if a.flags.writeable and a.flags.c_contiguous else np.array(a, order="C"))
+        raise ValueError(f"{who}: {name}: expected a numpy array or a torch tensor, got {type(a).__name__}")
+
+    cells, owner, cls, score = h(cells, "cells"), h(owner, "owner"), h(cls, "cls"), h(score, "score")
+    for t, name in ((cells, "cells"), (owner, "owner")):
+        if t.dtype != torch.int32 or t.dim() != 1:
+            raise ValueError(f"{who}: {name}: expected int32 [m], got {t.dtype} {tuple(t.shape)}")
+    m = cells.shape[0]
+    if owner.shape[0] != m:
+        raise ValueError(f"{who}: {m} cells and {owner.shape[0]} owners")
+    if m > MAX_POINTS:
+        raise ValueError(f"{who}: {m} points in one update (at most {MAX_POINTS})")
+    if cls.dim() != 1 or cls.dtype not in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64):
+        raise ValueError(f"{who}: cls: expected integers [p], got {cls.dtype} {tuple(cls.shape)}")
+    p = cls.shape[0]
+    if score.dtype != torch.float32 or tuple(score.shape) != (p,):
+        raise ValueError(f"{who}: score: expected float32 [{p}], got {score.dtype} {tuple(score.shape)}")
+    if keep is None:
+        keep = torch.ones(p, dtype=torch.bool, device=score.device)
+    else:
+        keep = h(keep, "keep")
+        if keep.dtype != torch.bool or tuple(keep.shape) != (p,):
+            raise ValueError(f"{who}: keep: expected bool [{p}], got {keep.dtype} {tuple(keep.shape)}")
+    if p > TRACK_MAX_ROWS:
+        raise ValueError(f"{who}: {p} rows in one update (at most {TRACK_MAX_ROWS})")
+    if T + p > TRACK_MAX_TRACKS:
+        raise ValueError(f"{who}: {T} tracks so far and {p} rows: a tracker holds at most {TRACK_MAX_TRACKS} tracks")
+    if not cls.is_cuda and p and not (-2 ** 31 <= int(cls.min()) and int(cls.max()) < 2 ** 31):
+        raise ValueError(f"{who}: cls holds a value that is no int32")
+    if not cells.is_cuda and m:
+        c = cells.numpy()
+        if int(c[0]) < 0 or (m > 1 and not (c[1:] > c[:-1]).all()):
+            raise ValueError(f"{who}: {_CELLS_ASCEND}")
+    if not owner.is_cuda and m and not (int(owner.min()) >= -1 and int(owner.max()) < p):
+        raise ValueError(f"{who}: {_OWNER_RANGE} {p - 1}")
+    return cells, owner, cls.to(torch.int32), score, keep
+
+
+class TrackerHost:
+    """The statement of Tracker, in numpy: instance ids that persist over successive model runs on the snapshots of one
+    Fuser, keyed by its persistent cell numbers.
+
+    State after u updates: M cells with track_of int32 [M] (-1: none) and T tracks, ids 0 .. T - 1, never reused, with
+    the columns of TrackTable.
+
+    update(cells, owner, cls, score, keep=None) -> Tracked.  cells int32 [m], non-negative and strictly ascending (what
+    fuser.kept(min_obs) returns): point i of the snapshot is cell cells[i].  owner int32 [m] in [-1, p): the row of this
+    run that owns the point (SceneLabels.owner).  cls integers [p], score fp32 [p], keep bool [p] (default all true).
+      0. the map is extended to M' = max(M, cells[-1] + 1) cells, new ones -1;
+      1. r_i = owner[i] when it is >= 0 and kept, else -1; t_i = track_of[cells[i]] when the cell is < M and that track
+         alive, else -1; a[r], b[t], n[r, t] count the points with that row, that track, and both;
+      2. best_row[r]: among the t with n[r, t] > 0 (and cls equal when same_class) the one of the largest IoU
+         n / (a[r] + b[t] - n), compared exactly (cross-multiplied integers), a tie to the smaller t; best_track[t]
+         likewise over r, a tie to the smaller r; (r, t) match when each is the other's best and
+         float64(n) >= iou * float64(union): one to one, so the threshold alone cannot glue two objects together;
+      3. a matched row takes its track's id; the other kept rows with a[r] >= min_points get new ids T, T + 1, .. in
+         ascending r; every other row gets -1 and its points count as unowned;
+      4. a matched track: hits + 1, misses 0, seen = u, and when score[r] >= its score (fp32) it takes the row's score and
+         cls; a new track: born = seen = u, hits 1; an alive unmatched track with b[t] > 0 (it was in view): misses + 1,
+         retired when misses > max_misses; a track with b[t] == 0 is untouched (a partial update leaves the rest alone);
+      5. point by point, with tid the row's id: tid >= 0 sets track_of[c] = tid; else a cell whose old track matched or
+         retired in this update is set to -1; else the cell is unchanged (a track that was merely missed holds its
+         cells).  size follows; a retired track has size 0 and its remaining cells read as -1; after the pass an alive
+         track with size 0 is retired too.
+    A failed update (a ValueError) changes nothing.
+
+    labels(cells) reads the map (int32, any shape, -1 allowed and answered by -1; a value from M on is a ValueError);
+    table() is the TrackTable; state() is (track_of [M] with retired tracks as -1, table) as numpy copies.
+
+    The defaults (iou 0.3, max_misses 2, min_points 1, same_class False) are chosen by reasoning -- a half-seen object is
+    often misclassified, and its identity should survive the class flipping --; their effect on a tracking metric is NOT
+    measured: there is no trained checkpoint and no sequence ground truth here."""
+
+    def __init__(self, iou=0.3, max_misses=2, min_points=1, same_class=False):
+        self._who = "frames." + type(self).__name__
+        self._iou, self._max_misses, self._min_points, self._same_class = \
+            _tracker_init_args(iou, max_misses, min_points, same_class, self._who)
+        self._map = np.zeros(0, np.int32)
+        self._tab = TrackTable(*(np.zeros(0, np.float32 if f == "score" else bool if f == "alive" else np.int32)
+                                 for f in TrackTable._fields))
+        self._updates = 0
+
+    tracks = property(lambda self: int(self._tab.alive.shape[0]), doc="the tracks so far, alive or retired: the next new id")
+    live = property(lambda self: int(self._tab.alive.sum()), doc="the tracks alive")
+    cells = property(lambda self: int(self._map.shape[0]), doc="the cells of the map")
+    updates = property(lambda self: self._updates, doc="the updates that succeeded")
+
+    def table(self):
+        return TrackTable(*(c.copy() for c in self._tab))
+
+    def state(self):
+        t, alive = self._map, self._tab.alive
+        shown = np.where((t >= 0) & alive[np.maximum(t, 0)], t, -1).astype(np.int32) if alive.size else t.copy()
+        return shown, self.table()
+
+    def labels(self, cells):
+        who = self._who + ".labels"
+        c = _cells_arg(cells, self.cells, "cpu", who).numpy()
+        if c.size and not (int(c.min()) >= -1 and int(c.max()) < self.cells):
+            raise ValueError(f"{who}: {_CELLS_RANGE} {self.cells} cells")
+        shown = self.state()[0]
+        return torch.from_numpy(np.where(c >= 0, shown[np.maximum(c, 0)], -1).astype(np.int32) if shown.size
+                                else np.full(c.shape, -1, np.int32))
+
+    def update(self, cells, owner, cls, score, keep=None):
+        who = self._who + ".update"
+        T, u = self.tracks, self._updates
+        cells, owner, cls, score, keep = (t.cpu().numpy() for t in _tracker_update_args(cells, owner, cls, score, keep, T, who))
+        m, p = cells.shape[0], cls.shape[0]
+        if m and (int(cells[0]) < 0 or (m > 1 and not (cells[1:] > cells[:-1]).all())):
+            raise ValueError(f"{who}: {_CELLS_ASCEND}")
+        if m and not (int(owner.min()) >= -1 and int(owner.max()) < p):
+            raise ValueError(f"{who}: {_OWNER_RANGE} {p - 1}")
+        M = self.cells
+        tab = [c.copy() for c in self._tab]
+        t_cls, t_score, t_born, t_seen, t_hits, t_misses, t_size, t_alive = tab
+        track_of = np.concatenate([self._map, np.full(max(0, (int(cells[-1]) + 1 if m else 0) - M), -1, np.int32)])
+        # 1. rows, tracks, counts
+        r = np.where((owner >= 0) & keep[np.maximum(owner, 0)], owner, -1).astype(np.int64) if p else np.full(m, -1, np.int64)
+        was = track_of[cells].astype(np.int64)
+        t = np.where((was >= 0) & t_alive[np.maximum(was, 0)], was, -1) if T else np.full(m, -1, np.int64)
+        a = np.bincount(r[r >= 0], minlength=p).astype(np.int64)
+        b = np.bincount(t[t >= 0], minlength=T).astype(np.int64)
+        both = (r >= 0) & (t >= 0)
+        keys, n = np.unique((r[both] << 32) | t[both], return_counts=True)
+        pr, pt, n = keys >> 32, keys & 0xffffffff, n.astype(np.int64)
+        if self._same_class:
+            on = cls[pr] == t_cls[pt]
+            pr, pt, n = pr[on], pt[on], n[on]
+        uni = a[pr] + b[pt] - n
+        # 2. the best of every row and of every track under the exact order: the larger IoU by cross-multiplied python
+        # integers, then the smaller index (one pass over the pairs; there are few of them)
+        def best_of(group, index, size):
+            best = [-1] * size
+            for k, (g, x, nk, uk) in enumerate(zip(group.tolist(), index.tolist(), n.tolist(), uni.tolist())):
+                c = best[g]
+                if c >= 0:
+                    l, rr = nk * int(uni[c]), int(n[c]) * uk
+                    if l < rr or (l == rr and x > int(index[c])):
+                        continue
+                best[g] = k
+            return np.array(best, np.int64).reshape(size)
+
+        best_row, best_track = best_of(pr, pt, p), best_of(pt, pr, T)
+        # 3. ids
+        track = np.full(p, -1, np.int64)
+        row_of = np.full(T, -1, np.int64)
+        for g in range(p):
+            k = best_row[g]
+            if k >= 0 and best_track[pt[k]] == k and np.float64(n[k]) >= np.float64(self._iou) * np.float64(uni[k]):
+                track[g], row_of[pt[k]] = pt[k], g
+        matched = track >= 0
+        fresh = ~matched & keep & (a >= self._min_points)
+        track[fresh] = T + np.arange(int(fresh.sum()))
+        # 4. the table
+        k = int(fresh.sum())
+        for g in np.nonzero(matched)[0]:
+            q = track[g]
+            t_hits[q] += 1
+            t_misses[q] = 0
+            t_seen[q] = u
+            if score[g] >= t_score[q]:
+                t_score[q], t_cls[q] = score[g], cls[g]
+        missed = t_alive & (row_of < 0) & (b > 0)
+        t_misses[missed] += 1
+        gone = missed & (t_misses > self._max_misses)
+        t_alive[gone] = False
+        t_size[gone] = 0
+        rows = np.nonzero(fresh)[0]
+        i32 = lambda v: np.full(k, v, np.int32)  # noqa: E731
+        t_cls, t_score = np.concatenate([t_cls, cls[rows].astype(np.int32)]), np.concatenate([t_score, score[rows]])
+        t_born, t_seen = np.concatenate([t_born, i32(u)]), np.concatenate([t_seen, i32(u)])
+        t_hits, t_misses, t_size = np.concatenate([t_hits, i32(1)]), np.concatenate([t_misses, i32(0)]), np.concatenate([t_size, i32(0)])
+        t_alive = np.concatenate([t_alive, np.ones(k, bool)])
+        gone = np.concatenate([gone, np.zeros(k, bool)])
+        # 5. the map
+        tid = np.where(r >= 0, track[np.maximum(r, 0)], -1) if p else np.full(m, -1, np.int64)
+        cleared = (t >= 0) & ((row_of[np.maximum(t, 0)] >= 0) | gone[np.maximum(t, 0)]) if T else np.zeros(m, bool)
+        now = np.where(tid >= 0, tid, np.where(cleared, -1, t))
+        write = (tid >= 0) | cleared
+        track_of[cells[write]] = now[write]
+        moved = now != t
+        lose = moved & (t >= 0)
+        lose[lose] = ~gone[t[lose]]
+        t_size = t_size - np.bincount(t[lose], minlength=T + k).astype(np.int32) + \
+            np.bincount(now[moved & (now >= 0)], minlength=T + k).astype(np.int32)
+        empty = t_alive & (t_size == 0)
+        t_alive = t_alive & ~empty
+        gone |= empty
+        self._map = track_of.astype(np.int32)
+        self._tab = TrackTable(t_cls.astype(np.int32), t_score.astype(np.float32), t_born, t_seen, t_hits, t_misses,
+                               t_size.astype(np.int32), t_alive)
+        self._updates = u + 1
+        f = lambda v: torch.from_numpy(np.ascontiguousarray(v))  # noqa: E731
+        return Tracked(f(now.astype(np.int32)), f(track.astype(np.int32)), f(matched), f(np.arange(T, T + k, dtype=np.int32)),
+                       f(np.nonzero(gone)[0].astype(np.int32)))
+
+
+class Tracker:
+    """TrackerHost on the GPU (csrc/frames_track.hip): the same update, labels, table, state and properties,
+    bit-identical to the statement after every update and from run to run.  The state is two torch tensors owned here, the
+    map int32 [capacity] and the table int32 [8, capacity], each grown by doubling (map_growths, row_growths).  Inputs on
+    the host are moved to `device` per update; a tensor on another GPU is a ValueError.
+
+    update: gf_frames_track_update on the current stream (count, best, match, apply, finish); its words are read back
+    once, the only synchronisation.  Whatever is on the host is checked before the first launch; on the device the
+    count pass raises a word for cells that do not ascend, an owner outside [-1, p) or an overflowing pair table, every
+    later launch switches itself off, and the ValueError leaves state() exactly as it was.
+
+    slots: the pair table's entries, a power of two.  None: the smaller of tracker_slots' two sizes; when an update
+    overflows it, the update runs ONCE more at the proven size >= 2 m (retries counts these).  A given `slots` is kept:
+    overflowing it is a ValueError that names the proven size.  aggregate: whether adjacent lanes of one (row, track)
+    pair add once (None: TRACK_AGGREGATE; the result is the same).  pairs: the (row, track) pairs the last update
+    counted.  device "cpu": TrackerHost."""
+
+    def __init__(self, iou=0.3, max_misses=2, min_points=1, same_class=False, device="cuda", slots=None, aggregate=None):
+        self._who = who = "frames.Tracker"
+        dev = torch.device(device)
+        self._host = None
+        self.retries = self.row_growths = self.map_growths = self.pairs = 0
+        if dev.type != "cuda":
+            self._host = TrackerHost(iou, max_misses, min_points, same_class)
+            return
+        self._iou, self._max_misses, self._min_points, self._same_class = \
+            _tracker_init_args(iou, max_misses, min_points, same_class, who)
+        self._aggregate = int(TRACK_AGGREGATE if aggregate is None else aggregate)
+        if slots is not None:
+            s = int(slots)
+            if not (TRACK_MIN_SLOTS <= s <= TRACK_MAX_SLOTS and s & (s - 1) == 0):
+                raise ValueError(f"{who}: slots = {slots} (None, or a power of two from {TRACK_MIN_SLOTS} to {TRACK_MAX_SLOTS})")
+        self._slots_arg = None if slots is None else int(slots)
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        tracker_limits()
+        self._dev = dev
+        self._map = torch.full((_TRACK_MIN_MAP,), -1, dtype=torch.int32, device=dev)
+        self._tab = torch.zeros((len(TrackTable._fields), _TRACK_MIN_TABLE), dtype=torch.int32, device=dev)
+        self._M = self._T = self._live = self._updates = 0
+
+    tracks = property(lambda self: self._host.tracks if self._host is not None else self._T,
+                      doc="the tracks so far, alive or retired: the next new id")
+    live = property(lambda self: self._host.live if self._host is not None else self._live, doc="the tracks alive")
+    cells = property(lambda self: self._host.cells if self._host is not None else self._M, doc="the cells of the map")
+    updates = property(lambda self: self._host.updates if self._host is not None else self._updates,
+                       doc="the updates that succeeded")
+
+    def table(self):
+        """The TrackTable as torch tensors on the device (copies)."""
+        if self._host is not None:
+            return self._host.table()
+        t = self._tab[:, :self._T]
+        return TrackTable(t[0].clone(), t[1].clone().view(torch.float32), t[2].clone(), t[3].clone(), t[4].clone(), t[5].clone(),
+                          t[6].clone(), t[7] != 0)
+
+    def _shown(self):
+        t = self._map[:self._M]
+        if not self._T:
+            return t.clone()
+        alive = self._tab[7, :self._T] != 0
+        return torch.where((t >= 0) & alive[t.clamp(min=0).long()], t, torch.full_like(t, -1))
+
+    def state(self):
+        if self._host is not None:
+            return self._host.state()
+        with torch.cuda.device(self._dev):
+            return self._shown().cpu().numpy(), TrackTable(*(c.cpu().numpy() for c in self.table()))
+
+    def labels(self, cells):
+        if self._host is not None:
+            return self._host.labels(cells)
+        who = self._who + ".labels"
+        if torch.is_tensor(cells) and cells.is_cuda and cells.device != self._dev:
+            raise ValueError(f"{who}: cells on {cells.device}, the tracker on {self._dev}")
+        on_host = not (torch.is_tensor(cells) and cells.is_cuda)
+        with torch.cuda.device(self._dev):
+            c = _cells_arg(cells, self._M, "cpu" if on_host else self._dev, who).to(self._dev)
+            if not on_host and c.numel() and bool(((c < -1) | (c >= self._M)).any()):
+                raise ValueError(f"{who}: {_CELLS_RANGE} {self._M} cells")
+            if not self._M:
+                return torch.full_like(c, -1)
+            return torch.where(c >= 0, self._shown()[c.clamp(min=0).long()], torch.full_like(c, -1))
+
+    def _grow(self, cells_needed, tracks_needed):
+        if cells_needed > self._map.shape[0]:
+            cap = self._map.shape[0]
+            while cap < cells_needed:
+                cap *= 2
+            new = torch.full((cap,), -1, dtype=torch.int32, device=self._dev)
+            new[:self._M] = self._map[:self._M]
+            self._map = new
+            self.map_growths += 1
+        if tracks_needed > self._tab.shape[1]:
+            cap = self._tab.shape[1]
+            while cap < tracks_needed:
+                cap *= 2
+            new = torch.zeros((self._tab.shape[0], cap), dtype=torch.int32, device=self._dev)
+            new[:, :self._T] = self._tab[:, :self._T]
+            self._tab = new
+            self.row_growths += 1
+
+    def update(self, cells, owner, cls, score, keep=None):
+        if self._host is not None:
+            return self._host.update(cells, owner, cls, score, keep)
+        from . import _lib
+        from ._lib import check, ptr, stream_ptr
+
+        who = self._who + ".update"
+        dev, T, M = self._dev, self._T, self._M
+        args = _tracker_update_args(cells, owner, cls, score, keep, T, who)
+        for t, name in zip(args, ("cells", "owner", "cls", "score", "keep")):
+            if t.is_cuda and t.device != dev:
+                raise ValueError(f"{who}: {name} on {t.device}, the tracker on {dev}")
+        m, p = args[0].shape[0], args[2].shape[0]
+        last = int(args[0][-1]) if m and not args[0].is_cuda else -1  # (cells on the device: the count pass reports it)
+        if last >= 2 ** 31 - 1:
+            raise ValueError(f"{who}: cell {last}: a map holds at most {2 ** 31 - 1} cells")
+        lib = _lib.load()
+        default, proven = tracker_slots(p, self._live, m)
+        slots = min(default, proven) if self._slots_arg is None else self._slots_arg
+        with torch.cuda.device(dev):
+            cells, owner, cls, score, keep = (t.to(dev).contiguous() for t in args)
+            keep = keep.to(torch.uint8)
+            self._grow(last + 1, T + p)
+            ids = torch.empty(m, dtype=torch.int32, device=dev)
+            track = torch.empty(p, dtype=torch.int32, device=dev)
+            gone = torch.empty(max(T, 1), dtype=torch.int32, device=dev)
+            words = torch.empty(_TRACK_WORDS, dtype=torch.int32, device=dev)
+            for attempt in range(4):
+                ws = torch.empty(lib.gf_frames_track_scratch_bytes(m, p, T, slots) // 8 + 1, dtype=torch.int64, device=dev)
+                check(lib.gf_frames_track_update(ptr(cells), ptr(owner), m, ptr(cls), ptr(score), ptr(keep), p, ptr(self._map), M,
+                                                 self._map.shape[0], ptr(self._tab), T, self._tab.shape[1], self._iou,
+                                                 self._max_misses, self._min_points, int(self._same_class), self._updates, slots,
+                                                 self._aggregate, ptr(ws), ptr(ids), ptr(track), ptr(gone), ptr(words),
+                                                 stream_ptr()), "gf_frames_track_update")
+                order, outside, overflow, new, retired, pairs, room, last = words.tolist()[:8]  # the one read-back
+                if order:
+                    raise ValueError(f"{who}: {_CELLS_ASCEND}")
+                if outside:
+                    raise ValueError(f"{who}: {_OWNER_RANGE} {p - 1}")
+                if room and last >= 2 ** 31 - 1:
+                    raise ValueError(f"{who}: cell {last}: a map holds at most {2 ** 31 - 1} cells")
+                if room and self._map.shape[0] <= last:
+                    self._grow(last + 1, 0)  # cells came on the device: the map is grown and the update run again
+                    continue
+                if overflow and self._slots_arg is None and slots < proven:
+                    slots = proven
+                    self.retries += 1
+                    continue
+                if overflow and self._slots_arg is not None:
+                    raise ValueError(f"{who}: the pair table of slots = {slots} overflowed; {proven} slots are always enough "
+                                     f"for {m} points")
+                if overflow or room:
+                    raise RuntimeError(f"{who}: the update failed at {slots} slots and a map of {self._map.shape[0]} cells")
+                break
+            else:
+                raise RuntimeError(f"{who}: the update did not settle")
+            self._M = max(M, last + 1) if m else M
+            self._T, self._live, self._updates, self.pairs = T + new, self._live + new - retired, self._updates + 1, pairs
+            matched = (track >= 0) & (track < T)
+            fresh = torch.arange(T, T + new, dtype=torch.int32, device=dev)
+            lost = torch.nonzero(gone[:T]).reshape(-1).to(torch.int32) if retired else torch.zeros(0, dtype=torch.int32, device=dev)
+        return Tracked(ids, track, matched, fresh, lost)
+
+
+def track_scene(tracker, fuser, labels, min_obs=1):
+    """tracker.update over the points of fuser.snapshot(min_obs) with the model's labels of that snapshot (a SceneLabels of
+    batch_eval.label_batches): update(fuser.kept(min_obs), labels.owner, table.label_id, table.score, table.kept).
+    frames.gather(fused, tracked.ids) then gives every depth pixel its persistent id."""
+    if not isinstance(tracker, (Tracker, TrackerHost)) or not isinstance(fuser, (Fuser, FuserHost)):
+        raise ValueError("frames.track_scene: expected a Tracker and a Fuser (or their host statements)")
+    t = labels.table
+    return tracker.update(fuser.kept(min_obs), labels.owner, t.label_id, t.score, t.kept)

@@ -1837,6 +1837,63 @@ int gf_frames_votes_rehash(const unsigned long long* old_keys, const uint32_t* o
 int gf_frames_votes_pick(const unsigned long long* keys, const uint32_t* cnt, long long slots, long long n, int fill,
                          void* scratch, int32_t* label, int32_t* votes, int32_t* total, int32_t* d_words, void* stream);
 
+/* ===================================================================================
+ * frames_track.hip -- instance ids that persist over successive snapshots.  One update of a
+ * tracker keyed by the persistent cell numbers of a map (gf_frames_map_*): this run's rows are matched to the tracks so
+ * far by exact mask IoU over the cells both saw, one to one.  The statement is frames.TrackerHost.  The state belongs
+ * to the caller: track_of int32 [map_cap] (the track of every cell, -1 for none and from M on) and table int32
+ * [gf_frames_track_columns(), table_cap], one column per track, the rows {cls, score (the bits of a float), born,
+ * seen, hits, misses, size, alive}.  A retired track has alive 0 and size 0; cells that still name it read as none.
+ * Integer atomics only; no thread waits for another thread or workgroup; every launch goes on `stream`; nothing is
+ * read back.  Every argument is checked before the first launch (GF_ERR_INVALID_ARG, nothing launched).
+ * =================================================================================== */
+
+/* Limits, as functions: the rows of one update (4096); the probes of a thread in a pair table of fewer than 2 m slots
+ * (128); the tracks of a table (2^30); the rows of the table (8) and the words of d_words (16); the default pair table
+ * for p rows and `live` alive tracks: the smallest power of two >= 8 (p + live), at least 64 (0 for an argument out of
+ * range); the scratch of an update (0 for an argument out of range: m outside 0 .. gf_resample_max_points(), p above
+ * the rows, T above the tracks, slots no power of two from 64 to 2^30). */
+int gf_frames_track_max_rows(void);
+int gf_frames_track_max_probes(void);
+long long gf_frames_track_max_tracks(void);
+int gf_frames_track_columns(void);
+int gf_frames_track_words(void);
+long long gf_frames_track_default_slots(long long p, long long live);
+size_t gf_frames_track_scratch_bytes(long long m, long long p, long long T, long long slots);
+
+/* gf_frames_track_update (three memsets, five launches).  Point i of the snapshot is cell cells[i] (int32 [m], >= 0 and
+ * strictly ascending) and belongs to row owner[i] (int32 [m], -1 .. p - 1) of this run; cls int32 [p], score fp32 [p],
+ * keep uint8 [p] describe the rows.  M: the cells of the map before the update, T: the tracks.
+ *   count    one thread per point: r = owner when >= 0 and kept, t = track_of[cell] when the cell is < M and the track
+ *            alive (t is kept in scratch); a[r], b[t] and the pair count n[r, t] by integer adds, the pair in an
+ *            open-addressing table of `slots` entries (64-bit CAS on an empty slot only).  With aggregate != 0 a run of
+ *            equal (r, t) among adjacent lanes adds once.  With slots >= 2 m probing is unbounded; with fewer a thread
+ *            gives up after gf_frames_track_max_probes() probes.  Raises d_words[0] (cells negative or not ascending),
+ *            [1] (owner out of range), [2] (pair table overflow), [6] (a cell >= map_cap); [7] = cells[m - 1].
+ *   best     per stored pair (same cls as the track's when same_class): a CAS loop on the best slot of its row and of
+ *            its track under the total order (larger IoU n / (a + b - n), by int64 cross-products; then the smaller
+ *            index), whose maximum is unique.
+ *   match    one workgroup: row and track match when each is the other's best and (double)n >= iou * (double)union.
+ *            track[r] = the matched track; else, for a kept row with a[r] >= min_points, a new id T, T + 1, .. in
+ *            ascending r (table_cap >= T + p is required); else -1.  Then the table: a matched track gets hits + 1,
+ *            misses 0, seen = update and, when score[r] >= its score, the row's score and cls; a new one born = seen =
+ *            update, hits 1; an alive unmatched track with b[t] > 0 gets misses + 1 and retires above max_misses; a
+ *            track with b[t] == 0 is untouched.
+ *   apply    one thread per point, tid = track[r]: tid >= 0 writes track_of[cell] = tid; else a cell whose old track
+ *            matched or retired in this update is set to -1; else it is unchanged.  ids[i] = the cell's track after
+ *            that (-1 for none).  size follows by integer adds.
+ *   finish   an alive track with size 0 retires; retired int32 [T] = 1 for every track retired by this update;
+ *            d_words[3] = new tracks, [4] = retired tracks, [5] = stored pairs.
+ * With one of d_words[0], [1], [2], [6] raised nothing but scratch and d_words has been written: track_of, table, ids,
+ * track and retired are as before.  d_words int32 [gf_frames_track_words()] (device).  scratch:
+ * gf_frames_track_scratch_bytes(m, p, T, slots).  m, p, T or slots out of range, M above map_cap, T + p above table_cap,
+ * iou outside 0 .. 1, max_misses < 0, min_points < 1, update < 0 or a NULL pointer are GF_ERR_INVALID_ARG. */
+int gf_frames_track_update(const int32_t* cells, const int32_t* owner, long long m, const int32_t* cls, const float* score,
+                           const unsigned char* keep, int p, int32_t* track_of, long long M, long long map_cap,
+                           int32_t* table, long long T, long long table_cap, double iou, int max_misses, int min_points,
+                           int same_class, int update, long long slots, int aggregate, void* scratch, int32_t* ids,
+                           int32_t* track, int32_t* retired, int32_t* d_words, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,11 @@ Under "stream_vote" (with --stream K): frames.Voter (csrc/frames_vote_stream.hip
 beside the Fuser, next to one gf_frames_vote over everything; see voter_leg.
 Under "stream" (with --stream K): frames.Fuser (csrc/frames_stream.hip) fed K frames per add, next to the one-shot
 frames.fuse on the same input in the same process; see stream_leg.
+
+    python tools/frames_trace.py --no-host --track 8                # ... and a tracker updated after every 8 frames
+
+Under "track" (with --track K): frames.Tracker (csrc/frames_track.hip) updated on the Fuser's snapshot after every chunk of
+K frames, with synthetic owners (the 50 blocks of 1.2 x 1 x 1.5 m a point lies in); see track_leg.
 """
 import argparse
 import json
@@ -78,6 +83,9 @@ def main():
     ap.add_argument("--stream", type=int, default=0, metavar="K",
                     help="also run the frames K at a time through frames.Fuser (K divides --frames); see stream_leg")
     ap.add_argument("--stream-no-host", action="store_true", help="with --stream: skip frames.VoterHost on the host")
+    ap.add_argument("--track", type=int, default=0, metavar="K",
+                    help="also update a frames.Tracker on the snapshot after every K frames (K divides --frames); see track_leg")
+    ap.add_argument("--track-host", action="store_true", help="with --track and --no-host: run frames.TrackerHost all the same")
     args = ap.parse_args()
     W, H = (int(v) for v in args.size.lower().split("x"))
 
@@ -208,7 +216,83 @@ def main():
         labels = block.to(torch.uint8).reshape(F, Hs, Ws).contiguous()
         del block, group
         out["stream_vote"] = voter_leg(args, fr, dfr, labels, timed)
+    if args.track:
+        out["track"] = track_leg(args, dfr, timed)
     print(json.dumps(out))
+
+
+def track_leg(args, dfr, timed):
+    """frames.Tracker (csrc/frames_track.hip) beside a Fuser fed --track K frames at a time: after every chunk the tracker is
+    updated on fuser.kept(1) with synthetic owners -- the block of 1.2 x 1 x 1.5 m the fused point lies in, 50 rows, numbered
+    in a different order at every snapshot.  Reported: the device time of every update from events (its one read-back
+    included); gf_frames_track_update alone on the last snapshot (every row continues its track: the steady state), median
+    of --reps, with and without the aggregation of equal pairs among adjacent lanes; the share of the HBM peak on the
+    algorithmic bytes (cells, owner and ids, 4 bytes each per point, one read and one write of the map per point);
+    TrackerHost on the same updates (wall clock) and whether the two agree."""
+    from geoformer_amd import _lib, frames
+    from geoformer_amd._lib import check, ptr, stream_ptr
+
+    lib = _lib.load()
+    F, K = args.frames, args.track
+    if K < 1 or F % K:
+        raise SystemExit(f"--track {K}: a divisor of --frames {F}")
+    dev = dfr.depth.device
+    cut = lambda f, a, b: f._replace(depth=f.depth[a:b], color=f.color[a:b], table=f.table[a:b])  # noqa: E731
+    fu = frames.Fuser(cell=args.cell, stride=args.stride, near=0.1, far=10.0, edge=args.edge)
+    trackers = {agg: frames.Tracker(aggregate=agg) for agg in (1, 0)}
+    host = frames.TrackerHost() if args.track_host or not args.no_host else None
+    updates, cells, res, equal, host_ms = [], [], {"chunk_frames": K, "aggregate_default": frames.TRACK_AGGREGATE}, True, []
+    per = {1: [], 0: []}
+    for k, a in enumerate(range(0, F, K)):
+        cells.append(fu.add(cut(dfr, a, a + K)))
+        fused = fu.snapshot(1, torch.cat(cells))
+        kept = fu.kept(1)
+        b = (fused.xyz / torch.tensor([1.2, 1.0, 1.5], device=dev)).floor().to(torch.int64)
+        block = b[:, 0].clamp(0, 4) + 5 * b[:, 1].clamp(0, 4) + 25 * b[:, 2].clamp(0, 1)
+        turn = torch.from_numpy(np.random.default_rng(k).permutation(50)).to(dev)
+        owner = turn[block].to(torch.int32)
+        cls = (torch.arange(50, device=dev) % 7).to(torch.int32)
+        score = torch.full((50,), 0.5 + k / 64, dtype=torch.float32, device=dev)
+        updates.append((kept, owner, cls, score))
+        for agg, t in trackers.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            got = t.update(kept, owner, cls, score)
+            e1.record()
+            torch.cuda.synchronize()
+            per[agg].append(round(e0.elapsed_time(e1) * 1e3, 1))
+        if host is not None:
+            t0 = time.perf_counter()
+            want = host.update(kept.cpu().numpy(), owner.cpu().numpy(), cls.cpu().numpy(), score.cpu().numpy())
+            host_ms.append(round((time.perf_counter() - t0) * 1e3, 2))
+            equal = equal and all(torch.equal(x.cpu(), y) for x, y in zip(got, want))
+    t = trackers[1]
+    m, p, T = int(kept.shape[0]), 50, t.tracks
+    res.update(points=m, rows=p, tracks=T, live=t.live, pairs_last=t.pairs, retries=t.retries, map_growths=t.map_growths,
+               update_with_readback_us_aggregated=per[1], update_with_readback_us_plain=per[0])
+    if host is not None:
+        res.update(tracker_host_numpy_ms=host_ms, equal_to_numpy=bool(equal))
+    # the library call alone, on copies of the state: the last snapshot again and again (every row continues its track)
+    slots = min(frames.tracker_slots(p, t.live, m))
+    table, track_of = t._tab.clone(), t._map.clone()
+    i32 = lambda n: torch.empty(max(n, 1), dtype=torch.int32, device=dev)  # noqa: E731
+    ids, track, gone, words = i32(m), i32(p), i32(T), i32(16)
+    ws = torch.empty(lib.gf_frames_track_scratch_bytes(m, p, T, slots) // 8 + 1, dtype=torch.int64, device=dev)
+    keep = torch.ones(p, dtype=torch.uint8, device=dev)
+
+    def run(agg):
+        check(lib.gf_frames_track_update(ptr(kept), ptr(owner), m, ptr(cls), ptr(score), ptr(keep), p, ptr(track_of), t.cells,
+                                         track_of.shape[0], ptr(table), T, table.shape[1], 0.3, 2, 1, 0, t.updates, slots, agg,
+                                         ptr(ws), ptr(ids), ptr(track), ptr(gone), ptr(words), stream_ptr()), "gf_frames_track_update")
+
+    res["update_us_aggregated"], res["update_us_plain"] = timed(lambda: run(1)), timed(lambda: run(0))
+    res["update_us_aggregated_again"] = timed(lambda: run(1))
+    run(1)
+    res["words"] = words.tolist()[:8]
+    nbytes = m * (4 + 4 + 4 + 4 + 4)
+    best = min(res["update_us_aggregated"], res["update_us_plain"])
+    res.update(slots=slots, bytes=nbytes, share_of_hbm_peak=round(nbytes / (best * 1e-6) / HBM_PEAK, 4))
+    return res
 
 
 def stream_leg(args, fr, dfr, timed):

@@ -29,6 +29,14 @@ and it is scored: batch_eval.evaluate (AP) and evaluation.SemanticEvaluator (mIo
 With --chunk-frames K and --labels together, the label and instance images go through two frames.Voter
 (csrc/frames_vote_stream.hip) K frames at a time beside the Fuser and the labelled scene comes from
 frames.lift_scene_stream: the same bytes, with one chunk of images on the device at a time ("voter" in the JSON line).
+
+    python tools/predict_frames.py --frames scan.npz --chunk-frames 8 --track --track-every 2 --out out
+
+With --track (only with --chunk-frames) the model also runs on the Fuser's snapshot after every J-th chunk (--track-every,
+default 1) and after the last one, and a frames.Tracker (csrc/frames_track.hip) carries the instance ids from run to run
+(--track-iou, --track-max-misses: its parameters).  The per-frame .npy then hold the track id of every pixel (-1 without
+a track or a point) and the .png its colour in render.instance_colors; <out>/tracks.npz holds the track table and
+"track" in the JSON line the counts.  Without --track the output is what it was.
 """
 import argparse
 import json
@@ -63,6 +71,11 @@ def build_parser():
                     help='the value of "unannotated" pixels, which do not vote (0 for ScanNet\'s label-filt / instance-filt)')
     ap.add_argument("--min-votes", type=int, default=1, help="pixels an instance label needs on a point")
     ap.add_argument("--min-share", type=float, default=None, help="share of a point's votes its instance label needs")
+    ap.add_argument("--track", action="store_true",
+                    help="with --chunk-frames: run the model while the frames arrive and keep instance ids over the runs")
+    ap.add_argument("--track-every", type=int, default=1, metavar="J", help="run the model after every J-th chunk (and the last)")
+    ap.add_argument("--track-iou", type=float, default=0.3, help="frames.Tracker's iou")
+    ap.add_argument("--track-max-misses", type=int, default=2, help="frames.Tracker's max_misses")
     return ap
 
 
@@ -75,13 +88,14 @@ def lifted_labels(fused, label, instance, ignore, stride, min_votes=1, min_share
     return frames.lift_scene(fused, label, instance, ignore=ignore, stride=stride, min_votes=min_votes, min_share=min_share)
 
 
-def fuse_in_chunks(depth, K, pose, color, shift, args, label=None, instance=None):
+def fuse_in_chunks(depth, K, pose, color, shift, args, label=None, instance=None, after_chunk=None):
     """(Fused, {"chunk_frames", "adds", "cells", "table_slots", "rehashes"}, voters): the frames through a frames.Fuser,
     --chunk-frames at a time.  Only one chunk's depth and colour are on the device at a time: the arrays stay in host
     memory (as np.load gave them) and are sliced per add.  The Fused is the one frames.fuse would return for all frames
     with origin=the Fuser's, so everything after it is the same.  With label and instance images, each chunk's go
     through two frames.Voter (csrc/frames_vote_stream.hip) beside the Fuser, one chunk of images on the device at a
-    time; voters = (the Fuser, the semantic Voter, the instance Voter), what frames.lift_scene_stream takes (else None)."""
+    time; voters = (the Fuser, the semantic Voter, the instance Voter), what frames.lift_scene_stream takes (else None).
+    after_chunk(fu, cells so far, chunk number, last): called after every add (--track)."""
     from geoformer_amd import frames
 
     F, step = int(depth.shape[0]), int(args.chunk_frames)
@@ -101,6 +115,8 @@ def fuse_in_chunks(depth, K, pose, color, shift, args, label=None, instance=None
             stride = None if tuple(cells[-1].shape) == tuple(label[a:b].shape) else args.stride
             voters[1].add(cells[-1], label[a:b], stride)
             voters[2].add(cells[-1], instance[a:b], stride)
+        if after_chunk is not None:
+            after_chunk(fu, cells, len(cells), b == F)
     fused = fu.snapshot(args.min_obs, torch.cat(cells))
     return (fused, {"chunk_frames": step, "adds": len(cells), "cells": fu.cells, "table_slots": fu.slots, "rehashes": fu.rehashes},
             voters)
@@ -118,6 +134,59 @@ def score(model, name, raw, config_classes=0):
     num = lambda v: None if np.isnan(v) else float(v)  # noqa: E731
     return {"ap": num(avgs["all_ap"]), "ap50": num(avgs["all_ap_50%"]), "ap25": num(avgs["all_ap_25%"]),
             "miou": num(res["miou"]), "labelled_points": int(res["points"])}
+
+
+def make_model(args, raw, dev):
+    """The GeoFormer of --config with --checkpoint's weights, or the benchmark's synthetic model probed with `raw`."""
+    import bench
+    from geoformer_amd import batch_eval, scene
+    from geoformer_amd.model import GeoFormer, load_config
+
+    if args.checkpoint:
+        model = GeoFormer(load_config(args.config))
+        sd = torch.load(args.checkpoint, map_location="cpu")
+        model.load_state_dict(sd.get("state_dict", sd) if isinstance(sd, dict) else sd)
+        model.to(dev)
+        model.eval()
+        return model
+    probe = scene.make_batch([batch_eval.scene_dict(raw)])
+    return bench.build_model(dev, probe_batch=bench.to_device(probe, dev), cfg_name=args.config)
+
+
+class Tracking:
+    """--track: the model on the snapshot after every J-th chunk and a frames.Tracker updated with its labels."""
+
+    def __init__(self, args, name):
+        from geoformer_amd import frames
+
+        self.args, self.name, self.model, self.runs, self.ms = args, name, None, 0, 0.0
+        self.tracker = frames.Tracker(iou=args.track_iou, max_misses=args.track_max_misses)
+
+    def __call__(self, fu, cells, number, last):
+        from geoformer_amd import batch_eval, frames
+
+        self.fu = fu
+        if not last and number % self.args.track_every:
+            return
+        raw, _ = fu.snapshot(self.args.min_obs, torch.cat(cells)).raw_scene()
+        if raw.shape[0] == 0:
+            return
+        if self.model is None:
+            self.model = make_model(self.args, raw, torch.device("cuda"))
+        np.random.seed(0)
+        (_, labels), = batch_eval.label_batches(self.model, [(self.name, raw)], 1)
+        t = time.perf_counter()
+        frames.track_scene(self.tracker, fu, labels, self.args.min_obs)
+        torch.cuda.synchronize()
+        self.ms += (time.perf_counter() - t) * 1e3
+        self.runs += 1
+
+    def frame_outputs(self, fused):
+        """frame_outputs with the track id in place of the label id and the owner."""
+        from geoformer_amd import frames, render
+
+        ids = self.tracker.labels(self.fu.kept(self.args.min_obs))
+        return frames.gather(fused, ids, fill=-1), frames.gather(fused, render.instance_colors(ids), fill=255)
 
 
 def frame_outputs(fused, labels):
@@ -138,10 +207,12 @@ def main():
     import geoformer_amd
 
     geoformer_amd.configure_runtime()
-    import bench
-    from geoformer_amd import batch_eval, export, frames, scene
-    from geoformer_amd.model import GeoFormer, load_config
+    from geoformer_amd import batch_eval, export, frames
 
+    if args.track and not args.chunk_frames:
+        ap.error("--track needs --chunk-frames")
+    if args.track_every < 1:
+        ap.error(f"--track-every {args.track_every} (>= 1)")
     name = os.path.splitext(os.path.basename(args.frames))[0]
     with np.load(args.frames) as z:
         missing = [k for k in ("depth", "K", "pose") if k not in z.files]
@@ -159,7 +230,8 @@ def main():
     try:
         if args.chunk_frames:
             t = time.perf_counter()
-            fused, stream, voters = fuse_in_chunks(depth, K, pose, color, shift, args, label, instance)
+            tracking = Tracking(args, name) if args.track else None
+            fused, stream, voters = fuse_in_chunks(depth, K, pose, color, shift, args, label, instance, tracking)
         else:
             fr = frames.make(depth, K, pose, color, shift)
             t = time.perf_counter()
@@ -185,21 +257,13 @@ def main():
             ap.error(str(e))
     raw, _ = fused.raw_scene(semantic=sem, instance=ins)
     dev = torch.device("cuda")
-    if args.checkpoint:
-        model = GeoFormer(load_config(args.config))
-        sd = torch.load(args.checkpoint, map_location="cpu")
-        model.load_state_dict(sd.get("state_dict", sd) if isinstance(sd, dict) else sd)
-        model.to(dev)
-        model.eval()
-    else:
-        probe = scene.make_batch([batch_eval.scene_dict(raw)])
-        model = bench.build_model(dev, probe_batch=bench.to_device(probe, dev), cfg_name=args.config)
+    model = tracking.model if args.track and tracking.model is not None else make_model(args, raw, dev)
     np.random.seed(0)
     (_, labels), = batch_eval.label_batches(model, [(name, raw)], 1)
     os.makedirs(os.path.join(args.out, "frames"), exist_ok=True)
     export.write_ply(os.path.join(args.out, f"{name}.ply"), fused.xyz, fused.rgb)
     export.save_labels(os.path.join(args.out, f"{name}.npz"), labels)
-    ids, image = frame_outputs(fused, labels)
+    ids, image = frame_outputs(fused, labels) if not args.track else tracking.frame_outputs(fused)
     ids, image = ids.cpu().numpy(), image.cpu().numpy()
     for f in range(ids.shape[0]):
         np.save(os.path.join(args.out, "frames", f"{name}_{f:04d}.npy"), ids[f])
@@ -207,7 +271,12 @@ def main():
     out = {"frames": int(ids.shape[0]), "sampled_pixels": int(ids.size), "pixels_with_a_point": int((ids >= 0).sum()),
            "fused_points": n, "fuse_ms": round(fuse_s * 1e3, 2), "picked": int(len(labels.table.kept)),
            "kept": int(np.sum(labels.table.kept)), "labelled_points": int((np.asarray(labels.owner) >= 0).sum()),
-           "out": args.out}
+           "out": args.out}  # (with --track: pixels_with_a_point counts the pixels with a track, fuse_ms includes the model runs)
+    if args.track:
+        tr = tracking.tracker
+        np.savez(os.path.join(args.out, "tracks.npz"), **{f: c.cpu().numpy() for f, c in zip(tr.table()._fields, tr.table())})
+        out["track"] = {"runs": tracking.runs, "tracks": tr.tracks, "live": tr.live, "update_ms": round(tracking.ms, 2),
+                        "retries": tr.retries, "tracked_pixels": int((ids >= 0).sum())}
     if args.chunk_frames:
         out["stream"] = stream  # (fuse_ms then includes the upload of every chunk)
     if sem is not None:
