@@ -35,6 +35,14 @@ While the sensor is still moving (csrc/frames_stream.hip): a map th
     tracker = frames.Tracker(iou=0.3, max_misses=2)
     tracked = frames.track_scene(tracker, fuser, labels)        # labels: label_batches on fuser.snapshot()'s scene
     ids = frames.gather(fused, tracked.ids)                     # the persistent id of every depth pixel
+
+... and cells that later frames look through are dropped (csrc/frames_carve.hip): free-space evidence.
+
+    carver = frames.Carver(fuser)
+    for chunk in chunks:
+        cells = fuser.add(chunk); carver.observe(chunk)         # seen / free counts and a clamped score per cell
+    fused = fuser.snapshot(1, cells, keep=carver.keep())        # ... lift_scene_stream and track_scene take keep= too
+    vis = frames.visibility(points, chunk)                      # on its own: in how many frames is a point seen
 """
 from __future__ import annotations
 
@@ -74,6 +82,10 @@ TRACK_MIN_SLOTS, TRACK_MAX_SLOTS = 64, 1 << 30
 TRACK_AGGREGATE = True    # runs of equal (row, track) pairs among adjacent lanes add once
 _TRACK_WORDS = 16         # gf_frames_track_words()
 _TRACK_MIN_MAP, _TRACK_MIN_TABLE = 1024, 64   # the first capacities of a Tracker's map and table, doubled as needed
+CARVE_STAGE = 16          # gf_frames_carve_stage_frames(): the frame records a workgroup holds in LDS at a time
+CARVE_THREADS = 256       # gf_frames_carve_threads(): the points of one workgroup
+CARVE_VARIANT = 0         # the launch shape: 0 a thread per point over the frames, 1 a thread per probe
+_CARVE_MIN_ROWS = 1024    # the first capacity of a Carver's state, doubled as needed
 
 
 class Frames(NamedTuple):
@@ -837,6 +849,18 @@ def _cells_arg(cells, M, device, who):
     return c
 
 
+def _keep_arg(keep, M, device, who):
+    """keep as a bool tensor [M] on `device`, or None."""
+    if keep is None:
+        return None
+    k = keep if torch.is_tensor(keep) else torch.from_numpy(np.ascontiguousarray(keep))
+    if k.dtype not in (torch.bool, torch.uint8) or k.dim() != 1:
+        raise ValueError(f"{who}: keep: expected bool or uint8 [{M}], got {k.dtype} {tuple(k.shape)}")
+    if k.shape[0] != M:
+        raise ValueError(f"{who}: keep holds {k.shape[0]} cells, the map {M}")
+    return (k != 0).to(device)
+
+
 class FuserHost:
     """The statement of Fuser, in numpy: a map (cell, origin, stride, near, far, edge) that frames are added to a chunk
     at a time.  Per cell, in order of first occurrence: count and six int64 sums (three coordinates in units of 2^-20 m,
@@ -855,6 +879,8 @@ class FuserHost:
     (float)((double)o + ((double)sum_q / (double)count) 2^-20), colour (sum + count // 2) // count, cells with
     count >= min_obs kept in order and renumbered densely; point_of = new_id[cells] (-1 stays -1) for the cells given
     (one add's, or several concatenated along the frame axis), an empty [0, 0, 0] without.  Changes nothing.
+    keep: bool or uint8 [cells] (a Carver's keep()): only cells with count >= min_obs AND keep are kept; a dropped cell's
+    pixels get -1.  None and all True give the same bits; another length is a ValueError.
 
     For chunks c1..ck, snapshot(min_obs, cat(cells_1..cells_k)) equals fuse_host(concat(c1..ck), ..., min_obs,
     origin=map.origin) in every field, bit for bit.  origin=None: fixed at the first add with a valid pixel, at that
@@ -946,16 +972,19 @@ class FuserHost:
             return torch.zeros(0, dtype=torch.int32)
         return torch.from_numpy(self._insert(xyz, rgb, who).astype(np.int32))
 
-    def snapshot(self, min_obs=1, cells=None):
+    def snapshot(self, min_obs=1, cells=None, keep=None):
         who = self._who + ".snapshot"
         if int(min_obs) < 1:
             raise ValueError(f"{who}: min_obs = {min_obs} (>= 1)")
         M = self._keys.shape[0]
         cells = _cells_arg(cells, M, "cpu", who)
+        mask = _keep_arg(keep, M, "cpu", who)
         if M == 0:
             return _empty((0, 0, 0) if cells is None else cells.shape, "cpu")
         o = self._origin.astype(np.float64)
         keep = self._count >= int(min_obs)
+        if mask is not None:
+            keep &= mask.numpy()
         new_id = np.where(keep, np.cumsum(keep) - 1, -1).astype(np.int32)
         cnt = self._count[keep]
         mean = (self._sums[keep, :3].astype(np.float64) / cnt[:, None].astype(np.float64)) * (1.0 / UNITS)
@@ -968,11 +997,16 @@ class FuserHost:
             point_of = np.where(c >= 0, new_id[np.maximum(c, 0)], -1).astype(np.int32)
         return Fused(*(torch.from_numpy(np.ascontiguousarray(a)) for a in (xyz_out, rgb_out, cnt.astype(np.int32), point_of)))
 
-    def kept(self, min_obs=1):
-        """int32 [m]: the cell number of every point of snapshot(min_obs), ascending -- the cells with count >= min_obs."""
+    def kept(self, min_obs=1, keep=None):
+        """int32 [m]: the cell number of every point of snapshot(min_obs, keep=keep), ascending -- the cells with
+        count >= min_obs (and keep, when given)."""
         if int(min_obs) < 1:
             raise ValueError(f"{self._who}.kept: min_obs = {min_obs} (>= 1)")
-        return torch.from_numpy(np.nonzero(self._count >= int(min_obs))[0].astype(np.int32))
+        mask = _keep_arg(keep, self._keys.shape[0], "cpu", self._who + ".kept")
+        on = self._count >= int(min_obs)
+        if mask is not None:
+            on &= mask.numpy()
+        return torch.from_numpy(np.nonzero(on)[0].astype(np.int32))
 
 
 class Fuser:
@@ -988,7 +1022,9 @@ class Fuser:
     rehashed (which drops what the insert claimed) before the ValueError is raised: the map is exactly as it was.
     snapshot: gf_frames_map_means, gf_frames_map_lookup; the words {m, accumulate's flag, a cell out of range} are read
     back once, the only synchronisation (the lookup checks every cell against the map's M as it reads it: a value
-    below -1 or >= M is a ValueError).
+    below -1 or >= M is a ValueError).  With keep= (FuserHost's rule) gf_frames_map_means gets a copy of the counts
+    with zeros at the dropped cells, which its count >= min_obs test refuses before anything is divided; the map itself
+    is not touched.
 
     slots: the table's entries, a power of two.  None: the table starts at stream_slots' default and is doubled by
     gf_frames_map_rehash until slots >= 4 M' after an add; when an insert overflows it, the table is rehashed ONCE to
@@ -1177,9 +1213,9 @@ class Fuser:
             x = up(xyz)
             return self._insert(x, up(rgb), x.min(0).values, who)
 
-    def snapshot(self, min_obs=1, cells=None):
+    def snapshot(self, min_obs=1, cells=None, keep=None):
         if self._host is not None:
-            return self._host.snapshot(min_obs, cells)
+            return self._host.snapshot(min_obs, cells, keep)
         from . import _lib
         from ._lib import check, ptr, stream_ptr
 
@@ -1190,13 +1226,17 @@ class Fuser:
         dev, M = self._dev, self._M
         with torch.cuda.device(dev):
             cells = _cells_arg(cells, M, dev, who)
+            mask = _keep_arg(keep, M, dev, who)
             if M == 0:
                 return _empty((0, 0, 0) if cells is None else cells.shape, dev)
+            count = self._count
+            if mask is not None:  # a dropped cell's count reads 0 < min_obs: FmKept refuses it before anything is divided
+                count = torch.where(mask, count[:M], torch.zeros((), dtype=torch.int32, device=dev))
             xyz_out = torch.empty((M, 3), dtype=torch.float32, device=dev)
             rgb_out = torch.empty((M, 3), dtype=torch.uint8, device=dev)
             out_i = torch.empty((2, M), dtype=torch.int32, device=dev)
             ws = torch.empty(lib.gf_frames_map_means_scratch_bytes(M, self._chunk) // 8 + 1, dtype=torch.int64, device=dev)
-            check(lib.gf_frames_map_means(ptr(self._count), ptr(self._sums), M, ptr(self._org), int(min_obs), self._chunk, ptr(ws),
+            check(lib.gf_frames_map_means(ptr(count), ptr(self._sums), M, ptr(self._org), int(min_obs), self._chunk, ptr(ws),
                                           ptr(xyz_out), ptr(rgb_out), ptr(out_i[0]), ptr(out_i[1]), ptr(self._words),
                                           stream_ptr()), "gf_frames_map_means")
             if cells is None:
@@ -1213,15 +1253,19 @@ class Fuser:
             raise RuntimeError(f"{who}: an accumulate met a point beyond the map's reach")
         return Fused(xyz_out[:m], rgb_out[:m], out_i[0, :m], point_of)
 
-    def kept(self, min_obs=1):
+    def kept(self, min_obs=1, keep=None):
         """FuserHost.kept on the device: int32 [m], a torch reduction over the M counts (nothing of the map is read back
         but m, the length of the result)."""
         if self._host is not None:
-            return self._host.kept(min_obs)
+            return self._host.kept(min_obs, keep)
         if int(min_obs) < 1:
             raise ValueError(f"{self._who}.kept: min_obs = {min_obs} (>= 1)")
         with torch.cuda.device(self._dev):
-            return torch.nonzero(self._count[:self._M] >= int(min_obs)).reshape(-1).to(torch.int32)
+            mask = _keep_arg(keep, self._M, self._dev, self._who + ".kept")
+            on = self._count[:self._M] >= int(min_obs)
+            if mask is not None:
+                on = on & mask
+            return torch.nonzero(on).reshape(-1).to(torch.int32)
 
 
 # ---- votes that persist between calls: labels lifted chunk by chunk ---------------------------------------------------
@@ -1540,14 +1584,15 @@ class Voter:
         return Lifted(out[0], out[1], out[2]), pairs
 
 
-def lift_scene_stream(fuser, sem_voter, ins_voter, min_obs=1, min_votes=1, min_share=None):
+def lift_scene_stream(fuser, sem_voter, ins_voter, min_obs=1, min_votes=1, min_share=None, keep=None):
     """(semantic int32 [m], instance int32 [m]) of the points of fuser.snapshot(min_obs): scene_labels of the two voters'
     snapshots over fuser.kept(min_obs).  sem_voter and ins_voter were fed every chunk's cells (what fuser.add returned)
     with its label and its instance images.  Equal, as bits, to lift_scene(fuser.snapshot(min_obs, all cells), all label
-    images, all instance images, ...) -- with nothing kept but the map and the two tables."""
+    images, all instance images, ...) -- with nothing kept but the map and the two tables.  keep: the points are those of
+    fuser.snapshot(min_obs, keep=keep) (a Carver's keep(): bool or uint8 [fuser.cells])."""
     if not isinstance(fuser, (Fuser, FuserHost)) or not all(isinstance(v, (Voter, VoterHost)) for v in (sem_voter, ins_voter)):
         raise ValueError("frames.lift_scene_stream: expected a Fuser and two Voters (or their host statements)")
-    rows, n = fuser.kept(min_obs), fuser.cells
+    rows, n = fuser.kept(min_obs, keep), fuser.cells
     sem = sem_voter.snapshot(n, IGNORE_LABEL, rows)[0]
     ins = ins_voter.snapshot(n, IGNORE_LABEL, rows)[0]
     return scene_labels(sem, ins, min_votes, min_share, host=not sem.label.is_cuda)
@@ -1991,11 +2036,361 @@ class Tracker:
         return Tracked(ids, track, matched, fresh, lost)
 
 
-def track_scene(tracker, fuser, labels, min_obs=1):
+def track_scene(tracker, fuser, labels, min_obs=1, keep=None):
     """tracker.update over the points of fuser.snapshot(min_obs) with the model's labels of that snapshot (a SceneLabels of
     batch_eval.label_batches): update(fuser.kept(min_obs), labels.owner, table.label_id, table.score, table.kept).
-    frames.gather(fused, tracked.ids) then gives every depth pixel its persistent id."""
+    frames.gather(fused, tracked.ids) then gives every depth pixel its persistent id.  keep: the points are those of
+    fuser.snapshot(min_obs, keep=keep)."""
     if not isinstance(tracker, (Tracker, TrackerHost)) or not isinstance(fuser, (Fuser, FuserHost)):
         raise ValueError("frames.track_scene: expected a Tracker and a Fuser (or their host statements)")
     t = labels.table
-    return tracker.update(fuser.kept(min_obs), labels.owner, t.label_id, t.score, t.kept)
+    return tracker.update(fuser.kept(min_obs, keep), labels.owner, t.label_id, t.score, t.kept)
+
+
+# ---- free-space evidence: what later frames see of the map's cells ----------------------------------------------------
+OUTSIDE, UNKNOWN, OCCLUDED, SEEN, FREE = 0, 1, 2, 3, 4   # the class of a probe, as `codes` holds it
+
+
+class Visibility(NamedTuple):
+    """Per point, int32 [n]: the frames in which it was seen (the depth pixel it projects into measures it, within the
+    tolerance), in which the ray went through it (free: the pixel measures a surface well behind it) and in which
+    something nearer hides it (occluded).  Frames in which it projects outside the image or onto an invalid pixel count
+    nowhere."""
+    seen: object
+    free: object
+    occluded: object
+
+
+def inverse_records(fr):
+    """float32 [F, 12]: per frame the inverse of the 3 x 3 block A of the frame's float32 record (fr.table[f, 4:], the
+    camera-to-world P = [A | t]) row-major, then t.  inv = adj(A) / det(A) in float64, written out as cofactors (no
+    library call: the bits depend on nothing but the record), rounded to float32 once.  A need not be orthonormal.
+    ValueError when a determinant is zero or a value is not finite in float32.  Host only: the statement and the device
+    wrapper both call it."""
+    if not isinstance(fr, Frames):
+        raise ValueError("frames.inverse_records: expected the Frames of frames.make")
+    P = fr.table[:, 4:].astype(np.float64).reshape(-1, 3, 4)
+    a = lambda r, c: P[:, r, c]  # noqa: E731
+    with np.errstate(all="ignore"):
+        cof = [a(1, 1) * a(2, 2) - a(1, 2) * a(2, 1), a(0, 2) * a(2, 1) - a(0, 1) * a(2, 2), a(0, 1) * a(1, 2) - a(0, 2) * a(1, 1),
+               a(1, 2) * a(2, 0) - a(1, 0) * a(2, 2), a(0, 0) * a(2, 2) - a(0, 2) * a(2, 0), a(0, 2) * a(1, 0) - a(0, 0) * a(1, 2),
+               a(1, 0) * a(2, 1) - a(1, 1) * a(2, 0), a(0, 1) * a(2, 0) - a(0, 0) * a(2, 1), a(0, 0) * a(1, 1) - a(0, 1) * a(1, 0)]
+        det = (a(0, 0) * cof[0] + a(0, 1) * cof[3]) + a(0, 2) * cof[6]
+        if not (np.isfinite(det) & (det != 0)).all():
+            raise ValueError(f"frames.inverse_records: frame {int(np.argmin(np.isfinite(det) & (det != 0)))}: the pose's 3 x 3 "
+                             "block is singular")
+        out = np.concatenate([np.stack(cof, axis=1) / det[:, None], P[:, :, 3]], axis=1).astype(np.float32)
+    if not np.isfinite(out).all():
+        raise ValueError("frames.inverse_records: an inverse record is not finite in float32")
+    return np.ascontiguousarray(out)
+
+
+def _vis_args(near, far, edge, band, rel, who):
+    f32 = np.float32
+    near, far, e, band, rel = f32(near), f32(far), f32(0.0 if edge is None else edge), f32(band), f32(rel)
+    if np.isnan(near) or np.isnan(far):
+        raise ValueError(f"{who}: near and far must be numbers")
+    for name, v in (("edge", e), ("band", band), ("rel", rel)):
+        if not (v >= 0 and np.isfinite(v)):
+            raise ValueError(f"{who}: {name} must be >= 0 and finite in float32, got {v!r}")
+    return near, far, e, band, rel
+
+
+def _vis_points(xyz, who):
+    """xyz as it came (a tensor or an array), checked: float32 [n, 3], n <= MAX_POINTS."""
+    if not (torch.is_tensor(xyz) or isinstance(xyz, np.ndarray)):
+        raise ValueError(f"{who}: xyz: expected a numpy array or a torch tensor, got {type(xyz).__name__}")
+    dt = xyz.dtype
+    if dt not in (torch.float32, np.float32) or len(xyz.shape) != 2 or xyz.shape[1] != 3:
+        raise ValueError(f"{who}: xyz: expected float32 [n, 3], got {dt} {tuple(xyz.shape)}")
+    if xyz.shape[0] > MAX_POINTS:
+        raise ValueError(f"{who}: {xyz.shape[0]} points (at most {MAX_POINTS})")
+    return xyz
+
+
+def _visibility_host(xyz, fr, inv, near, far, e, band, rel, codes):
+    """(counts int32 [3, n] = seen, free, occluded; codes uint8 [F, n] or None) of checked arguments: the rule, one
+    frame at a time over all the points."""
+    f32 = np.float32
+    d = fr.depth.detach().cpu().numpy()
+    F, H, W = d.shape
+    n = xyz.shape[0]
+    counts = np.zeros((3, n), np.int32)
+    out = np.zeros((F, n), np.uint8) if codes else None
+    x = [np.ascontiguousarray(xyz[:, a]) for a in range(3)]
+    with np.errstate(all="ignore"):
+        for f in range(F):
+            fx, fy, cx, cy = (f32(v) for v in fr.table[f, :4])
+            m, t = inv[f, :9].reshape(3, 3), inv[f, 9:]
+            dd = [x[a] - t[a] for a in range(3)]
+            c = [(m[a, 0] * dd[0] + m[a, 1] * dd[1]) + m[a, 2] * dd[2] for a in range(3)]
+            zc = c[2]
+            u = ((c[0] * fx) / zc) + cx
+            v = ((c[1] * fy) / zc) + cy
+            assert zc.dtype == u.dtype == v.dtype == np.float32
+            i, j = np.floor(u), np.floor(v)
+            inside = (zc >= near) & (i >= 0) & (i < f32(W)) & (j >= 0) & (j < f32(H))
+            ii, jj = np.where(inside, i, 0).astype(np.int64), np.where(inside, j, 0).astype(np.int64)
+            z = d[f].astype(np.float32) / f32(fr.depth_shift)  # the frame at full resolution; backproject_host's rule
+            inr = (z >= near) & (z <= far)
+            ok = inr.copy()
+            if e > 0:
+                lim = e * z
+                for dx, dy in ((-1, 0), (1, 0), (0, -1), (0, 1)):
+                    zn = _shift2(z[None], dx, dy, f32(0))[0]
+                    ok &= ~(_shift2(inr[None], dx, dy, False)[0] & (np.abs(zn - z) > lim))
+            zp = z[jj, ii]
+            tol = (rel * zp) + band
+            assert tol.dtype == np.float32
+            cls = np.where(zc < zp - tol, FREE, np.where(zc > zp + tol, OCCLUDED, SEEN))
+            cls = np.where(inside, np.where(ok[jj, ii], cls, UNKNOWN), OUTSIDE).astype(np.uint8)
+            for row, k in enumerate((SEEN, FREE, OCCLUDED)):
+                counts[row] += cls == k
+            if codes:
+                out[f] = cls
+    return counts, out
+
+
+def visibility_host(xyz, fr, near=0.1, far=10.0, edge=None, band=0.06, rel=0.02, codes=False):
+    """The statement of gf_frames_visibility: Visibility of numpy int32 [n] arrays -- per point of xyz (float32 [n, 3],
+    world coordinates) the frames of fr that see it, see through it and see something nearer -- and with codes=True
+    (Visibility, codes uint8 [F, n]): the class of every probe, 0 OUTSIDE, 1 UNKNOWN, 2 OCCLUDED, 3 SEEN, 4 FREE.  One
+    probe, point X in frame f, in float32 with every operation rounded on its own (inv, t: inverse_records):
+        d = X - t;  c_a = ((inv[a,0] d0 + inv[a,1] d1) + inv[a,2] d2);  zc = c_2;  !(zc >= near) -> OUTSIDE
+        u = ((c_0 fx) / zc) + cx, v likewise; i = floor u, j = floor v; !(0 <= i < W && 0 <= j < H) -> OUTSIDE
+        z = depth[f, j, i] / depth_shift (full resolution); the pixel invalid by backproject_host's rule -> UNKNOWN
+        tol = (rel z) + band;  zc < z - tol -> FREE;  zc > z + tol -> OCCLUDED;  else SEEN.
+    A point that is not finite is OUTSIDE everywhere.  band is metres, rel a share of the measured depth."""
+    who = "visibility_host"
+    if not isinstance(fr, Frames):
+        raise ValueError(f"{who}: expected the Frames of frames.make")
+    xyz = _vis_points(xyz, who)
+    xyz = xyz.detach().cpu().numpy() if torch.is_tensor(xyz) else xyz
+    near, far, e, band, rel = _vis_args(near, far, edge, band, rel, who)
+    counts, out = _visibility_host(xyz, fr, inverse_records(fr), near, far, e, band, rel, bool(codes))
+    vis = Visibility(counts[0], counts[1], counts[2])
+    return (vis, out) if codes else vis
+
+
+def carve_limits():
+    """(stage frames, threads, points, launch shapes) of the library, asserted against this module's constants."""
+    from . import _lib
+
+    lib = _lib.load()
+    got = (lib.gf_frames_carve_stage_frames(), lib.gf_frames_carve_threads(), lib.gf_frames_carve_max_points(),
+           lib.gf_frames_visibility_variants())
+    if got != (CARVE_STAGE, CARVE_THREADS, MAX_POINTS, 2):
+        raise RuntimeError(f"frames: the library's carve limits {got} are not this module's")
+    return got
+
+
+def _variant_arg(variant, who):
+    v = CARVE_VARIANT if variant is None else int(variant)
+    if v not in (0, 1):
+        raise ValueError(f"{who}: variant = {variant!r} (None, 0: a thread per point, or 1: a thread per probe)")
+    return v
+
+
+def _visibility_device(xyz, fr, inv, near, far, e, band, rel, codes, state, variant, who):
+    """(out int32 [3, n], codes uint8 [F, n] or None) on xyz's device; state: None or (seen, free, score, hit, miss, floor,
+    ceil), updated by the same call.  Every argument has been checked."""
+    from . import _lib
+    from ._lib import check, ptr, stream_ptr
+
+    dev, n = xyz.device, xyz.shape[0]
+    F, H, W = fr.depth.shape
+    with torch.cuda.device(dev):
+        depth = (fr.depth if fr.depth.device == dev else fr.depth.to(dev)).contiguous()
+        table =torch.from_numpy(fr.table).to(dev, non_blocking=True)
+        invd = torch.from_numpy(inv).to(dev, non_blocking=True)
+        out = torch.empty((3, n), dtype=torch.int32, device=dev)
+        cod = torch.empty((F, n), dtype=torch.uint8, device=dev) if codes else None
+        s = state or (None, None, None, 0, 0, 0, 0)
+        check(_lib.load().gf_frames_visibility(ptr(xyz), n, ptr(depth), int(depth.dtype == torch.float32), F, H, W,
+                                               fr.depth_shift, ptr(table), ptr(invd), float(near), float(far), float(e),
+                                               float(band), float(rel), ptr(out), ptr(cod), ptr(s[0]), ptr(s[1]), ptr(s[2]),
+                                               *s[3:], variant, stream_ptr()), "gf_frames_visibility")
+    return out, cod
+
+
+def visibility(xyz, fr, near=0.1, far=10.0, edge=None, band=0.06, rel=0.02, codes=False, variant=None):
+    """visibility_host on xyz's device: Visibility of int32 [n] tensors (and codes uint8 [F, n] with codes=True), by
+    gf_frames_visibility on the current stream -- bit-identical to the statement and from call to call, nothing read
+    back.  xyz: a contiguous float32 tensor [n, 3]; the frames are moved to its device when they are elsewhere, as fuse
+    does.  variant: the launch shape (None: CARVE_VARIANT; the result is the same).  A CPU tensor runs the statement."""
+    who = "frames.visibility"
+    if not isinstance(fr, Frames):
+        raise ValueError(f"{who}: expected the Frames of frames.make")
+    if not torch.is_tensor(xyz):
+        raise ValueError(f"{who}: xyz: expected a torch tensor (visibility_host takes arrays)")
+    xyz = _vis_points(xyz, who).contiguous()
+    near, far, e, band, rel = _vis_args(near, far, edge, band, rel, who)
+    variant = _variant_arg(variant, who)
+    inv = inverse_records(fr)
+    if not xyz.is_cuda:
+        counts, out = _visibility_host(xyz.detach().numpy(), fr, inv, near, far, e, band, rel, bool(codes))
+        counts, out = torch.from_numpy(counts), None if out is None else torch.from_numpy(out)
+    else:
+        counts, out = _visibility_device(xyz, fr, inv, near, far, e, band, rel, bool(codes), None, variant, who)
+    vis = Visibility(counts[0], counts[1], counts[2])
+    return (vis, out) if codes else vis
+
+
+def _carve_args(fuser, band, rel, hit, miss, floor, ceil, drop, who):
+    band = 3.0 * float(fuser._cell) if band is None else band
+    near, far, e, band, rel = _vis_args(fuser._near, fuser._far, fuser._edge, band, rel, who)
+    ints = []
+    for name, v in (("hit", hit), ("miss", miss), ("floor", floor), ("ceil", ceil), ("drop", drop)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not -2 ** 31 <= int(v) < 2 ** 31:
+            raise ValueError(f"{who}: {name} = {v!r} (an int32)")
+        ints.append(int(v))
+    hit, miss, floor, ceil, drop = ints
+    if hit < 0 or miss < 0 or floor > ceil:
+        raise ValueError(f"{who}: hit = {hit}, miss = {miss} (each >= 0), floor = {floor} <= ceil = {ceil}")
+    return (near, far, e, band, rel), (hit, miss, floor, ceil), drop
+
+
+class CarverHost:
+    """The statement of Carver, in numpy, bound to one FuserHost: per cell of the map int32 seen, free (the probes so
+    far that saw the cell and that went through it, saturating at 2^31 - 1) and score, OctoMap's clamped occupancy update
+    in integers.  A cell that is new since the last call starts at zeros.
+
+    observe(fr) -> Visibility (int32 [fuser.cells] CPU tensors): every cell's current mean (fuser.snapshot(1).xyz) probed
+    in every frame of the chunk by visibility_host's rule (near, far and edge are the fuser's; band=None is three times
+    its cell), then per cell, with s and f the call's seen and free counts: seen += s, free += f, score = min(ceil,
+    max(floor, score + hit s - miss f)) in int64 -- one clamp per cell per call, so the result depends on the order of
+    the calls and on nothing inside one.  The chunk need not have the size, dtype or depth_shift of the fuser's stream.
+    ValueError -- and the state exactly as it was -- for anything but Frames, a singular pose, or an empty map.
+
+    keep(drop=None) -> bool [fuser.cells]: score > drop (cells newer than the last observe: True).  state() -> (seen,
+    free, score) int32 [cells observed so far], copies.  The typical loop is cells = fuser.add(chunk);
+    carver.observe(chunk): a cell the chunk created is seen by its own pixels, one it looks through loses score."""
+
+    def __init__(self, fuser, band=None, rel=0.02, hit=1, miss=1, floor=-8, ceil=8, drop=-2):
+        self._who = "frames." + type(self).__name__
+        if not isinstance(fuser, FuserHost):
+            raise ValueError(f"{self._who}: expected a FuserHost")
+        self._fuser = fuser
+        self._probe, self._rule, self._drop = _carve_args(fuser, band, rel, hit, miss, floor, ceil, drop, self._who)
+        self._state = np.zeros((3, 0), np.int32)
+
+    fuser = property(lambda self: self._fuser, doc="the map this carver is bound to")
+    cells = property(lambda self: int(self._state.shape[1]), doc="the cells observed so far")
+    band = property(lambda self: float(self._probe[3]), doc="the tolerance in metres, as float32")
+    drop = property(lambda self: self._drop, doc="keep() drops the cells whose score is at or below it")
+
+    def state(self):
+        """(seen, free, score) int32 [cells], copies."""
+        return tuple(self._state[k].copy() for k in range(3))
+
+    def observe(self, fr):
+        who = self._who + ".observe"
+        if not isinstance(fr, Frames):
+            raise ValueError(f"{who}: expected the Frames of frames.make")
+        M = self._fuser.cells
+        if M == 0:
+            raise ValueError(f"{who}: the map is empty")
+        inv = inverse_records(fr)
+        xyz = self._fuser.snapshot(1).xyz.numpy()
+        counts, _ = _visibility_host(xyz, fr, inv, *self._probe, False)
+        hit, miss, floor, ceil = self._rule
+        old = np.zeros((3, M), np.int64)
+        old[:, :self._state.shape[1]] = self._state
+        s, f = counts[0].astype(np.int64), counts[1].astype(np.int64)
+        new = np.empty((3, M), np.int64)
+        new[0] = np.minimum(old[0] + s, 2 ** 31 - 1)
+        new[1] = np.minimum(old[1] + f, 2 ** 31 - 1)
+        new[2] = np.minimum(ceil, np.maximum(floor, old[2] + hit * s - miss * f))
+        self._state = new.astype(np.int32)  # nothing above changed the state
+        return Visibility(*(torch.from_numpy(np.ascontiguousarray(c)) for c in counts))
+
+    def keep(self, drop=None):
+        drop = self._drop if drop is None else int(drop)
+        k = np.ones(self._fuser.cells, bool)
+        k[:self._state.shape[1]] = self._state[2] > drop
+        return torch.from_numpy(k)
+
+
+class Carver:
+    """CarverHost's state on the GPU (csrc/frames_carve.hip), bound to one Fuser: the same observe, keep,
+    state and cells, bit-identical to the statement after every call.  seen, free and score are three int32 tensors
+    owned here; they grow with fuser.cells (to at least double, zero filled, the old rows copied).  observe is
+    fuser.snapshot(1) and one gf_frames_visibility on the current stream, which probes and updates the state in the same
+    call; it synchronises nothing itself (the snapshot reads its three words back).  Every check is made before the
+    launch: a failed observe leaves the state as it was.  Frames are moved to the fuser's device per observe.  variant:
+    the launch shape (None: CARVE_VARIANT; the result is the same).  device "cpu", or a FuserHost: CarverHost."""
+
+    def __init__(self, fuser, band=None, rel=0.02, hit=1, miss=1, floor=-8, ceil=8, drop=-2, device=None, variant=None):
+        self._who = who = "frames.Carver"
+        self._host = None
+        if isinstance(fuser, Fuser) and fuser._host is not None:
+            fuser = fuser._host
+        if isinstance(fuser, FuserHost):
+            if device is not None and torch.device(device).type != "cpu":
+                raise ValueError(f"{who}: a FuserHost's carver lives on the CPU, got device = {device!r}")
+            self._host = CarverHost(fuser, band, rel, hit, miss, floor, ceil, drop)
+            return
+        if not isinstance(fuser, Fuser):
+            raise ValueError(f"{who}: expected a Fuser (or a FuserHost)")
+        if device is not None and torch.device(device).type != "cuda":
+            raise ValueError(f"{who}: a Fuser's carver lives on its device {fuser._dev}, got device = {device!r}")
+        self._fuser = fuser
+        self._probe, self._rule, self._drop = _carve_args(fuser, band, rel, hit, miss, floor, ceil, drop, who)
+        self._variant = _variant_arg(variant, who)
+        carve_limits()
+        self._dev = fuser._dev
+        self._M = 0
+        self.row_growths = 0
+        with torch.cuda.device(self._dev):
+            self._seen, self._free, self._score = (torch.zeros(_CARVE_MIN_ROWS, dtype=torch.int32, device=self._dev)
+                                                   for _ in range(3))
+
+    fuser = property(lambda self: self._host.fuser if self._host is not None else self._fuser,
+                     doc="the map this carver is bound to")
+    cells = property(lambda self: self._host.cells if self._host is not None else self._M, doc="the cells observed so far")
+    band = property(lambda self: self._host.band if self._host is not None else float(self._probe[3]),
+                    doc="the tolerance in metres, as float32")
+    drop = property(lambda self: self._host.drop if self._host is not None else self._drop,
+                    doc="keep() drops the cells whose score is at or below it")
+
+    def state(self):
+        """CarverHost.state() of this carver: (seen, free, score) int32 [cells] numpy arrays, read back."""
+        if self._host is not None:
+            return self._host.state()
+        return tuple(t[:self._M].cpu().numpy() for t in (self._seen, self._free, self._score))
+
+    def observe(self, fr):
+        if self._host is not None:
+            return self._host.observe(fr)
+        who = self._who + ".observe"
+        if not isinstance(fr, Frames):
+            raise ValueError(f"{who}: expected the Frames of frames.make")
+        M, dev = self._fuser.cells, self._dev
+        if M == 0:
+            raise ValueError(f"{who}: the map is empty")
+        inv = inverse_records(fr)
+        with torch.cuda.device(dev):
+            xyz = self._fuser.snapshot(1).xyz.contiguous()  # all M cells in cell order
+            cap = self._seen.shape[0]
+            if M > cap:
+                cap = max(2 * cap, M)
+                grown = []
+                for old in (self._seen, self._free, self._score):
+                    t = torch.zeros(cap, dtype=torch.int32, device=dev)
+                    t[:self._M] = old[:self._M]
+                    grown.append(t)
+                self._seen, self._free, self._score = grown
+                self.row_growths += 1
+            out, _ = _visibility_device(xyz, fr, inv, *self._probe, False, (self._seen, self._free, self._score) + self._rule,
+                                        self._variant, who)
+        self._M = M
+        return Visibility(out[0], out[1], out[2])
+
+    def keep(self, drop=None):
+        if self._host is not None:
+            return self._host.keep(drop)
+        drop = self._drop if drop is None else int(drop)
+        with torch.cuda.device(self._dev):
+            k = torch.ones(self._fuser.cells, dtype=torch.bool, device=self._dev)
+            k[:self._M] = self._score[:self._M] > drop
+        return k

@@ -1894,6 +1894,45 @@ int gf_frames_track_update(const int32_t* cells, const int32_t* owner, long long
                            int same_class, int update, long long slots, int aggregate, void* scratch, int32_t* ids,
                            int32_t* track, int32_t* retired, int32_t* d_words, void* stream);
 
+/* ===================================================================================
+ * frames_carve.hip -- what posed depth frames see of world points, and the free-space score of a map's cells
+ * (DESIGN.md section 30).  The statement is frames.visibility_host / frames.CarverHost.  The state (seen, free, score,
+ * int32 per cell) belongs to the caller.  No scratch; no thread waits for another thread or workgroup; every launch
+ * goes on `stream`; nothing is read back.  Every argument is checked before the first launch (GF_ERR_INVALID_ARG,
+ * nothing launched).
+ * =================================================================================== */
+
+/* Limits, as functions: the frame records a workgroup of the per-point shape stages in LDS at a time (16), the threads
+ * of a workgroup (256), the points of one call (gf_resample_max_points()), the launch shapes (2). */
+int gf_frames_carve_stage_frames(void);
+int gf_frames_carve_threads(void);
+int gf_frames_carve_max_points(void);
+int gf_frames_visibility_variants(void);
+
+/* gf_frames_visibility.  xyz fp32 [n, 3] world points; depth uint16 (dtype 0) or fp32 (dtype 1) [F, H, W], a value d
+ * is d / depth_shift metres; table fp32 [F, gf_frames_record_floats()] (only {fx, fy, cx, cy} are read); inv fp32
+ * [F, 12]: per frame the inverse of the record's 3 x 3 block, row-major, then its translation t
+ * (frames.inverse_records).  One probe = point X in frame f, float32, every operation rounded on its own:
+ *   d = X - t;  c_a = ((inv[a,0] d0 + inv[a,1] d1) + inv[a,2] d2);  zc = c_2
+ *   !(zc >= near)                                        -> 0 outside
+ *   u = ((c_0 fx) / zc) + cx, v likewise; i = floor u, j = floor v;  !(0 <= i < W && 0 <= j < H) as floats -> 0 outside
+ *   z = depth[f, j, i] / depth_shift, read only now;  !(near <= z <= far), or with edge > 0 an in-image 4-neighbour zn
+ *   with near <= zn <= far and |zn - z| > edge z         -> 1 unknown
+ *   tol = (rel z) + band;  zc < z - tol -> 4 free;  zc > z + tol -> 2 occluded;  else 3 seen
+ * out int32 [3, n]: per point the probes over the F frames that were seen, free, occluded.  codes uint8 [F, n] or NULL:
+ * the class of every probe.  seen, free, score int32 [n], all three or all NULL: seen += s and free += f (saturating
+ * at 2^31 - 1), score = min(ceil, max(floor, score + hit s - miss f)), in 64-bit integers, one clamp per call.
+ * variant 0: one launch, a thread per point loops over the frames (records staged in LDS, counts in registers, plain
+ * stores).  variant 1: a memset of out, a thread per (frame, point) with one integer atomicAdd per probe that is not
+ * outside or unknown, and a finishing launch for the state.  The same bits either way.  n == 0 succeeds with nothing
+ * launched.  n, F, H, W, dtype or variant out of range, depth_shift not positive and finite, near or far NaN, edge,
+ * band or rel negative or not finite, hit or miss negative, floor > ceil, some but not all of the state pointers, state
+ * pointers that coincide, or a NULL xyz, depth, table, inv or out are GF_ERR_INVALID_ARG. */
+int gf_frames_visibility(const float* xyz, int n, const void* depth, int dtype, int F, int H, int W, float depth_shift,
+                         const float* table, const float* inv, float near, float far, float edge, float band, float rel,
+                         int32_t* out, unsigned char* codes, int32_t* seen, int32_t* free, int32_t* score, int hit, int miss,
+                         int floor, int ceil, int variant, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

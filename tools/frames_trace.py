@@ -26,6 +26,11 @@ frames.fuse on the same input in the same process; see stream_leg.
 
 Under "track" (with --track K): frames.Tracker (csrc/frames_track.hip) updated on the Fuser's snapshot after every chunk of
 K frames, with synthetic owners (the 50 blocks of 1.2 x 1 x 1.5 m a point lies in); see track_leg.
+
+    python tools/frames_trace.py --no-host --carve 8 --carve-host   # ... and a carver that observes every 8 frames
+
+Under "carve" (with --carve K): frames.Carver (csrc/frames_carve.hip) observing every chunk of K frames after the Fuser
+added it, in both launch shapes; see carve_leg.
 """
 import argparse
 import json
@@ -86,6 +91,9 @@ def main():
     ap.add_argument("--track", type=int, default=0, metavar="K",
                     help="also update a frames.Tracker on the snapshot after every K frames (K divides --frames); see track_leg")
     ap.add_argument("--track-host", action="store_true", help="with --track and --no-host: run frames.TrackerHost all the same")
+    ap.add_argument("--carve", type=int, default=0, metavar="K",
+                    help="also observe every K frames with a frames.Carver after the Fuser added them (K divides --frames); see carve_leg")
+    ap.add_argument("--carve-host", action="store_true", help="with --carve and --no-host: run frames.CarverHost all the same")
     args = ap.parse_args()
     W, H = (int(v) for v in args.size.lower().split("x"))
 
@@ -218,7 +226,90 @@ def main():
         out["stream_vote"] = voter_leg(args, fr, dfr, labels, timed)
     if args.track:
         out["track"] = track_leg(args, dfr, timed)
+    if args.carve:
+        out["carve"] = carve_leg(args, fr, dfr, timed)
     print(json.dumps(out))
+
+
+def carve_leg(args, fr, dfr, timed):
+    """frames.Carver (csrc/frames_carve.hip) beside a Fuser fed --carve K frames at a time: after every add both launch
+    shapes observe the chunk (a carver each).  Reported: the device time of every observe from events (the snapshot and its
+    read-back included); gf_frames_visibility alone with the state update on the last chunk and the whole map, median of
+    --reps after a warm-up, per launch shape; Fuser.snapshot over every cell so far with and without keep=; the kept
+    shape's time against the least its algorithmic bytes allow at the HBM peak (the points, 12 bytes; the state read and
+    written and the three counts written, 36 bytes per cell; one depth value per probe that reaches the depth read);
+    FuserHost + CarverHost on the same chunks (wall clock of every observe) and whether state and keep agree."""
+    from geoformer_amd import _lib, frames
+    from geoformer_amd._lib import check, ptr, stream_ptr
+
+    lib = _lib.load()
+    F, K = args.frames, args.carve
+    if K < 1 or F % K:
+        raise SystemExit(f"--carve {K}: a divisor of --frames {F}")
+    dev = dfr.depth.device
+    cut = lambda f, a, b: f._replace(depth=f.depth[a:b], color=f.color[a:b], table=f.table[a:b])  # noqa: E731
+    kw = dict(cell=args.cell, stride=args.stride, near=0.1, far=10.0, edge=args.edge)
+    fu = frames.Fuser(**kw)
+    carvers = {v: frames.Carver(fu, variant=v) for v in (0, 1)}
+    per, cells = {0: [], 1: []}, []
+    for a in range(0, F, K):
+        part = cut(dfr, a, a + K)
+        cells.append(fu.add(part))
+        for v, c in carvers.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            c.observe(part)
+            e1.record()
+            torch.cuda.synchronize()
+            per[v].append(round(e0.elapsed_time(e1) * 1e3, 1))
+    ca = carvers[0]
+    keep = ca.keep()
+    same = all(torch.equal(x, y) for x, y in zip((ca._seen[:ca.cells], ca._free[:ca.cells], ca._score[:ca.cells]),
+                                                 (carvers[1]._seen[:ca.cells], carvers[1]._free[:ca.cells], carvers[1]._score[:ca.cells])))
+    M = fu.cells
+    res = {"chunk_frames": K, "variant_default": frames.CARVE_VARIANT, "cells": M, "dropped": int((~keep).sum()),
+           "band": ca.band, "observe_with_snapshot_us_per_point": per[0], "observe_with_snapshot_us_per_probe": per[1],
+           "shapes_agree": bool(same)}
+    # the library call alone: the last chunk against the whole map, the state updated in place on copies
+    xyz = fu.snapshot(1).xyz.contiguous()
+    inv = torch.from_numpy(frames.inverse_records(part)).to(dev)
+    table = torch.from_numpy(part.table).to(dev)
+    near, far, e, band, rel = (float(v) for v in ca._probe)
+    state = torch.stack([ca._seen[:M], ca._free[:M], ca._score[:M]]).contiguous()
+    out = torch.empty((3, M), dtype=torch.int32, device=dev)
+    codes = torch.empty((K, M), dtype=torch.uint8, device=dev)
+    H, W = part.depth.shape[1:]
+
+    def run(variant, with_codes=False):
+        check(lib.gf_frames_visibility(ptr(xyz), M, ptr(part.depth), int(part.depth.dtype == torch.float32), K, H, W,
+                                       part.depth_shift, ptr(table), ptr(inv), near, far, e, band, rel, ptr(out),
+                                       ptr(codes) if with_codes else None, ptr(state[0]), ptr(state[1]), ptr(state[2]),
+                                       *ca._rule, variant, stream_ptr()), "gf_frames_visibility")
+
+    res["visibility_us_per_point"], res["visibility_us_per_probe"] = timed(lambda: run(0)), timed(lambda: run(1))
+    res["visibility_us_per_point_again"] = timed(lambda: run(0))
+    run(0, True)
+    classes = torch.bincount(codes.reshape(-1).long(), minlength=5).tolist()
+    reads = sum(classes[1:])  # the probes that read a depth value
+    nbytes = M * (12 + 36) + reads * part.depth.element_size()
+    best = min(res["visibility_us_per_point"], res["visibility_us_per_probe"])
+    res.update(probes=K * M, classes=classes, bytes=nbytes, least_us_at_hbm_peak=round(nbytes / HBM_PEAK * 1e6, 2),
+               share_of_hbm_peak=round(nbytes / (best * 1e-6) / HBM_PEAK, 4))
+    every = torch.cat(cells)
+    res["snapshot_us"] = timed(lambda: fu.snapshot(1, every))
+    res["snapshot_keep_us"] = timed(lambda: fu.snapshot(1, every, keep=keep))
+    if args.carve_host or not args.no_host:
+        fh = frames.FuserHost(**kw)
+        ch, host_ms = frames.CarverHost(fh), []
+        for a in range(0, F, K):
+            part = cut(fr, a, a + K)
+            fh.add(part)
+            t0 = time.perf_counter()
+            ch.observe(part)
+            host_ms.append(round((time.perf_counter() - t0) * 1e3, 1))
+        res["carver_host_numpy_ms"] = host_ms
+        res["equal_to_numpy"] = bool(all((x == y).all() for x, y in zip(ca.state(), ch.state())) and torch.equal(keep.cpu(), ch.keep()))
+    return res
 
 
 def track_leg(args, dfr, timed):

@@ -37,6 +37,13 @@ default 1) and after the last one, and a frames.Tracker (csrc/frames_track.hip) 
 (--track-iou, --track-max-misses: its parameters).  The per-frame .npy then hold the track id of every pixel (-1 without
 a track or a point) and the .png its colour in render.instance_colors; <out>/tracks.npz holds the track table and
 "track" in the JSON line the counts.  Without --track the output is what it was.
+
+    python tools/predict_frames.py --frames scan.npz --chunk-frames 8 --carve --out out
+
+With --carve (only with --chunk-frames) a frames.Carver (csrc/frames_carve.hip) observes every chunk after it is added:
+a cell that later frames look through loses score, and cells at or below --carve-drop (default -2) are left out of the
+scene, of the lifted labels and of the tracker's points (--carve-band: the tolerance in metres, default three cells).
+"carve" under "stream" in the JSON line holds the counts.  Without --carve the output is what it was.
 """
 import argparse
 import json
@@ -76,6 +83,10 @@ def build_parser():
     ap.add_argument("--track-every", type=int, default=1, metavar="J", help="run the model after every J-th chunk (and the last)")
     ap.add_argument("--track-iou", type=float, default=0.3, help="frames.Tracker's iou")
     ap.add_argument("--track-max-misses", type=int, default=2, help="frames.Tracker's max_misses")
+    ap.add_argument("--carve", action="store_true",
+                    help="with --chunk-frames: observe every chunk and drop the cells that later frames look through")
+    ap.add_argument("--carve-band", type=float, default=None, metavar="B", help="frames.Carver's band in metres (three cells)")
+    ap.add_argument("--carve-drop", type=int, default=-2, metavar="D", help="drop cells whose score is at or below D")
     return ap
 
 
@@ -89,13 +100,15 @@ def lifted_labels(fused, label, instance, ignore, stride, min_votes=1, min_share
 
 
 def fuse_in_chunks(depth, K, pose, color, shift, args, label=None, instance=None, after_chunk=None):
-    """(Fused, {"chunk_frames", "adds", "cells", "table_slots", "rehashes"}, voters): the frames through a frames.Fuser,
+    """(Fused, {"chunk_frames", "adds", "cells", "table_slots", "rehashes"}, voters, keep): the frames through a frames.Fuser,
     --chunk-frames at a time.  Only one chunk's depth and colour are on the device at a time: the arrays stay in host
     memory (as np.load gave them) and are sliced per add.  The Fused is the one frames.fuse would return for all frames
     with origin=the Fuser's, so everything after it is the same.  With label and instance images, each chunk's go
     through two frames.Voter (csrc/frames_vote_stream.hip) beside the Fuser, one chunk of images on the device at a
     time; voters = (the Fuser, the semantic Voter, the instance Voter), what frames.lift_scene_stream takes (else None).
-    after_chunk(fu, cells so far, chunk number, last): called after every add (--track)."""
+    after_chunk(fu, cells so far, chunk number, last): called after every add (--track).  With --carve a frames.Carver
+    observes every chunk after its add; its keep() goes to after_chunk as keep=, restricts the snapshot and is returned
+    (what lift_scene_stream takes as keep=; None without --carve)."""
     from geoformer_amd import frames
 
     F, step = int(depth.shape[0]), int(args.chunk_frames)
@@ -107,19 +120,26 @@ def fuse_in_chunks(depth, K, pose, color, shift, args, label=None, instance=None
     if label is not None:
         voters = (fu, frames.Voter(args.label_ignore), frames.Voter(args.label_ignore))
     cells = []
+    carver = frames.Carver(fu, band=args.carve_band, drop=args.carve_drop) if getattr(args, "carve", False) else None
     for a in range(0, F, step):
         b = min(F, a + step)
         part = frames.make(depth[a:b], K if K.ndim == 1 else K[a:b], pose[a:b], None if color is None else color[a:b], shift)
         cells.append(fu.add(part))
+        if carver is not None:
+            carver.observe(part)
         if voters is not None:
             stride = None if tuple(cells[-1].shape) == tuple(label[a:b].shape) else args.stride
             voters[1].add(cells[-1], label[a:b], stride)
             voters[2].add(cells[-1], instance[a:b], stride)
         if after_chunk is not None:
-            after_chunk(fu, cells, len(cells), b == F)
-    fused = fu.snapshot(args.min_obs, torch.cat(cells))
-    return (fused, {"chunk_frames": step, "adds": len(cells), "cells": fu.cells, "table_slots": fu.slots, "rehashes": fu.rehashes},
-            voters)
+            after_chunk(fu, cells, len(cells), b == F, **({} if carver is None else {"keep": carver.keep()}))
+    stream = {"chunk_frames": step, "adds": len(cells), "cells": fu.cells, "table_slots": fu.slots, "rehashes": fu.rehashes}
+    if carver is None:
+        return fu.snapshot(args.min_obs, torch.cat(cells)), stream, voters, None
+    keep = carver.keep()
+    stream["carve"] = {"observed": carver.cells, "dropped": int((~keep).sum()), "band": carver.band,
+                       "drop": args.carve_drop}
+    return fu.snapshot(args.min_obs, torch.cat(cells), keep=keep), stream, voters, keep
 
 
 def score(model, name, raw, config_classes=0):
@@ -159,16 +179,16 @@ class Tracking:
     def __init__(self, args, name):
         from geoformer_amd import frames
 
-        self.args, self.name, self.model, self.runs, self.ms = args, name, None, 0, 0.0
+        self.args, self.name, self.model, self.runs, self.ms, self.keep = args, name, None, 0, 0.0, None
         self.tracker = frames.Tracker(iou=args.track_iou, max_misses=args.track_max_misses)
 
-    def __call__(self, fu, cells, number, last):
+    def __call__(self, fu, cells, number, last, keep=None):
         from geoformer_amd import batch_eval, frames
 
-        self.fu = fu
+        self.fu, self.keep = fu, keep
         if not last and number % self.args.track_every:
             return
-        raw, _ = fu.snapshot(self.args.min_obs, torch.cat(cells)).raw_scene()
+        raw, _ = fu.snapshot(self.args.min_obs, torch.cat(cells), keep=keep).raw_scene()
         if raw.shape[0] == 0:
             return
         if self.model is None:
@@ -176,7 +196,7 @@ class Tracking:
         np.random.seed(0)
         (_, labels), = batch_eval.label_batches(self.model, [(self.name, raw)], 1)
         t = time.perf_counter()
-        frames.track_scene(self.tracker, fu, labels, self.args.min_obs)
+        frames.track_scene(self.tracker, fu, labels, self.args.min_obs, keep=keep)
         torch.cuda.synchronize()
         self.ms += (time.perf_counter() - t) * 1e3
         self.runs += 1
@@ -185,7 +205,7 @@ class Tracking:
         """frame_outputs with the track id in place of the label id and the owner."""
         from geoformer_amd import frames, render
 
-        ids = self.tracker.labels(self.fu.kept(self.args.min_obs))
+        ids = self.tracker.labels(self.fu.kept(self.args.min_obs, self.keep))
         return frames.gather(fused, ids, fill=-1), frames.gather(fused, render.instance_colors(ids), fill=255)
 
 
@@ -211,6 +231,8 @@ def main():
 
     if args.track and not args.chunk_frames:
         ap.error("--track needs --chunk-frames")
+    if args.carve and not args.chunk_frames:
+        ap.error("--carve needs --chunk-frames")
     if args.track_every < 1:
         ap.error(f"--track-every {args.track_every} (>= 1)")
     name = os.path.splitext(os.path.basename(args.frames))[0]
@@ -231,7 +253,7 @@ def main():
         if args.chunk_frames:
             t = time.perf_counter()
             tracking = Tracking(args, name) if args.track else None
-            fused, stream, voters = fuse_in_chunks(depth, K, pose, color, shift, args, label, instance, tracking)
+            fused, stream, voters, keep = fuse_in_chunks(depth, K, pose, color, shift, args, label, instance, tracking)
         else:
             fr = frames.make(depth, K, pose, color, shift)
             t = time.perf_counter()
@@ -248,7 +270,7 @@ def main():
         try:
             t = time.perf_counter()
             if args.chunk_frames:  # the votes are in: only the snapshot and the scene's tail are left
-                sem, ins = frames.lift_scene_stream(*voters, args.min_obs, args.min_votes, args.min_share)
+                sem, ins = frames.lift_scene_stream(*voters, args.min_obs, args.min_votes, args.min_share, keep=keep)
             else:
                 sem, ins = lifted_labels(fused, label, instance, args.label_ignore, args.stride, args.min_votes, args.min_share)
             torch.cuda.synchronize()
