@@ -3,8 +3,8 @@
 // frames.CarverHost; see include/geoformer_hip.h for the arguments and every arithmetic step.
 //
 // A probe is one point in one frame: the point into the camera by the frame's inverse record, the pixel it falls into,
-// that pixel's depth (valid by the back-projection's own rule) against the point's, one of five classes.  fc_probe is
-// the one statement of it; both launch shapes call it, so they give the same bits.
+// that pixel's depth (valid by the back-projection's own rule, fs_depth_valid) against the point's, one of five
+// classes.  fc_probe is the one statement of it; both launch shapes call it, so they give the same bits.
 //
 // gf_frames_visibility, variant 0 (per point):  one launch.  k_fc_point: a thread per point loops over the frames; a
 //                         workgroup stages FC_STAGE frame records in LDS at a time; the three counts stay in registers;
@@ -18,20 +18,14 @@
 // k_fc_point order a workgroup's own LDS writes and reads; every thread of the workgroup reaches each of them); integer
 // atomics only; nothing is read back.
 #include "common.h"
+#include "frames_steps.h"
 
 namespace {
 
-typedef long long i64;
-
-constexpr int FC_THREADS = 256;
-constexpr int FC_STAGE = 16;            // frame records one workgroup of k_fc_point holds in LDS at a time
-constexpr int FC_RECORD = 16;           // {fx, fy, cx, cy, inv[9], t[3]}: what a probe reads of a frame
-constexpr int FC_TABLE = 16;            // gf_frames_record_floats(): asserted in gf_frames_visibility
-constexpr int FC_INV = 12;              // floats of an inverse record: inv row-major, then t
-constexpr int FC_MAX_FRAMES = 1 << 16;  // gf_frames_max_frames()
-constexpr int FC_MAX_SIDE = 1 << 13;    // gf_frames_max_side()
-constexpr int FC_MAX_POINTS = 1 << 29;  // gf_resample_max_points()
-constexpr int FC_MAX_ROWS = 32768;      // the most frame rows of k_fc_probe's grid: a row strides over the frames
+constexpr int FC_STAGE = 16;        // frame records one workgroup of k_fc_point holds in LDS at a time
+constexpr int FC_RECORD = 16;       // {fx, fy, cx, cy, inv[9], t[3]}: what a probe reads of a frame
+constexpr int FC_INV = 12;          // floats of an inverse record: inv row-major, then t
+constexpr int FC_MAX_ROWS = 32768;  // the most frame rows of k_fc_probe's grid: a row strides over the frames
 enum { FC_OUTSIDE = 0, FC_UNKNOWN = 1, FC_OCCLUDED = 2, FC_SEEN = 3, FC_FREE = 4 };
 constexpr int FC_INT_MAX = 2147483647;
 
@@ -50,7 +44,6 @@ template <class D>
 __device__ __forceinline__ float fc_depth(const FcImage& im, size_t at) {
     return __fdiv_rn((float)((const D*)im.depth)[at], im.shift);
 }
-__device__ __forceinline__ bool fc_in_range(const FcImage& im, float z) { return z >= im.near && z <= im.far; }
 
 // the class of point x in frame f, whose record is rec[FC_RECORD]; every operation rounded on its own
 template <class D, bool EDGE>
@@ -67,19 +60,9 @@ __device__ __forceinline__ int fc_probe(const FcImage& im, const float* rec, int
     if (!(fi >= 0.0f && fi < (float)im.W && fj >= 0.0f && fj < (float)im.H)) return FC_OUTSIDE;
     const int i = (int)fi, j = (int)fj;  // 0 <= i < W, 0 <= j < H: exact
     const size_t at = ((size_t)f * im.H + j) * im.W + i;
-    const float z = fc_depth<D>(im, at);
-    if (!fc_in_range(im, z)) return FC_UNKNOWN;
-    if (EDGE) {
-        const float lim = im.edge * z;
-        const bool inside[4] = {i > 0, i + 1 < im.W, j > 0, j + 1 < im.H};
-        const size_t nb[4] = {at - 1, at + 1, at - (size_t)im.W, at + (size_t)im.W};
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (inside[k]) {
-                const float zn = fc_depth<D>(im, nb[k]);
-                if (fc_in_range(im, zn) && fabsf(zn - z) > lim) return FC_UNKNOWN;
-            }
-    }
+    float z;
+    if (!fs_depth_valid<EDGE>([&](size_t a) { return fc_depth<D>(im, a); }, at, i, j, im.W, im.H, im.near, im.far, im.edge, &z))
+        return FC_UNKNOWN;
     const float tol = im.rel * z + im.band;
     if (zc < z - tol) return FC_FREE;
     if (zc > z + tol) return FC_OCCLUDED;
@@ -100,23 +83,23 @@ __device__ __forceinline__ void fc_update(const FcState& st, int p, int s, int f
 // record f of the two tables as a probe reads it
 __device__ __forceinline__ void fc_record(const float* __restrict__ table, const float* __restrict__ inv, int f, int k,
                                           float* out) {
-    out[k] = k < 4 ? table[(size_t)f * FC_TABLE + k] : inv[(size_t)f * FC_INV + (k - 4)];
+    out[k] = k < 4 ? table[(size_t)f * FS_RECORD + k] : inv[(size_t)f * FC_INV + (k - 4)];
 }
 
 template <class D, bool EDGE>
-__global__ __launch_bounds__(FC_THREADS) void k_fc_point(const float* __restrict__ xyz, int n, FcImage im, int F,
+__global__ __launch_bounds__(FS_THREADS) void k_fc_point(const float* __restrict__ xyz, int n, FcImage im, int F,
                                                          const float* __restrict__ table, const float* __restrict__ inv,
                                                          int32_t* __restrict__ out, unsigned char* __restrict__ codes,
                                                          FcState st) {
     __shared__ float s_rec[FC_STAGE][FC_RECORD];
-    const int p = blockIdx.x * FC_THREADS + threadIdx.x;  // n <= 2^29: fits
+    const int p = blockIdx.x * FS_THREADS + threadIdx.x;  // n <= 2^29: fits
     const bool on = p < n;
     float x0 = 0.0f, x1 = 0.0f, x2 = 0.0f;
     if (on) x0 = xyz[(size_t)p * 3], x1 = xyz[(size_t)p * 3 + 1], x2 = xyz[(size_t)p * 3 + 2];
     int seen = 0, free = 0, occ = 0;
     for (int f0 = 0; f0 < F; f0 += FC_STAGE) {  // (every thread of the workgroup takes every round)
         const int nf = min(FC_STAGE, F - f0);
-        if (threadIdx.x < nf * FC_RECORD)  // FC_STAGE FC_RECORD == FC_THREADS: one float per thread
+        if (threadIdx.x < nf * FC_RECORD)  // FC_STAGE FC_RECORD == FS_THREADS: one float per thread
             fc_record(table, inv, f0 + threadIdx.x / FC_RECORD, threadIdx.x % FC_RECORD, s_rec[threadIdx.x / FC_RECORD]);
         __syncthreads();
         if (on)
@@ -137,10 +120,10 @@ __global__ __launch_bounds__(FC_THREADS) void k_fc_point(const float* __restrict
 }
 
 template <class D, bool EDGE>
-__global__ __launch_bounds__(FC_THREADS) void k_fc_probe(const float* __restrict__ xyz, int n, FcImage im, int F,
+__global__ __launch_bounds__(FS_THREADS) void k_fc_probe(const float* __restrict__ xyz, int n, FcImage im, int F,
                                                          const float* __restrict__ table, const float* __restrict__ inv,
                                                          int32_t* __restrict__ out, unsigned char* __restrict__ codes) {
-    const int p = blockIdx.x * FC_THREADS + threadIdx.x;
+    const int p = blockIdx.x * FS_THREADS + threadIdx.x;
     if (p >= n) return;
     const float x0 = xyz[(size_t)p * 3], x1 = xyz[(size_t)p * 3 + 1], x2 = xyz[(size_t)p * 3 + 2];
     for (int f = blockIdx.y; f < F; f += gridDim.y) {  // f: the same for the whole workgroup
@@ -154,21 +137,21 @@ __global__ __launch_bounds__(FC_THREADS) void k_fc_probe(const float* __restrict
     }
 }
 
-__global__ __launch_bounds__(FC_THREADS) void k_fc_finish(const int32_t* __restrict__ out, int n, FcState st) {
-    const int p = blockIdx.x * FC_THREADS + threadIdx.x;
+__global__ __launch_bounds__(FS_THREADS) void k_fc_finish(const int32_t* __restrict__ out, int n, FcState st) {
+    const int p = blockIdx.x * FS_THREADS + threadIdx.x;
     if (p < n) fc_update(st, p, out[p], out[(size_t)n + p]);
 }
 
 template <class D, bool EDGE>
 void fc_launch(const float* xyz, int n, const FcImage& im, int F, const float* table, const float* inv, int32_t* out,
                unsigned char* codes, const FcState& st, int variant, hipStream_t s) {
-    const int g = gf_div_up(n, FC_THREADS);
+    const int g = gf_div_up(n, FS_THREADS);
     if (variant == 0) {
-        hipLaunchKernelGGL((k_fc_point<D, EDGE>), dim3(g), dim3(FC_THREADS), 0, s, xyz, n, im, F, table, inv, out, codes, st);
+        hipLaunchKernelGGL((k_fc_point<D, EDGE>), dim3(g), dim3(FS_THREADS), 0, s, xyz, n, im, F, table, inv, out, codes, st);
     } else {
-        hipLaunchKernelGGL((k_fc_probe<D, EDGE>), dim3(g, F < FC_MAX_ROWS ? F : FC_MAX_ROWS), dim3(FC_THREADS), 0, s, xyz, n, im,
+        hipLaunchKernelGGL((k_fc_probe<D, EDGE>), dim3(g, F < FC_MAX_ROWS ? F : FC_MAX_ROWS), dim3(FS_THREADS), 0, s, xyz, n, im,
                            F, table, inv, out, codes);
-        if (st.score) hipLaunchKernelGGL(k_fc_finish, dim3(g), dim3(FC_THREADS), 0, s, out, n, st);
+        if (st.score) hipLaunchKernelGGL(k_fc_finish, dim3(g), dim3(FS_THREADS), 0, s, out, n, st);
     }
 }
 
@@ -176,11 +159,11 @@ bool fc_finite(float v) { return v == v && v >= -3.402823466e38f && v <= 3.40282
 
 }  // namespace
 
-static_assert(FC_STAGE * FC_RECORD == FC_THREADS, "k_fc_point stages one float per thread");
+static_assert(FC_STAGE * FC_RECORD == FS_THREADS, "k_fc_point stages one float per thread");
 
 extern "C" int gf_frames_carve_stage_frames(void) { return FC_STAGE; }
-extern "C" int gf_frames_carve_threads(void) { return FC_THREADS; }
-extern "C" int gf_frames_carve_max_points(void) { return FC_MAX_POINTS; }
+extern "C" int gf_frames_carve_threads(void) { return FS_THREADS; }
+extern "C" int gf_frames_carve_max_points(void) { return FS_MAX_POINTS; }
 extern "C" int gf_frames_visibility_variants(void) { return 2; }
 
 extern "C" int gf_frames_visibility(const float* xyz, int n, const void* depth, int dtype, int F, int H, int W,
@@ -188,13 +171,11 @@ extern "C" int gf_frames_visibility(const float* xyz, int n, const void* depth, 
                                     float band, float rel, int32_t* out, unsigned char* codes, int32_t* seen, int32_t* free,
                                     int32_t* score, int hit, int miss, int floor, int ceil, int variant, void* stream) {
     const char* who = "gf_frames_visibility";
-    GF_CHECK_ARG(n >= 0 && n <= FC_MAX_POINTS && gf_resample_max_points() == FC_MAX_POINTS, "%s: n = %d points (0 to %d)", who, n,
-                 FC_MAX_POINTS);
+    GF_CHECK_ARG(n >= 0 && n <= FS_MAX_POINTS && gf_resample_max_points() == FS_MAX_POINTS, "%s: n = %d points (0 to %d)", who, n,
+                 FS_MAX_POINTS);
     GF_CHECK_ARG(dtype == 0 || dtype == 1, "%s: dtype = %d (0: uint16, 1: float32)", who, dtype);
-    GF_CHECK_ARG(F >= 1 && F <= FC_MAX_FRAMES && H >= 1 && H <= FC_MAX_SIDE && W >= 1 && W <= FC_MAX_SIDE &&
-                     gf_frames_max_frames() == FC_MAX_FRAMES && gf_frames_max_side() == FC_MAX_SIDE &&
-                     gf_frames_record_floats() == FC_TABLE,
-                 "%s: %d frames of %d x %d pixels (1 to %d frames, each side 1 to %d)", who, F, W, H, FC_MAX_FRAMES, FC_MAX_SIDE);
+    GF_CHECK_ARG(F >= 1 && F <= FS_MAX_FRAMES && H >= 1 && H <= FS_MAX_SIDE && W >= 1 && W <= FS_MAX_SIDE,
+                 "%s: %d frames of %d x %d pixels (1 to %d frames, each side 1 to %d)", who, F, W, H, FS_MAX_FRAMES, FS_MAX_SIDE);
     GF_CHECK_ARG(depth_shift > 0.0f && fc_finite(depth_shift), "%s: depth_shift = %g (positive and finite)", who,
                  (double)depth_shift);
     GF_CHECK_ARG(near == near && far == far, "%s: near = %g, far = %g (numbers)", who, (double)near, (double)far);

@@ -8,58 +8,36 @@
 //   k_fm_claim              one thread per point: the cell key by k_rs_insert's arithmetic, the reach by k_fr_sums'
 //                           float64 comparison; the key found or claimed (slot read first, CAS on an empty slot only);
 //                           a slot that has no number takes an integer atomicMin of the point index (read first)
-//   k_fm_count, k_fm_top, k_fm_emit<FmNumber>   exclusive scan in POINT order of "my slot has no number and I am its
+//   k_fs_count, k_fs_top, k_fs_emit<FmNumber>   exclusive scan in POINT order of "my slot has no number and I am its
 //                           first point": a new cell's first point writes id = M + rank
 //   k_fm_cell_of            one thread per point: cell_of = ids[slot]
 // gf_frames_map_accumulate  k_fm_add<AGG>: 64-bit integer atomic adds of the fixed-point coordinates and the colours, a
 //                           32-bit one of the count; runs of equal cells among adjacent lanes added in the wave first
-// gf_frames_map_means       k_fm_count, k_fm_top, k_fm_emit<FmMean>: the kept cells renumbered in order, their means
+// gf_frames_map_means       k_fs_count, k_fs_top, k_fs_emit<FsMean>: the kept cells renumbered in order, their means
 // gf_frames_map_lookup      one launch, out = table[index] or -1; an index outside the table raises a flag
 //
-// The compaction (count / top / emit: a ballot per wave kept as a mask word, one workgroup scanning the chunk counts
-// 256 at a time with a carry, the row of an element from popcounts) is frames.hip's, restated here because that file's
-// kernels must keep their ISA; a later same-ISA refactor should share the three kernels through a header.  No
-// workgroup waits for another, there is no look-back and no spin.
+// The compaction (k_fs_count / k_fs_top / k_fs_emit) and the means are frames_steps.h's, and so is the termination
+// argument of the probing ("a key found or claimed").  k_fm_claim is unbounded with slots >= 2 (M + n): the table holds
+// at most M + n keys.  k_fm_move: the new table has at least as many slots as there are numbered cells, all of distinct
+// keys.
 //
-// Termination of k_fm_claim.  With slots >= 2 (M + n) the table is never more than half full (at most M + n keys), so a
-// probe always meets its own key or an empty slot: unbounded, as in k_rs_insert.  With fewer slots (`bounded`) a thread
-// gives up after FM_MAX_PROBES probes and raises the overflow word.  k_fm_move: the new table has at least as many slots
-// as there are numbered cells, all of distinct keys.
-//
-// A failed insert.  k_fm_emit<FmNumber> and k_fm_cell_of read the three failure words first and return when one is set
+// A failed insert.  k_fs_emit<FmNumber> and k_fm_cell_of read the three failure words first and return when one is set
 // (every thread reads the same words: the branch is uniform), so no id is written; count and sums are not touched by
 // the insert at all.  What remains are claimed keys without a number, which the rehash drops.
 #include "common.h"
+#include "frames_steps.h"
 
 namespace {
 
-typedef unsigned long long u64;
-typedef long long i64;
-
-constexpr int FM_THREADS = 256;
-constexpr int FM_CHUNK = 2048;          // gf_frames_default_chunk(): asserted in gf_frames_map_insert
-constexpr int FM_MAX_CHUNK = 1 << 16;
-constexpr int FM_MAX_POINTS = 1 << 29;  // gf_resample_max_points(): asserted in gf_frames_map_insert
 constexpr int FM_AXIS_BITS = 21;
-constexpr int FM_MAX_PROBES = 128;
 constexpr i64 FM_MIN_SLOTS = 64;
 constexpr i64 FM_MAX_SLOTS = 1ll << 31;
 constexpr i64 FM_MAX_PIXELS = 2147483647ll;  // every count fits an int32, every id too
-constexpr int FM_MAX_CELLS = 2147483647 - FM_MAX_CHUNK;  // the cells gf_frames_map_means indexes with ints
+constexpr int FM_MAX_CELLS = 2147483647 - FS_MAX_CHUNK;  // the cells gf_frames_map_means indexes with ints
 constexpr int FM_NO_POINT = 2147483647;  // `first` of a slot no point of the current call has claimed
-constexpr u64 FM_EMPTY = 0xffffffffffffffffull;
-constexpr double FM_UNITS = 1048576.0;  // fixed-point units per metre
-constexpr double FM_REACH = 4096.0;     // q < 2^32: 2^31 - 1 pixels sum below 2^63
+constexpr double FM_REACH = 4096.0;      // q < 2^32: 2^31 - 1 pixels sum below 2^63
 
-template <class T>
-__device__ __forceinline__ T fm_peek(const T* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ unsigned fm_hash(u64 key, unsigned mask) {
-    return (unsigned)((key * 0x9E3779B97F4A7C15ull) >> 32) & mask;
-}
-bool fm_chunk_ok(int chunk) { return chunk == 0 || (chunk >= 64 && chunk <= FM_MAX_CHUNK && chunk % 64 == 0); }
-bool fm_slots_ok(i64 slots) { return slots >= FM_MIN_SLOTS && slots <= FM_MAX_SLOTS && (slots & (slots - 1)) == 0; }
+bool fm_slots_ok(i64 slots) { return fs_slots_ok(slots, FM_MIN_SLOTS, FM_MAX_SLOTS); }
 
 struct FmTable {
     u64* keys;
@@ -68,118 +46,30 @@ struct FmTable {
 };
 
 // ------------------------------------------------------------------------------------------------------------------
-// ordered compaction: frames.hip's k_fr_count / k_fr_top / k_fr_emit, restated
-// ------------------------------------------------------------------------------------------------------------------
-struct FmScratch {
-    u64* masks;   // [ceil(T / 64)]
-    int* bcount;  // [nb]
-    int* boff;    // [nb]
-};
-int fm_nb(i64 T, int chunk) { return (int)((T + chunk - 1) / chunk); }
-size_t fm_scan_bytes(i64 T, int chunk) { return (size_t)((T + 63) / 64) * 8 + (size_t)fm_nb(T, chunk) * 8 + 64; }
-FmScratch fm_carve(void* scratch, i64 T, int chunk) {
-    FmScratch s;
-    s.masks = (u64*)scratch;
-    s.bcount = (int*)(s.masks + (T + 63) / 64);
-    s.boff = s.bcount + fm_nb(T, chunk);
-    return s;
-}
-
-// T <= 2^31 - 1 - 2^16 and chunk <= 2^16: base + chunk fits an int
-template <class Pred>
-__global__ __launch_bounds__(FM_THREADS) void k_fm_count(Pred pred, int T, int chunk, FmScratch s) {
-    __shared__ int s_cnt[FM_THREADS / 64];
-    const int base = blockIdx.x * chunk, end = min(T, base + chunk);
-    int cnt = 0;
-    for (int t0 = base + (threadIdx.x & ~63); t0 < end; t0 += FM_THREADS) {  // t0: wave-uniform, a multiple of 64
-        const int t = t0 + (threadIdx.x & 63);
-        const u64 m = __ballot(t < end && pred(t));
-        if ((threadIdx.x & 63) == 0) s.masks[t0 >> 6] = m;
-        cnt += __popcll(m);
-    }
-    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int c = 0;
-#pragma unroll
-        for (int w = 0; w < FM_THREADS / 64; ++w) c += s_cnt[w];
-        s.bcount[blockIdx.x] = c;
-    }
-}
-
-// *total_out = add + the number of flagged elements
-__global__ __launch_bounds__(SCAN_THREADS) void k_fm_top(FmScratch s, int nb, int add, int32_t* __restrict__ total_out) {
-    int carry = 0;  // (every thread adds the same totals)
-    for (int base = 0; base < nb; base += SCAN_THREADS) {
-        const int i = base + threadIdx.x;
-        int total;
-        const int ex = block_excl_scan(i < nb ? s.bcount[i] : 0, &total);
-        if (i < nb) s.boff[i] = carry + ex;
-        carry += total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total_out = add + carry;
-}
-
-template <class Emit>
-__global__ __launch_bounds__(FM_THREADS) void k_fm_emit(Emit emit, int T, int chunk, FmScratch s) {
-    if (emit.off()) return;  // (the same words for every thread)
-    const int base = blockIdx.x * chunk, end = min(T, base + chunk);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int running = s.boff[blockIdx.x];
-    for (int r0 = base; r0 < end; r0 += FM_THREADS) {  // the round's four words, read by every wave
-        int before = running;
-        u64 mine = 0;
-#pragma unroll
-        for (int w = 0; w < FM_THREADS / 64; ++w) {
-            const int t0 = r0 + w * 64;
-            const u64 m = t0 < end ? s.masks[t0 >> 6] : 0;
-            if (w < wave) before += __popcll(m);
-            if (w == wave) mine = m;
-            running += __popcll(m);
-        }
-        const int t = r0 + threadIdx.x;
-        if (t < end) {
-            const bool on = (mine >> lane) & 1;
-            emit(t, on ? before + __popcll(mine & ((1ull << lane) - 1)) : -1);
-        }
-    }
-}
-
-template <class Pred, class Emit>
-void fm_compact(const Pred& pred, const Emit& emit, int T, int chunk, void* scratch, int add, int32_t* total, hipStream_t st) {
-    const FmScratch s = fm_carve(scratch, T, chunk);
-    const int nb = fm_nb(T, chunk);
-    hipLaunchKernelGGL(k_fm_count<Pred>, dim3(nb), dim3(FM_THREADS), 0, st, pred, T, chunk, s);
-    hipLaunchKernelGGL(k_fm_top, dim3(1), dim3(SCAN_THREADS), 0, st, s, nb, add, total);
-    hipLaunchKernelGGL(k_fm_emit<Emit>, dim3(nb), dim3(FM_THREADS), 0, st, emit, T, chunk, s);
-}
-
-// ------------------------------------------------------------------------------------------------------------------
 // rehash
 // ------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(FM_THREADS) void k_fm_clear(FmTable tab, i64 slots) {
-    const i64 stride = (i64)gridDim.x * FM_THREADS;
-    for (i64 s = (i64)blockIdx.x * FM_THREADS + threadIdx.x; s < slots; s += stride) {
-        tab.keys[s] = FM_EMPTY;
+__global__ __launch_bounds__(FS_THREADS) void k_fm_clear(FmTable tab, i64 slots) {
+    const i64 stride = (i64)gridDim.x * FS_THREADS;
+    for (i64 s = (i64)blockIdx.x * FS_THREADS + threadIdx.x; s < slots; s += stride) {
+        tab.keys[s] = FS_EMPTY;
         tab.ids[s] = -1;
         tab.first[s] = FM_NO_POINT;
     }
 }
 
 // the new table holds at least one slot per numbered cell and the keys are distinct: a free slot is always found
-__global__ __launch_bounds__(FM_THREADS) void k_fm_move(const u64* __restrict__ old_keys, const int32_t* __restrict__ old_ids,
+__global__ __launch_bounds__(FS_THREADS) void k_fm_move(const u64* __restrict__ old_keys, const int32_t* __restrict__ old_ids,
                                                         i64 old_slots, FmTable tab) {
-    const i64 stride = (i64)gridDim.x * FM_THREADS;
-    for (i64 s = (i64)blockIdx.x * FM_THREADS + threadIdx.x; s < old_slots; s += stride) {
+    const i64 stride = (i64)gridDim.x * FS_THREADS;
+    for (i64 s = (i64)blockIdx.x * FS_THREADS + threadIdx.x; s < old_slots; s += stride) {
         const int id = old_ids[s];
         const u64 key = old_keys[s];
-        if (id < 0 || key == FM_EMPTY) continue;  // empty, or claimed by a failed insert and never numbered
-        unsigned slot = fm_hash(key, tab.mask);
+        if (id < 0 || key == FS_EMPTY) continue;  // empty, or claimed by a failed insert and never numbered
+        unsigned slot = fs_hash(key, tab.mask);
         while (true) {
-            u64 old = fm_peek(&tab.keys[slot]);
-            if (old == FM_EMPTY) old = atomicCAS(&tab.keys[slot], FM_EMPTY, key);
-            if (old == FM_EMPTY) break;  // (old == key cannot happen: the old table holds a key once)
+            u64 old = fs_peek(&tab.keys[slot]);
+            if (old == FS_EMPTY) old = atomicCAS(&tab.keys[slot], FS_EMPTY, key);
+            if (old == FS_EMPTY) break;  // (old == key cannot happen: the old table holds a key once)
             slot = (slot + 1) & tab.mask;
         }
         tab.ids[slot] = id;
@@ -189,10 +79,10 @@ __global__ __launch_bounds__(FM_THREADS) void k_fm_move(const u64* __restrict__ 
 // ------------------------------------------------------------------------------------------------------------------
 // insert
 // ------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(FM_THREADS) void k_fm_claim(const float* __restrict__ xyz, int n, float cell,
+__global__ __launch_bounds__(FS_THREADS) void k_fm_claim(const float* __restrict__ xyz, int n, float cell,
                                                          const float* __restrict__ origin, FmTable tab, int bounded,
                                                          int32_t* __restrict__ slot_of, int32_t* __restrict__ words) {
-    const int i = blockIdx.x * FM_THREADS + threadIdx.x;
+    const int i = blockIdx.x * FS_THREADS + threadIdx.x;
     if (i >= n) return;
     const float lim = (float)(1 << FM_AXIS_BITS);
     float c[3];
@@ -213,22 +103,20 @@ __global__ __launch_bounds__(FM_THREADS) void k_fm_claim(const float* __restrict
         return;
     }
     const u64 key = (u64)(unsigned)c[0] | ((u64)(unsigned)c[1] << FM_AXIS_BITS) | ((u64)(unsigned)c[2] << (2 * FM_AXIS_BITS));
-    unsigned slot = fm_hash(key, tab.mask);
-    // A key is written once and a minimum only falls: each word is read first and the atomic issued only when it can
-    // change something; a stale read costs an atomic, never loses one.
-    for (int probes = 1;; ++probes) {
-        u64 old = fm_peek(&tab.keys[slot]);
-        if (old == FM_EMPTY) old = atomicCAS(&tab.keys[slot], FM_EMPTY, key);
-        if (old == FM_EMPTY || old == key) break;
-        if (bounded && probes >= FM_MAX_PROBES) {  // fewer than 2 (M + n) slots: give up, the caller rehashes
+    unsigned slot = fs_hash(key, tab.mask);
+    for (int probes = 1;; ++probes) {  // (frames_steps.h, "a key found or claimed")
+        u64 old = fs_peek(&tab.keys[slot]);
+        if (old == FS_EMPTY) old = atomicCAS(&tab.keys[slot], FS_EMPTY, key);
+        if (old == FS_EMPTY || old == key) break;
+        if (bounded && probes >= FS_MAX_PROBES) {  // fewer than 2 (M + n) slots: give up, the caller rehashes
             words[2] = 1;
             slot_of[i] = -1;
             return;
         }
         slot = (slot + 1) & tab.mask;  // slots >= 2 (M + n) otherwise: a free slot is always found
     }
-    // ids change only in k_fm_emit<FmNumber>, a later launch: a plain read
-    if (tab.ids[slot] < 0 && i < fm_peek(&tab.first[slot])) atomicMin(&tab.first[slot], i);
+    // ids change only in k_fs_emit<FmNumber>, a later launch: a plain read.  The minimum only falls: read first
+    if (tab.ids[slot] < 0 && i < fs_peek(&tab.first[slot])) atomicMin(&tab.first[slot], i);
     slot_of[i] = (int)slot;
 }
 
@@ -247,29 +135,33 @@ struct FmNumber {
     int32_t* ids;
     const int32_t* words;
     int M;
+    struct State {};
     __device__ bool off() const { return fm_failed(words); }
-    __device__ void operator()(int i, int rank) const {
+    __device__ void finish(const State&) const {}
+    __device__ void operator()(int i, int rank, State&) const {
         if (rank >= 0) ids[slot_of[i]] = M + rank;  // one writer per slot: the slot's first point
     }
 };
 
-__global__ __launch_bounds__(FM_THREADS) void k_fm_cell_of(const int32_t* __restrict__ slot_of, const int32_t* __restrict__ ids,
+__global__ __launch_bounds__(FS_THREADS) void k_fm_cell_of(const int32_t* __restrict__ slot_of, const int32_t* __restrict__ ids,
                                                            int n, const int32_t* __restrict__ words,
                                                            int32_t* __restrict__ cell_of) {
     if (fm_failed(words)) return;
-    const int i = blockIdx.x * FM_THREADS + threadIdx.x;
+    const int i = blockIdx.x * FS_THREADS + threadIdx.x;
     if (i < n) cell_of[i] = ids[slot_of[i]];  // no flag: every slot_of is a slot, every claimed slot has its number
 }
 
 // ------------------------------------------------------------------------------------------------------------------
 // accumulate
 // ------------------------------------------------------------------------------------------------------------------
+// k_fr_sums' body (frames.hip) with the count, kept written out in both: as one inlined function the <true>
+// instantiations need 41 VGPRs instead of 32 (see there)
 template <bool AGG>
-__global__ __launch_bounds__(FM_THREADS) void k_fm_add(const float* __restrict__ xyz, const unsigned char* __restrict__ rgb,
+__global__ __launch_bounds__(FS_THREADS) void k_fm_add(const float* __restrict__ xyz, const unsigned char* __restrict__ rgb,
                                                        const int32_t* __restrict__ cell_of, int n, int M,
                                                        const float* __restrict__ origin, int32_t* __restrict__ count,
                                                        i64* __restrict__ sums, int32_t* __restrict__ flag) {
-    const int p = blockIdx.x * FM_THREADS + threadIdx.x, lane = threadIdx.x & 63;
+    const int p = blockIdx.x * FS_THREADS + threadIdx.x, lane = threadIdx.x & 63;
     int cell = -1;
     i64 v[6] = {0, 0, 0, 0, 0, 0};
     if (p < n) {
@@ -279,7 +171,7 @@ __global__ __launch_bounds__(FM_THREADS) void k_fm_add(const float* __restrict__
         for (int a = 0; a < 3; ++a) {
             const double e = (double)xyz[(size_t)p * 3 + a] - (double)origin[a];
             ok = ok && e >= 0.0 && e < FM_REACH;
-            v[a] = ok ? (i64)floor(e * FM_UNITS) : 0;
+            v[a] = ok ? (i64)floor(e * FS_UNITS) : 0;
             v[3 + a] = rgb[(size_t)p * 3 + a];
         }
         if (!ok) {
@@ -318,42 +210,11 @@ __global__ __launch_bounds__(FM_THREADS) void k_fm_add(const float* __restrict__
     }
 }
 
-// ------------------------------------------------------------------------------------------------------------------
-// means
-// ------------------------------------------------------------------------------------------------------------------
-struct FmKept {
-    const int32_t* count;
-    int min_obs;
-    __device__ bool operator()(int c) const { return count[c] >= min_obs; }
-};
-
-struct FmMean {
-    const i64* sums;
-    const int32_t* count;
-    const float* origin;
-    float* xyz_out;
-    unsigned char* rgb_out;
-    int32_t *count_out, *new_id;
-    __device__ bool off() const { return false; }
-    __device__ void operator()(int c, int row) const {
-        new_id[c] = row;
-        if (row < 0) return;
-        const int cnt = count[c];  // >= min_obs >= 1
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const double mean = ((double)sums[(size_t)c * 6 + a] / (double)cnt) * (1.0 / FM_UNITS);
-            xyz_out[(size_t)row * 3 + a] = (float)((double)origin[a] + mean);  // row < m <= M
-            rgb_out[(size_t)row * 3 + a] = (unsigned char)((sums[(size_t)c * 6 + 3 + a] + cnt / 2) / cnt);
-        }
-        count_out[row] = cnt;
-    }
-};
-
 // an index outside [-1, len) reads nothing, gives -1 and raises the flag
-__global__ __launch_bounds__(FM_THREADS) void k_fm_lookup(const int32_t* __restrict__ index, i64 T,
+__global__ __launch_bounds__(FS_THREADS) void k_fm_lookup(const int32_t* __restrict__ index, i64 T,
                                                           const int32_t* __restrict__ table, int len, int32_t* __restrict__ out,
                                                           int32_t* __restrict__ flag) {
-    const i64 t = (i64)blockIdx.x * FM_THREADS + threadIdx.x;
+    const i64 t = (i64)blockIdx.x * FS_THREADS + threadIdx.x;
     if (t >= T) return;
     const int p = index[t];
     const bool in = p >= 0 && p < len;
@@ -361,23 +222,15 @@ __global__ __launch_bounds__(FM_THREADS) void k_fm_lookup(const int32_t* __restr
     if (!in && p != -1 && flag) *flag = 1;
 }
 
-int fm_blocks(i64 work) {  // workgroups that stride over `work` elements: at most 4096
-    const i64 g = (work + FM_THREADS - 1) / FM_THREADS;
-    return (int)(g < 4096 ? (g > 0 ? g : 1) : 4096);
-}
-
 }  // namespace
 
-extern "C" int gf_frames_map_max_probes(void) { return FM_MAX_PROBES; }
+extern "C" int gf_frames_map_max_probes(void) { return FS_MAX_PROBES; }
 extern "C" double gf_frames_map_reach(void) { return FM_REACH; }
 extern "C" long long gf_frames_map_max_pixels(void) { return FM_MAX_PIXELS; }
 
 extern "C" long long gf_frames_map_default_slots(long long M, long long T) {
     if (M < 0 || M > FM_MAX_PIXELS || T < 0 || T > FM_MAX_PIXELS) return 0;
-    const i64 want = 4 * M > T / 8 ? 4 * M : T / 8;
-    i64 p = FM_MIN_SLOTS;
-    while (p < want && p < FM_MAX_SLOTS) p <<= 1;
-    return p;
+    return fs_default_slots(M, T, FM_MIN_SLOTS, FM_MAX_SLOTS);
 }
 
 extern "C" int gf_frames_map_rehash(const unsigned long long* old_keys, const int32_t* old_ids, long long old_slots, int cells,
@@ -395,43 +248,44 @@ extern "C" int gf_frames_map_rehash(const unsigned long long* old_keys, const in
     GF_CHECK_ARG(old_slots == 0 || (old_keys != new_keys && old_ids != new_ids), "gf_frames_map_rehash: the tables overlap");
     hipStream_t st = (hipStream_t)stream;
     const FmTable tab = {new_keys, new_ids, new_first, (unsigned)(new_slots - 1)};
-    hipLaunchKernelGGL(k_fm_clear, dim3(fm_blocks(new_slots)), dim3(FM_THREADS), 0, st, tab, (i64)new_slots);
+    hipLaunchKernelGGL(k_fm_clear, dim3(fs_blocks(new_slots, 4096)), dim3(FS_THREADS), 0, st, tab, (i64)new_slots);
     if (old_slots > 0 && cells > 0)
-        hipLaunchKernelGGL(k_fm_move, dim3(fm_blocks(old_slots)), dim3(FM_THREADS), 0, st, old_keys, old_ids, (i64)old_slots, tab);
+        hipLaunchKernelGGL(k_fm_move, dim3(fs_blocks(old_slots, 4096)), dim3(FS_THREADS), 0, st, old_keys, old_ids,
+                           (i64)old_slots, tab);
     GF_CHECK_LAUNCH("gf_frames_map_rehash");
     return GF_OK;
 }
 
 extern "C" size_t gf_frames_map_insert_scratch_bytes(int n, int chunk) {
-    if (n < 0 || n > FM_MAX_POINTS || !fm_chunk_ok(chunk)) return 0;
-    return (size_t)(n + 2) / 2 * 8 + fm_scan_bytes(n, chunk ? chunk : FM_CHUNK);  // slot_of [n] (8-byte granules), the scan
+    if (n < 0 || n > FS_MAX_POINTS || !fs_chunk_ok(chunk)) return 0;
+    return (size_t)(n + 2) / 2 * 8 + fs_scan_bytes(n, chunk ? chunk : FS_CHUNK);  // slot_of [n] (8-byte granules), the scan
 }
 
 extern "C" int gf_frames_map_insert(const float* xyz, int n, float cell, const float* origin, unsigned long long* keys,
                                     int32_t* ids, int32_t* first, long long slots, int M, int chunk, void* scratch,
                                     int32_t* cell_of, int32_t* d_words, void* stream) {
-    GF_CHECK_ARG(n >= 0 && n <= FM_MAX_POINTS && gf_resample_max_points() == FM_MAX_POINTS,
-                 "gf_frames_map_insert: n = %d points (0 to %d)", n, FM_MAX_POINTS);
+    GF_CHECK_ARG(n >= 0 && n <= FS_MAX_POINTS && gf_resample_max_points() == FS_MAX_POINTS,
+                 "gf_frames_map_insert: n = %d points (0 to %d)", n, FS_MAX_POINTS);
     GF_CHECK_ARG(M >= 0 && (i64)M + n <= FM_MAX_PIXELS,
                  "gf_frames_map_insert: M = %d cells and n = %d points (M >= 0, M + n <= %lld)", M, n, FM_MAX_PIXELS);
     GF_CHECK_ARG(cell > 0.0f && cell <= 3.402823466e38f, "gf_frames_map_insert: cell = %g (positive and finite)", (double)cell);
     GF_CHECK_ARG(fm_slots_ok(slots), "gf_frames_map_insert: slots = %lld (a power of two from %lld to %lld)", slots, FM_MIN_SLOTS,
                  FM_MAX_SLOTS);
-    GF_CHECK_ARG(fm_chunk_ok(chunk) && gf_frames_default_chunk() == FM_CHUNK,
-                 "gf_frames_map_insert: chunk = %d (0, or a multiple of 64 from 64 to %d)", chunk, FM_MAX_CHUNK);
+    GF_CHECK_ARG(fs_chunk_ok(chunk), "gf_frames_map_insert: chunk = %d (0, or a multiple of 64 from 64 to %d)", chunk,
+                 FS_MAX_CHUNK);
     if (n == 0) return GF_OK;
     GF_CHECK_ARG(xyz && origin && keys && ids && first && scratch && cell_of && d_words,
                  "gf_frames_map_insert: NULL xyz, origin, keys, ids, first, scratch, cell_of or d_words");
     hipStream_t st = (hipStream_t)stream;
-    if (!chunk) chunk = FM_CHUNK;
+    if (!chunk) chunk = FS_CHUNK;
     const FmTable tab = {keys, ids, first, (unsigned)(slots - 1)};
     int32_t* slot_of = (int32_t*)scratch;
     void* rest = (char*)scratch + (size_t)(n + 2) / 2 * 8;
-    const int bounded = slots < 2 * ((i64)M + n), g = gf_div_up(n, FM_THREADS);
+    const int bounded = slots < 2 * ((i64)M + n), g = gf_div_up(n, FS_THREADS);
     GF_TRY(hipMemsetAsync(d_words, 0, 4 * 4, st));
-    hipLaunchKernelGGL(k_fm_claim, dim3(g), dim3(FM_THREADS), 0, st, xyz, n, cell, origin, tab, bounded, slot_of, d_words);
-    fm_compact(FmIsNew{slot_of, ids, first}, FmNumber{slot_of, ids, d_words, M}, n, chunk, rest, M, d_words, st);
-    hipLaunchKernelGGL(k_fm_cell_of, dim3(g), dim3(FM_THREADS), 0, st, slot_of, ids, n, d_words, cell_of);
+    hipLaunchKernelGGL(k_fm_claim, dim3(g), dim3(FS_THREADS), 0, st, xyz, n, cell, origin, tab, bounded, slot_of, d_words);
+    fs_compact(FmIsNew{slot_of, ids, first}, FmNumber{slot_of, ids, d_words, M}, n, chunk, rest, M, d_words, st);
+    hipLaunchKernelGGL(k_fm_cell_of, dim3(g), dim3(FS_THREADS), 0, st, slot_of, ids, n, d_words, cell_of);
     GF_CHECK_LAUNCH("gf_frames_map_insert");
     return GF_OK;
 }
@@ -439,25 +293,25 @@ extern "C" int gf_frames_map_insert(const float* xyz, int n, float cell, const f
 extern "C" int gf_frames_map_accumulate(const float* xyz, const unsigned char* rgb, const int32_t* cell_of, int n, int M,
                                         const float* origin, int aggregate, int32_t* count, long long* sums, int32_t* d_flag,
                                         void* stream) {
-    GF_CHECK_ARG(n >= 0 && n <= FM_MAX_POINTS, "gf_frames_map_accumulate: n = %d points (0 to %d)", n, FM_MAX_POINTS);
+    GF_CHECK_ARG(n >= 0 && n <= FS_MAX_POINTS, "gf_frames_map_accumulate: n = %d points (0 to %d)", n, FS_MAX_POINTS);
     if (n == 0) return GF_OK;
     GF_CHECK_ARG(M >= 1, "gf_frames_map_accumulate: M = %d cells (>= 1)", M);
     GF_CHECK_ARG(xyz && rgb && cell_of && origin && count && sums && d_flag,
                  "gf_frames_map_accumulate: NULL xyz, rgb, cell_of, origin, count, sums or d_flag");
     hipStream_t st = (hipStream_t)stream;
     if (aggregate)
-        hipLaunchKernelGGL(k_fm_add<true>, dim3(gf_div_up(n, FM_THREADS)), dim3(FM_THREADS), 0, st, xyz, rgb, cell_of, n, M,
+        hipLaunchKernelGGL(k_fm_add<true>, dim3(gf_div_up(n, FS_THREADS)), dim3(FS_THREADS), 0, st, xyz, rgb, cell_of, n, M,
                            origin, count, sums, d_flag);
     else
-        hipLaunchKernelGGL(k_fm_add<false>, dim3(gf_div_up(n, FM_THREADS)), dim3(FM_THREADS), 0, st, xyz, rgb, cell_of, n, M,
+        hipLaunchKernelGGL(k_fm_add<false>, dim3(gf_div_up(n, FS_THREADS)), dim3(FS_THREADS), 0, st, xyz, rgb, cell_of, n, M,
                            origin, count, sums, d_flag);
     GF_CHECK_LAUNCH("gf_frames_map_accumulate");
     return GF_OK;
 }
 
 extern "C" size_t gf_frames_map_means_scratch_bytes(int M, int chunk) {
-    if (M < 1 || M > FM_MAX_CELLS || !fm_chunk_ok(chunk)) return 0;
-    return fm_scan_bytes(M, chunk ? chunk : FM_CHUNK);
+    if (M < 1 || M > FM_MAX_CELLS || !fs_chunk_ok(chunk)) return 0;
+    return fs_scan_bytes(M, chunk ? chunk : FS_CHUNK);
 }
 
 extern "C" int gf_frames_map_means(const int32_t* count, const long long* sums, int M, const float* origin, int min_obs,
@@ -465,11 +319,11 @@ extern "C" int gf_frames_map_means(const int32_t* count, const long long* sums, 
                                    int32_t* new_id, int32_t* d_m, void* stream) {
     GF_CHECK_ARG(M >= 1 && M <= FM_MAX_CELLS, "gf_frames_map_means: M = %d cells (1 to %d)", M, FM_MAX_CELLS);
     GF_CHECK_ARG(min_obs >= 1, "gf_frames_map_means: min_obs = %d (>= 1)", min_obs);
-    GF_CHECK_ARG(fm_chunk_ok(chunk), "gf_frames_map_means: chunk = %d (0, or a multiple of 64 from 64 to %d)", chunk, FM_MAX_CHUNK);
+    GF_CHECK_ARG(fs_chunk_ok(chunk), "gf_frames_map_means: chunk = %d (0, or a multiple of 64 from 64 to %d)", chunk, FS_MAX_CHUNK);
     GF_CHECK_ARG(count && sums && origin && scratch && xyz_out && rgb_out && count_out && new_id && d_m,
                  "gf_frames_map_means: NULL pointer");
-    if (!chunk) chunk = FM_CHUNK;
-    fm_compact(FmKept{count, min_obs}, FmMean{sums, count, origin, xyz_out, rgb_out, count_out, new_id}, M, chunk, scratch, 0, d_m,
+    if (!chunk) chunk = FS_CHUNK;
+    fs_compact(FsKept{count, min_obs}, FsMean{sums, count, origin, xyz_out, rgb_out, count_out, new_id}, M, chunk, scratch, 0, d_m,
                (hipStream_t)stream);
     GF_CHECK_LAUNCH("gf_frames_map_means");
     return GF_OK;
@@ -480,9 +334,9 @@ extern "C" int gf_frames_map_lookup(const int32_t* index, long long T, const int
     GF_CHECK_ARG(T >= 0 && len >= 0, "gf_frames_map_lookup: T = %lld elements, a table of %d (each >= 0)", T, len);
     if (T == 0) return GF_OK;
     GF_CHECK_ARG(index && table && out, "gf_frames_map_lookup: NULL index, table or out");
-    GF_CHECK_ARG((T + FM_THREADS - 1) / FM_THREADS <= 2147483647ll,
+    GF_CHECK_ARG((T + FS_THREADS - 1) / FS_THREADS <= 2147483647ll,
                  "gf_frames_map_lookup: T = %lld elements (too many for one launch)", T);
-    hipLaunchKernelGGL(k_fm_lookup, dim3((unsigned)((T + FM_THREADS - 1) / FM_THREADS)), dim3(FM_THREADS), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(k_fm_lookup, dim3((unsigned)((T + FS_THREADS - 1) / FS_THREADS)), dim3(FS_THREADS), 0, (hipStream_t)stream,
                        index, (i64)T, table, len, out, d_flag);
     GF_CHECK_LAUNCH("gf_frames_map_lookup");
     return GF_OK;

@@ -20,47 +20,28 @@
 // k_ft_best, k_ft_match, k_ft_apply and k_ft_finish read the four flag words first and return when one is raised (the
 // same words for every thread: the branch is uniform): a failed update writes nothing but scratch.
 //
-// The key's hash and the run detection are frames_vote_stream.hip's, restated here because that file's kernels must keep
-// their ISA.
-//
-// Termination.  k_ft_count: with slots >= 2 m the table is never more than half full, so a probe always meets its own key
-// or an empty slot: unbounded.  With fewer (`bounded`) a thread gives up after FT_MAX_PROBES probes.  k_ft_best: a word
-// changes only to a slot that is larger under the total order, so every failed CAS means another thread's progress and
-// the word changes at most `pairs` times.  No thread waits for another thread or workgroup; there is no spin.  Integer
-// atomics only; the one floating-point operation is the threshold (one double multiplication, one compare).
+// Termination.  k_ft_count (frames_steps.h, "a key found or claimed") is unbounded with slots >= 2 m: the table holds at
+// most m pairs; with fewer (`bounded`) a thread gives up after FS_MAX_PROBES probes.
+// k_ft_best: a word changes only to a slot that is larger under the total order, so every failed CAS means another
+// thread's progress and the word changes at most `pairs` times.  No thread waits for another thread or workgroup; there
+// is no spin.  Integer atomics only; the one floating-point operation is the threshold (one double multiplication, one
+// compare).
 #include "common.h"
+#include "frames_steps.h"
 
 namespace {
 
-typedef unsigned long long u64;
-typedef long long i64;
-
-constexpr int FT_THREADS = 256;
 constexpr int FT_MATCH_THREADS = 1024;
 constexpr int FT_MAX_ROWS = 4096;  // rows of one update: FT_MATCH_THREADS threads scan four rows each
-constexpr int FT_MAX_POINTS = 1 << 29;  // gf_resample_max_points(): asserted in gf_frames_track_update
 constexpr i64 FT_MAX_TRACKS = 1ll << 30;
 constexpr i64 FT_MIN_SLOTS = 64;
 constexpr i64 FT_MAX_SLOTS = 1ll << 30;  // 2 m at m = 2^29
-constexpr int FT_MAX_PROBES = 128;
 constexpr int FT_BLOCKS = 2048;  // the most workgroups that stride over the slots or the tracks
-constexpr u64 FT_EMPTY = 0xffffffffffffffffull;  // no key: a row is below 2^31
 constexpr int FT_WORDS = 16;
 enum { W_ORDER = 0, W_OWNER = 1, W_OVERFLOW = 2, W_NEW = 3, W_RETIRED = 4, W_PAIRS = 5, W_ROOM = 6, W_LAST = 7 };
 enum { C_CLS = 0, C_SCORE = 1, C_BORN = 2, C_SEEN = 3, C_HITS = 4, C_MISSES = 5, C_SIZE = 6, C_ALIVE = 7, FT_COLUMNS = 8 };
 
-template <class T>
-__device__ __forceinline__ T ft_peek(const T* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ unsigned ft_hash(u64 key, unsigned mask) {
-    return (unsigned)((key * 0x9E3779B97F4A7C15ull) >> 32) & mask;
-}
-bool ft_slots_ok(i64 slots) { return slots >= FT_MIN_SLOTS && slots <= FT_MAX_SLOTS && (slots & (slots - 1)) == 0; }
-int ft_blocks(i64 work, int threads) {
-    const i64 g = (work + threads - 1) / threads;
-    return (int)(g < FT_BLOCKS ? (g > 0 ? g : 1) : FT_BLOCKS);
-}
+bool ft_slots_ok(i64 slots) { return fs_slots_ok(slots, FT_MIN_SLOTS, FT_MAX_SLOTS); }
 
 struct FtScratch {
     int32_t* words;    // [FT_WORDS]   zeroed
@@ -122,21 +103,11 @@ __device__ __forceinline__ bool ft_failed(const int32_t* words) {
     return (words[W_ORDER] | words[W_OWNER] | words[W_OVERFLOW] | words[W_ROOM]) != 0;
 }
 
-// the run of this lane's key among adjacent lanes: whether it is the head, and the run's length when it is
-__device__ __forceinline__ bool ft_run(u64 key, int lane, unsigned* add) {
-    const u64 left = __shfl_up(key, 1, 64);
-    const bool head = lane == 0 || left != key;
-    const u64 heads = __ballot(head);
-    const u64 above = (heads >> lane) >> 1;  // the heads after this lane
-    *add = above ? (unsigned)__ffsll((i64)above) : (unsigned)(64 - lane);
-    return head;
-}
-
 // m <= 2^29: a point's index fits an int.  Every index used as an address is checked here: c in [0, M) before track_of,
 // the owner in [0, p) before keep, the track in [0, T) before the table.
 template <bool AGG>
-__global__ __launch_bounds__(FT_THREADS) void k_ft_count(FtIn in, FtState st, FtScratch sc, unsigned mask, int bounded) {
-    const int i = blockIdx.x * FT_THREADS + threadIdx.x, lane = threadIdx.x & 63;
+__global__ __launch_bounds__(FS_THREADS) void k_ft_count(FtIn in, FtState st, FtScratch sc, unsigned mask, int bounded) {
+    const int i = blockIdx.x * FS_THREADS + threadIdx.x, lane = threadIdx.x & 63;
     int r = -1, t = -1;
     if (i < in.m) {
         const int c = in.cells[i], o = in.owner[i];
@@ -158,17 +129,17 @@ __global__ __launch_bounds__(FT_THREADS) void k_ft_count(FtIn in, FtState st, Ft
     const u64 key = ((u64)(unsigned)r << 32) | (u64)(unsigned)t;  // (-1, -1) for a lane without a point: it adds nothing
     unsigned add = 1;
     bool go = true;
-    if (AGG) go = ft_run(key, lane, &add);
+    if (AGG) go = fs_run(key, lane, &add);
     if (!go) return;
     if (r >= 0) atomicAdd(&sc.a[r], (int)add);
     if (t >= 0) atomicAdd(&sc.b[t], (int)add);
     if (r < 0 || t < 0) return;
-    unsigned s = ft_hash(key, mask);
-    for (int probes = 1;; ++probes) {
-        u64 old = ft_peek(&sc.keys[s]);
-        if (old == FT_EMPTY) {  // a key is written once: the CAS is issued on an empty slot only
-            old = atomicCAS(&sc.keys[s], FT_EMPTY, key);
-            if (old == FT_EMPTY) {
+    unsigned s = fs_hash(key, mask);
+    for (int probes = 1;; ++probes) {  // (frames_steps.h, "a key found or claimed")
+        u64 old = fs_peek(&sc.keys[s]);
+        if (old == FS_EMPTY) {
+            old = atomicCAS(&sc.keys[s], FS_EMPTY, key);
+            if (old == FS_EMPTY) {
                 atomicAdd(&sc.words[W_PAIRS], 1);
                 old = key;
             }
@@ -177,7 +148,7 @@ __global__ __launch_bounds__(FT_THREADS) void k_ft_count(FtIn in, FtState st, Ft
             atomicAdd(&sc.cnt[s], (int)add);
             return;
         }
-        if (bounded && probes >= FT_MAX_PROBES) {  // fewer than 2 m slots: give up, every later launch returns at once
+        if (bounded && probes >= FS_MAX_PROBES) {  // fewer than 2 m slots: give up, every later launch returns at once
             sc.words[W_OVERFLOW] = 1;
             return;
         }
@@ -195,7 +166,7 @@ __device__ __forceinline__ bool ft_before(int n1, int u1, int i1, int n2, int u2
 // *word becomes `slot` unless it holds a slot that comes before it.  `by_row`: the word is a row's (candidates differ in
 // the track; the index of the order is the track), else a track's.
 __device__ __forceinline__ void ft_offer(int32_t* word, int slot, int n, int uni, int index, bool by_row, const FtScratch& sc) {
-    int cur = ft_peek(word);
+    int cur = fs_peek(word);
     while (true) {
         if (cur >= 0) {
             const u64 k2 = sc.keys[cur];
@@ -209,12 +180,12 @@ __device__ __forceinline__ void ft_offer(int32_t* word, int slot, int n, int uni
     }
 }
 
-__global__ __launch_bounds__(FT_THREADS) void k_ft_best(FtIn in, FtState st, FtScratch sc, i64 slots, int same_class) {
+__global__ __launch_bounds__(FS_THREADS) void k_ft_best(FtIn in, FtState st, FtScratch sc, i64 slots, int same_class) {
     if (ft_failed(sc.words)) return;
-    const i64 stride = (i64)gridDim.x * FT_THREADS;
-    for (i64 s = (i64)blockIdx.x * FT_THREADS + threadIdx.x; s < slots; s += stride) {
+    const i64 stride = (i64)gridDim.x * FS_THREADS;
+    for (i64 s = (i64)blockIdx.x * FS_THREADS + threadIdx.x; s < slots; s += stride) {
         const u64 key = sc.keys[s];
-        if (key == FT_EMPTY) continue;
+        if (key == FS_EMPTY) continue;
         const int r = (int)(key >> 32), t = (int)(unsigned)key, n = sc.cnt[s];  // (r < p and t < T: k_ft_count's checks)
         if (n <= 0) continue;
         if (same_class && in.cls[r] != st.col(C_CLS, t)) continue;
@@ -305,10 +276,10 @@ __global__ __launch_bounds__(FT_MATCH_THREADS) void k_ft_match(FtIn in, FtState 
 }
 
 template <bool AGG>
-__global__ __launch_bounds__(FT_THREADS) void k_ft_apply(FtIn in, FtState st, FtScratch sc, const int32_t* __restrict__ track,
+__global__ __launch_bounds__(FS_THREADS) void k_ft_apply(FtIn in, FtState st, FtScratch sc, const int32_t* __restrict__ track,
                                                          int32_t* __restrict__ ids) {
     if (ft_failed(sc.words)) return;
-    const int i = blockIdx.x * FT_THREADS + threadIdx.x, lane = threadIdx.x & 63;
+    const int i = blockIdx.x * FS_THREADS + threadIdx.x, lane = threadIdx.x & 63;
     int was = -1, now = -1;
     if (i < in.m) {
         const int o = in.owner[i];
@@ -323,16 +294,16 @@ __global__ __launch_bounds__(FT_THREADS) void k_ft_apply(FtIn in, FtState st, Ft
     const u64 key = ((u64)(unsigned)was << 32) | (u64)(unsigned)now;
     unsigned add = 1;
     bool go = was != now;
-    if (AGG) go = ft_run(key, lane, &add) && go;
+    if (AGG) go = fs_run(key, lane, &add) && go;
     if (!go) return;
     if (was >= 0 && !sc.retired[was]) atomicSub(&st.col(C_SIZE, was), (int)add);  // (a retired track's size is 0 already)
     if (now >= 0) atomicAdd(&st.col(C_SIZE, now), (int)add);
 }
 
-__global__ __launch_bounds__(FT_THREADS) void k_ft_finish(FtState st, FtScratch sc, int32_t* __restrict__ retired,
+__global__ __launch_bounds__(FS_THREADS) void k_ft_finish(FtState st, FtScratch sc, int32_t* __restrict__ retired,
                                                           int32_t* __restrict__ words) {
     const bool failed = ft_failed(sc.words);
-    const int x = blockIdx.x * FT_THREADS + threadIdx.x, stride = gridDim.x * FT_THREADS;
+    const int x = blockIdx.x * FS_THREADS + threadIdx.x, stride = gridDim.x * FS_THREADS;
     int gone = 0;
     if (!failed) {
         for (int t = x; t < st.T; t += stride) {
@@ -353,21 +324,18 @@ __global__ __launch_bounds__(FT_THREADS) void k_ft_finish(FtState st, FtScratch 
 }  // namespace
 
 extern "C" int gf_frames_track_max_rows(void) { return FT_MAX_ROWS; }
-extern "C" int gf_frames_track_max_probes(void) { return FT_MAX_PROBES; }
+extern "C" int gf_frames_track_max_probes(void) { return FS_MAX_PROBES; }
 extern "C" long long gf_frames_track_max_tracks(void) { return FT_MAX_TRACKS; }
 extern "C" int gf_frames_track_columns(void) { return FT_COLUMNS; }
 extern "C" int gf_frames_track_words(void) { return FT_WORDS; }
 
 extern "C" long long gf_frames_track_default_slots(long long p, long long live) {
     if (p < 0 || p > FT_MAX_ROWS || live < 0 || live > FT_MAX_TRACKS) return 0;
-    const i64 want = 8 * (p + live);
-    i64 s = FT_MIN_SLOTS;
-    while (s < want && s < FT_MAX_SLOTS) s <<= 1;
-    return s;
+    return fs_pow2_slots(8 * (p + live), FT_MIN_SLOTS, FT_MAX_SLOTS);
 }
 
 extern "C" size_t gf_frames_track_scratch_bytes(long long m, long long p, long long T, long long slots) {
-    if (m < 0 || m > FT_MAX_POINTS || p < 0 || p > FT_MAX_ROWS || T < 0 || T > FT_MAX_TRACKS || !ft_slots_ok(slots)) return 0;
+    if (m < 0 || m > FS_MAX_POINTS || p < 0 || p > FT_MAX_ROWS || T < 0 || T > FT_MAX_TRACKS || !ft_slots_ok(slots)) return 0;
     return ft_carve(nullptr, m, p, T, slots).bytes + 16;
 }
 
@@ -378,8 +346,8 @@ extern "C" int gf_frames_track_update(const int32_t* cells, const int32_t* owner
                                       int aggregate, void* scratch, int32_t* ids, int32_t* track, int32_t* retired,
                                       int32_t* d_words, void* stream) {
     const char* who = "gf_frames_track_update";
-    GF_CHECK_ARG(m >= 0 && m <= FT_MAX_POINTS && gf_resample_max_points() == FT_MAX_POINTS, "%s: m = %lld points (0 to %d)", who,
-                 m, FT_MAX_POINTS);
+    GF_CHECK_ARG(m >= 0 && m <= FS_MAX_POINTS && gf_resample_max_points() == FS_MAX_POINTS, "%s: m = %lld points (0 to %d)", who,
+                 m, FS_MAX_POINTS);
     GF_CHECK_ARG(p >= 0 && p <= FT_MAX_ROWS, "%s: p = %d rows (0 to %d)", who, p, FT_MAX_ROWS);
     GF_CHECK_ARG(M >= 0 && M <= map_cap && map_cap <= 2147483647ll, "%s: M = %lld cells in a map of %lld (0 <= M <= capacity < 2^31)",
                  who, M, map_cap);
@@ -400,24 +368,24 @@ extern "C" int gf_frames_track_update(const int32_t* cells, const int32_t* owner
     GF_TRY(hipMemsetAsync(scratch, 0, sc.zero_bytes, s));
     GF_TRY(hipMemsetAsync((char*)scratch + sc.ones_at, 0xff, sc.ones_bytes, s));
     GF_TRY(hipMemsetAsync(d_words, 0, FT_WORDS * 4, s));
-    const int g = gf_div_up(m, FT_THREADS), bounded = slots < 2 * m;
+    const int g = gf_div_up(m, FS_THREADS), bounded = slots < 2 * m;
     if (m > 0) {
         if (aggregate)
-            hipLaunchKernelGGL(k_ft_count<true>, dim3(g), dim3(FT_THREADS), 0, s, in, st, sc, (unsigned)(slots - 1), bounded);
+            hipLaunchKernelGGL(k_ft_count<true>, dim3(g), dim3(FS_THREADS), 0, s, in, st, sc, (unsigned)(slots - 1), bounded);
         else
-            hipLaunchKernelGGL(k_ft_count<false>, dim3(g), dim3(FT_THREADS), 0, s, in, st, sc, (unsigned)(slots - 1), bounded);
+            hipLaunchKernelGGL(k_ft_count<false>, dim3(g), dim3(FS_THREADS), 0, s, in, st, sc, (unsigned)(slots - 1), bounded);
         if (T > 0 && p > 0)
-            hipLaunchKernelGGL(k_ft_best, dim3(ft_blocks(slots, FT_THREADS)), dim3(FT_THREADS), 0, s, in, st, sc, (i64)slots,
+            hipLaunchKernelGGL(k_ft_best, dim3(fs_blocks(slots, FT_BLOCKS)), dim3(FS_THREADS), 0, s, in, st, sc, (i64)slots,
                                same_class != 0);
     }
     hipLaunchKernelGGL(k_ft_match, dim3(1), dim3(FT_MATCH_THREADS), 0, s, in, st, sc, iou, max_misses, min_points, update, track);
     if (m > 0) {
         if (aggregate)
-            hipLaunchKernelGGL(k_ft_apply<true>, dim3(g), dim3(FT_THREADS), 0, s, in, st, sc, (const int32_t*)track, ids);
+            hipLaunchKernelGGL(k_ft_apply<true>, dim3(g), dim3(FS_THREADS), 0, s, in, st, sc, (const int32_t*)track, ids);
         else
-            hipLaunchKernelGGL(k_ft_apply<false>, dim3(g), dim3(FT_THREADS), 0, s, in, st, sc, (const int32_t*)track, ids);
+            hipLaunchKernelGGL(k_ft_apply<false>, dim3(g), dim3(FS_THREADS), 0, s, in, st, sc, (const int32_t*)track, ids);
     }
-    hipLaunchKernelGGL(k_ft_finish, dim3(ft_blocks(T > FT_WORDS ? T : FT_WORDS, FT_THREADS)), dim3(FT_THREADS), 0, s, st, sc, retired,
+    hipLaunchKernelGGL(k_ft_finish, dim3(fs_blocks(T > FT_WORDS ? T : FT_WORDS, FT_BLOCKS)), dim3(FS_THREADS), 0, s, st, sc, retired,
                        d_words);
     GF_CHECK_LAUNCH(who);
     return GF_OK;

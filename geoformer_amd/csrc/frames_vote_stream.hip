@@ -18,47 +18,26 @@
 //                          persistent table: slots with cnt == 0 skipped, a group >= n raises a word instead of writing)
 //                          and k_vs_write (label, votes and total per group; the two words copied out)
 //
-// The key, the hash, the run detection and pick / write are frames_vote.hip's, restated here because that file's kernels
-// must keep their ISA; a later same-ISA refactor should share them through a header.
-//
 // A failed add.  Claiming and counting are two launches so that an add that overflows its table changes no count: what
 // it leaves are claimed keys with cnt == 0.  Such a slot is debris: k_vs_pick and k_vs_move treat cnt == 0 as absent, and
 // no count of pairs includes it.  A successful add leaves none: every claimed key belongs to a head that adds >= 1.
 //
-// Termination.  k_vs_claim: with slots >= 2 (P + T) (P: the occupied slots before the call, T: this call's elements) the
-// table is never more than half full, so a probe always meets its own key or an empty slot: unbounded.  With fewer slots
-// (`bounded`) a thread gives up after VS_MAX_PROBES probes and raises the overflow word.  k_vs_move: the new table has at
-// least one slot per moved pair and the keys are distinct, so a free slot is always found.  No thread waits for another
-// thread or workgroup; there is no spin.  Integer atomics and an integer maximum only.
+// Termination (frames_steps.h, "a key found or claimed").  k_vs_claim is unbounded with slots >= 2 (P + T) (P: the
+// occupied slots before the call, T: this call's elements).  k_vs_move: the new table has at least one slot per moved
+// pair and the keys are distinct.  No thread waits for another thread or workgroup; there is no spin.  Integer atomics
+// and an integer maximum only.
 #include "common.h"
+#include "frames_steps.h"
 
 namespace {
 
-typedef unsigned long long u64;
-typedef long long i64;
-
-constexpr int VS_THREADS = 256;
-constexpr int VS_MAX_POINTS = 1 << 29;  // gf_resample_max_points(): asserted in gf_frames_votes_add
 constexpr i64 VS_MIN_SLOTS = 64;
 constexpr i64 VS_MAX_SLOTS = 1ll << 31;  // a slot is recorded as a non-negative int32; >= 2 (P + T) up to P + T = 2^30
-constexpr int VS_MAX_PROBES = 128;
 constexpr i64 VS_MAX_ELEMENTS = 2147483647ll;  // offered in all: every count and total fits an int32
 constexpr i64 VS_MAX_GROUPS = 2147483647ll;
 constexpr int VS_PICK_BLOCKS = 1024;  // the workgroups that stride over the table in k_vs_pick
-constexpr u64 VS_EMPTY = 0xffffffffffffffffull;  // no key: a group is a non-negative int32
 
-template <class T>
-__device__ __forceinline__ T vs_peek(const T* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ unsigned vs_hash(u64 key, unsigned mask) {
-    return (unsigned)((key * 0x9E3779B97F4A7C15ull) >> 32) & mask;
-}
-bool vs_slots_ok(i64 slots) { return slots >= VS_MIN_SLOTS && slots <= VS_MAX_SLOTS && (slots & (slots - 1)) == 0; }
-int vs_blocks(i64 work, int most) {
-    const i64 g = (work + VS_THREADS - 1) / VS_THREADS;
-    return (int)(g < most ? (g > 0 ? g : 1) : most);
-}
+bool vs_slots_ok(i64 slots) { return fs_slots_ok(slots, VS_MIN_SLOTS, VS_MAX_SLOTS); }
 
 struct VsInput {
     const int32_t* group;  // [F, Hs, Ws]
@@ -73,13 +52,15 @@ struct VsHead {  // what an element leaves for the commit pass
 
 // T <= 2^29: every index of a sampled element fits an int; the value image is addressed in 64 bits
 template <bool AGG>
-__global__ __launch_bounds__(VS_THREADS) void k_vs_claim(VsInput in, u64* __restrict__ keys, unsigned mask, int bounded,
+__global__ __launch_bounds__(FS_THREADS) void k_vs_claim(VsInput in, u64* __restrict__ keys, unsigned mask, int bounded,
                                                          VsHead* __restrict__ heads_out, int32_t* __restrict__ words) {
-    __shared__ int s_new[VS_THREADS / 64];
-    const int t = blockIdx.x * VS_THREADS + threadIdx.x, lane = threadIdx.x & 63;
-    u64 key = VS_EMPTY;
+    __shared__ int s_new[FS_THREADS / 64];
+    const int t = blockIdx.x * FS_THREADS + threadIdx.x, lane = threadIdx.x & 63;
+    u64 key = FS_EMPTY;
     if (t < in.T) {
         const int g = in.group[t];
+        // k_fv_insert's key (frames_vote.hip), kept written out in both: through one inlined function either kernel
+        // comes out 1 to 4 lines longer
         if (g >= 0) {
             size_t at = (size_t)t;
             if (in.stride != 1) {  // (stride 1: H = Hs and W = Ws, the sampled element is the element)
@@ -97,10 +78,9 @@ __global__ __launch_bounds__(VS_THREADS) void k_vs_claim(VsInput in, u64* __rest
         }
     }
     unsigned add = 1;
-    bool go = key != VS_EMPTY;
+    bool go = key != FS_EMPTY;  // (lanes without a vote form runs of FS_EMPTY, dropped here)
     if (AGG) {
-        // a run: adjacent lanes holding the same key (lanes without a vote form runs of VS_EMPTY, dropped by `go`).  Two
-        // runs of one key with another key between them stay two runs; each records its own add.
+        // fs_run, kept written out (through the helper the same 362 lines come out with other registers and order)
         const u64 left = __shfl_up(key, 1, 64);
         const bool head = lane == 0 || left != key;
         const u64 heads = __ballot(head);
@@ -111,20 +91,18 @@ __global__ __launch_bounds__(VS_THREADS) void k_vs_claim(VsInput in, u64* __rest
     int slot = -1;
     bool won = false;
     if (go) {
-        unsigned s = vs_hash(key, mask);
-        // A key is written once and never changes: the slot is read first and the CAS issued only on an empty one; a
-        // stale read costs an atomic, never loses one.
-        for (int probes = 1;; ++probes) {
-            u64 old = vs_peek(&keys[s]);
-            if (old == VS_EMPTY) {
-                old = atomicCAS(&keys[s], VS_EMPTY, key);
-                won = old == VS_EMPTY;
+        unsigned s = fs_hash(key, mask);
+        for (int probes = 1;; ++probes) {  // (frames_steps.h, "a key found or claimed")
+            u64 old = fs_peek(&keys[s]);
+            if (old == FS_EMPTY) {
+                old = atomicCAS(&keys[s], FS_EMPTY, key);
+                won = old == FS_EMPTY;
             }
             if (won || old == key) {
                 slot = (int)s;
                 break;
             }
-            if (bounded && probes >= VS_MAX_PROBES) {  // fewer than 2 (P + T) slots: give up, the commit writes nothing
+            if (bounded && probes >= FS_MAX_PROBES) {  // fewer than 2 (P + T) slots: give up, the commit writes nothing
                 words[1] = 1;
                 break;
             }
@@ -139,42 +117,42 @@ __global__ __launch_bounds__(VS_THREADS) void k_vs_claim(VsInput in, u64* __rest
     if (threadIdx.x == 0) {
         int p = 0;
 #pragma unroll
-        for (int w = 0; w < VS_THREADS / 64; ++w) p += s_new[w];
+        for (int w = 0; w < FS_THREADS / 64; ++w) p += s_new[w];
         if (p) atomicAdd(&words[0], p);
     }
 }
 
-__global__ __launch_bounds__(VS_THREADS) void k_vs_commit(const VsHead* __restrict__ heads, int T, unsigned* __restrict__ cnt,
+__global__ __launch_bounds__(FS_THREADS) void k_vs_commit(const VsHead* __restrict__ heads, int T, unsigned* __restrict__ cnt,
                                                           const int32_t* __restrict__ words) {
     if (words[1]) return;  // the claim pass overflowed: no count changes (the same word for every thread)
-    const int t = blockIdx.x * VS_THREADS + threadIdx.x;
+    const int t = blockIdx.x * FS_THREADS + threadIdx.x;
     if (t >= T) return;
     const VsHead h = heads[t];
     if (h.slot >= 0) atomicAdd(&cnt[h.slot], h.add);
 }
 
-__global__ __launch_bounds__(VS_THREADS) void k_vs_clear(u64* __restrict__ keys, unsigned* __restrict__ cnt, i64 slots) {
-    const i64 stride = (i64)gridDim.x * VS_THREADS;
-    for (i64 s = (i64)blockIdx.x * VS_THREADS + threadIdx.x; s < slots; s += stride) {
-        keys[s] = VS_EMPTY;
+__global__ __launch_bounds__(FS_THREADS) void k_vs_clear(u64* __restrict__ keys, unsigned* __restrict__ cnt, i64 slots) {
+    const i64 stride = (i64)gridDim.x * FS_THREADS;
+    for (i64 s = (i64)blockIdx.x * FS_THREADS + threadIdx.x; s < slots; s += stride) {
+        keys[s] = FS_EMPTY;
         cnt[s] = 0;
     }
 }
 
 // the new table holds at least one slot per moved pair and the keys are distinct: a free slot is always found
-__global__ __launch_bounds__(VS_THREADS) void k_vs_move(const u64* __restrict__ old_keys, const unsigned* __restrict__ old_cnt,
+__global__ __launch_bounds__(FS_THREADS) void k_vs_move(const u64* __restrict__ old_keys, const unsigned* __restrict__ old_cnt,
                                                         i64 old_slots, u64* __restrict__ keys, unsigned* __restrict__ cnt,
                                                         unsigned mask) {
-    const i64 stride = (i64)gridDim.x * VS_THREADS;
-    for (i64 s = (i64)blockIdx.x * VS_THREADS + threadIdx.x; s < old_slots; s += stride) {
+    const i64 stride = (i64)gridDim.x * FS_THREADS;
+    for (i64 s = (i64)blockIdx.x * FS_THREADS + threadIdx.x; s < old_slots; s += stride) {
         const unsigned c = old_cnt[s];
         const u64 key = old_keys[s];
-        if (c == 0 || key == VS_EMPTY) continue;  // empty, or claimed by a failed add and never counted
-        unsigned slot = vs_hash(key, mask);
+        if (c == 0 || key == FS_EMPTY) continue;  // empty, or claimed by a failed add and never counted
+        unsigned slot = fs_hash(key, mask);
         while (true) {
-            u64 old = vs_peek(&keys[slot]);
-            if (old == VS_EMPTY) old = atomicCAS(&keys[slot], VS_EMPTY, key);
-            if (old == VS_EMPTY) break;  // (old == key cannot happen: the old table holds a key once)
+            u64 old = fs_peek(&keys[slot]);
+            if (old == FS_EMPTY) old = atomicCAS(&keys[slot], FS_EMPTY, key);
+            if (old == FS_EMPTY) break;  // (old == key cannot happen: the old table holds a key once)
             slot = (slot + 1) & mask;
         }
         cnt[slot] = c;
@@ -197,15 +175,15 @@ VsPick vs_carve(void* scratch, i64 n) {
 
 // At most VS_PICK_BLOCKS workgroups stride over the table, so the pairs are counted with at most that many atomics on
 // their one word.  slots and the stride are multiples of 64: a wave is inside the table or outside it as a whole.
-__global__ __launch_bounds__(VS_THREADS) void k_vs_pick(const u64* __restrict__ keys, const unsigned* __restrict__ cnt, i64 slots,
+__global__ __launch_bounds__(FS_THREADS) void k_vs_pick(const u64* __restrict__ keys, const unsigned* __restrict__ cnt, i64 slots,
                                                         i64 n, VsPick out) {
-    __shared__ int s_pairs[VS_THREADS / 64];
-    const i64 stride = (i64)gridDim.x * VS_THREADS;
+    __shared__ int s_pairs[FS_THREADS / 64];
+    const i64 stride = (i64)gridDim.x * FS_THREADS;
     int pairs = 0;
-    for (i64 s = (i64)blockIdx.x * VS_THREADS + threadIdx.x; s < slots; s += stride) {
+    for (i64 s = (i64)blockIdx.x * FS_THREADS + threadIdx.x; s < slots; s += stride) {
         const u64 key = keys[s];
         const unsigned c = cnt[s];
-        const bool live = key != VS_EMPTY && c > 0;  // cnt == 0: the debris of a failed add
+        const bool live = key != FS_EMPTY && c > 0;  // cnt == 0: the debris of a failed add
         pairs += __popcll(__ballot(live));
         if (live) {
             const i64 g = (i64)(key >> 32);
@@ -214,7 +192,7 @@ __global__ __launch_bounds__(VS_THREADS) void k_vs_pick(const u64* __restrict__ 
             } else {
                 atomicAdd(&out.total[g], (int)c);
                 const u64 mine = ((u64)c << 32) | (u64)(0xffffffffu - (unsigned)key);
-                if (mine > vs_peek(&out.best[g])) atomicMax(&out.best[g], mine);  // the word only rises
+                if (mine > fs_peek(&out.best[g])) atomicMax(&out.best[g], mine);  // the word only rises
             }
         }
     }
@@ -223,15 +201,15 @@ __global__ __launch_bounds__(VS_THREADS) void k_vs_pick(const u64* __restrict__ 
     if (threadIdx.x == 0) {
         int p = 0;
 #pragma unroll
-        for (int w = 0; w < VS_THREADS / 64; ++w) p += s_pairs[w];
+        for (int w = 0; w < FS_THREADS / 64; ++w) p += s_pairs[w];
         if (p) atomicAdd(&out.words[0], p);
     }
 }
 
-__global__ __launch_bounds__(VS_THREADS) void k_vs_write(VsPick in, i64 n, int fill, int32_t* __restrict__ label,
+__global__ __launch_bounds__(FS_THREADS) void k_vs_write(VsPick in, i64 n, int fill, int32_t* __restrict__ label,
                                                          int32_t* __restrict__ votes, int32_t* __restrict__ total,
                                                          int32_t* __restrict__ words) {
-    const i64 g = (i64)blockIdx.x * VS_THREADS + threadIdx.x;
+    const i64 g = (i64)blockIdx.x * FS_THREADS + threadIdx.x;
     if (g < 2) words[g] = in.words[g];  // (n >= 1: the first workgroup exists)
     if (g >= n) return;
     const u64 b = in.best[g];  // 0: no vote (a count is at least 1)
@@ -247,19 +225,16 @@ struct VsShape {
 
 }  // namespace
 
-extern "C" int gf_frames_votes_max_probes(void) { return VS_MAX_PROBES; }
+extern "C" int gf_frames_votes_max_probes(void) { return FS_MAX_PROBES; }
 extern "C" long long gf_frames_votes_max_elements(void) { return VS_MAX_ELEMENTS; }
 
 extern "C" long long gf_frames_votes_default_slots(long long P, long long T) {
     if (P < 0 || P > VS_MAX_ELEMENTS || T < 0 || T > VS_MAX_ELEMENTS) return 0;
-    const i64 want = 4 * P > T / 8 ? 4 * P : T / 8;
-    i64 p = VS_MIN_SLOTS;
-    while (p < want && p < VS_MAX_SLOTS) p <<= 1;
-    return p;
+    return fs_default_slots(P, T, VS_MIN_SLOTS, VS_MAX_SLOTS);
 }
 
 extern "C" size_t gf_frames_votes_add_scratch_bytes(long long T) {
-    if (T < 0 || T > VS_MAX_POINTS) return 0;
+    if (T < 0 || T > FS_MAX_POINTS) return 0;
     return (size_t)T * sizeof(VsHead) + 64;
 }
 
@@ -276,8 +251,8 @@ static int vs_check_add(const char* who, int kind, int F, int W, int H, int stri
     GF_CHECK_ARG(kind >= 0 && kind <= 2, "%s: kind = %d (0 uint8, 1 uint16, 2 int32)", who, kind);
     const int Ws = gf_div_up(W, stride), Hs = gf_div_up(H, stride);
     const long long per = (long long)Hs * Ws;  // below 2^62
-    GF_CHECK_ARG(per <= VS_MAX_POINTS && per * F <= VS_MAX_POINTS && gf_resample_max_points() == VS_MAX_POINTS,
-                 "%s: %d x %d x %d sampled elements (at most %d)", who, F, Hs, Ws, VS_MAX_POINTS);
+    GF_CHECK_ARG(per <= FS_MAX_POINTS && per * F <= FS_MAX_POINTS && gf_resample_max_points() == FS_MAX_POINTS,
+                 "%s: %d x %d x %d sampled elements (at most %d)", who, F, Hs, Ws, FS_MAX_POINTS);
     GF_CHECK_ARG(vs_slots_ok(slots), "%s: slots = %lld (a power of two from %lld to %lld)", who, slots, VS_MIN_SLOTS,
                  VS_MAX_SLOTS);
     GF_CHECK_ARG(pairs >= 0 && pairs <= slots && pairs + per * F <= VS_MAX_ELEMENTS,
@@ -299,13 +274,13 @@ extern "C" int gf_frames_votes_claim(const int32_t* group, const void* value, in
     GF_CHECK_ARG(group && value && keys && scratch && d_words, "gf_frames_votes_claim: NULL group, value, keys, scratch or d_words");
     hipStream_t st = (hipStream_t)stream;
     const VsInput in = {group, value, kind, W, H, sh.Ws, sh.Hs, stride, (int)sh.T, ignore, has_ignore != 0};
-    const int bounded = slots < 2 * (pairs + sh.T), g = gf_div_up(sh.T, VS_THREADS);
+    const int bounded = slots < 2 * (pairs + sh.T), g = gf_div_up(sh.T, FS_THREADS);
     GF_TRY(hipMemsetAsync(d_words, 0, 2 * 4, st));
     if (aggregate)
-        hipLaunchKernelGGL(k_vs_claim<true>, dim3(g), dim3(VS_THREADS), 0, st, in, keys, (unsigned)(slots - 1), bounded,
+        hipLaunchKernelGGL(k_vs_claim<true>, dim3(g), dim3(FS_THREADS), 0, st, in, keys, (unsigned)(slots - 1), bounded,
                            (VsHead*)scratch, d_words);
     else
-        hipLaunchKernelGGL(k_vs_claim<false>, dim3(g), dim3(VS_THREADS), 0, st, in, keys, (unsigned)(slots - 1), bounded,
+        hipLaunchKernelGGL(k_vs_claim<false>, dim3(g), dim3(FS_THREADS), 0, st, in, keys, (unsigned)(slots - 1), bounded,
                            (VsHead*)scratch, d_words);
     GF_CHECK_LAUNCH("gf_frames_votes_claim");
     return GF_OK;
@@ -313,12 +288,12 @@ extern "C" int gf_frames_votes_claim(const int32_t* group, const void* value, in
 
 extern "C" int gf_frames_votes_commit(const void* scratch, long long T, uint32_t* cnt, long long slots, const int32_t* d_words,
                                       void* stream) {
-    GF_CHECK_ARG(T >= 0 && T <= VS_MAX_POINTS, "gf_frames_votes_commit: T = %lld elements (0 to %d)", T, VS_MAX_POINTS);
+    GF_CHECK_ARG(T >= 0 && T <= FS_MAX_POINTS, "gf_frames_votes_commit: T = %lld elements (0 to %d)", T, FS_MAX_POINTS);
     GF_CHECK_ARG(vs_slots_ok(slots), "gf_frames_votes_commit: slots = %lld (a power of two from %lld to %lld)", slots,
                  VS_MIN_SLOTS, VS_MAX_SLOTS);
     if (T == 0) return GF_OK;
     GF_CHECK_ARG(scratch && cnt && d_words, "gf_frames_votes_commit: NULL scratch, cnt or d_words");
-    hipLaunchKernelGGL(k_vs_commit, dim3(gf_div_up(T, VS_THREADS)), dim3(VS_THREADS), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(k_vs_commit, dim3(gf_div_up(T, FS_THREADS)), dim3(FS_THREADS), 0, (hipStream_t)stream,
                        (const VsHead*)scratch, (int)T, cnt, d_words);
     GF_CHECK_LAUNCH("gf_frames_votes_commit");
     return GF_OK;
@@ -353,9 +328,9 @@ extern "C" int gf_frames_votes_rehash(const unsigned long long* old_keys, const 
                  "gf_frames_votes_rehash: NULL old_keys, old_cnt, new_keys or new_cnt");
     GF_CHECK_ARG(old_slots == 0 || (old_keys != new_keys && old_cnt != new_cnt), "gf_frames_votes_rehash: the tables overlap");
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_vs_clear, dim3(vs_blocks(new_slots, 4096)), dim3(VS_THREADS), 0, st, new_keys, new_cnt, (i64)new_slots);
+    hipLaunchKernelGGL(k_vs_clear, dim3(fs_blocks(new_slots, 4096)), dim3(FS_THREADS), 0, st, new_keys, new_cnt, (i64)new_slots);
     if (old_slots > 0 && pairs > 0)
-        hipLaunchKernelGGL(k_vs_move, dim3(vs_blocks(old_slots, 4096)), dim3(VS_THREADS), 0, st, old_keys, old_cnt, (i64)old_slots,
+        hipLaunchKernelGGL(k_vs_move, dim3(fs_blocks(old_slots, 4096)), dim3(FS_THREADS), 0, st, old_keys, old_cnt, (i64)old_slots,
                            new_keys, new_cnt, (unsigned)(new_slots - 1));
     GF_CHECK_LAUNCH("gf_frames_votes_rehash");
     return GF_OK;
@@ -373,8 +348,8 @@ extern "C" int gf_frames_votes_pick(const unsigned long long* keys, const uint32
     hipStream_t st = (hipStream_t)stream;
     const VsPick p = vs_carve(scratch, n);
     GF_TRY(hipMemsetAsync(scratch, 0, vs_pick_bytes(n), st));
-    hipLaunchKernelGGL(k_vs_pick, dim3(vs_blocks(slots, VS_PICK_BLOCKS)), dim3(VS_THREADS), 0, st, keys, cnt, (i64)slots, (i64)n, p);
-    hipLaunchKernelGGL(k_vs_write, dim3((unsigned)((n + VS_THREADS - 1) / VS_THREADS)), dim3(VS_THREADS), 0, st, p, (i64)n, fill,
+    hipLaunchKernelGGL(k_vs_pick, dim3(fs_blocks(slots, VS_PICK_BLOCKS)), dim3(FS_THREADS), 0, st, keys, cnt, (i64)slots, (i64)n, p);
+    hipLaunchKernelGGL(k_vs_write, dim3((unsigned)((n + FS_THREADS - 1) / FS_THREADS)), dim3(FS_THREADS), 0, st, p, (i64)n, fill,
                        label, votes, total, d_words);
     GF_CHECK_LAUNCH("gf_frames_votes_pick");
     return GF_OK;
